@@ -7,12 +7,15 @@ data.  Sampling shards over GPUs as independent sample batches: no data-path col
 ("scaling": "weak", batch per GPU fixed).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full --dump-outputs out/    # + every extra measurement, + the last step's arrays
     python bench.py --gpus 8 --steps 20 --warmup 3      # no launcher around it: starts the 8 ranks itself (self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0).  `value` = N * B * K / wall  (sample-steps per second, whole job); the timed
-region carries no instrumentation.  Extra objects, all measured AFTER the timed region:
+region carries no instrumentation.  A plain run sets up (weights, load-time calibration), warms up, times the K
+steps, writes the last step's arrays if --dump-outputs is given, and prints the line.  --full adds these objects,
+all measured AFTER the timed region (null without --full):
   roofline      dominant kernel (md_conv3_wino: the 3x3x3 convs as Winograd F(2,3) along w): HIP events around every launch of
                 a second, untimed pass; its operand pass md_wino_prep priced beside it (`operand_prep`), and the direct 27-tap
                 kernel on the same convs in the same process (`direct_build`)
@@ -44,6 +47,7 @@ FLOPS_PER_SAMPLE_STEP_RES128 = 3.453e13
 PEAK_BF16_TFLOPS = 2500.0     # dense bf16 MFMA peak, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "conv_traffic.json")   # PMC-derived HBM bytes per launch, keyed by kernel source
+DUMP_CAP_BYTES = 48 << 20     # --dump-outputs: all arrays of all ranks together
 
 
 def parse():
@@ -71,6 +75,13 @@ def parse():
     ap.add_argument("--graph", action="store_true", help="replay the denoise step from a captured hipGraph")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU-only check of the multi-process control flow (gloo, no kernels, fake timing)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the extra measurements (roofline / direct-kernel events, bf16x3 mode, res64 B=1, "
+                         "cond_gen + marching tets, training step, HBM-bound kernels, res128, CPU baseline); the --no-* options "
+                         "above skip single ones of them")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write x.npy and x_mean.npy (float32) of the last timed step to DIR: the arrays AncestralStepper.step "
+                         "returns, as a fixed seeded sample when they are larger than the size cap")
     return ap.parse_args()
 
 
@@ -101,6 +112,8 @@ def main():
         raise SystemExit("--gpus must be >= 1")
     if a.steps < 1 or a.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0: the line reports the time of exactly --steps timed steps")
+    if not a.full:      # a plain run measures the headline only: set-up, warm-up, the timed steps, the JSON line
+        a.no_kernel_events = a.no_fast_mode = a.no_train_step = a.no_res128 = a.no_cpu_baseline = True
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(a)
     rank = int(os.environ.get("RANK", "0"))
@@ -190,6 +203,8 @@ def main():
         barrier()
         wall = time.perf_counter() - t0
         assert bool(torch.isfinite(xm).all()), "non-finite samples"
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"x": x, "x_mean": xm}, rank, world)
         # ---- second, UNTIMED pass of the same steps with HIP events around every GEMM / conv launch ----
         events = events_unfused = None
         if not a.no_kernel_events:
@@ -305,7 +320,7 @@ def main():
             if train:
                 roof["train_step_ms"] = train.get("ms_per_step")
                 roof["train_step_mfma_frac"] = train.get("mfma_frac_step")
-        hbm_kernels = hbm_bound_kernels(dev, B) if world == 1 else None
+        hbm_kernels = hbm_bound_kernels(dev, B) if world == 1 and a.full else None
         other = None
         if world == 1 and not a.no_res128:
             other = {"res128_b2": res128_step(dev)}
@@ -354,6 +369,21 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: each array as <name>.npy in float32 (<name>_rank<r>.npy with more than one rank).  An array larger than
+    its share of DUMP_CAP_BYTES is stored flattened as a fixed sample: the elements at the sorted indices of a permutation drawn
+    from a generator seeded with 0, the same on every run of the same shape, so that two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_CAP_BYTES // (4 * len(arrays) * world)
+    for name, t in arrays.items():
+        v = t.detach().float().cpu()
+        if v.numel() > cap:
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), v.numpy())
 
 
 def launch_arithmetic(hip_ops, step, configured):

@@ -302,6 +302,25 @@ def test_bench_refuses_fewer_ranks_than_gpus_flag():
         assert out.returncode != 0 and "refusing to run fewer ranks" in out.stderr and "{" not in out.stdout
 
 
+def test_bench_dump_outputs_fixed_sample_under_cap(tmp_path):
+    """`bench.py --dump-outputs`: one float32 .npy per array; an array larger than its share of the cap (the bench's x at
+    B = 8 is) is stored as the elements at the sorted indices of a permutation seeded with 0 -- the same on every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    big, small = torch.randn((8, 4, 64, 64, 64)), torch.randn((3, 5))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": big, "x_mean": small}, 0, 1)
+    cap = bench.DUMP_CAP_BYTES // (4 * 2)
+    idx = torch.randperm(big.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+    xa, xb = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert xa.dtype == np.float32 and np.array_equal(xa, xb) and np.array_equal(xa, big.reshape(-1)[idx].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "x_mean.npy"), small.numpy())
+    assert os.path.getsize(tmp_path / "a" / "x.npy") + os.path.getsize(tmp_path / "a" / "x_mean.npy") <= 64 << 20
+    bench.dump_outputs(str(tmp_path / "r"), {"x": big}, 1, 2)          # one file per rank; the ranks share the cap
+    assert os.listdir(tmp_path / "r") == ["x_rank1.npy"] and np.load(tmp_path / "r" / "x_rank1.npy").size == bench.DUMP_CAP_BYTES // 8
+
+
 def _evaler_worker(rank, world, port, tmp, total):
     """One rank of `main_diffusion.py --mode=uncond_gen` / cond_gen under torchrun; the sampler is a stub (the HIP path
     needs a GPU; tests/test_gpu_dist.py runs the same flow through the real kernels)."""

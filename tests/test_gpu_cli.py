@@ -133,17 +133,23 @@ def test_cli_train_mode_runs_checkpoints_and_resumes(hip_lib, tmp_path, monkeypa
     assert ck2["ema"]["num_updates"] == 6
 
 
-def test_bench_contract_on_gpu(hip_lib):
-    """`python bench.py` (one GPU): exactly one JSON line with the driver's keys, the roofline of the dominant kernel
-    measured from in-region HIP events, and the HBM-bound kernel figures (short run: no CPU baseline / fast mode)."""
+def _bench_line(*args):
     import json
     import subprocess
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-fast-mode"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", *args],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_bench_contract_on_gpu(hip_lib, tmp_path):
+    """`python bench.py --full` (one GPU): exactly one JSON line with the driver's keys, the roofline of the dominant kernel
+    measured from in-region HIP events, and the HBM-bound kernel figures (short run: no CPU baseline / fast mode).  A plain
+    run prints the headline keys with the extra measurements null, and --dump-outputs writes the same last-step arrays in
+    both: the extra measurements run after the timed steps and do not touch them."""
+    d = _bench_line("--full", "--no-cpu-baseline", "--no-fast-mode", "--dump-outputs", str(tmp_path / "full"))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -159,3 +165,18 @@ def test_bench_contract_on_gpu(hip_lib):
     assert r["direct_build"]["frac"] < r["frac"]
     h = d["hbm_bound_kernels"]
     assert h["md_gn_apply"]["bound"] == "hbm" and 0.3 < h["md_gn_apply"]["frac"] < 1.0
+
+    p = _bench_line("--dump-outputs", str(tmp_path / "plain"))
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert p[k] == d[k], k
+    assert p["steps"] == 2 and abs(p["value"] - 8 * 2 / (p["ms_per_step"] * 2e-3)) / p["value"] < 1e-3
+    for k in ("roofline", "train_step", "other_configs", "hbm_bound_kernels", "cpu_baseline", "bf16x3_mode"):
+        assert p[k] is None, k
+    total = 0
+    for name in ("x", "x_mean"):
+        a, b = np.load(tmp_path / "full" / f"{name}.npy"), np.load(tmp_path / "plain" / f"{name}.npy")
+        assert a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all()
+        e = float(np.linalg.norm(a.astype(np.float64) - b) / np.linalg.norm(b.astype(np.float64)))
+        assert e < 1e-5, f"{name}: plain and --full runs differ by rel-L2 {e:.3e}"
+        total += os.path.getsize(tmp_path / "plain" / f"{name}.npy")
+    assert total <= 64 << 20

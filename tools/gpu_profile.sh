@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/prof
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 STEPS=${STEPS:-3}
-BASE_ARGS="--no-res128 --no-train-step --no-fast-mode"   # the sampling step only (configs[1])
+BASE_ARGS="--full --no-res128 --no-train-step --no-fast-mode"   # the sampling step (configs[1]) with its kernel-event pass
 run() {  # name, rocprof args...
   local name=$1; shift
   rm -rf /tmp/rp_$name
