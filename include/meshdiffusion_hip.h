@@ -41,7 +41,7 @@ extern "C" {
 #define MD_ERR_UNSUPPORTED (-2)
 #define MD_ERR_NO_DEVICE (-3)
 
-#define MD_ABI_VERSION 15
+#define MD_ABI_VERSION 16
 
 /* ---- tile configurations of md_gemm_conv (compile-time instantiations) ---- */
 enum {
@@ -469,6 +469,39 @@ int md_ancestral_step(const float* x, const float* eps, const float* z, const fl
 int md_ddim_step(const double* x, const float* eps, const float* mask, const double* coef, const float* partial,
                  const float* pmask, int32_t ch, double* x_out, double* x0_out, float* x_f32, int32_t batch,
                  int32_t C, int64_t P, void* stream);
+/*
+ * Predictor-corrector sampling (ABI 16; sampling.py:185-210 predictors, :259-321 correctors), all NCDHW fp32 [B][C][P],
+ * mask [P] binary or NULL, per-sample coefficient rows built by the host with the reference's float32 expressions.
+ * Bit-identical to the reference's elementwise torch chains for the same eps / z / coefficient rows.
+ *
+ * Langevin / ALD corrector step, two launches on one stream, deterministic (no atomics):
+ *   md_langevin_norms: slabs[b][s] = {sum eps^2, sum z^2} (fp64) over workgroup s's share of sample b;
+ *                      slabs is double[batch][MD_LANGEVIN_SLABS][2]
+ *   md_langevin_step : step_b = (snr * mean_b' sqrt(sum z^2) / mean_b' (sqrt(sum eps^2)/sigma_b'))^2 * 2 * alpha_b
+ *                      (mode MD_CORRECTOR_LANGEVIN, reduces the slabs of the whole batch in its prologue) or
+ *                      step_b = coef[b][2] (mode MD_CORRECTOR_ALD, slabs may be NULL); then with score = -eps/sigma_b
+ *                      x_mean = x + step_b*score ; x = x_mean + sqrt(step_b*2)*z ; both *= mask ; step_out[b] = step_b
+ *   coef[b][3] = {sigma = sqrt(1-abar_t), alpha = 1-beta_t, (snr*std(t))^2*2*alpha}
+ *
+ * SDE predictor step, one launch; coef[b][5] = {sigma, c1, c2, c3, c4}, score = -eps/sigma:
+ *   MD_SDE_REVERSE_DIFFUSION: x_mean = x - ((c1*x - x) - (c2*score)*c3) ; x = x_mean + c4*z
+ *                             c1 = sqrt(alpha), c2 = sqrt(beta)^2, c3 = 1 (0.5 probability flow), c4 = sqrt(beta) (0 p.f.)
+ *   MD_SDE_EULER_MARUYAMA   : x_mean = x + (c1*x - c2*score)*c3 ; x = x_mean + c4*z
+ *                             c1 = -0.5*beta(t), c2 = sqrt(beta(t))^2, c3 = -1/N, c4 = sqrt(beta(t))*sqrt(1/N)
+ *   x, x_mean *= mask
+ * P % 4 == 0 for all three.
+ */
+#define MD_LANGEVIN_SLABS 64
+#define MD_CORRECTOR_LANGEVIN 0
+#define MD_CORRECTOR_ALD 1
+#define MD_SDE_REVERSE_DIFFUSION 0
+#define MD_SDE_EULER_MARUYAMA 1
+int md_langevin_norms(const float* eps, const float* z, int32_t batch, int32_t C, int64_t P, double* slabs, void* stream);
+int md_langevin_step(const float* x, const float* eps, const float* z, const float* mask, const float* coef,
+                     const double* slabs, float snr, int32_t mode, float* x_out, float* x_mean_out, float* step_out,
+                     int32_t batch, int32_t C, int64_t P, void* stream);
+int md_sde_step(const float* x, const float* eps, const float* z, const float* mask, const float* coef, int32_t kind,
+                float* x_out, float* x_mean_out, int32_t batch, int32_t C, int64_t P, void* stream);
 /*
  * Inpainting blend of one channel (sampling.py:443-467):
  *   v = (x*(1-m) + src*m) * gm     applied in place to channel `ch` of x [B][C][P];

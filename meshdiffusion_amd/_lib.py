@@ -19,6 +19,9 @@ OUT_F32B, OUT_S16B, OUT_NCDHW = 0, 1, 2
 PREC_BF16X3, PREC_FP16X2 = 0, 1
 A_PACKED, A_S16B = 0, 1
 B_S16B, B_F32B_GN = 0, 1
+CORRECTOR_LANGEVIN, CORRECTOR_ALD = 0, 1                 # MD_CORRECTOR_*
+SDE_REVERSE_DIFFUSION, SDE_EULER_MARUYAMA = 0, 1         # MD_SDE_*
+LANGEVIN_SLABS = 64                                      # MD_LANGEVIN_SLABS
 
 # (NT, KC) of each cfg -- must match csrc/gemm_conv.hip; checked against the library at load.
 CFG_NT_KC = {
@@ -53,7 +56,7 @@ class MdPackJob(C.Structure):
 
 
 PACK_WPK, PACK_WINO, PACK_WINO_F6 = 0, 1, 2
-ABI_VERSION = 15     # MD_ABI_VERSION of include/meshdiffusion_hip.h this host code was written against
+ABI_VERSION = 16     # MD_ABI_VERSION of include/meshdiffusion_hip.h this host code was written against
 _P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
 
 # name -> (restype, argtypes); exactly the entry points of include/meshdiffusion_hip.h
@@ -111,6 +114,9 @@ SIGNATURES = {
     "md_softmax_keys": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),
     "md_ancestral_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I64, _P]),
     "md_ddim_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _I64, _P]),
+    "md_langevin_norms": (C.c_int, [_P, _P, _I32, _I32, _I64, _P, _P]),
+    "md_langevin_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _I32, _P, _P, _P, _I32, _I32, _I64, _P]),
+    "md_sde_step": (C.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P, _I32, _I32, _I64, _P]),
     "md_inpaint_blend": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I64, _I64, _P]),
     "md_inpaint_renoise": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I64, _P]),
     "md_ddpm_perturb": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I64, _P]),

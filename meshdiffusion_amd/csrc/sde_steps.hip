@@ -1,0 +1,203 @@
+// Predictor-corrector sampling updates other than the ancestral one (reference lib/diffusion/sampling.py:185-210
+// predictors, :259-321 correctors, sde_lib.py:83-111 reverse SDE, :198-232 VPSDE).  All NCDHW fp32 [B][C][P]; the
+// per-sample coefficients come from the host, built once per sampler with the reference's float32 torch expressions.
+// Same operation order as the reference, no FMA contraction: with identical eps / z the updates are bit-identical to the
+// PyTorch elementwise chains.
+#include "md_common.h"
+
+#pragma clang fp contract(off)
+
+typedef __attribute__((ext_vector_type(2))) double f64x2;
+
+// ---- Langevin corrector, launch 1: per-workgroup partial sums of eps^2 and z^2 ---------------------------------
+// grid (MD_LANGEVIN_SLABS, B): workgroup (s, b) writes slabs[b][s] = {sum eps^2, sum z^2} over its strided share of
+// sample b.  Fixed grid and fixed per-thread order: the partial sums do not depend on scheduling.
+__global__ __launch_bounds__(256) void md_langevin_norms_kernel(const float* __restrict__ eps, const float* __restrict__ z,
+                                                                double* __restrict__ slabs, int64_t CP) {
+  const int b = blockIdx.y;
+  const int64_t base = (int64_t)b * CP;
+  double ae = 0.0, az = 0.0;
+#pragma unroll 4
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
+    const f32x4 ev = *(const f32x4*)(eps + base + i);
+    const f32x4 zv = *(const f32x4*)(z + base + i);
+    ae += (double)(ev[0] * ev[0] + ev[1] * ev[1]) + (double)(ev[2] * ev[2] + ev[3] * ev[3]);
+    az += (double)(zv[0] * zv[0] + zv[1] * zv[1]) + (double)(zv[2] * zv[2] + zv[3] * zv[3]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ae += __shfl_xor(ae, o, 64);
+    az += __shfl_xor(az, o, 64);
+  }
+  __shared__ double red[2][4];
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = ae;
+    red[1][threadIdx.x >> 6] = az;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    f64x2 v;
+    v[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    v[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    *(f64x2*)(slabs + ((int64_t)b * MD_LANGEVIN_SLABS + blockIdx.x) * 2) = v;
+  }
+}
+
+// ---- Langevin / ALD corrector, launch 2 ---------------------------------------------------------------------------
+// coef[b] = {sigma, alpha, ald_step}.  Prologue (wave 0, Langevin only): the slabs of every sample are reduced in a fixed
+// order (one slab per lane, xor butterfly: every lane ends with the same bits), giving
+//   grad_norm  = mean_b sqrt(sum eps_b^2) / sigma_b      (score = -eps/sigma, models/utils.py:191-198)
+//   noise_norm = mean_b sqrt(sum z_b^2)
+//   step_b     = (snr * noise_norm / grad_norm)^2 * 2 * alpha_b                                     (sampling.py:282-284)
+// ALD takes step_b = coef[b][2] = (snr*std_b)^2 * 2 * alpha_b (sampling.py:312-315).  Then
+//   x_mean = x + step_b*score ; x = x_mean + sqrt(step_b*2)*z ; both times the grid mask        (sampling.py:285-286, 450)
+static_assert(MD_LANGEVIN_SLABS == 64, "the prologue reduces one slab per lane of a wave64");
+
+__global__ __launch_bounds__(256) void md_langevin_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                               const float* __restrict__ z, const float* __restrict__ mask,
+                                                               const float* __restrict__ coef, const double* __restrict__ slabs,
+                                                               float snr, int mode, float* __restrict__ x_out,
+                                                               float* __restrict__ xm_out, float* __restrict__ step_out,
+                                                               int B, int64_t CP, int64_t P) {
+  const int b = blockIdx.y;
+  __shared__ float s_step;
+  if (threadIdx.x < 64) {
+    float step;
+    if (mode == MD_CORRECTOR_LANGEVIN) {
+      const int lane = threadIdx.x;
+      double gsum = 0.0, nsum = 0.0;
+      for (int bb = 0; bb < B; ++bb) {
+        const f64x2 v = *(const f64x2*)(slabs + ((int64_t)bb * MD_LANGEVIN_SLABS + lane) * 2);
+        double se = v[0], sz = v[1];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          se += __shfl_xor(se, o, 64);
+          sz += __shfl_xor(sz, o, 64);
+        }
+        gsum += sqrt(se) / (double)coef[bb * 3 + 0];
+        nsum += sqrt(sz);
+      }
+      const float grad_norm = (float)(gsum / (double)B), noise_norm = (float)(nsum / (double)B);
+      const float r = (snr * noise_norm) / grad_norm;
+      step = ((r * r) * 2.f) * coef[b * 3 + 1];
+    } else {
+      step = coef[b * 3 + 2];
+    }
+    if (threadIdx.x == 0) {
+      s_step = step;
+      if (blockIdx.x == 0) step_out[b] = step;
+    }
+  }
+  __syncthreads();
+  const float step = s_step;
+  const float sigma = coef[b * 3 + 0];
+  const float sq = sqrtf(step * 2.f);
+  const int64_t base = (int64_t)b * CP;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
+    const f32x4 xv = *(const f32x4*)(x + base + i);
+    const f32x4 ev = *(const f32x4*)(eps + base + i);
+    const f32x4 zv = *(const f32x4*)(z + base + i);
+    f32x4 mv = {1.f, 1.f, 1.f, 1.f};
+    if (mask) mv = *(const f32x4*)(mask + (i % P));
+    f32x4 xo, xmo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float score = (-ev[e]) / sigma;
+      const float xm = xv[e] + step * score;
+      const float xn = xm + sq * zv[e];
+      xo[e] = xn * mv[e];
+      xmo[e] = xm * mv[e];
+    }
+    *(f32x4*)(x_out + base + i) = xo;
+    *(f32x4*)(xm_out + base + i) = xmo;
+  }
+}
+
+// ---- SDE predictors, one launch ------------------------------------------------------------------------------------
+// coef[b] = {sigma, c1, c2, c3, c4}; score = -eps/sigma.
+//   MD_SDE_REVERSE_DIFFUSION (sde_lib.py:106-111 with VPSDE.discretize :224-232, sampling.py:204-209):
+//     c1 = sqrt(alpha), c2 = G^2 = sqrt(beta)^2, c3 = h (1, or 0.5 under probability flow), c4 = G' (sqrt(beta), or 0)
+//     f = c1*x - x ; rev_f = f - (c2*score)*c3 ; x_mean = x - rev_f ; x = x_mean + c4*z
+//   MD_SDE_EULER_MARUYAMA (sde_lib.py:93-99 with VPSDE.sde :198-202, sampling.py:190-196):
+//     c1 = -0.5*beta_t, c2 = diffusion^2 = sqrt(beta_t)^2, c3 = dt = -1/N, c4 = diffusion*sqrt(-dt)
+//     drift = c1*x - c2*score ; x_mean = x + drift*c3 ; x = x_mean + c4*z
+// both results times the grid mask (sampling.py:452, 478).
+__global__ __launch_bounds__(256) void md_sde_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                          const float* __restrict__ z, const float* __restrict__ mask,
+                                                          const float* __restrict__ coef, int kind, float* __restrict__ x_out,
+                                                          float* __restrict__ xm_out, int64_t CP, int64_t P) {
+  const int b = blockIdx.y;
+  const float sigma = coef[b * 5 + 0], c1 = coef[b * 5 + 1], c2 = coef[b * 5 + 2], c3 = coef[b * 5 + 3], c4 = coef[b * 5 + 4];
+  const int64_t base = (int64_t)b * CP;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
+    const f32x4 xv = *(const f32x4*)(x + base + i);
+    const f32x4 ev = *(const f32x4*)(eps + base + i);
+    const f32x4 zv = *(const f32x4*)(z + base + i);
+    f32x4 mv = {1.f, 1.f, 1.f, 1.f};
+    if (mask) mv = *(const f32x4*)(mask + (i % P));
+    f32x4 xo, xmo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float score = (-ev[e]) / sigma;
+      float xm;
+      if (kind == MD_SDE_REVERSE_DIFFUSION) {
+        const float f = c1 * xv[e] - xv[e];
+        const float rev_f = f - (c2 * score) * c3;
+        xm = xv[e] - rev_f;
+      } else {
+        const float drift = c1 * xv[e] - c2 * score;
+        xm = xv[e] + drift * c3;
+      }
+      const float xn = xm + c4 * zv[e];
+      xo[e] = xn * mv[e];
+      xmo[e] = xm * mv[e];
+    }
+    *(f32x4*)(x_out + base + i) = xo;
+    *(f32x4*)(xm_out + base + i) = xmo;
+  }
+}
+
+// one workgroup per 1024 values, at most 1024 workgroups in all (B*S <= 1024 keeps the slab prologue's L2 reads small)
+static int stream_blocks(int64_t CP, int batch) {
+  int64_t blocks = (CP / 4 + 255) / 256;
+  const int64_t cap = batch >= 1024 ? 1 : 1024 / batch;
+  return (int)(blocks < cap ? blocks : cap);
+}
+
+extern "C" int md_langevin_norms(const float* eps, const float* z, int32_t batch, int32_t C, int64_t P, double* slabs,
+                                 void* stream) {
+  if (!eps || !z || !slabs || batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
+  MD_HIP_CLEAR_ERROR();
+  hipLaunchKernelGGL(md_langevin_norms_kernel, dim3(MD_LANGEVIN_SLABS, (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
+                     eps, z, slabs, (int64_t)C * P);
+  MD_HIP_CHECK_LAUNCH();
+  return MD_OK;
+}
+
+extern "C" int md_langevin_step(const float* x, const float* eps, const float* z, const float* mask, const float* coef,
+                                const double* slabs, float snr, int32_t mode, float* x_out, float* x_mean_out,
+                                float* step_out, int32_t batch, int32_t C, int64_t P, void* stream) {
+  if (!x || !eps || !z || !coef || !x_out || !x_mean_out || !step_out || batch <= 0 || C <= 0 || P <= 0 || (P % 4))
+    return MD_ERR_BAD_ARG;
+  if (mode != MD_CORRECTOR_LANGEVIN && mode != MD_CORRECTOR_ALD) return MD_ERR_BAD_ARG;
+  if (mode == MD_CORRECTOR_LANGEVIN && !slabs) return MD_ERR_BAD_ARG;
+  const int64_t CP = (int64_t)C * P;
+  MD_HIP_CLEAR_ERROR();
+  hipLaunchKernelGGL(md_langevin_step_kernel, dim3((unsigned)stream_blocks(CP, batch), (unsigned)batch), dim3(256), 0,
+                     (hipStream_t)stream, x, eps, z, mask, coef, slabs, snr, (int)mode, x_out, x_mean_out, step_out, (int)batch,
+                     CP, P);
+  MD_HIP_CHECK_LAUNCH();
+  return MD_OK;
+}
+
+extern "C" int md_sde_step(const float* x, const float* eps, const float* z, const float* mask, const float* coef,
+                           int32_t kind, float* x_out, float* x_mean_out, int32_t batch, int32_t C, int64_t P, void* stream) {
+  if (!x || !eps || !z || !coef || !x_out || !x_mean_out || batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
+  if (kind != MD_SDE_REVERSE_DIFFUSION && kind != MD_SDE_EULER_MARUYAMA) return MD_ERR_BAD_ARG;
+  const int64_t CP = (int64_t)C * P;
+  MD_HIP_CLEAR_ERROR();
+  hipLaunchKernelGGL(md_sde_step_kernel, dim3((unsigned)stream_blocks(CP, batch), (unsigned)batch), dim3(256), 0,
+                     (hipStream_t)stream, x, eps, z, mask, coef, (int)kind, x_out, x_mean_out, CP, P);
+  MD_HIP_CHECK_LAUNCH();
+  return MD_OK;
+}

@@ -1095,6 +1095,48 @@ def ancestral_step(x, eps, z, mask, coef):
     return x_out, xm_out
 
 
+def langevin_step(x, eps, z, mask, coef, snr, mode="langevin"):
+    """One Langevin ('langevin') or annealed Langevin ('ald') corrector step, grid mask applied.  x, eps, z: [B,C,D,H,W]
+    fp32; mask [P] or None; coef [B,3] = sigma, alpha, (snr*std)^2*2*alpha.  The Langevin step size couples the batch
+    through its mean norms: two launches (md_langevin_norms, md_langevin_step), no host synchronisation.
+    Returns (x, x_mean, step [B])."""
+    lib = _lib.load()
+    for name, t in (("x", x), ("eps", eps), ("z", z), ("coef", coef)):
+        _require_cuda(t, name)
+    x, eps, z, coef = x.contiguous(), eps.contiguous(), z.contiguous(), coef.contiguous()
+    B, Cc = x.shape[0], x.shape[1]
+    P = x[0, 0].numel()
+    assert coef.dtype == torch.float32 and coef.shape == (B, 3), coef.shape
+    kind = {"langevin": _lib.CORRECTOR_LANGEVIN, "ald": _lib.CORRECTOR_ALD}[mode]
+    x_out, xm_out = torch.empty_like(x), torch.empty_like(x)
+    step = torch.empty(B, dtype=torch.float32, device=x.device)
+    slabs = None
+    if kind == _lib.CORRECTOR_LANGEVIN:
+        slabs = torch.empty((B, _lib.LANGEVIN_SLABS, 2), dtype=torch.float64, device=x.device)
+        check(lib.md_langevin_norms(_ptr(eps), _ptr(z), B, Cc, P, _ptr(slabs), _stream()), "md_langevin_norms")
+    check(lib.md_langevin_step(_ptr(x), _ptr(eps), _ptr(z), _ptr(mask), _ptr(coef), _ptr(slabs), float(snr), kind,
+                               _ptr(x_out), _ptr(xm_out), _ptr(step), B, Cc, P, _stream()), "md_langevin_step")
+    return x_out, xm_out, step
+
+
+def sde_step(x, eps, z, mask, coef, kind):
+    """One reverse-diffusion ('reverse_diffusion') or Euler-Maruyama ('euler_maruyama') predictor step, grid mask
+    applied.  x, eps, z: [B,C,D,H,W] fp32; mask [P] or None; coef [B,5] (include/meshdiffusion_hip.h md_sde_step).
+    Returns (x, x_mean)."""
+    lib = _lib.load()
+    for name, t in (("x", x), ("eps", eps), ("z", z), ("coef", coef)):
+        _require_cuda(t, name)
+    x, eps, z, coef = x.contiguous(), eps.contiguous(), z.contiguous(), coef.contiguous()
+    B, Cc = x.shape[0], x.shape[1]
+    P = x[0, 0].numel()
+    assert coef.dtype == torch.float32 and coef.shape == (B, 5), coef.shape
+    k = {"reverse_diffusion": _lib.SDE_REVERSE_DIFFUSION, "euler_maruyama": _lib.SDE_EULER_MARUYAMA}[kind]
+    x_out, xm_out = torch.empty_like(x), torch.empty_like(x)
+    check(lib.md_sde_step(_ptr(x), _ptr(eps), _ptr(z), _ptr(mask), _ptr(coef), k, _ptr(x_out), _ptr(xm_out), B, Cc, P,
+                          _stream()), "md_sde_step")
+    return x_out, xm_out
+
+
 def ddim_step(x64, eps, mask, coef, partial=None, pmask=None, ch=0):
     """x64 [B,C,D,H,W] float64 state, eps float32 U-Net output, mask [P] or None, coef [B,4] float64 = a1, a2, r1, r2;
     partial / pmask: [P] float32 each or None.  Returns (x_new f64, x0_pred f64, x_new as f32)."""

@@ -1,15 +1,16 @@
-"""DDPM ancestral (predictor-only) sampler with grid-mask and partial-grid inpainting.
+"""Predictor-corrector and DDIM samplers with grid-mask and partial-grid inpainting.
 
-Host-side mirror of the reference's lib/diffusion/sampling.py: `get_sampling_fn` :83-117,
-`AncestralSamplingPredictor.vpsde_update_fn` :222-230, `NoneCorrector` :324-332,
+Host-side mirror of the reference's lib/diffusion/sampling.py: `get_sampling_fn` :83-117, predictors
+`EulerMaruyamaPredictor` :185-196, `ReverseDiffusionPredictor` :199-210, `AncestralSamplingPredictor` :213-237,
+correctors `LangevinCorrector` :259-286, `AnnealedLangevinDynamics` :289-321, `NoneCorrector` :324-332,
 `get_pc_sampler`/`pc_sampler` :357-487 (unconditional loop :471-481, inpainting :429-467), `DDIMPredictor` :249-257,
 `get_ddim_sampler`/`ddim_sampler` :500-570 (with sde_lib.py:113-140 `discretize_ddim`).
 
 Same call surface:
     fn = get_sampling_fn(config, sde, shape, inverse_scaler, eps, grid_mask=None)
     samples, nfe = fn(model, partial=None, partial_mask=None, partial_channel=0, freeze_iters=None)
-The per-step arithmetic (score scaling, x_mean, re-noising, masking) is ONE HIP kernel
-(md_ancestral_step); the noise still comes from torch's global generator (CPU generator for the
+The per-step arithmetic (score scaling, x_mean, re-noising, masking) is ONE HIP kernel per predictor step
+(md_ancestral_step, md_sde_step) and two per corrector step (md_langevin_norms + md_langevin_step); the noise still comes from torch's global generator (CPU generator for the
 prior, device generator per step) so that, on the same device and seed, the stream of random
 numbers is the reference's.  Two optional keyword extensions used by tests/bench:
     n_iters  -- run only the first n iterations of the N-step schedule
@@ -84,6 +85,20 @@ class AncestralSamplingPredictor(Predictor):
         return ops.ancestral_step(x, eps_hat, z, mask, coef)
 
 
+@register_predictor(name="reverse_diffusion")
+class ReverseDiffusionPredictor(Predictor):
+    """f = sqrt(alpha)*x - x, rev_f = f - G^2*score*h, x_mean = x - rev_f, x = x_mean + G'*z (VPSDE.discretize and the
+    reverse SDE, sde_lib.py:106-111; h = 0.5 and G' = 0 under probability flow).  One md_sde_step launch."""
+    kind = "reverse_diffusion"
+
+
+@register_predictor(name="euler_maruyama")
+class EulerMaruyamaPredictor(Predictor):
+    """drift = -0.5*beta(t)*x - diffusion^2*score, x_mean = x + drift*dt, x = x_mean + diffusion*sqrt(-dt)*z with
+    dt = -1/N (sampling.py:190-196, VPSDE.sde).  One md_sde_step launch."""
+    kind = "euler_maruyama"
+
+
 @register_predictor(name="ddim")
 class DDIMPredictor(Predictor):
     """Deterministic DDIM update between two (not necessarily adjacent) time levels; state in float64 like the
@@ -108,6 +123,19 @@ class DDIMPredictor(Predictor):
 class NonePredictor(Predictor):
     def update_fn(self, x, t, **_):
         return x, x
+
+
+@register_corrector(name="langevin")
+class LangevinCorrector(Corrector):
+    """step = (snr * mean|z| / mean|score|)^2 * 2 * alpha over the batch, x_mean = x + step*score,
+    x = x_mean + sqrt(2*step)*z (sampling.py:270-286).  md_langevin_norms + md_langevin_step per step."""
+    mode = "langevin"
+
+
+@register_corrector(name="ald")
+class AnnealedLangevinDynamics(Corrector):
+    """The same update with step = (snr*std(t))^2 * 2 * alpha, std of VPSDE.marginal_prob (sampling.py:300-321)."""
+    mode = "ald"
 
 
 @register_corrector(name="none")
@@ -226,17 +254,69 @@ class GraphedStepper:
         return self.out[0].clone(), self.out[1].clone()
 
 
-def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_steps=1, probability_flow=False,
-                   continuous=False, denoise=True, eps=1e-3, device="cuda", grid_mask=None, return_traj=False):
-    if predictor is not AncestralSamplingPredictor or corrector is not NoneCorrector:
-        raise NotImplementedError("the HIP path implements the configured sampler only: predictor "
-                                  "'ancestral_sampling' + corrector 'none' (configs/res64.py:24-26)")
-    if continuous or probability_flow:
-        raise NotImplementedError("continuous / probability-flow sampling is not part of this path")
+def _pc_tables(sde, timesteps, B, predictor, corrector, snr, probability_flow):
+    """Per-iteration coefficient rows of md_sde_step ([N,B,5]) and md_langevin_step ([N,B,3]), built once with the
+    reference's float32 expressions (sampling.py:190-196, :270-321; sde_lib.py:93-111, :198-232; score scaling
+    models/utils.py:191-198) and pre-expanded over the batch: no host-side tensor math inside the loop."""
+    dev = timesteps.device
+    k = (timesteps * (sde.N - 1) / sde.T).long()
+    sigma = sde.sqrt_1m_alphas_cumprod.to(dev)[k]
+    pcoef = ccoef = None
+    if predictor is ReverseDiffusionPredictor:
+        beta, alpha = sde.discrete_betas.to(dev)[k], sde.alphas.to(dev)[k]
+        G = torch.sqrt(beta)
+        rows = [sigma, torch.sqrt(alpha), G ** 2, torch.full_like(G, 0.5 if probability_flow else 1.0),
+                torch.zeros_like(G) if probability_flow else G]
+        pcoef = torch.stack(rows, dim=1)
+    elif predictor is EulerMaruyamaPredictor:
+        beta_t = sde.beta_0 + timesteps * (sde.beta_1 - sde.beta_0)
+        diffusion = torch.sqrt(beta_t)
+        dt = -1.0 / sde.N
+        rows = [sigma, -0.5 * beta_t, diffusion ** 2, torch.full_like(beta_t, dt), diffusion * np.sqrt(-dt)]
+        pcoef = torch.stack(rows, dim=1)
+    if corrector is not NoneCorrector:
+        alpha = sde.alphas.to(dev)[k]
+        _, std = sde.marginal_prob(torch.zeros((len(timesteps), 1, 1, 1, 1), device=dev), timesteps)
+        ccoef = torch.stack([sigma, alpha, (snr * std) ** 2 * 2 * alpha], dim=1)
+    expand = (lambda t: None if t is None else t[:, None, :].expand(t.shape[0], B, t.shape[1]).contiguous())
+    return expand(pcoef), expand(ccoef)
+
+
+def _check_pc_pair(sde, predictor, corrector, n_steps, probability_flow, continuous, return_traj):
+    """Refuse, before any GPU work, what the reference itself cannot run (or what this path does not implement)."""
+    supported = (AncestralSamplingPredictor, ReverseDiffusionPredictor, EulerMaruyamaPredictor, NonePredictor)
+    if predictor not in supported:
+        raise NotImplementedError(f"predictor {predictor.__name__} does not run in the PC loop (the reference calls "
+                                  "DDIMPredictor.update_fn without tprev); use config.sampling.method = 'ddim'")
+    if corrector not in (LangevinCorrector, AnnealedLangevinDynamics, NoneCorrector):
+        raise NotImplementedError(f"corrector {corrector.__name__} is not implemented")
+    if not isinstance(sde, sde_lib.VPSDE):
+        raise NotImplementedError(f"SDE class {sde.__class__.__name__} not yet supported.")
+    if continuous:
+        raise NotImplementedError("continuous=True: the reference's get_score_fn asserts it away (models/utils.py:183)")
+    if probability_flow and predictor is AncestralSamplingPredictor:
+        raise NotImplementedError("probability flow is not supported by ancestral sampling (reference sampling.py:219)")
+    if probability_flow and predictor is EulerMaruyamaPredictor:
+        raise NotImplementedError("euler_maruyama with probability_flow: the reference's reverse ODE returns the float "
+                                  "diffusion 0. and EulerMaruyamaPredictor indexes it (sde_lib.py:100, sampling.py:195)")
+    if corrector is not NoneCorrector and n_steps < 1:
+        raise NotImplementedError("a corrector needs n_steps_each >= 1 (the reference returns an unbound x_mean)")
     if return_traj:
         raise NotImplementedError("return_traj is only used by the reference's unreachable uncond_gen_interp")
+
+
+def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_steps=1, probability_flow=False,
+                   continuous=False, denoise=True, eps=1e-3, device="cuda", grid_mask=None, return_traj=False):
+    """Each iteration runs the reference's order (sampling.py:443-481): corrector x n_steps (one U-Net evaluation and
+    one draw each), mask, predictor, mask, then the inpainting blend / re-noise of the conditional branch.  The masks
+    are applied inside the kernels.  The Langevin step size is a mean over the batch this sampler sees (one shard
+    per rank under torchrun).  The ancestral predictor is AncestralStepper.step, unchanged."""
+    predictor = NonePredictor if predictor is None else predictor
+    corrector = NoneCorrector if corrector is None else corrector
+    _check_pc_pair(sde, predictor, corrector, n_steps, probability_flow, continuous, return_traj)
     B = shape[0]
     P = int(shape[2] * shape[3] * shape[4])
+    n_corr = 0 if corrector is NoneCorrector else int(n_steps)
 
     def pc_sampler(model, partial=None, partial_mask=None, partial_channel=0, freeze_iters=None,
                    n_iters=None, noise_fn=None):
@@ -245,6 +325,7 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
                 freeze_iters = sde.N + 10
             st = AncestralStepper(sde, shape, eps=eps, device=device, grid_mask=grid_mask)
             dev, timesteps, gm_flat = st.dev, st.timesteps, st.gm_flat
+            pcoef, ccoef = _pc_tables(sde, timesteps, B, predictor, corrector, snr, probability_flow)
             model_fn = mutils.get_model_fn(model, train=False)
             draw = torch.randn_like if noise_fn is None else noise_fn
             x = st.prior()
@@ -271,7 +352,19 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
                 total = min(total, int(n_iters))
             x_mean = x
             for i in range(total):
-                x, x_mean = st.step(model_fn, x, i, draw)
+                for j in range(n_corr):   # the reference masks once, after all n_steps corrector steps (:449-450)
+                    eps_hat = model_fn(x, st.labels[i])
+                    z = draw(x)
+                    x, x_mean, _ = ops.langevin_step(x, eps_hat, z, gm_flat if j == n_corr - 1 else None, ccoef[i], snr,
+                                                     corrector.mode)
+                if predictor is AncestralSamplingPredictor:
+                    x, x_mean = st.step(model_fn, x, i, draw)
+                elif predictor is not NonePredictor:
+                    eps_hat = model_fn(x, st.labels[i])
+                    z = draw(x)
+                    x, x_mean = ops.sde_step(x, eps_hat, z, gm_flat, pcoef[i], predictor.kind)
+                else:   # the reference's predictor returns (x, x) and masks them into two tensors
+                    x_mean = x.clone() if cond else x
                 if cond and i != sde.N - 1 and i < freeze_iters:
                     ops.inpaint_blend_(x, src, pm_flat, gm_flat, ch, src_bstride=src_bstride)
                     ops.inpaint_blend_(x_mean, src, pm_flat, gm_flat, ch, src_bstride=src_bstride)
