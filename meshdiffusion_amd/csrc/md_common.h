@@ -64,8 +64,11 @@ __device__ __forceinline__ void md_split_f16(float x, uint32_t& hi, uint32_t& lo
 // 8 values -> `hi`: 8 fp16; `q`: [q8(t0..7) | q8(lo0..7 * 2^11)] (an activation item; weights swap the halves, see
 // md_pack_wino_f8_item).
 __device__ __forceinline__ float md_clamp448(float x) { return __builtin_amdgcn_fmed3f(x, -448.f, 448.f); }
+// the hi plane saturates FINITE values at the fp16 range; inf and NaN pass (v_med3 alone maps NaN to -65504 and inf to 65504: a
+// non-finite operand must reach the MFMA as what it is, tests/test_gpu_nonfinite.py)
+__device__ __forceinline__ float md_sat_f16_finite(float x) { return __builtin_isfinite(x) ? __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f) : x; }
 __device__ __forceinline__ uint32_t md_f16f8_pair(float a, float b, float& la, float& lb) {      // fp16 pair (RNE) + the scaled remainders
-  const _Float16 ha = (_Float16)__builtin_amdgcn_fmed3f(a, -65504.f, 65504.f), hb = (_Float16)__builtin_amdgcn_fmed3f(b, -65504.f, 65504.f);
+  const _Float16 ha = (_Float16)md_sat_f16_finite(a), hb = (_Float16)md_sat_f16_finite(b);
   la = (a - (float)ha) * 2048.f;
   lb = (b - (float)hb) * 2048.f;
   return (uint32_t)__builtin_bit_cast(unsigned short, ha) | ((uint32_t)__builtin_bit_cast(unsigned short, hb) << 16);

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void md_adam_ema_kernel(float* __restrict__ p,
   if (sqnorm != nullptr && max_norm >= 0.f) {
     const float tn = (float)sqrt(*sqnorm);
     const float c = max_norm / (tn + 1e-6f);
-    clip = c < 1.f ? c : 1.f;
+    clip = c >= 1.f ? 1.f : c;      // torch.clamp(c, max=1): a NaN norm gives a NaN coefficient, every gradient turns NaN
   }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float gi = g[i] * clip;

@@ -105,18 +105,27 @@ __global__ __launch_bounds__(256) void md_wino_operand_ms_kernel(const float* __
 // measured form only: shift every exponent by the same u so that the largest equalised channel rms, max_c eq_c sqrt(a2m_c), lands at
 // 2^0 -- the operand's fp16 hi plane then sits mid-range whatever the tensor's absolute magnitude is (a 1e-5-magnitude residual
 // stream would otherwise be subnormal there); the packed weights absorb 2^-u in their own power-of-two pre-scale.  One workgroup.
+// The raw stream (gamma = null) has no GroupNorm bound on its values: a channel that was quiet in the calibration batch (rms 1e-8) and
+// carries ordinary magnitudes later would get a huge eq_c (2^13 at rms 1e-8) and leave the fp16 hi plane, or dominate its e2m3 block.
+// Its exponent is bounded so that a channel at the largest measured channel rms R lands at most 2^5 above the unit level the shift gives
+// the loudest one: eq_c R <= 2^5.  A 16-sigma peak doubled by the transform then stays at 2^10, far inside fp16, and the block's other
+// channels keep their cross-term codes.  Channels within 2^+-4 of each other (any ordinary stream) never meet the bound.
 __global__ __launch_bounds__(256) void md_wino_equaliser_level_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                       const float* __restrict__ a2m, int cin, float* __restrict__ eq) {
-  __shared__ float red[4];
-  float m = 0.f;
+  __shared__ float red[8];
+  float m = 0.f, r = 0.f;
   for (int c = threadIdx.x; c < cin; c += 256) {
-    const float v = eq[c] * sqrtf(fmaxf(a2m[c], 0.f));
+    const float a = sqrtf(fmaxf(a2m[c], 0.f));
+    const float v = eq[c] * a;
     m = (v > m && v < 1e30f) ? v : m;
+    r = (a > r && a < 1e30f) ? a : r;
   }
   m = md_wave_max(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  r = md_wave_max(r);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = m; red[4 + (threadIdx.x >> 6)] = r; }
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  r = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
   if (!(m > 0.f)) return;
   const int u = -(int)rintf(log2f(m));
   for (int c = threadIdx.x; c < cin; c += 256) {
@@ -124,6 +133,8 @@ __global__ __launch_bounds__(256) void md_wino_equaliser_level_kernel(const floa
     if (gamma != nullptr) {
       const float top = 8.0f * fabsf(gamma[c]) + fabsf(beta[c]);
       if (top > 0.f && top < 1e30f) e = min(e, (int)floorf(14.f - log2f(top)));
+    } else if (r > 0.f) {
+      e = min(e, (int)floorf(5.f - log2f(r)));
     }
     eq[c] = ldexpf(1.0f, max(-60, min(60, e)));
   }

@@ -316,8 +316,9 @@ __global__ __launch_bounds__(256) void md_wino_prep2_f6_kernel(const float* __re
       for (int e = 0; e < 16; ++e) {
         t[e] = f == 0 ? d[0][e] - d[2][e] : f == 1 ? d[1][e] + d[2][e] : f == 2 ? d[2][e] - d[1][e] : d[1][e] - d[3][e];
         // the lift (dynamic: max |dy| lands in [16, 32); or the caller's constant), saturated at the fp16 plane's range so that a
-        // constant lift can clip an element but never turn the whole data gradient into inf / NaN
-        if constexpr (DUAL) t[e] = fminf(fmaxf(t[e] * tscale, -60000.f), 60000.f);
+        // constant lift can clip an element but never turn the whole data gradient into inf / NaN; only FINITE values saturate:
+        // a NaN / inf of dy (a diverged step) stays one, as it does in torch autograd
+        if constexpr (DUAL) t[e] = __builtin_isfinite(t[e]) ? fminf(fmaxf(t[e] * tscale, -60000.f), 60000.f) : t[e];
       }
       uint4 h0, h1, r0, r1;
       md_split_f16f6(t, false, 0, h0, h1, r0, r1);

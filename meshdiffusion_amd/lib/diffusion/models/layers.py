@@ -194,7 +194,8 @@ def run_conv3(pw, act_s16, B, S_out, *, bias=None, bias_bstride=0, residual=None
             rec[3] += 1
         f8 = (not b_f32.get("wino_only")) and ops.wino_f8_ok(
             S_out, drop=b_f32.get("drop"), keep=bool(b_f32.get("keep")), parts=b_f32["parts"],
-            normalised=b_f32.get("ac") is not None or (hasattr(wino, "measured") and wino.measured() is not None))
+            normalised=b_f32.get("ac") is not None
+            or (ops.WINO_EQ and hasattr(wino, "measured") and wino.measured() is not None))     # measured: only with its equaliser
         if f8 and owner is not None and wino.site in getattr(owner, "md_bf16x3_sites", ()):
             f8 = False                   # this conv was taken off the reduced-precision path (layer.md_bf16x3_sites: tools/audit_precision.py)
         t = ops.wino_prep(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), ups, B, S_out, drop=b_f32.get("drop"),

@@ -620,6 +620,8 @@ def _equaliser_reference(gamma, beta, w, a2m=None):
     if a2m is not None:      # the measured form's common level shift: the largest equalised channel rms at 2^0
         u = -torch.round(torch.log2((torch.exp2(e) * a2.sqrt()).max()))
         e = torch.minimum(e + u, hi)
+        if gamma is None:    # raw stream: a channel at the largest measured rms R lands at most 2^5 above unit (eq_c R <= 2^5)
+            e = torch.minimum(e, torch.floor(5.0 - torch.log2(a2.sqrt().max())))
     return torch.exp2(e).float(), ex
 
 
