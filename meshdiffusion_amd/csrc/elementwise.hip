@@ -324,7 +324,9 @@ __global__ __launch_bounds__(256) void md_softmax_keys_kernel(const float* __res
   const int q = blockIdx.x * 32 + ql;
   const int nkb = nk / 8;
   const f32x4* sp = (const f32x4*)(s + (int64_t)b * nk * nq);
-  float m = -INFINITY, l = 0.f;
+  // A finite start value: with n_keys < 32 some key slices are empty, and two empty partners at -inf merged below as
+  // 0 * exp(-inf - -inf) = NaN, which the sum over the four slices then spread to the whole column.
+  float m = -3.0e38f, l = 0.f;
   for (int kb = ks; kb < nkb; kb += 4) {
     const f32x4 v = sp[((int64_t)kb * nq + q) * 2 + half];
     const float vm = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
