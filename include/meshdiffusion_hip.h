@@ -119,10 +119,12 @@ typedef struct MdGemmConvArgs {
   double* stats;         /* optional [B][rows_alloc][2]: per-(sample, output channel) sum and sum of   */
                          /* squares of the values written to `out`, ADDED with fp64 atomics (caller    */
                          /* zeroes) -- the GroupNorm statistics of the consumer without another pass   */
-                         /* over the tensor.  MD_CFG_C3_128_FAST, F32B output, no split-K; else error  */
+                         /* over the tensor.  F32B output; written by MD_CFG_C3_128_FAST's epilogue or,  */
+                         /* with ksplit > 1, by the split-K finish kernel of any configuration; else error */
   int32_t stagger;       /* MD_CFG_C3_128_FAST: shader cycles over which the start of the first workgroup */
                          /* of each CU is spread (0 = off); measured neutral on MI355X, kept as A/B switch */
-  int32_t b_mode;        /* MD_B_S16B (0) or MD_B_F32B_GN (MD_CFG_C3_128_FAST, MD_PREC_BF16X3 only): `b` (and  */
+  int32_t b_mode;        /* MD_B_S16B (0) or MD_B_F32B_GN (MD_PREC_BF16X3; MD_CFG_C3_128_FAST, MD_CFG_C3_LOW without  */
+                         /* `ups`, and split-only -- b_ac NULL -- MD_CFG_G1_128 / MD_CFG_G1_128_N128): `b` (and  */
                          /* `b2`) are fp32 F32B tensors [B][C/8][P_in][8]; the kernel applies                 */
                          /* y = x*ac[c][0] + ac[c][1] (GroupNorm affine), SiLU (b_silu) and the bf16 hi/lo    */
                          /* split while it stages the halo tile in LDS -- nn.GroupNorm + nn.SiLU              */

@@ -349,9 +349,10 @@ def gemm_conv(*, cfg, a, b, out, batch, rows, rows_alloc, kdim, dims, bias=None,
               b_bstride=None, out_mode=OUT_F32B, ksplit=1, prec=PREC_BF16X3, stats=None, stagger=None,
               b_f32=None):
     """stats: optional zeroed float64 [batch][rows_alloc][2] receiving per-(sample, channel) sum / sum of squares of
-    the output (CFG_C3_128_FAST without split-K only).
+    the output (F32B output: CFG_C3_128_FAST's epilogue, or with ksplit > 1 any configuration's split-K finish kernel).
     b_f32: dict(parts=[(F32B tensor, C), ...] (1 or 2), ac=[B][K][2] or None, silu=bool): the B operand is read as fp32
-    and GroupNorm affine + SiLU + the bf16 split happen in the kernel's halo loader (MD_B_F32B_GN; `b` is ignored)."""
+    and GroupNorm affine + SiLU + the bf16 split happen in the kernel's halo loader (MD_B_F32B_GN; `b` is ignored):
+    CFG_C3_128_FAST (also with `ups`), CFG_C3_LOW, and split-only (ac = None) the 1x1x1 configurations CFG_G1_128 / _N128."""
     lib = _lib.load()
     D, H, W = dims
     args = MdGemmConvArgs()
@@ -653,19 +654,21 @@ def wino_f8_ok(S, drop=None, keep=False, parts=None, normalised=True):
     return WINO_F8
 
 
-def wino_prep(parts, ac, silu, ups, B, S, drop=None, keep=False, dual=False, sums=None, f8=False, eq=None, tscale=1.0, amax=None):
+def wino_prep(parts, ac, silu, ups, B, S, drop=None, keep=False, dual=False, sums=None, f8=False, eq=None, tscale=1.0, amax=None, dims=None):
     """fp32 F32B parts (+ folded GroupNorm affine, SiLU, nearest-x2 upsampling) -> transformed split operand T.
     drop = (p, seed): training dropout after SiLU, the mask gn_apply(drop=...) produces for the same pair.
     keep: T goes to its own tensor instead of the shared scratch buffer (training forward: the Winograd weight gradient of the
     backward reads it again).  dual: returns (T, U) -- U = the dY operand of md_wgrad_wino (md_wino_prep_dual); sums (with dual):
     zeroed float [B, C] receiving the per-(sample, channel) sums of the tensor in the same pass (bias gradients).
-    f8: False | "f8" (True) | "f6": the operand format of md_conv3_wino_f8 / _f6; eq (with f8): the layer's equaliser (wino_equaliser)."""
+    f8: False | "f8" (True) | "f6": the operand format of md_conv3_wino_f8 / _f6; eq (with f8): the layer's equaliser (wino_equaliser).
+    dims: the OUTPUT grid (D, H, W) where it is not the cube S^3 (`S` is ignored then)."""
     lib = _lib.load()
+    D, H, W = dims if dims is not None else (S, S, S)
     cin = sum(c for _, c in parts)
     assert 1 <= len(parts) <= 2
     assert eq is None or (f8 and eq.numel() == cin and eq.dtype == torch.float32 and eq.is_cuda), "eq belongs to the f16f8 / f16f6 operand"
     assert ac is not None or not silu, "SiLU is applied together with the folded GroupNorm affine (pass `ac`)"
-    nbytes = lib.md_wino_operand_bytes(B, cin, S, S, S)
+    nbytes = lib.md_wino_operand_bytes(B, cin, D, H, W)
     if nbytes <= 0:
         raise _lib.MeshDiffusionHipError("md_wino_operand_bytes: unsupported operand shape")
     dev = parts[0][0].device
@@ -673,30 +676,30 @@ def wino_prep(parts, ac, silu, ups, B, S, drop=None, keep=False, dual=False, sum
     x2, c2 = (parts[1][0], parts[1][1]) if len(parts) == 2 else (None, 0)
     ev = _prof_begin()
     args = (_ptr(parts[0][0]), _ptr(x2), parts[0][1], c2, _ptr(ac), 1 if silu else 0, 1 if ups else 0)
-    tail = (B, S, S, S, drop[0] if drop else 0.0, drop[1] if drop else 0, _stream())
+    tail = (B, D, H, W, drop[0] if drop else 0.0, drop[1] if drop else 0, _stream())
     if f8 and dual:
         # training backward: T = the f16f6 operand of tscale x the output gradient (data-gradient conv), U = the bf16 operand of the
         # unscaled gradient (md_wgrad_wino), sums = its channel sums
-        assert f8 == "f6" and len(parts) == 1 and ac is None and not (ups or keep or drop or eq is not None) and 256 % S == 0
+        assert f8 == "f6" and len(parts) == 1 and ac is None and not (ups or keep or drop or eq is not None) and 256 % W == 0
         u = _wino_scratch(nbytes // 2, dev, slot="u")
-        check(lib.md_wino_prep_dual_f6(_ptr(parts[0][0]), cin, _ptr(t), _ptr(u), _ptr(sums), float(tscale), _ptr(amax), B, S, S, S, _stream()),
+        check(lib.md_wino_prep_dual_f6(_ptr(parts[0][0]), cin, _ptr(t), _ptr(u), _ptr(sums), float(tscale), _ptr(amax), B, D, H, W, _stream()),
               "md_wino_prep_dual_f6")
     elif f8:
         assert not (dual or keep or drop), "the f16f8 / f16f6 operand is an inference format"
         if f8 == "f6":
-            check(lib.md_wino_prep_f6(*args, _ptr(eq), _ptr(t), B, S, S, S, _stream()), "md_wino_prep_f6")
+            check(lib.md_wino_prep_f6(*args, _ptr(eq), _ptr(t), B, D, H, W, _stream()), "md_wino_prep_f6")
         else:
-            check(lib.md_wino_prep_f8(*args, _ptr(eq), _ptr(t), B, S, S, S, _stream()), "md_wino_prep_f8")
+            check(lib.md_wino_prep_f8(*args, _ptr(eq), _ptr(t), B, D, H, W, _stream()), "md_wino_prep_f8")
     elif dual:
-        if 256 % S:
+        if 256 % W:
             raise _lib.MeshDiffusionHipError("md_wino_prep_dual needs W | 256")
         u = _wino_scratch(nbytes // 2, dev, slot="u")
         check(lib.md_wino_prep_dual(*args, _ptr(t), _ptr(u), _ptr(sums), *tail), "md_wino_prep_dual")
     else:
-        fn = lib.md_wino_prep_v2 if (WINO_PREP_V2 and 256 % S == 0) else lib.md_wino_prep
+        fn = lib.md_wino_prep_v2 if (WINO_PREP_V2 and 256 % W == 0 and (D * H * W) % 256 == 0) else lib.md_wino_prep
         check(fn(*args, _ptr(t), *tail), "md_wino_prep")
-    _prof_end(ev, "wino_prep", 0.0, 4.0 * B * cin * (S ** 3 // (8 if ups else 1)) + (16.0 if dual else 8.0) * B * cin * S ** 3,   # fp32 in, 2 x bf16 x 2 out
-              f"{cin}@{S}x{S}x{S}" + ("/ups" if ups else "") + ("/dual" if dual else "") + (("/f6" if f8 == "f6" else "/f8") if f8 else ""))
+    _prof_end(ev, "wino_prep", 0.0, 4.0 * B * cin * (D * H * W // (8 if ups else 1)) + (16.0 if dual else 8.0) * B * cin * D * H * W,   # fp32 in, 2 x bf16 x 2 out
+              f"{cin}@{D}x{H}x{W}" + ("/ups" if ups else "") + ("/dual" if dual else "") + (("/f6" if f8 == "f6" else "/f8") if f8 else ""))
     # what this operand is, for conv3_wino's pairing check (an f8 T under f6 weights, or a T equalised with another layer's vector,
     # would be silently wrong: the kernel cannot tell)
     t._md_fmt = ("f6" if f8 == "f6" else "f8") if f8 else False
@@ -733,9 +736,11 @@ WINO_VARIANT = int(os.environ.get("MD_WINO_VARIANT", "0"))
 
 
 def conv3_wino(ww, t, B, S, *, bias=None, bias_bstride=0, residual=None, res_bstride=0, stats=None, out=None, variant=None, out_scale=1.0,
-               amax=None):
+               amax=None, dims=None):
+    """dims: the output grid (D, H, W) where it is not the cube S^3 (`S` is ignored then)."""
     lib = _lib.load()
-    P = S ** 3
+    D, H, W = dims if dims is not None else (S, S, S)
+    P = D * H * W
     if out is None:
         out = f32b_empty(B, ww.rows, P, t.device)
     ev = _prof_begin()
@@ -748,19 +753,19 @@ def conv3_wino(ww, t, B, S, *, bias=None, bias_bstride=0, residual=None, res_bst
     if f8 and (out_scale != 1.0 or amax is not None):
         assert ww.fmt == "f6"
         check(lib.md_conv3_wino_f6_scaled(_ptr(t), _ptr(ww.data), _ptr(out), _ptr(bias), bias_bstride, _ptr(residual), res_bstride,
-                                          _ptr(stats), B, ww.kdim, ww.rows, S, S, S, float(out_scale), _ptr(amax), _stream()),
+                                          _ptr(stats), B, ww.kdim, ww.rows, D, H, W, float(out_scale), _ptr(amax), _stream()),
               "md_conv3_wino_f6_scaled")
     elif f8:
         fn = lib.md_conv3_wino_f6 if ww.fmt == "f6" else lib.md_conv3_wino_f8
         check(fn(_ptr(t), _ptr(ww.data), _ptr(out), _ptr(bias), bias_bstride, _ptr(residual), res_bstride,
-                 _ptr(stats), B, ww.kdim, ww.rows, S, S, S, _stream()), "md_conv3_wino_" + ww.fmt)
+                 _ptr(stats), B, ww.kdim, ww.rows, D, H, W, _stream()), "md_conv3_wino_" + ww.fmt)
     else:
         check(lib.md_conv3_wino(_ptr(t), _ptr(ww.data), _ptr(out), _ptr(bias), bias_bstride, _ptr(residual), res_bstride,
-                                _ptr(stats), B, ww.kdim, ww.rows, S, S, S, WINO_VARIANT if variant is None else variant, _stream()),
+                                _ptr(stats), B, ww.kdim, ww.rows, D, H, W, WINO_VARIANT if variant is None else variant, _stream()),
               "md_conv3_wino")
     _prof_end(ev, "wino", 2.0 * B * ww.rows * ww.kdim * 27 * P,
               4.0 * (2 * B * ww.kdim * P + ww.rows * ww.kdim * 36 + B * ww.rows * P * (2 if residual is not None else 1)),
-              f"{ww.kdim}->{ww.rows}@{S}x{S}x{S}" + ("/res" if residual is not None else "") + ("/stats" if stats is not None else "")
+              f"{ww.kdim}->{ww.rows}@{D}x{H}x{W}" + ("/res" if residual is not None else "") + ("/stats" if stats is not None else "")
               + (("/" + ww.fmt) if f8 else ""))
     return out
 
@@ -780,19 +785,20 @@ def conv3_s2_ok(rows, kdim, S_out, B=None):
     return ok and (B is None or B * (S_out ** 3 // 256) * ((rows + 127) // 128) >= S2_MIN_WGS)
 
 
-def conv3_s2(pw, x, B, S_out, *, bias=None, bias_bstride=0, stats=None, out=None):
+def conv3_s2(pw, x, B, S_out, *, bias=None, bias_bstride=0, stats=None, out=None, dims=None):
     """out F32B [B][rows][S_out^3] = stride-2 conv (pad (0, 1)) of the F32B tensor x [B][kdim/8][(2 S_out)^3][8] with the
-    CFG_S2_PACK tiles `pw` -- md_conv3_s2."""
+    CFG_S2_PACK tiles `pw` -- md_conv3_s2.  dims: the output grid (D, H, W) where it is not the cube S_out^3."""
     lib = _lib.load()
-    P = S_out ** 3
+    D, H, W = dims if dims is not None else (S_out, S_out, S_out)
+    P = D * H * W
     rows_alloc = ((pw.rows + 7) // 8) * 8
     if out is None:
         out = f32b_empty(B, rows_alloc, P, x.device)
     ev = _prof_begin()
     check(lib.md_conv3_s2(_ptr(x), _ptr(pw.data), _ptr(out), _ptr(bias), bias_bstride, _ptr(stats), B, pw.kdim, pw.rows,
-                          rows_alloc, S_out, S_out, S_out, _stream()), "md_conv3_s2")
+                          rows_alloc, D, H, W, _stream()), "md_conv3_s2")
     _prof_end(ev, "s2", 2.0 * B * pw.rows * pw.kdim * 27 * P, 4.0 * (B * pw.kdim * 8 * P + pw.rows * pw.kdim * 27 + B * pw.rows * P),
-              f"{pw.kdim}->{pw.rows}@{S_out}x{S_out}x{S_out}" + ("/stats" if stats is not None else ""))
+              f"{pw.kdim}->{pw.rows}@{D}x{H}x{W}" + ("/stats" if stats is not None else ""))
     return out
 
 
@@ -804,16 +810,18 @@ def conv3_stem_ok(rows, kdim, S):
     return CONV3_STEM and PRECISION == "bf16x3" and kdim == 16 and rows % 8 == 0 and S % 8 == 0
 
 
-def conv3_stem(pw, x16, B, S, *, bias=None, residual=None, stats=None):
-    """out F32B [B][rows][S^3] of the dx-folded stem on the x-folded S16B operand (md_ncdhw_to_s16b_xfold) -- md_conv3_stem."""
+def conv3_stem(pw, x16, B, S, *, bias=None, residual=None, stats=None, dims=None):
+    """out F32B [B][rows][S^3] of the dx-folded stem on the x-folded S16B operand (md_ncdhw_to_s16b_xfold) -- md_conv3_stem.
+    dims: the grid (D, H, W) where it is not the cube S^3."""
     lib = _lib.load()
-    P = S ** 3
+    D, H, W = dims if dims is not None else (S, S, S)
+    P = D * H * W
     out = f32b_empty(B, pw.rows, P, x16.device)
     ev = _prof_begin()
-    check(lib.md_conv3_stem(_ptr(x16), _ptr(pw.data), _ptr(out), _ptr(bias), _ptr(residual), _ptr(stats), B, pw.rows, S, S, S,
+    check(lib.md_conv3_stem(_ptr(x16), _ptr(pw.data), _ptr(out), _ptr(bias), _ptr(residual), _ptr(stats), B, pw.rows, D, H, W,
                             _stream()), "md_conv3_stem")
     _prof_end(ev, "stem", 2.0 * B * pw.rows * pw.kdim * 9 * P, 4.0 * (B * pw.kdim * P + pw.rows * pw.kdim * 9 + B * pw.rows * P),
-              f"{pw.kdim}->{pw.rows}@{S}x{S}x{S}" + ("/res" if residual is not None else "") + ("/stats" if stats is not None else ""))
+              f"{pw.kdim}->{pw.rows}@{D}x{H}x{W}" + ("/res" if residual is not None else "") + ("/stats" if stats is not None else ""))
     return out
 
 
@@ -826,16 +834,17 @@ def conv3_head_ok(rows, cin, S):
     return CONV3_HEAD and FUSE_GN_APPLY and PRECISION == "bf16x3" and rows <= 32 and cin % 32 == 0 and S % 8 == 0
 
 
-def conv3_head(pw, x, ac, B, S, rows_alloc):
+def conv3_head(pw, x, ac, B, S, rows_alloc, dims=None):
     """y F32B [B][rows_alloc][S^3] (rows = (co, kw)) of the dx-folded head on the un-normalised F32B tensor x with the folded
-    GroupNorm affine `ac`; SiLU inside -- md_conv3_head."""
+    GroupNorm affine `ac`; SiLU inside -- md_conv3_head.  dims: the grid (D, H, W) where it is not the cube S^3."""
     lib = _lib.load()
-    P = S ** 3
+    D, H, W = dims if dims is not None else (S, S, S)
+    P = D * H * W
     y = f32b_empty(B, rows_alloc, P, x.device)
     ev = _prof_begin()
-    check(lib.md_conv3_head(_ptr(x), _ptr(ac), _ptr(pw.data), _ptr(y), B, pw.kdim, rows_alloc, S, S, S, _stream()), "md_conv3_head")
+    check(lib.md_conv3_head(_ptr(x), _ptr(ac), _ptr(pw.data), _ptr(y), B, pw.kdim, rows_alloc, D, H, W, _stream()), "md_conv3_head")
     _prof_end(ev, "head", 2.0 * B * pw.rows * pw.kdim * 9 * P, 4.0 * (B * pw.kdim * P + pw.rows * pw.kdim * 9 + B * rows_alloc * P),
-              f"{pw.kdim}->{pw.rows}@{S}x{S}x{S}")
+              f"{pw.kdim}->{pw.rows}@{D}x{H}x{W}")
     return y
 
 
@@ -963,12 +972,14 @@ def gn_apply(parts, params, B, P, norm=True, silu=True, out=None, fp16=False, wa
 # ---------------------------------------------------------------------------------------------
 # small ops
 # ---------------------------------------------------------------------------------------------
-def fold_dx(y, bias, B, co, kx, rows_alloc, S, out=None):
-    """Second half of the dx-folded head conv: F32B [B][rows_alloc][S^3] with rows (co, dx) -> NCDHW [B, co, S, S, S]."""
+def fold_dx(y, bias, B, co, kx, rows_alloc, S, out=None, dims=None):
+    """Second half of the dx-folded head conv: F32B [B][rows_alloc][S^3] with rows (co, dx) -> NCDHW [B, co, S, S, S].
+    dims: the grid (D, H, W) where it is not the cube S^3."""
     lib = _lib.load()
+    D, H, W = dims if dims is not None else (S, S, S)
     if out is None:
-        out = torch.empty((B, co, S, S, S), dtype=torch.float32, device=y.device)
-    check(lib.md_fold_dx(_ptr(y), _ptr(bias), _ptr(out), B, co, kx, rows_alloc, S, S, S, _stream()), "md_fold_dx")
+        out = torch.empty((B, co, D, H, W), dtype=torch.float32, device=y.device)
+    check(lib.md_fold_dx(_ptr(y), _ptr(bias), _ptr(out), B, co, kx, rows_alloc, D, H, W, _stream()), "md_fold_dx")
     return out
 
 
@@ -1049,10 +1060,11 @@ def nin_stream_ok(parts, rows, P):
             and P % 256 == 0 and P >= 32768)
 
 
-def nin_f32(parts, pw, bias, B, P):
+def nin_f32(parts, pw, bias, B, P, out=None):
     """out F32B [B][128][P] = NIN(cat(parts)) with `pw` = PackedWeight(W, "nin", CFG_G1_128 / _N128) -- md_nin_f32."""
     lib = _lib.load()
-    out = f32b_empty(B, 128, P, parts[0][0].device)
+    if out is None:
+        out = f32b_empty(B, 128, P, parts[0][0].device)
     x2, c2 = (parts[1][0], parts[1][1]) if len(parts) == 2 else (None, 0)
     check(lib.md_nin_f32(_ptr(parts[0][0]), _ptr(x2), parts[0][1], c2, _ptr(pw.data), _ptr(bias), _ptr(out), B, 128, P, 0,
                          _stream()), "md_nin_f32")
