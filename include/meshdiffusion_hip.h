@@ -654,6 +654,34 @@ int md_marching_tets(const float* pos, const float* sdf, const int32_t* tets,
                      int32_t n_verts, int32_t n_edges, int32_t n_tets, float* verts,
                      int64_t* faces, int64_t* face_tet, int32_t* counts, void* workspace,
                      int64_t workspace_bytes, void* stream);
+/*
+ * Backward of the vertex interpolation of md_marching_tets, and the SDF sign regulariser of dmtet.py:169-175 with its
+ * backward.  Purely additive: MD_ABI_VERSION stays 16, no existing entry point changes.
+ * Static incidence list of the edge table (CSR over grid vertices, see TetTables.incidence in meshdiffusion_amd/dmtet.py):
+ *   inc_ptr int32 [N+1], inc int32 [2E] = 2 * edge id + (0: the vertex is edges[e][0], 1: it is edges[e][1]),
+ *   ascending edge id inside a vertex.
+ * md_marching_tets_bwd: one launch for all meshes, one thread per (mesh, grid vertex), no atomics (bit-reproducible).
+ *   pos, sdf, edges as in md_marching_tets; vid int32 [M][E] = the first M*E words of that call's workspace (edge ->
+ *   vertex id or -1); counts int32 [M][4] of that call; grad_verts float32 [M][E][3] (rows >= counts[m][0] are never
+ *   read); dpos float32 [M][N][3], dsdf float32 [M][N]: every element is written (zero where no edge crosses).
+ * md_sdf_reg_loss: loss = mean bce_with_logits(s0, [s1 > 0]) + mean bce_with_logits(s1, [s0 > 0]) over the edges with
+ *   torch.sign(s0) != torch.sign(s1); sdf float32 [N], edges int32 [E][2] (8-byte aligned).  Two launches: fp64 partial
+ *   sums and integer counts of MD_SDF_REG_SLABS workgroups at fixed positions of `workspace`
+ *   (MD_SDF_REG_WORKSPACE_BYTES, 8-byte aligned), then a fixed-order reduction; loss float32 [1], count int32 [1] stay on
+ *   the device.  An empty mask gives loss = nan (the mean of an empty tensor), as the reference does.
+ * md_sdf_reg_loss_bwd: dsdf float32 [N] = grad_out[0] / count[0] * d(sum)/dsdf, every element written; exactly 0 at
+ *   vertices without a masked edge.  count and grad_out are device pointers.
+ */
+#define MD_SDF_REG_SLABS 64
+#define MD_SDF_REG_WORKSPACE_BYTES (MD_SDF_REG_SLABS * 24)
+int md_marching_tets_bwd(const float* pos, const float* sdf, const int32_t* edges, const int32_t* vid,
+                         const int32_t* counts, const float* grad_verts, const int32_t* inc_ptr, const int32_t* inc,
+                         int32_t n_meshes, int32_t n_verts, int32_t n_edges, float* dpos, float* dsdf, void* stream);
+int md_sdf_reg_loss(const float* sdf, const int32_t* edges, int32_t n_verts, int32_t n_edges, void* workspace,
+                    float* loss, int32_t* count, void* stream);
+int md_sdf_reg_loss_bwd(const float* sdf, const int32_t* edges, const int32_t* inc_ptr, const int32_t* inc,
+                        const int32_t* count, const float* grad_out, int32_t n_verts, int32_t n_edges, float* dsdf,
+                        void* stream);
 
 /*
  * Smooth vertex normals of an extracted mesh (nvdiffrec/lib/render/mesh.py:200-229 `auto_normals`, called from

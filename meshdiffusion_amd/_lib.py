@@ -139,7 +139,12 @@ SIGNATURES = {
     "md_marching_tets_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "md_vertex_normals": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
     "md_marching_tets": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P]),
+    "md_marching_tets_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "md_sdf_reg_loss": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "md_sdf_reg_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
 }
+SDF_REG_SLABS = 64                                  # MD_SDF_REG_SLABS
+SDF_REG_WORKSPACE_BYTES = SDF_REG_SLABS * 24        # MD_SDF_REG_WORKSPACE_BYTES
 
 # include/meshdiffusion_hip_experimental.h: MD_BUILD_ABLATIONS=1 builds only (same header)
 ABLATION_SIGNATURES = {"md_wgrad_set_debug": (None, [_I32])}

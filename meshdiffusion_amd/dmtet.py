@@ -7,8 +7,15 @@ data/get_tet_mask.py:9-37.
 
 Static preprocessing (once per tet grid, torch ops): the lexicographically sorted unique edge list
 of ALL tets and the [T,6] tet->edge-id table.  Per call: four launches (chunked over edges / tets) for M meshes.
+
+The vertex interpolation is differentiable as in the reference (only its topology part sits under no_grad there):
+when `pos` or `sdf` requires a gradient, `verts` carries a grad_fn whose backward is md_marching_tets_bwd, one gather
+launch over a static incidence list (no atomics: bit-reproducible).  `sdf_reg_loss` (dmtet.py:169-175) and the part of
+`DMTetGeometry` (dmtet.py:203-304) that needs no renderer complete the fitting loop fit -> dict -> training grid.
 """
 import ctypes as C
+import os
+import types
 
 import numpy as np
 import torch
@@ -33,6 +40,39 @@ class TetTables:
         self.edges = uniq.to(torch.int32).contiguous()
         self.tet_edges = inv.reshape(-1, 6).to(torch.int32).contiguous()
         self.tets64 = tets
+        self._incidence, self._all_edges = {}, None
+
+    def incidence(self, n_verts):
+        """(inc_ptr int32 [N+1], inc int32 [2E]) of the edge table, built at the first call that needs a gradient."""
+        if n_verts not in self._incidence:
+            self._incidence = {n_verts: build_incidence(self.edges, n_verts)}
+        return self._incidence[n_verts]
+
+    @property
+    def all_edges(self):
+        """The reference's `DMTetGeometry.all_edges` (int64 [E,2]); `sdf_reg_loss` recognises it and uses these tables."""
+        if self._all_edges is None:
+            self._all_edges = self.edges.long()
+            self._all_edges._md_tables = self
+        return self._all_edges
+
+
+def build_incidence(edges, n_verts):
+    """CSR over grid vertices of an edge table [E,2]: inc_ptr int32 [N+1], inc int32 [2E] with inc = 2 * edge id + (0 if the
+    vertex is the edge's first endpoint, 1 if its second), ascending edge id inside a vertex.  Every edge appears twice.
+    Checks once (on the host) that no edge names a vertex >= n_verts: the kernels index with these tables unchecked."""
+    e = edges.long()
+    E = e.shape[0]
+    if E == 0 or int(e.min()) < 0 or int(e.max()) >= n_verts:
+        raise ValueError(f"edge table names vertices outside [0, {n_verts})")
+    ids = torch.arange(E, dtype=torch.int64, device=e.device)
+    vert = torch.cat([e[:, 0], e[:, 1]])
+    code = torch.cat([2 * ids, 2 * ids + 1])
+    order = torch.argsort(vert * (2 * E) + code)          # unique keys: by vertex, then by edge id
+    inc = code[order].to(torch.int32).contiguous()
+    inc_ptr = torch.zeros(n_verts + 1, dtype=torch.int64, device=e.device)
+    inc_ptr[1:] = torch.cumsum(torch.bincount(vert, minlength=n_verts), 0)
+    return inc_ptr.to(torch.int32).contiguous(), inc
 
 
 class MeshCounts:
@@ -113,10 +153,58 @@ def release_workspace():
     _MT_WORKSPACE.clear()
 
 
+def _mt_launch(lib, pos, sdf, tables, ws, ws_bytes):
+    M, N = sdf.shape
+    E, T = tables.n_edges, tables.n_tets
+    dev = pos.device
+    verts = torch.empty((M, E, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((M, 2 * T, 4), dtype=torch.int64, device=dev)     # [..., :3] faces, then M * 2T face -> tet ids behind them
+    face_tet = faces.view(-1)[M * 2 * T * 3:].view(M, 2 * T)
+    counts = torch.empty((M, 4), dtype=torch.int32, device=dev)
+    _lib.check(lib.md_marching_tets(_ptr(pos), _ptr(sdf), _ptr(tables.tets), _ptr(tables.edges),
+                                    _ptr(tables.tet_edges), M, N, E, T, _ptr(verts), _ptr(faces),
+                                    _ptr(face_tet), _ptr(counts), _ptr(ws), ws_bytes, _stream()),
+               "md_marching_tets")
+    return verts, faces, counts
+
+
+class _MarchingTetsFn(torch.autograd.Function):
+    """md_marching_tets with md_marching_tets_bwd as the backward of `verts` w.r.t. (pos, sdf).  The call owns its workspace
+    (the per-stream one is overwritten by the next call) and keeps the edge -> vertex id table and the counts."""
+
+    @staticmethod
+    def forward(ctx, pos, sdf, tables):
+        lib = _lib.load()
+        M, N = sdf.shape
+        ws_bytes = lib.md_marching_tets_workspace_bytes(M, tables.n_edges, tables.n_tets)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
+        verts, faces, counts = _mt_launch(lib, pos, sdf, tables, ws, ws_bytes)
+        ctx.tables = tables
+        ctx.save_for_backward(pos, sdf, ws, counts)
+        ctx.mark_non_differentiable(faces, counts)
+        return verts, faces, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_verts, _gf, _gc):
+        lib = _lib.load()
+        pos, sdf, ws, counts = ctx.saved_tensors
+        tb = ctx.tables
+        M, N = sdf.shape
+        inc_ptr, inc = tb.incidence(N)
+        g = grad_verts.to(torch.float32).contiguous()
+        dpos, dsdf = torch.empty_like(pos), torch.empty_like(sdf)
+        _lib.check(lib.md_marching_tets_bwd(_ptr(pos), _ptr(sdf), _ptr(tb.edges), _ptr(ws), _ptr(counts), _ptr(g),
+                                            _ptr(inc_ptr), _ptr(inc), M, N, tb.n_edges, _ptr(dpos), _ptr(dsdf), _stream()),
+                   "md_marching_tets_bwd")
+        return (dpos if ctx.needs_input_grad[0] else None), (dsdf if ctx.needs_input_grad[1] else None), None
+
+
 def marching_tets_batch(pos, sdf, tables):
     """pos [M,N,3] f32, sdf [M,N] f32 on the GPU -> (MeshBatch, MeshCounts): meshes[m] = (verts [V,3], faces [F,3] int64,
     face_tet [F]), counts[m] = (V, F, 1-triangle tets, 2-triangle tets).  No host synchronisation inside the call: the counts
-    travel to a pinned buffer behind the kernels and are awaited at the first read."""
+    travel to a pinned buffer behind the kernels and are awaited at the first read.
+    When grad mode is on and `pos` or `sdf` requires a gradient, the vertices carry a grad_fn (first derivatives only)."""
     lib = _lib.load()
     if not pos.is_cuda:
         raise _lib.MeshDiffusionHipError("marching tets runs on the GPU only (no CPU fallback)")
@@ -124,18 +212,13 @@ def marching_tets_batch(pos, sdf, tables):
     sdf = sdf.to(torch.float32).contiguous()
     M, N = sdf.shape
     E, T = tables.n_edges, tables.n_tets
-    dev = pos.device
-    verts = torch.empty((M, E, 3), dtype=torch.float32, device=dev)
-    faces = torch.empty((M, 2 * T, 4), dtype=torch.int64, device=dev)     # [..., :3] faces, then M * 2T face -> tet ids behind them
+    if torch.is_grad_enabled() and (pos.requires_grad or sdf.requires_grad):
+        verts, faces, counts = _MarchingTetsFn.apply(pos, sdf, tables)
+    else:
+        ws_bytes = lib.md_marching_tets_workspace_bytes(M, E, T)
+        verts, faces, counts = _mt_launch(lib, pos, sdf, tables, _mt_workspace(ws_bytes, pos.device), ws_bytes)
     face_tet = faces.view(-1)[M * 2 * T * 3:].view(M, 2 * T)
     faces = faces.view(-1)[:M * 2 * T * 3].view(M, 2 * T, 3)
-    counts = torch.empty((M, 4), dtype=torch.int32, device=dev)
-    ws_bytes = lib.md_marching_tets_workspace_bytes(M, E, T)
-    ws = _mt_workspace(ws_bytes, dev)
-    _lib.check(lib.md_marching_tets(_ptr(pos), _ptr(sdf), _ptr(tables.tets), _ptr(tables.edges),
-                                    _ptr(tables.tet_edges), M, N, E, T, _ptr(verts), _ptr(faces),
-                                    _ptr(face_tet), _ptr(counts), _ptr(ws), ws_bytes, _stream()),
-               "md_marching_tets")
     cnt = MeshCounts(counts)
     return MeshBatch(verts, faces, face_tet, cnt), cnt
 
@@ -173,8 +256,10 @@ class DMTet:
     def __call__(self, pos_nx3, sdf_n, tet_fx4):
         with torch.no_grad():
             tb = self.tables_for(tet_fx4)
-            meshes, cnt = marching_tets_batch(pos_nx3[None], sdf_n[None], tb)
-            verts, faces, face_tet = meshes[0]
+        # as in the reference, only the topology is constant: verts is differentiable w.r.t. pos_nx3 and sdf_n
+        meshes, cnt = marching_tets_batch(pos_nx3[None], sdf_n[None], tb)
+        verts, faces, face_tet = meshes[0]
+        with torch.no_grad():
             uvs, uv_idx = _map_uv(face_tet, int(cnt[0, 2]), tb.n_tets, verts.device)
             tets_used = torch.unique(face_tet)
             valid_vert_idx = tb.tets64[tets_used].long().unique()
@@ -199,7 +284,9 @@ def grid_mask_from_tets(vertices, R):
 
 
 class GridMesher:
-    """`.npy` grids [M,4,R,R,R] -> meshes, the eval.py:400-431 path without the renderer."""
+    """`.npy` grids [M,4,R,R,R] -> meshes, the eval.py:400-431 path without the renderer.  With `grids` that require a gradient the
+    vertices are differentiable w.r.t. the deformation channels (zero outside [-1, 1], where the clip is flat); channel 0 goes
+    through `sign` and receives zero, as in eval.py:412-419."""
 
     def __init__(self, tet_vertices, tet_indices, R, mesh_scale=2.1, deform_scale=2.0, device="cuda"):
         self.R, self.deform_scale = R, deform_scale
@@ -224,6 +311,128 @@ class GridMesher:
 
 
 _ = C
+
+
+# ---- regulariser and geometry of the fitting loop -------------------------------------------------
+class _EdgeTables:
+    """Edge table + incidence list of an arbitrary [E,2] edge tensor handed to sdf_reg_loss."""
+
+    def __init__(self, edges):
+        self.edges = edges.to(torch.int32).contiguous()
+        self.n_edges = self.edges.shape[0]
+        self._incidence = {}
+
+    incidence = TetTables.incidence
+
+
+_EDGE_TABLES = {}
+
+
+def _edge_tables_for(all_edges):
+    if isinstance(all_edges, (TetTables, _EdgeTables)):
+        return all_edges
+    tb = getattr(all_edges, "_md_tables", None)
+    if tb is not None:
+        return tb
+    key = (all_edges.data_ptr(), tuple(all_edges.shape), str(all_edges.device), all_edges._version)
+    if key not in _EDGE_TABLES:
+        _EDGE_TABLES.clear()
+        _EDGE_TABLES[key] = _EdgeTables(all_edges.reshape(-1, 2))
+    return _EDGE_TABLES[key]
+
+
+class _SdfRegLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sdf, tables):
+        lib = _lib.load()
+        dev = sdf.device
+        ws = torch.empty(_lib.SDF_REG_WORKSPACE_BYTES // 8, dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.md_sdf_reg_loss(_ptr(sdf), _ptr(tables.edges), sdf.shape[0], tables.n_edges, _ptr(ws), _ptr(loss),
+                                       _ptr(count), _stream()), "md_sdf_reg_loss")
+        ctx.tables = tables
+        ctx.save_for_backward(sdf, count)
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        sdf, count = ctx.saved_tensors
+        tb = ctx.tables
+        inc_ptr, inc = tb.incidence(sdf.shape[0])
+        g = grad_out.to(torch.float32).reshape(1).contiguous()
+        dsdf = torch.empty_like(sdf)
+        _lib.check(lib.md_sdf_reg_loss_bwd(_ptr(sdf), _ptr(tb.edges), _ptr(inc_ptr), _ptr(inc), _ptr(count), _ptr(g),
+                                           sdf.shape[0], tb.n_edges, _ptr(dsdf), _stream()), "md_sdf_reg_loss_bwd")
+        return dsdf, None
+
+
+def sdf_reg_loss(sdf, all_edges):
+    """The reference's regulariser (dmtet.py:169-175), same signature: over the edges whose endpoints differ in `torch.sign`,
+    mean bce_with_logits(s0, [s1 > 0]) + mean bce_with_logits(s1, [s0 > 0]) -- md_sdf_reg_loss, differentiable w.r.t. sdf.
+    `all_edges`: `TetTables.all_edges` / `DMTetGeometry.all_edges` (their tables are reused), a `TetTables`, or any [E,2] edge
+    tensor on the GPU.  An empty mask returns nan with a zero gradient: the reference's mean of an empty tensor, kept."""
+    if not sdf.is_cuda:
+        raise _lib.MeshDiffusionHipError("sdf_reg_loss runs on the GPU only (no CPU fallback)")
+    tb = _edge_tables_for(all_edges)
+    if tb.edges.device != sdf.device:
+        raise _lib.MeshDiffusionHipError("sdf_reg_loss: the edge table and sdf are on different devices")
+    if getattr(tb, "_vertex_range", None) is None:                  # once per table: the kernel indexes sdf unchecked
+        tb._vertex_range = (int(tb.edges.min()), int(tb.edges.max()))
+    if tb._vertex_range[0] < 0 or tb._vertex_range[1] >= sdf.numel():
+        raise ValueError(f"sdf_reg_loss: the edge table names vertices outside [0, {sdf.numel()})")
+    return _SdfRegLossFn.apply(sdf.to(torch.float32).reshape(-1).contiguous(), tb)
+
+
+class DMTetGeometry(torch.nn.Module):
+    """The part of the reference's DMTetGeometry (dmtet.py:203-304) that needs no renderer: the `sdf` / `deform` parameters
+    of one tet grid with the reference's initialisation, the edge list of the regulariser, the deformed vertices and the
+    differentiable mesh.  The tet grid is read from `{root}/data/tets/{grid_res}_tets_cropped.npz` as in the reference, or
+    passed as `tets=(vertices, indices)`.  No EMA copies, no sign buffer, no material."""
+
+    def __init__(self, grid_res, scale, FLAGS=None, root="./", grid_to_tet=None, deform_scale=1.0, tets=None, device="cuda",
+                 **kwargs):
+        super().__init__()
+        self.FLAGS, self.grid_res, self.deform_scale, self.grid_to_tet = FLAGS, grid_res, deform_scale, grid_to_tet
+        self.marching_tets = DMTet()
+        self.tanh = False
+        if tets is None:
+            t = np.load(os.path.join(root, "data/tets/{}_tets_cropped.npz".format(grid_res)))
+            tets = (t["vertices"], t["indices"])
+        self.tet_vertices = torch.as_tensor(np.asarray(tets[0]), dtype=torch.float32)      # unscaled, for the grid index
+        self.verts = self.tet_vertices.to(device) * scale
+        self.indices = torch.as_tensor(np.asarray(tets[1]), dtype=torch.long).to(device)
+        self.generate_edges()
+        sdf = torch.rand_like(self.verts[:, 0]).clamp(-1.0, 1.0) - 0.1                       # dmtet.py:224
+        self.sdf = torch.nn.Parameter(sdf.clone().detach(), requires_grad=True)
+        self.deform = torch.nn.Parameter(torch.zeros_like(self.verts), requires_grad=True)
+
+    def generate_edges(self):
+        with torch.no_grad():
+            self.all_edges = self.marching_tets.tables_for(self.indices).all_edges
+
+    def getAABB(self):
+        return torch.min(self.verts, dim=0).values, torch.max(self.verts, dim=0).values
+
+    def get_deformed(self, no_grad=False):
+        deform = self.deform.detach() if no_grad else self.deform
+        if self.tanh:
+            return self.verts + 2 / (self.grid_res * 2) * torch.tanh(deform) * self.deform_scale
+        return self.verts + 2 / (self.grid_res * 2) * deform * self.deform_scale
+
+    def getMesh(self, material=None):
+        """Named like the reference's Mesh: v_pos (differentiable), t_pos_idx, v_tex, t_tex_idx, v_nrm / t_nrm_idx (smooth
+        normals, detached), valid_vert_idx."""
+        verts, faces, uvs, uv_idx, _tet_gidx, valid_vert_idx = self.marching_tets(self.get_deformed(), self.sdf, self.indices)
+        v_nrm = auto_normals(verts.detach(), faces)[0] if verts.shape[0] > 0 else torch.zeros_like(verts)
+        return types.SimpleNamespace(v_pos=verts, t_pos_idx=faces, v_tex=uvs, t_tex_idx=uv_idx, v_nrm=v_nrm, t_nrm_idx=faces,
+                                     material=material, valid_vert_idx=valid_vert_idx)
+
+    def state_to_dict(self):
+        """The `{'sdf', 'deform'}` dict fit_dmtets.py saves and mesh_export.dicts_to_grids reads."""
+        return {"sdf": self.sdf.detach().cpu(), "deform": self.deform.detach().cpu()}
 
 
 def auto_normals(verts, faces):
