@@ -692,6 +692,51 @@ int md_sdf_reg_loss_bwd(const float* sdf, const int32_t* edges, const int32_t* i
 int md_vertex_normals(const float* verts, const int64_t* faces, int64_t n_verts, int64_t n_faces, float* v_nrm,
                       float* f_nrm, void* stream);
 
+/*
+ * Point-cloud supervision of the fitting loop (nvdiffrec/lib/geometry/dmtet.py:454-459: sample_points + chamfer_distance;
+ * dmtet.py:249-251: nearest other vertex).  Purely additive: MD_ABI_VERSION stays 16.  Batched: `batch` clouds / meshes per
+ * call, batch <= 65535 (else MD_ERR_UNSUPPORTED).  The kernels index with the given tables unchecked: the host checks the
+ * ranges of faces / neighbour indices once (meshdiffusion_amd/pointcloud.py).
+ *
+ * md_nn_sided: for every point of p float32 [B][N][3] the squared distance to, and the index of, its nearest point of
+ *   q float32 [B][M][3]: dist float32 [B][N], idx int64 [B][N].  Distances in the direct form (px-qx)^2 + (py-qy)^2 +
+ *   (pz-qz)^2 in fp32 (multiply-adds may be fused), never the expanded |p|^2 + |q|^2 - 2 p.q.  Ties go to the lowest index.
+ *   skip_same_index != 0 excludes q[i] for query i (p == q: the nearest OTHER point).  A NaN distance wins, as in torch.min:
+ *   a query with a NaN coordinate gets NaN.  No candidate at all (M == 1 with skip_same_index): dist = +inf, idx = -1.
+ *   Two launches (partial minima per chunk of q, then the minimum over chunks of 64-bit (distance, index) keys); no atomics,
+ *   bit-identical from run to run.  workspace: md_nn_sided_workspace_bytes(B, N, M) bytes, 8-byte aligned.
+ * md_chamfer_bwd: gradient of  L[b] = w1 * mean_i dist(p_i, q_idx_pq(i)) + w2 * mean_j dist(q_j, p_idx_qp(j))  (squared
+ *   distances, neighbours held fixed) times grad_out float32 [B] (device): dp float32 [B][N][3], and dq float32 [B][M][3]
+ *   unless dq is NULL.  Gathers, no float atomics: (ptr_p int32 [B][N+1], order_p int32 [B][M]) is the CSR of idx_qp -- the
+ *   j sorted stably by idx_qp[b][j], ptr_p[b][i] = first position of target i -- and (ptr_q [B][M+1], order_q [B][N]) that of
+ *   idx_pq (needed when dq is given).  A negative neighbour index contributes nothing.
+ * md_face_areas: areas float32 [B][F] = 0.5 |(v1 - v0) x (v2 - v0)| of verts float32 [B][V][3], faces int64 [F][3] (shared).
+ * md_sample_points: S samples per mesh.  Face of sample s: face_choices_in int64 [B][S] if given, else the first f with
+ *   cdf[b][f] > r_face[b][s] * cdf[b][F-1], cdf float32 [B][F] = inclusive prefix sum of the areas, which must be
+ *   non-decreasing (the host accumulates it with torch.cumsum in float64 and rounds to float32; zero-area faces are never
+ *   chosen).  Point: u = sqrt(r_u), w0 = 1 - u, w1 = u (1 - r_v), w2 = u r_v, (w0 v0 + w1 v1) + w2 v2 unfused
+ *   (geometry/utils.py:34-45).  r_face, r_u, r_v float32 [B][S] in [0, 1).  Outputs: points float32 [B][S][3], face_choices
+ *   int64 [B][S], weights float32 [B][S][3] or NULL.
+ * md_sample_points_bwd: dverts float32 [B][V][3] (every element written) = sum over the (sample, corner) pairs naming the
+ *   vertex of weights * grad_points; (ptr int32 [B][V+1], order int32 [B][3S]) is the CSR of the codes 3 * sample + corner
+ *   sorted stably by faces[face_choices[sample]][corner].  A gather, no atomics.  The face choice is not differentiated.
+ */
+int64_t md_nn_sided_workspace_bytes(int32_t batch, int32_t n, int32_t m);
+int md_nn_sided(const float* p, const float* q, int32_t batch, int32_t n, int32_t m, int32_t skip_same_index,
+                float* dist, int64_t* idx, void* workspace, int64_t workspace_bytes, void* stream);
+int md_chamfer_bwd(const float* p, const float* q, const int64_t* idx_pq, const int64_t* idx_qp,
+                   const int32_t* ptr_p, const int32_t* order_p, const int32_t* ptr_q, const int32_t* order_q,
+                   int32_t batch, int32_t n, int32_t m, float w1, float w2, const float* grad_out, float* dp,
+                   float* dq, void* stream);
+int md_face_areas(const float* verts, const int64_t* faces, int32_t batch, int32_t n_verts, int32_t n_faces,
+                  float* areas, void* stream);
+int md_sample_points(const float* verts, const int64_t* faces, const float* cdf, const float* r_face,
+                     const float* r_u, const float* r_v, const int64_t* face_choices_in, int32_t batch,
+                     int32_t n_verts, int32_t n_faces, int32_t n_samples, float* points, int64_t* face_choices,
+                     float* weights, void* stream);
+int md_sample_points_bwd(const float* grad_points, const float* weights, const int32_t* ptr, const int32_t* order,
+                         int32_t batch, int32_t n_verts, int32_t n_samples, float* dverts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

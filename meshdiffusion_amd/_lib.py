@@ -142,6 +142,12 @@ SIGNATURES = {
     "md_marching_tets_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "md_sdf_reg_loss": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
     "md_sdf_reg_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
+    "md_nn_sided_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "md_nn_sided": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
+    "md_chamfer_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _F, _P, _P, _P, _P]),
+    "md_face_areas": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
+    "md_sample_points": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "md_sample_points_bwd": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
 }
 SDF_REG_SLABS = 64                                  # MD_SDF_REG_SLABS
 SDF_REG_WORKSPACE_BYTES = SDF_REG_SLABS * 24        # MD_SDF_REG_WORKSPACE_BYTES

@@ -416,6 +416,27 @@ class DMTetGeometry(torch.nn.Module):
     def getAABB(self):
         return torch.min(self.verts, dim=0).values, torch.max(self.verts, dim=0).values
 
+    def getVertNNDist(self):
+        """Squared distance of every deformed grid vertex to its nearest OTHER vertex (dmtet.py:249-251, the reference's
+        knn_points(v, v, K=2).dists[0, :, -1]): md_nn_sided with skip_same_index.  Detached, float32 [N]."""
+        from .pointcloud import sided_distance
+        v_deformed = (self.verts + 2 / (self.grid_res * 2) * torch.tanh(self.deform)).unsqueeze(0)
+        return sided_distance(v_deformed, v_deformed, skip_same_index=True)[0][0]
+
+    def getTetCenters(self):
+        return self.get_deformed()[self.indices].mean(dim=1)
+
+    def getValidTetIdx(self):
+        return self.marching_tets(self.get_deformed(), self.sdf, self.indices)[4].long()
+
+    def getValidVertsIdx(self):
+        return self.indices[self.getValidTetIdx()].unique()
+
+    def clamp_deform(self):
+        if not self.tanh:
+            self.deform.data[:] = self.deform.data.clamp(-0.99, 0.99)
+            self.sdf.data[:] = self.sdf.data.clamp(-1.0, 1.0)
+
     def get_deformed(self, no_grad=False):
         deform = self.deform.detach() if no_grad else self.deform
         if self.tanh:

@@ -1,0 +1,278 @@
+"""Point-cloud kernels, host side (no GPU): the new exports and their argument checks, the float64 restatements of
+tests/pointcloud_cases.py against the reference points of tests/golden/pointcloud.npz and against scipy's k-d tree, and the
+INPUT CONDITIONS the GPU tests rely on -- proven here so that a GPU test cannot hide a failure behind its exemptions."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import pointcloud_cases as pc
+from conftest import GOLD, ROOT
+
+NEW_EXPORTS = ("md_nn_sided", "md_chamfer_bwd", "md_face_areas", "md_sample_points", "md_sample_points_bwd")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+MAX_NEAR_SHARE = 1e-3
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(os.path.join(GOLD, "pointcloud.npz"))
+
+
+def test_new_exports_are_declared_everywhere_and_abi_stays_16(hip_lib):
+    from meshdiffusion_amd import _lib, build
+    header = open(os.path.join(ROOT, "include", "meshdiffusion_hip.h")).read()
+    raw = C.CDLL(_lib.LIB_PATH)
+    for name in NEW_EXPORTS:
+        assert re.search(rf"\bint {name}\(", header), name
+        assert name in _lib.SIGNATURES, name
+        assert hasattr(raw, name), name
+    assert re.search(r"\bint64_t md_nn_sided_workspace_bytes\(", header) and "md_nn_sided_workspace_bytes" in _lib.SIGNATURES
+    assert hasattr(raw, "md_nn_sided_workspace_bytes")
+    assert _lib.ABI_VERSION == 16 and "#define MD_ABI_VERSION 16" in header and hip_lib.md_abi_version() == 16
+    assert "pointcloud.hip" in build.SOURCES
+    from meshdiffusion_amd import pointcloud
+    from meshdiffusion_amd.dmtet import DMTetGeometry
+    for name in ("sample_points", "sided_distance", "chamfer_distance", "fit_to_points", "face_areas"):
+        assert callable(getattr(pointcloud, name)), name
+    for name in ("getVertNNDist", "getTetCenters", "getValidTetIdx", "getValidVertsIdx", "clamp_deform"):
+        assert callable(getattr(DMTetGeometry, name)), name
+
+
+def _refuses(fn, ok, pointers, sizes):
+    """-1 for each of `pointers` set to null and each of `sizes` set to 0 or a negative number; `ok` ends with a null stream."""
+    nul = C.c_void_p(0)
+    assert ok[-1].value is None
+    for k in pointers:
+        a = list(ok)
+        a[k] = nul
+        assert fn(*a) == -1, (fn.__name__, k)
+    for k in sizes:
+        for bad in (0, -3):
+            a = list(ok)
+            a[k] = bad
+            assert fn(*a) == -1, (fn.__name__, k, bad)
+
+
+def test_new_exports_refuse_bad_arguments_without_a_gpu(hip_lib):
+    nul, one, odd = C.c_void_p(0), C.c_void_p(64), C.c_void_p(68)
+    big = 1 << 40
+    # md_nn_sided(p, q, B, N, M, skip, dist, idx, ws, ws_bytes, stream)
+    ws = hip_lib.md_nn_sided_workspace_bytes
+    assert ws(1, 50000, 50000) > 0 and ws(1, 50000, 50000) % (50000 * 8) == 0 and ws(3, 1, 1) == 3 * 8
+    assert ws(1, 50000, 50000) // (50000 * 8) >= 16                  # q really is split across workgroups at the real size
+    assert ws(0, 5, 5) == -1 and ws(1, 0, 5) == -1 and ws(1, 5, -1) == -1
+    ok = [one, one, 2, 100, 300, 0, one, one, one, big, nul]
+    _refuses(hip_lib.md_nn_sided, ok, (0, 1, 6, 7, 8), (2, 3, 4))
+    a = list(ok); a[8] = odd
+    assert hip_lib.md_nn_sided(*a) == -1                             # 64-bit keys
+    a = list(ok); a[7] = odd
+    assert hip_lib.md_nn_sided(*a) == -1                             # int64 indices
+    a = list(ok); a[9] = ws(2, 100, 300) - 1
+    assert hip_lib.md_nn_sided(*a) == -1                             # a workspace that is too small
+    a = list(ok); a[2] = 70000
+    assert hip_lib.md_nn_sided(*a) == -2                             # gridDim.z
+    # md_chamfer_bwd(p, q, idx_pq, idx_qp, ptr_p, order_p, ptr_q, order_q, B, N, M, w1, w2, grad_out, dp, dq, stream)
+    ok = [one] * 8 + [2, 100, 300, 1.0, 1.0, one, one, one, nul]
+    _refuses(hip_lib.md_chamfer_bwd, ok, (0, 1, 2, 3, 4, 5, 6, 7, 13, 14), (8, 9, 10))
+    a = list(ok); a[6] = a[7] = a[15] = nul                          # without dq its CSR is not needed: passes the checks ...
+    a[8] = 70000
+    assert hip_lib.md_chamfer_bwd(*a) == -2                          # ... and stops at the launch limit
+    a = list(ok); a[2] = odd
+    assert hip_lib.md_chamfer_bwd(*a) == -1
+    a = list(ok); a[8] = 70000
+    assert hip_lib.md_chamfer_bwd(*a) == -2
+    # md_face_areas(verts, faces, B, V, F, areas, stream)
+    ok = [one, one, 2, 100, 300, one, nul]
+    _refuses(hip_lib.md_face_areas, ok, (0, 1, 5), (2, 3, 4))
+    a = list(ok); a[1] = odd
+    assert hip_lib.md_face_areas(*a) == -1
+    a = list(ok); a[2] = 70000
+    assert hip_lib.md_face_areas(*a) == -2
+    # md_sample_points(verts, faces, cdf, r_face, r_u, r_v, choices_in, B, V, F, S, points, choices, weights, stream)
+    ok = [one] * 7 + [2, 100, 300, 500, one, one, one, nul]
+    _refuses(hip_lib.md_sample_points, ok, (0, 1, 4, 5, 11, 12), (7, 8, 9, 10))
+    for k in (2, 3):                                                 # without given faces the CDF and r_face are needed
+        a = list(ok); a[6] = nul; a[k] = nul
+        assert hip_lib.md_sample_points(*a) == -1, k
+    a = list(ok); a[12] = odd
+    assert hip_lib.md_sample_points(*a) == -1
+    a = list(ok); a[7] = 70000
+    assert hip_lib.md_sample_points(*a) == -2
+    # md_sample_points_bwd(grad_points, weights, ptr, order, B, V, S, dverts, stream)
+    ok = [one, one, one, one, 2, 100, 500, one, nul]
+    _refuses(hip_lib.md_sample_points_bwd, ok, (0, 1, 2, 3, 7), (4, 5, 6))
+    a = list(ok); a[4] = 70000
+    assert hip_lib.md_sample_points_bwd(*a) == -2
+    a = list(ok); a[6] = 800_000_000
+    assert hip_lib.md_sample_points_bwd(*a) == -2                    # 3 S must fit the int32 corner codes
+
+
+def test_host_functions_refuse_cpu_tensors_and_unsupported_modes():
+    from meshdiffusion_amd import _lib, pointcloud
+    p = torch.zeros(1, 4, 3)
+    with pytest.raises(_lib.MeshDiffusionHipError):
+        pointcloud.sided_distance(p, p)
+    with pytest.raises(_lib.MeshDiffusionHipError):
+        pointcloud.chamfer_distance(p, p)
+    with pytest.raises(_lib.MeshDiffusionHipError):
+        pointcloud.sample_points(p, torch.tensor([[0, 1, 2]]), 8)
+    with pytest.raises(NotImplementedError):
+        pointcloud.chamfer_distance(p, p, squared=False)
+    assert pointcloud.sdf_regularizer_weight(0, 100, 0.2) == 0.2
+    assert abs(pointcloud.sdf_regularizer_weight(25, 100, 0.2) - 0.01) < 1e-15 and abs(pointcloud.sdf_regularizer_weight(90, 100, 0.2) - 0.01) < 1e-15
+
+
+def test_csr_of_a_dynamic_index_table():
+    from meshdiffusion_amd.pointcloud import _csr
+    g = torch.Generator().manual_seed(3)
+    idx = torch.randint(0, 37, (3, 200), generator=g)
+    idx[1] = 5                                                       # every entry on one target
+    ptr, order = _csr(idx, 37)
+    assert ptr.dtype == torch.int32 and order.dtype == torch.int32 and ptr.shape == (3, 38) and order.shape == (3, 200)
+    for b in range(3):
+        assert int(ptr[b, 0]) == 0 and int(ptr[b, -1]) == 200
+        assert torch.equal((ptr[b, 1:] - ptr[b, :-1]).long(), torch.bincount(idx[b], minlength=37))
+        o = order[b].long()
+        owner = torch.repeat_interleave(torch.arange(37), (ptr[b, 1:] - ptr[b, :-1]).long())
+        assert torch.equal(idx[b][o], owner)
+        same = owner[1:] == owner[:-1]
+        assert bool((o[1:] > o[:-1])[same].all())                    # stable: ascending position inside a target
+
+
+def test_float64_sampling_restatement_reproduces_the_reference_points(gold):
+    for name in pc.SAMPLE_CASES:
+        verts, faces = pc.sample_case(name)
+        ch = torch.as_tensor(gold[f"sample/{name}/choices"].astype(np.int64))
+        r_u, r_v = torch.as_tensor(gold[f"sample/{name}/r_u"]), torch.as_tensor(gold[f"sample/{name}/r_v"])
+        want = torch.as_tensor(gold[f"sample/{name}/points"])
+        assert ch.shape == (verts.shape[0], pc.SAMPLE_SIZES[name]) and want.dtype == torch.float32
+        pts, w = pc.sample_points_restated(verts, faces, ch, r_u, r_v)
+        err, bound = float((pts - want.double()).abs().max()), 4 * 2.0 ** -24 * float(verts.abs().max())
+        print(f"{name}: restatement vs reference points max|d| {err:.2e} (bound {bound:.2e})")
+        assert err <= bound, name
+        assert float((w.sum(-1) - 1).abs().max()) < 1e-15 and float(w.min()) >= 0
+        areas = pc.face_areas_restated(verts, faces)
+        assert bool((areas.gather(1, ch) > 0).all()), name           # the reference never drew a zero-area face either
+        assert 0 < float(gold[f"sample/{name}/ref_err_grad"]) < 1e-6
+    for name in pc.CHAMFER_CASES:
+        for k in ("value", "dp1", "dp2"):
+            assert 0 < float(gold[f"chamfer/{name}/ref_err_{k}"]) < 1e-6, (name, k)
+
+
+def test_float64_nearest_neighbours_agree_with_the_kd_tree():
+    cKDTree = pytest.importorskip("scipy.spatial").cKDTree
+    for name in pc.NN_CASES:
+        if name == "spheres":
+            continue                                                 # its brute force runs on the GPU; the tree covers it below
+        p, q, skip = pc.nn_case(name)
+        d1, i1, d2 = pc.nn_float64(p, q, skip)
+        qq = p if q is None else q
+        for b in range(p.shape[0]):
+            k = min(3 if skip else 2, qq.shape[1])
+            dd, ii = cKDTree(qq[b].double().numpy()).query(p[b].double().numpy(), k=k)
+            dd, ii = dd.reshape(p.shape[1], k) ** 2, ii.reshape(p.shape[1], k)
+            if skip:                                                 # drop the query itself (not necessarily column 0: duplicates)
+                rows = np.arange(p.shape[1])
+                own = ii == rows[:, None]
+                assert own.any(1).all()
+                col = own.argmax(1)
+                keep = np.ones_like(ii, bool)
+                keep[rows, col] = False
+                dd, ii = dd[keep].reshape(-1, k - 1), ii[keep].reshape(-1, k - 1)
+            assert np.abs(dd[:, 0] - d1[b].numpy()).max() <= 1e-12 * max(1.0, float(d1[b].max())), name
+            if dd.shape[1] > 1:
+                assert np.abs(dd[:, 1] - d2[b].numpy()).max() <= 1e-12 * max(1.0, float(d2[b].max())), name
+            clear = ~pc.near_tie(d1[b], d2[b]).numpy()
+            assert (ii[clear, 0] == i1[b].numpy()[clear]).all(), name
+
+
+def test_input_conditions_near_ties_are_rare():
+    """For each nearest-neighbour cloud pair the share of queries whose two nearest squared distances (float64) differ by less
+    than 2^-20 relative is <= 0.1 %: the index check of the GPU test exempts those queries and no more."""
+    cKDTree = pytest.importorskip("scipy.spatial").cKDTree
+    for name in pc.NN_CASES:
+        if name in pc.EXACT_TIE_CASES:
+            continue
+        p, q, skip = pc.nn_case(name)
+        qq = p if q is None else q
+        for b in range(p.shape[0]):
+            if qq.shape[1] < (3 if skip else 2):
+                continue
+            dd = cKDTree(qq[b].double().numpy()).query(p[b].double().numpy(), k=3 if skip else 2)[0] ** 2
+            d1, d2 = (dd[:, 1], dd[:, 2]) if skip else (dd[:, 0], dd[:, 1])      # no duplicates here: column 0 is the query itself
+            share = float(((d2 - d1) < pc.NEAR_TIE * d2).mean())
+            print(f"{name}[{b}]: N={p.shape[1]} M={qq.shape[1]} near-tie share {share:.2e}")
+            assert share <= MAX_NEAR_SHARE, name
+            if skip:
+                assert (dd[:, 0] == 0).all() and (d1 > 0).all()
+
+
+def test_input_conditions_exact_tie_cases_are_exact_in_fp32():
+    p, q, _ = pc.nn_case("lattice")
+    for t in (p, q):
+        assert torch.equal(t, t.round()) and float(t.abs().max()) <= 13
+    d1, i1, d2 = pc.nn_float64(p, q)
+    assert bool((d1 == 3).all()) and bool((d2 == 3).all())           # at least two (in fact eight) candidates tie
+    d32 = ((p[0, :, None] - q[0, None]) ** 2).sum(-1)                # fp32: small integers, every sum < 2^24
+    assert d32.dtype == torch.float32 and torch.equal(d32.double(), ((p[0, :, None].double() - q[0, None].double()) ** 2).sum(-1))
+    assert bool(((d32 == 3).sum(1) == 8).all())
+    first = torch.where(d32 == 3, torch.arange(q.shape[1])[None], q.shape[1]).min(1).values
+    assert torch.equal(first, i1[0]) and int((first[1:] != first[:-1]).sum()) > 100    # the lowest index is not a constant
+    x, _, skip = pc.nn_case("dups")
+    assert skip and torch.equal(x[0, 2000:], x[0, :500])
+    d1, i1, _ = pc.nn_float64(x, None, True)
+    assert bool((d1[0, :500] == 0).all()) and bool((d1[0, 2000:] == 0).all()) and bool((d1[0, 500:2000] > 0).all())
+    assert torch.equal(i1[0, :500], torch.arange(2000, 2500)) and torch.equal(i1[0, 2000:], torch.arange(500))
+
+
+def test_input_conditions_samples_near_a_cdf_boundary_are_rare():
+    cases = [(n, pc.sample_case(n), pc.SAMPLE_SIZES[n] * 8, pc.SAMPLE_SEEDS[n] + 7) for n in pc.SAMPLE_CASES]
+    cases.append(("unequal", pc.unequal_mesh(), 1_000_000, 5399))
+    for name, (verts, faces), S, seed in cases:
+        areas = pc.face_areas_restated(verts, faces)
+        r_face = pc.case_uniforms(verts.shape[0], S, seed)[0]
+        ch, near = pc.face_choices_restated(areas, r_face)
+        share = float(near.double().mean())
+        print(f"{name}: F={faces.shape[0]} S={S} zero-area faces {int((areas[0] == 0).sum())} near-boundary share {share:.2e}")
+        assert share <= MAX_NEAR_SHARE, name
+        assert bool((areas.gather(1, ch) > 0).all()), name           # the restated inverse CDF never lands on a zero-area face
+    assert int((pc.face_areas_restated(*pc.sample_case("degenerate"))[0] == 0).sum()) >= 10
+    a = pc.face_areas_restated(*pc.unequal_mesh())[0]
+    assert float(a.max() / a[a > 0].min()) > 1e4 and int((a == 0).sum()) == 1
+
+
+def test_fixture_is_small_and_its_fit_falls(gold):
+    assert os.path.getsize(os.path.join(GOLD, "pointcloud.npz")) < 200 * 1024
+    assert list(gold["fit/steps"]) == list(pc.FIT_STEPS)
+    l32, l64 = gold["fit/loss32"], gold["fit/loss64"]
+    assert l64[3] < 0.5 * l64[0] and l32[3] < 0.5 * l32[0]
+    assert (np.abs(l32 - l64) > 0).all()                             # a unit of zero would make the GPU bar unmeetable
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_new_kernels_use_no_scratch_and_no_atomics(tmp_path):
+    csrc = os.path.join(ROOT, "meshdiffusion_amd", "csrc")
+    out = tmp_path / "pointcloud.s"
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", f"-I{ROOT}/include",
+                    f"-I{csrc}", os.path.join(csrc, "pointcloud.hip"), "-o", str(out)], check=True, stderr=subprocess.DEVNULL)
+    text = out.read_text()
+    seen = {}
+    for blk in text.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))      # noqa: E731
+        assert get("vgpr_spill_count") == 0 and get("sgpr_spill_count") == 0 and get("private_segment_fixed_size") == 0, name
+        seen[name] = get("vgpr_count")
+    for k in ("md_nn_partial_kernel", "md_nn_final_kernel", "md_chamfer_bwd_kernel", "md_face_areas_kernel",
+              "md_sample_points_kernel", "md_sample_points_bwd_kernel"):
+        assert any(k in n for n in seen), (k, seen)
+    nn = [v for n, v in seen.items() if "md_nn_partial_kernel" in n][0]
+    assert nn <= 128                                                 # two workgroups of 256 per SIMD row at least
+    assert "scratch_" not in text and "global_atomic" not in text and "flat_atomic" not in text and "ds_add" not in text
+    # the distance loop is packed fp32 arithmetic in the direct form, fed by LDS reads: no matrix-core instruction anywhere
+    assert "v_pk_fma_f32" in text and "v_pk_add_f32" in text and "ds_read" in text and "v_mfma" not in text
