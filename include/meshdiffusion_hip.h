@@ -356,6 +356,25 @@ int md_conv3_wino_f6(const void* t_in, const void* wpk, float* out, const float*
                      int32_t D, int32_t H, int32_t W, void* stream);
 
 /*
+ * The operand of an Upsample conv without its duplicates (inference).  Purely additive: MD_ABI_VERSION stays 16, every entry point
+ * above keeps its signature, layout and bits.  fmt = MD_WINO_FMT_*: the arithmetic (md_wino_prep_v2 / _f8 / _f6 and md_conv3_wino /
+ * _f8 / _f6 above).
+ * md_wino_prep_upsdh: those passes with ups = 1 (no dropout), T in the COMPACT layout [B][C/8][4][2][D/2][H/2][W/2] items of 16 bytes:
+ *   one row per source (z', y') instead of the four identical rows (2z' + i, 2y' + j) -- the transform runs along w only -- i.e.
+ *   rows (2z', 2y') of the full operand, a quarter of md_wino_operand_bytes.  D, H, W: the OUTPUT grid, all even; W must divide 256
+ *   and D*H*W/4 be a multiple of 256, else MD_ERR_UNSUPPORTED.
+ * md_conv3_wino_upsdh: md_conv3_wino / _f8 / _f6 on the compact operand; arguments, supported shapes and results (bit for bit) as theirs.
+ */
+#define MD_WINO_FMT_BF16X3 0
+#define MD_WINO_FMT_F16F8 1
+#define MD_WINO_FMT_F16F6 2
+int md_wino_prep_upsdh(int32_t fmt, const float* x1, const float* x2, int32_t c1, int32_t c2, const float* ac, int32_t silu,
+                       const float* eq, void* t_out, int32_t batch, int32_t D, int32_t H, int32_t W, void* stream);
+int md_conv3_wino_upsdh(int32_t fmt, const void* t_in, const void* wpk, float* out, const float* bias, int64_t bias_bstride,
+                        const float* residual, int64_t res_bstride, double* stats, int32_t batch, int32_t cin, int32_t cout,
+                        int32_t D, int32_t H, int32_t W, void* stream);
+
+/*
  * md_conv3_stem: the dx-folded 3x3x3 input convolution from 4 channels (csrc/conv3_stem.hip; ddpm_res64.py:87-92 applied
  * :138-146: conv3x3(channels, nf)(x) + pos_layer(coords) + mask_layer(mask)) with the GroupNorm sums of its output: replaces
  * md_gemm_conv(MD_CFG_C3X_128_K16) + md_gn_stats.

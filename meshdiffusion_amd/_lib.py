@@ -56,6 +56,7 @@ class MdPackJob(C.Structure):
 
 
 PACK_WPK, PACK_WINO, PACK_WINO_F6 = 0, 1, 2
+WINO_FMT = {False: 0, "f8": 1, "f6": 2}                  # MD_WINO_FMT_*
 ABI_VERSION = 16     # MD_ABI_VERSION of include/meshdiffusion_hip.h this host code was written against
 _P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
 
@@ -100,6 +101,8 @@ SIGNATURES = {
     "md_wino_prep_f6": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "md_wino_pack_weights_f6": (C.c_int, [_P, _P, _P, _I32, _I32, _I64, _I64, _P]),
     "md_conv3_wino_f6": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "md_wino_prep_upsdh": (C.c_int, [_I32, _P, _P, _I32, _I32, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "md_conv3_wino_upsdh": (C.c_int, [_I32, _P, _P, _P, _P, _I64, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "md_conv3_stem": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "md_conv3_head": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "md_pack_batch": (C.c_int, [_P, _I32, _I64, _I32, _P]),

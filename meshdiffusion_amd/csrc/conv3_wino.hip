@@ -200,6 +200,7 @@ struct WnArgs {
   int batch, cin, cout, D, H, W;
   float out_scale;         // F8: multiplies the weights' descale (1, or 1 / tscale of md_wino_prep_dual_f6: a power of two)
   const uint32_t* amax;    // F8, may be null: the operand was lifted by 2^md_dgrad_lift_log2(amax[0]) (md_wino_prep_dual_f6's dynamic form)
+  int ups_dh;              // 1: T is the compact upsampled operand [..][D/2][H/2][W/2] (md_wino_prep_ex, ups = 2); else 0
 };
 
 // ABL (timing only, results invalid; -DMD_BUILD_ABLATIONS, tools/bench_wino.py): bit 0 no halo traffic, bit 1 halo traffic in the
@@ -225,6 +226,9 @@ typedef int wn_i32x4 __attribute__((ext_vector_type(4)));
 // 0], and register 6 of either fragment is that MFMA's per-lane scale operand.
 // RES: the launch has a residual operand (compile-time: with the request behind a run-time branch hipcc cannot count the loads in
 // flight and waits with vmcnt(0) -- for the NEXT round's prefetch and the round's own stores as well, profiles/r06_wino_epilogue_ab.txt)
+// A.ups_dh (md_conv3_wino_upsdh): T is the compact operand of a nearest-x2 upsampled input (md_wino_prep_ex, ups = 2): one row per
+// source (z', y'), so halo row (z, y) is read from row (z >> 1, y >> 1) of a T with a quarter of the items.  Only the offsets change
+// (two shifts by a wave-uniform amount; F8 / F6: in the prologue's table, nothing in the main loop).
 template <int ABL, bool F8 = false, bool F6 = false, bool RES = false>
 __global__ __launch_bounds__(WN_THREADS) void md_conv3_wino_kernel(const WnArgs A) {
   __shared__ __attribute__((aligned(16))) unsigned char wn_smem[WN_LDS_BYTES];
@@ -248,7 +252,8 @@ __global__ __launch_bounds__(WN_THREADS) void md_conv3_wino_kernel(const WnArgs 
     }
   }
   const int D = A.D, H = A.H, W = A.W, Wp = W >> 1;
-  const int64_t P = (int64_t)D * H * W, Ph = P >> 1;
+  const int64_t P = (int64_t)D * H * W, Ph = P >> (1 + 2 * A.ups_dh);      // Ph: items per (frequency, plane) slice of T
+  const int ush = A.ups_dh, Hrows = H >> ush;                      // T has D >> ush by H >> ush rows
   const int ntx = W / WN_TX, nty = H / WN_TY, ntz = D / WN_TZ;
   const int tiles = ntx * nty * ntz;
   int bid = blockIdx.x;     // XCD-aware order: one contiguous run of tiles per XCD (block b runs on XCD b % 8)
@@ -272,14 +277,15 @@ __global__ __launch_bounds__(WN_THREADS) void md_conv3_wino_kernel(const WnArgs 
     const int hp = e / WN_TPOS, tp = e % WN_TPOS;
     const int dz = tp / 40, hy = (tp >> 2) % 10, pr = tp & 3;
     const int z = z0 + dz - 1, y = y0 + hy - 1;
-    const bool live = (z >= 0) & (z < D) & (y >= 0) & (y < H);
+    const bool live = (z >= 0) & (z < D) & (y >= 0) & (y < H);      // of the full-resolution row, also with ups_dh
+    const int row = (z >> ush) * Hrows + (y >> ush);                // row of T
     // cg = 2 chunk + (hp >> 1); inside a cg: [f][plane][Ph]; the f term is in the base
     if constexpr (F8) {      // 32-bit and unconditional (16 Ph < 2^31 is checked at launch): stays a select, no branch in the loop
       const int Phi = (int)Ph;
-      const int off = (hp >> 1) * 8 * Phi + (hp & 1) * Phi + (z * H + y) * Wp + (x0 >> 1) + pr;
+      const int off = (hp >> 1) * 8 * Phi + (hp & 1) * Phi + row * Wp + (x0 >> 1) + pr;
       return live ? off : -1;
     }
-    return live ? (int)((int64_t)(hp >> 1) * 8 * Ph + (int64_t)(hp & 1) * Ph + ((int64_t)z * H + y) * Wp + (x0 >> 1) + pr) : -1;
+    return live ? (int)((int64_t)(hp >> 1) * 8 * Ph + (int64_t)(hp & 1) * Ph + (int64_t)row * Wp + (x0 >> 1) + pr) : -1;
   };
   const uint4* tbase = A.T + ((int64_t)b * CG * 8 + wid * 2) * Ph;                              // + chunk * 16 * Ph
   const uint4* zsrc = &wn_zero16;
@@ -957,7 +963,7 @@ extern "C" int md_wino_pack_weights_f6(const float* w, const float* eq, void* wp
 static int md_conv3_wino_f8_launch(bool f6, const void* t_in, const void* wpk, float* out, const float* bias, int64_t bias_bstride,
                                    const float* residual, int64_t res_bstride, double* stats, int32_t batch, int32_t cin,
                                    int32_t cout, int32_t D, int32_t H, int32_t W, void* stream, float out_scale = 1.0f,
-                                   const uint32_t* amax = nullptr) {
+                                   const uint32_t* amax = nullptr, bool upsdh = false) {
   if (!t_in || !wpk || !out || batch <= 0) return MD_ERR_BAD_ARG;
   if (cin <= 0 || cout <= 0 || (cin % 32) || (cout % 128)) return MD_ERR_UNSUPPORTED;
   if (D <= 0 || H <= 0 || W <= 0 || (D % WN_TZ) || (H % WN_TY) || (W % WN_TX)) return MD_ERR_UNSUPPORTED;
@@ -968,6 +974,7 @@ static int md_conv3_wino_f8_launch(bool f6, const void* t_in, const void* wpk, f
   a.out_scale = out_scale; a.amax = amax;
   a.bias_bstride = bias_bstride; a.res_bstride = res_bstride;
   a.batch = batch; a.cin = cin; a.cout = cout; a.D = D; a.H = H; a.W = W;
+  a.ups_dh = upsdh ? 1 : 0;      // (D and H are multiples of 4 and 8: the compact operand's rows are whole)
   const int tiles = (D / WN_TZ) * (H / WN_TY) * (W / WN_TX);
   const dim3 grid((unsigned)(tiles * batch), (unsigned)(cout / 128));
   MD_HIP_CLEAR_ERROR();
@@ -1004,9 +1011,9 @@ extern "C" int md_conv3_wino_f6_scaled(const void* t_in, const void* wpk, float*
                                  amax_bits);
 }
 
-extern "C" int md_conv3_wino(const void* t_in, const void* wpk, float* out, const float* bias, int64_t bias_bstride,
-                             const float* residual, int64_t res_bstride, double* stats, int32_t batch, int32_t cin,
-                             int32_t cout, int32_t D, int32_t H, int32_t W, int32_t variant, void* stream) {
+static int md_conv3_wino_launch(const void* t_in, const void* wpk, float* out, const float* bias, int64_t bias_bstride,
+                                const float* residual, int64_t res_bstride, double* stats, int32_t batch, int32_t cin,
+                                int32_t cout, int32_t D, int32_t H, int32_t W, int32_t variant, void* stream, bool upsdh) {
   if (!t_in || !wpk || !out || batch <= 0) return MD_ERR_BAD_ARG;
   if (cin <= 0 || cout <= 0 || (cin % 32) || (cout % 128)) return MD_ERR_UNSUPPORTED;
   if (D <= 0 || H <= 0 || W <= 0 || (D % WN_TZ) || (H % WN_TY) || (W % WN_TX)) return MD_ERR_UNSUPPORTED;
@@ -1017,11 +1024,13 @@ extern "C" int md_conv3_wino(const void* t_in, const void* wpk, float* out, cons
   a.out_scale = 1.0f; a.amax = nullptr;
   a.bias_bstride = bias_bstride; a.res_bstride = res_bstride;
   a.batch = batch; a.cin = cin; a.cout = cout; a.D = D; a.H = H; a.W = W;
+  a.ups_dh = upsdh ? 1 : 0;
   const int tiles = (D / WN_TZ) * (H / WN_TY) * (W / WN_TX);
   MD_HIP_CLEAR_ERROR();
   const dim3 grid((unsigned)(tiles * batch), (unsigned)(cout / 128));
 #define WN_LAUNCH(A_) hipLaunchKernelGGL((md_conv3_wino_kernel<A_, false, false, true>), grid, dim3(WN_THREADS), 0, (hipStream_t)stream, a)
   if (variant != 0 && residual == nullptr) return MD_ERR_UNSUPPORTED;      // the timing-only variants are built in the residual form
+  if (upsdh && variant != 0) return MD_ERR_BAD_ARG;
   switch (variant) {
     case 0:
       if (residual) WN_LAUNCH(0);
@@ -1045,4 +1054,20 @@ extern "C" int md_conv3_wino(const void* t_in, const void* wpk, float* out, cons
 #undef WN_LAUNCH
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
+}
+
+extern "C" int md_conv3_wino(const void* t_in, const void* wpk, float* out, const float* bias, int64_t bias_bstride,
+                             const float* residual, int64_t res_bstride, double* stats, int32_t batch, int32_t cin,
+                             int32_t cout, int32_t D, int32_t H, int32_t W, int32_t variant, void* stream) {
+  return md_conv3_wino_launch(t_in, wpk, out, bias, bias_bstride, residual, res_bstride, stats, batch, cin, cout, D, H, W, variant, stream, false);
+}
+
+extern "C" int md_conv3_wino_upsdh(int32_t fmt, const void* t_in, const void* wpk, float* out, const float* bias, int64_t bias_bstride,
+                                   const float* residual, int64_t res_bstride, double* stats, int32_t batch, int32_t cin,
+                                   int32_t cout, int32_t D, int32_t H, int32_t W, void* stream) {
+  if (fmt == MD_WINO_FMT_BF16X3)
+    return md_conv3_wino_launch(t_in, wpk, out, bias, bias_bstride, residual, res_bstride, stats, batch, cin, cout, D, H, W, 0, stream, true);
+  if (fmt != MD_WINO_FMT_F16F8 && fmt != MD_WINO_FMT_F16F6) return MD_ERR_BAD_ARG;
+  return md_conv3_wino_f8_launch(fmt == MD_WINO_FMT_F16F6, t_in, wpk, out, bias, bias_bstride, residual, res_bstride, stats, batch, cin, cout, D, H,
+                                 W, stream, 1.0f, nullptr, true);
 }

@@ -37,6 +37,9 @@ __device__ __forceinline__ int p2_slot(int p) { return (p & 1) * P2_REGION + (p 
 // eq (F8 / f6 only, may be null): the static per-input-channel power-of-two equaliser s_c of md_wino_equaliser, [c1 + c2] floats; the
 //   activated value is multiplied by it (exact) and the packed weights carry 1 / s_c, so that the channels of a 16-channel K block
 //   reach the 4-bit-significand cross-term images with comparable magnitudes whatever the GroupNorm gammas in front are.
+// ups = 2 (inference): the nearest-x2 upsampled operand ONCE per source (z', y') row -- the transform runs along w only, so the four
+//   rows (2z' + i, 2y' + j) of the ups = 1 operand are the same bits.  D and H are then the SOURCE's (the launcher halves them), W the
+//   output's: T[B][cin/8][4][2][D/2][H/2][W/2] items, read by md_conv3_wino_upsdh.
 template <bool DUAL, bool F8 = false>
 __global__ __launch_bounds__(256) void md_wino_prep2_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
                                                             int c1, int c2, const float* __restrict__ ac, int silu, int ups,
@@ -55,7 +58,8 @@ __global__ __launch_bounds__(256) void md_wino_prep2_kernel(const float* __restr
   const int cg = (blockIdx.x / nblk) % CG;
   const int b = blockIdx.x / (nblk * CG);
   int Di = D, Hi = H, Wi = W;
-  if (ups) { Di >>= 1; Hi >>= 1; Wi >>= 1; }
+  const int ush = ups == 1;                        // source rows per row of T: ups = 2 has the source's rows already
+  if (ups) { Di >>= ush; Hi >>= ush; Wi >>= 1; }
   const int64_t Pin = (int64_t)Di * Hi * Wi;
   const float* src = (cg * 8 < c1) ? x1 + ((int64_t)b * (c1 >> 3) + cg) * Pin * 8
                                    : x2 + ((int64_t)b * (c2 >> 3) + (cg - (c1 >> 3))) * Pin * 8;
@@ -63,7 +67,7 @@ __global__ __launch_bounds__(256) void md_wino_prep2_kernel(const float* __restr
   {
     const int64_t p = (int64_t)blk * P2_POS + tid;                  // position of the OUTPUT grid
     const int x = (int)(p % W), y = (int)((p / W) % H), z = (int)(p / ((int64_t)W * H));
-    const int64_t spos = ups ? ((int64_t)(z >> 1) * Hi + (y >> 1)) * Wi + (x >> 1) : p;
+    const int64_t spos = ups ? ((int64_t)(z >> ush) * Hi + (y >> ush)) * Wi + (x >> 1) : p;
     const f32x4* sp = (const f32x4*)(src + spos * 8);
     const f32x4 v0 = sp[0], v1 = sp[1];
     float a[8], c[8];
@@ -204,6 +208,7 @@ __global__ __launch_bounds__(256) void md_wino_prep2_kernel(const float* __restr
 //   T = the f16f6 operand of md_conv3_wino_f6 of `tscale` x the tensor (a power of two that lifts gradient magnitudes into the
 //   fp16 plane's normal range; the conv's launch divides it out again), U = the bf16 hi / lo operand of md_wgrad_wino of the
 //   UNSCALED tensor (bit-identical to md_wino_prep_dual's), sums = its per-(sample, channel) sums (bias gradients).
+// ups = 2: as in md_wino_prep2_kernel.
 template <bool DUAL>
 __global__ __launch_bounds__(256) void md_wino_prep2_f6_kernel(const float* __restrict__ x1, const float* __restrict__ x2, int c1, int c2,
                                                                const float* __restrict__ ac, int silu, int ups, uint4* __restrict__ T, int batch,
@@ -223,13 +228,14 @@ __global__ __launch_bounds__(256) void md_wino_prep2_f6_kernel(const float* __re
   const int cgp = (blockIdx.x / nblk) % CGP;
   const int b = blockIdx.x / (nblk * CGP);
   int Di = D, Hi = H, Wi = W;
-  if (ups) { Di >>= 1; Hi >>= 1; Wi >>= 1; }
+  const int ush = ups == 1;                        // source rows per row of T: ups = 2 has the source's rows already
+  if (ups) { Di >>= ush; Hi >>= ush; Wi >>= 1; }
   const int64_t Pin = (int64_t)Di * Hi * Wi;
   // ---- phase 1 ----
   {
     const int64_t p = (int64_t)blk * P2_POS + tid;
     const int x = (int)(p % W), y = (int)((p / W) % H), z = (int)(p / ((int64_t)W * H));
-    const int64_t spos = ups ? ((int64_t)(z >> 1) * Hi + (y >> 1)) * Wi + (x >> 1) : p;
+    const int64_t spos = ups ? ((int64_t)(z >> ush) * Hi + (y >> ush)) * Wi + (x >> 1) : p;
 #pragma unroll
     for (int g2 = 0; g2 < 2; ++g2) {
       const int cg = 2 * cgp + g2;
@@ -355,6 +361,7 @@ __global__ __launch_bounds__(256) void md_wino_prep2_f6_kernel(const float* __re
 static int md_wino_prep2_launch(const float* x1, const float* x2, int32_t c1, int32_t c2, const float* ac, int32_t silu,
                                 int32_t ups, void* t_out, void* u_out, float* sums, int32_t batch, int32_t D, int32_t H, int32_t W, float drop_p,
                                 uint64_t drop_seed, void* stream, bool f8 = false, const float* eq = nullptr) {
+  ups = ups ? 1 : 0;      // (2, the compact operand, is md_wino_prep_upsdh's)
   if (!x1 || !t_out || batch <= 0 || c1 <= 0 || c2 < 0 || (c1 & 7) || (c2 & 7) || (c2 > 0 && !x2)) return MD_ERR_BAD_ARG;
   if (silu && !ac) return MD_ERR_BAD_ARG;      // SiLU is applied together with the folded GroupNorm affine only
   if (D <= 0 || H <= 0 || W <= 0 || (W & 1) || (ups && ((D | H | W) & 1))) return MD_ERR_BAD_ARG;
@@ -401,6 +408,7 @@ extern "C" int md_wino_prep_f8(const float* x1, const float* x2, int32_t c1, int
 
 extern "C" int md_wino_prep_f6(const float* x1, const float* x2, int32_t c1, int32_t c2, const float* ac, int32_t silu,
                                int32_t ups, const float* eq, void* t_out, int32_t batch, int32_t D, int32_t H, int32_t W, void* stream) {
+  ups = ups ? 1 : 0;
   if (!x1 || !t_out || batch <= 0 || c1 <= 0 || c2 < 0 || (c1 & 15) || (c2 & 15) || (c2 > 0 && !x2)) return MD_ERR_BAD_ARG;   // whole 16-channel blocks per part
   if (silu && !ac) return MD_ERR_BAD_ARG;
   if (D <= 0 || H <= 0 || W <= 0 || (W & 1) || (ups && ((D | H | W) & 1))) return MD_ERR_BAD_ARG;
@@ -426,6 +434,36 @@ extern "C" int md_wino_prep_dual_f6(const float* x, int32_t c, void* t_out, void
   MD_HIP_CLEAR_ERROR();
   hipLaunchKernelGGL(md_wino_prep2_f6_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (const float*)nullptr, c, 0,
                      (const float*)nullptr, 0, 0, (uint4*)t_out, batch, D, H, W, (const float*)nullptr, (uint4*)u_out, sums, tscale, amax_bits);
+  MD_HIP_CHECK_LAUNCH();
+  return MD_OK;
+}
+
+// The inference operand pass of an Upsample conv in the compact layout of md_conv3_wino_upsdh (fmt: MD_WINO_FMT_*): the nearest-x2
+// upsampled operand once per source (z', y') row.  D, H, W: the OUTPUT grid, as with ups = 1 of the passes above.
+extern "C" int md_wino_prep_upsdh(int32_t fmt, const float* x1, const float* x2, int32_t c1, int32_t c2, const float* ac, int32_t silu,
+                                  const float* eq, void* t_out, int32_t batch, int32_t D, int32_t H, int32_t W, void* stream) {
+  if (fmt < MD_WINO_FMT_BF16X3 || fmt > MD_WINO_FMT_F16F6) return MD_ERR_BAD_ARG;
+  const int cmask = fmt == MD_WINO_FMT_F16F6 ? 15 : 7;
+  if (!x1 || !t_out || batch <= 0 || c1 <= 0 || c2 < 0 || (c1 & cmask) || (c2 & cmask) || (c2 > 0 && !x2)) return MD_ERR_BAD_ARG;
+  if ((eq && fmt == MD_WINO_FMT_BF16X3) || (silu && !ac)) return MD_ERR_BAD_ARG;
+  if (D <= 0 || H <= 0 || W <= 0 || ((D | H | W) & 1)) return MD_ERR_BAD_ARG;
+  D >>= 1; H >>= 1;      // the compact operand has the source's rows
+  const int64_t P = (int64_t)D * H * W;
+  if ((P2_POS % W) || (P % P2_POS)) return MD_ERR_UNSUPPORTED;
+  const int64_t blocks = (int64_t)batch * ((c1 + c2) / (cmask + 1)) * (P / P2_POS);
+  if (blocks > 0x7fffffff) return MD_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)blocks);
+  hipStream_t st = (hipStream_t)stream;
+  MD_HIP_CLEAR_ERROR();
+  if (fmt == MD_WINO_FMT_F16F6)
+    hipLaunchKernelGGL(md_wino_prep2_f6_kernel<false>, grid, dim3(256), 0, st, x1, x2, c1, c2, ac, silu, 2, (uint4*)t_out, batch, D, H, W, eq,
+                       (uint4*)nullptr, (float*)nullptr, 1.0f, (const uint32_t*)nullptr);
+  else if (fmt == MD_WINO_FMT_F16F8)
+    hipLaunchKernelGGL((md_wino_prep2_kernel<false, true>), grid, dim3(256), 0, st, x1, x2, c1, c2, ac, silu, 2, (uint4*)t_out, (uint4*)nullptr,
+                       (float*)nullptr, batch, D, H, W, 0u, 1.0f, (uint64_t)0, eq);
+  else
+    hipLaunchKernelGGL((md_wino_prep2_kernel<false>), grid, dim3(256), 0, st, x1, x2, c1, c2, ac, silu, 2, (uint4*)t_out, (uint4*)nullptr,
+                       (float*)nullptr, batch, D, H, W, 0u, 1.0f, (uint64_t)0, (const float*)nullptr);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }

@@ -654,30 +654,50 @@ def wino_f8_ok(S, drop=None, keep=False, parts=None, normalised=True):
     return WINO_F8
 
 
-def wino_prep(parts, ac, silu, ups, B, S, drop=None, keep=False, dual=False, sums=None, f8=False, eq=None, tscale=1.0, amax=None, dims=None):
+# An Upsample conv's operand once per source (z', y') row (md_wino_prep_upsdh + md_conv3_wino_upsdh; A/B switch, same bits either way)
+PREP_COMPACT_UPS = os.environ.get("MD_PREP_COMPACT_UPS", "1") == "1"
+
+
+def prep_compact_ok(ups, D, H, W, drop=None, keep=False):
+    """The compact upsampled operand: inference launches (a kept T is read by md_wgrad_wino in the full layout) on grids whose
+    quarter the two-phase pass takes."""
+    return bool(PREP_COMPACT_UPS and WINO_PREP_V2 and ups and not drop and not keep and not ((D | H | W) & 1) and 256 % W == 0
+                and ((D // 2) * (H // 2) * W) % 256 == 0)
+
+
+def wino_prep(parts, ac, silu, ups, B, S, drop=None, keep=False, dual=False, sums=None, f8=False, eq=None, tscale=1.0, amax=None, dims=None,
+              compact=False):
     """fp32 F32B parts (+ folded GroupNorm affine, SiLU, nearest-x2 upsampling) -> transformed split operand T.
     drop = (p, seed): training dropout after SiLU, the mask gn_apply(drop=...) produces for the same pair.
     keep: T goes to its own tensor instead of the shared scratch buffer (training forward: the Winograd weight gradient of the
     backward reads it again).  dual: returns (T, U) -- U = the dY operand of md_wgrad_wino (md_wino_prep_dual); sums (with dual):
     zeroed float [B, C] receiving the per-(sample, channel) sums of the tensor in the same pass (bias gradients).
     f8: False | "f8" (True) | "f6": the operand format of md_conv3_wino_f8 / _f6; eq (with f8): the layer's equaliser (wino_equaliser).
-    dims: the OUTPUT grid (D, H, W) where it is not the cube S^3 (`S` is ignored then)."""
+    dims: the OUTPUT grid (D, H, W) where it is not the cube S^3 (`S` is ignored then).
+    compact (with ups; prep_compact_ok): T in the compact layout of md_conv3_wino_upsdh (conv3_wino picks it up from the operand)."""
     lib = _lib.load()
     D, H, W = dims if dims is not None else (S, S, S)
     cin = sum(c for _, c in parts)
     assert 1 <= len(parts) <= 2
+    assert not (compact and (dual or keep or drop)), "the compact operand is an inference layout"
     assert eq is None or (f8 and eq.numel() == cin and eq.dtype == torch.float32 and eq.is_cuda), "eq belongs to the f16f8 / f16f6 operand"
     assert ac is not None or not silu, "SiLU is applied together with the folded GroupNorm affine (pass `ac`)"
     nbytes = lib.md_wino_operand_bytes(B, cin, D, H, W)
     if nbytes <= 0:
         raise _lib.MeshDiffusionHipError("md_wino_operand_bytes: unsupported operand shape")
     dev = parts[0][0].device
+    if compact:
+        assert ups and prep_compact_ok(ups, D, H, W)
+        nbytes //= 4
     t = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=dev) if keep else _wino_scratch(nbytes // 2, dev)
     x2, c2 = (parts[1][0], parts[1][1]) if len(parts) == 2 else (None, 0)
     ev = _prof_begin()
     args = (_ptr(parts[0][0]), _ptr(x2), parts[0][1], c2, _ptr(ac), 1 if silu else 0, 1 if ups else 0)
     tail = (B, D, H, W, drop[0] if drop else 0.0, drop[1] if drop else 0, _stream())
-    if f8 and dual:
+    if compact:
+        check(lib.md_wino_prep_upsdh(_lib.WINO_FMT["f6" if f8 == "f6" else ("f8" if f8 else False)], *args[:6], _ptr(eq), _ptr(t), B, D, H, W,
+                                     _stream()), "md_wino_prep_upsdh")
+    elif f8 and dual:
         # training backward: T = the f16f6 operand of tscale x the output gradient (data-gradient conv), U = the bf16 operand of the
         # unscaled gradient (md_wgrad_wino), sums = its channel sums
         assert f8 == "f6" and len(parts) == 1 and ac is None and not (ups or keep or drop or eq is not None) and 256 % W == 0
@@ -698,12 +718,13 @@ def wino_prep(parts, ac, silu, ups, B, S, drop=None, keep=False, dual=False, sum
     else:
         fn = lib.md_wino_prep_v2 if (WINO_PREP_V2 and 256 % W == 0 and (D * H * W) % 256 == 0) else lib.md_wino_prep
         check(fn(*args, _ptr(t), *tail), "md_wino_prep")
-    _prof_end(ev, "wino_prep", 0.0, 4.0 * B * cin * (D * H * W // (8 if ups else 1)) + (16.0 if dual else 8.0) * B * cin * D * H * W,   # fp32 in, 2 x bf16 x 2 out
+    _prof_end(ev, "wino_prep", 0.0, 4.0 * B * cin * (D * H * W // (8 if ups else 1)) + (16.0 if dual else 8.0) * B * cin * (D * H * W // (4 if compact else 1)),   # fp32 in, 2 x bf16 x 2 out
               f"{cin}@{D}x{H}x{W}" + ("/ups" if ups else "") + ("/dual" if dual else "") + (("/f6" if f8 == "f6" else "/f8") if f8 else ""))
     # what this operand is, for conv3_wino's pairing check (an f8 T under f6 weights, or a T equalised with another layer's vector,
     # would be silently wrong: the kernel cannot tell)
     t._md_fmt = ("f6" if f8 == "f6" else "f8") if f8 else False
     t._md_eq = eq.data_ptr() if eq is not None else 0
+    t._md_compact = bool(compact)
     return (t, u) if dual else t
 
 
@@ -750,7 +771,11 @@ def conv3_wino(ww, t, B, S, *, bias=None, bias_bstride=0, residual=None, res_bst
         want = ww.fmt if f8 else False
         if t_fmt != want or getattr(t, "_md_eq", 0) != ((ww.eq.data_ptr() if ww.eq is not None else 0) if f8 else 0):
             raise _lib.MeshDiffusionHipError(f"conv3_wino: operand format {t_fmt!r} / equaliser does not belong to these weights ({want!r})")
-    if f8 and (out_scale != 1.0 or amax is not None):
+    if getattr(t, "_md_compact", False):      # the compact upsampled operand of wino_prep(compact=True)
+        assert out_scale == 1.0 and amax is None and variant is None
+        check(lib.md_conv3_wino_upsdh(_lib.WINO_FMT[ww.fmt if f8 else False], _ptr(t), _ptr(ww.data), _ptr(out), _ptr(bias), bias_bstride,
+                                      _ptr(residual), res_bstride, _ptr(stats), B, ww.kdim, ww.rows, D, H, W, _stream()), "md_conv3_wino_upsdh")
+    elif f8 and (out_scale != 1.0 or amax is not None):
         assert ww.fmt == "f6"
         check(lib.md_conv3_wino_f6_scaled(_ptr(t), _ptr(ww.data), _ptr(out), _ptr(bias), bias_bstride, _ptr(residual), res_bstride,
                                           _ptr(stats), B, ww.kdim, ww.rows, D, H, W, float(out_scale), _ptr(amax), _stream()),

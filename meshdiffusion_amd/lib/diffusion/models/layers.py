@@ -198,8 +198,10 @@ def run_conv3(pw, act_s16, B, S_out, *, bias=None, bias_bstride=0, residual=None
             or (ops.WINO_EQ and hasattr(wino, "measured") and wino.measured() is not None))     # measured: only with its equaliser
         if f8 and owner is not None and wino.site in getattr(owner, "md_bf16x3_sites", ()):
             f8 = False                   # this conv was taken off the reduced-precision path (layer.md_bf16x3_sites: tools/audit_precision.py)
+        # inference: an upsampled operand is written once per source row (the training forward keeps the full layout: md_wgrad_wino reads it)
+        compact = (not b_f32.get("wino_only")) and ops.prep_compact_ok(ups, S_out, S_out, S_out, drop=b_f32.get("drop"), keep=bool(b_f32.get("keep")))
         t = ops.wino_prep(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), ups, B, S_out, drop=b_f32.get("drop"),
-                          keep=bool(b_f32.get("keep")), f8=f8, eq=wino.eq() if f8 and hasattr(wino, "eq") else None)
+                          keep=bool(b_f32.get("keep")), f8=f8, eq=wino.eq() if f8 and hasattr(wino, "eq") else None, compact=compact)
         if b_f32.get("keep"):
             b_f32["t_out"] = t           # training: the Winograd weight gradient reads the operand again (tape)
         ops.conv3_wino(wino(f8) if f8 else wino(), t, B, S_out, bias=bias, bias_bstride=bias_bstride, residual=residual,
@@ -207,7 +209,7 @@ def run_conv3(pw, act_s16, B, S_out, *, bias=None, bias_bstride=0, residual=None
         if f8 and ops.AUDIT is not None:
             # diagnostic mode (tools/audit_precision.py): the same launch once more in bf16x3; the pair's relative difference is the
             # error the reduced-precision format adds on THIS layer with THESE weights and activations
-            t3 = ops.wino_prep(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), ups, B, S_out)
+            t3 = ops.wino_prep(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), ups, B, S_out, compact=compact)      # the audited launch's layout
             ref = ops.conv3_wino(wino(), t3, B, S_out, bias=bias, bias_bstride=bias_bstride, residual=residual, res_bstride=res_bstride or 0)
             ops.AUDIT.append(dict(owner=getattr(wino, "owner", None), site=getattr(wino, "site", None), fmt=f8, cin=pw.kdim, cout=pw.rows,
                                   S=S_out, rel_l2=float((torch.linalg.vector_norm(out - ref, dtype=torch.float64)
