@@ -356,6 +356,20 @@ int md_conv3_wino_f6(const void* t_in, const void* wpk, float* out, const float*
                      int32_t D, int32_t H, int32_t W, void* stream);
 
 /*
+ * md_wino_prep_f6_nin: one pass over the input of a ResnetBlock with a NIN shortcut (inference).  Purely additive: MD_ABI_VERSION stays
+ * 16.  The block input cat(x1, x2) is read ONCE by a persistent workgroup of md_nin_f32's structure, which writes
+ *   t_out : exactly the bytes md_wino_prep_f6(x1, x2, c1, c2, ac, silu, ups = 0, eq, ...) writes (Conv_0's f16f6 operand), and
+ *   res   : exactly the bytes md_nin_f32(x1, x2, c1, c2, wpk, bias, ..., cout = 128) writes (the shortcut), F32B [B][16][P][8].
+ * wpk == NULL: the operand only (bias and res are ignored) -- a persistent, prefetching form of md_wino_prep_f6.
+ * Supported: what both take -- c1 + c2 in {128, 256}, c1 % 16 == c2 % 16 == 0, W even and a divisor of 256, D H W % 256 == 0 (and
+ * D H W <= 2^25); the argument errors of md_wino_prep_f6 / md_nin_f32 are MD_ERR_BAD_ARG, other shapes MD_ERR_UNSUPPORTED.
+ * n_cu: workgroups to launch (0 = 256, one per CU).
+ */
+int md_wino_prep_f6_nin(const float* x1, const float* x2, int32_t c1, int32_t c2, const float* ac, int32_t silu, const float* eq,
+                        void* t_out, const void* wpk, const float* bias, float* res, int32_t batch, int32_t D, int32_t H, int32_t W,
+                        int32_t n_cu, void* stream);
+
+/*
  * The operand of an Upsample conv without its duplicates (inference).  Purely additive: MD_ABI_VERSION stays 16, every entry point
  * above keeps its signature, layout and bits.  fmt = MD_WINO_FMT_*: the arithmetic (md_wino_prep_v2 / _f8 / _f6 and md_conv3_wino /
  * _f8 / _f6 above).

@@ -101,6 +101,7 @@ SIGNATURES = {
     "md_wino_prep_f6": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "md_wino_pack_weights_f6": (C.c_int, [_P, _P, _P, _I32, _I32, _I64, _I64, _P]),
     "md_conv3_wino_f6": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "md_wino_prep_f6_nin": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "md_wino_prep_upsdh": (C.c_int, [_I32, _P, _P, _I32, _I32, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "md_conv3_wino_upsdh": (C.c_int, [_I32, _P, _P, _P, _P, _I64, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "md_conv3_stem": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),

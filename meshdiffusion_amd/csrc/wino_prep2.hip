@@ -9,6 +9,7 @@
 //   phase 2  one (pair, frequency half) per thread: waves 0-1 write d0-d2 and d1+d2, waves 2-3 d2-d1 and d1-d3 of the 128
 //            pairs, 3 positions each out of LDS; every store instruction writes 1 KB contiguous
 #include "md_common.h"
+#include "md_prep_f6.h"
 
 namespace {
 constexpr int P2_POS = 256;               // positions per workgroup
@@ -258,17 +259,14 @@ __global__ __launch_bounds__(256) void md_wino_prep2_f6_kernel(const float* __re
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         float t = e < 4 ? v0[e] : v1[e - 4];
-        if (ac != nullptr) {
-          t = t * a[e] + c[e];
-          if (silu) t = t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -1.4426950408889634f));
-        }
+        if (ac != nullptr) t = md_prep_act(t, a[e], c[e], silu);
         yv[e] = t;
       }
       if (eq != nullptr) {
         const f32x4* ep = (const f32x4*)(eq + cg * 8);
         const f32x4 e0 = ep[0], e1 = ep[1];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) yv[e] *= e < 4 ? e0[e] : e1[e - 4];
+        for (int e = 0; e < 8; ++e) yv[e] = md_prep_eq(yv[e], e < 4 ? e0[e] : e1[e - 4]);
       }
       float* dst = act + g2 * P2_GROUP + p2_slot(tid);
       *(f32x4*)dst = f32x4{yv[0], yv[1], yv[2], yv[3]};
@@ -320,7 +318,7 @@ __global__ __launch_bounds__(256) void md_wino_prep2_f6_kernel(const float* __re
       float t[16];
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        t[e] = f == 0 ? d[0][e] - d[2][e] : f == 1 ? d[1][e] + d[2][e] : f == 2 ? d[2][e] - d[1][e] : d[1][e] - d[3][e];
+        t[e] = md_wino_bt(f, d[0][e], d[1][e], d[2][e], d[3][e]);
         // the lift (dynamic: max |dy| lands in [16, 32); or the caller's constant), saturated at the fp16 plane's range so that a
         // constant lift can clip an element but never turn the whole data gradient into inf / NaN; only FINITE values saturate:
         // a NaN / inf of dy (a diverged step) stays one, as it does in torch autograd

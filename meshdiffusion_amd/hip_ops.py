@@ -1096,6 +1096,48 @@ def nin_f32(parts, pw, bias, B, P, out=None):
     return out
 
 
+# A ResnetBlock with a NIN shortcut reads its input once: Conv_0's f16f6 operand and the shortcut from one kernel
+# (md_wino_prep_f6_nin; A/B switch, 0 = md_wino_prep_f6 + md_nin_f32, same bits either way)
+BLOCK_PASS = os.environ.get("MD_BLOCK_PASS", "1") == "1"
+
+
+def block_pass_ok(parts, rows, B, D, H, W):
+    """Shapes md_wino_prep_f6_nin takes: those of the f16f6 operand pass and of md_nin_f32 (nin_stream_ok)."""
+    P = D * H * W
+    return bool(BLOCK_PASS and WINO_PREP_V2 and nin_stream_ok(parts, rows, P) and 256 % W == 0 and W % 2 == 0 and P <= 1 << 25
+                and B * (P // 256) < 1 << 31)
+
+
+def wino_prep_nin(parts, ac, silu, B, S, eq, pw, bias, dims=None, n_cu=0):
+    """(t, res): t = wino_prep(parts, ac, silu, 0, B, S, f8="f6", eq=eq), res = nin_f32(parts, pw, bias, B, P) -- the same bits, from ONE
+    pass over the fp32 parts (md_wino_prep_f6_nin).  pw None: the operand only (res is None)."""
+    lib = _lib.load()
+    D, H, W = dims if dims is not None else (S, S, S)
+    P = D * H * W
+    cin = sum(c for _, c in parts)
+    assert 1 <= len(parts) <= 2
+    assert eq is None or (eq.numel() == cin and eq.dtype == torch.float32 and eq.is_cuda), "eq: one float per input channel"
+    assert ac is not None or not silu, "SiLU is applied together with the folded GroupNorm affine (pass `ac`)"
+    nbytes = lib.md_wino_operand_bytes(B, cin, D, H, W)
+    if nbytes <= 0:
+        raise _lib.MeshDiffusionHipError("md_wino_operand_bytes: unsupported operand shape")
+    dev = parts[0][0].device
+    t = _wino_scratch(nbytes // 2, dev)
+    res = f32b_empty(B, 128, P, dev) if pw is not None else None
+    x2, c2 = (parts[1][0], parts[1][1]) if len(parts) == 2 else (None, 0)
+    ev = _prof_begin()
+    check(lib.md_wino_prep_f6_nin(_ptr(parts[0][0]), _ptr(x2), parts[0][1], c2, _ptr(ac), 1 if silu else 0, _ptr(eq), _ptr(t),
+                                  _ptr(pw.data) if pw is not None else None, _ptr(bias) if pw is not None else None, _ptr(res),
+                                  B, D, H, W, n_cu, _stream()), "md_wino_prep_f6_nin")
+    _prof_end(ev, "wino_prep", 2.0 * B * 128 * cin * P if pw is not None else 0.0,
+              4.0 * B * cin * P + 8.0 * B * cin * P + (4.0 * B * 128 * P if pw is not None else 0.0),   # fp32 in, operand out, fp32 shortcut out
+              f"{cin}@{D}x{H}x{W}/f6" + ("/nin" if pw is not None else "/bp"))
+    t._md_fmt = "f6"
+    t._md_eq = eq.data_ptr() if eq is not None else 0
+    t._md_compact = False
+    return t, res
+
+
 FUSE_ATTN = os.environ.get("MD_FUSE_ATTN", "1") == "1"   # fused QK^T / online softmax / PV kernel where it applies (inference)
 
 

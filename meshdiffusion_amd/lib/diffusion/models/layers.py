@@ -169,6 +169,8 @@ def run_conv3(pw, act_s16, B, S_out, *, bias=None, bias_bstride=0, residual=None
     kernel keeps reading `act_s16`.
     wino (with b_f32): builder of the layer's WinoWeight (conv3_wino_packed); where hip_ops.wino_ok says so the conv runs as
     md_wino_prep + md_conv3_wino (Winograd F(2,3) along w: 2/3 of the matrix-core work) instead of the direct kernel.
+    b_f32["nin"] = (pwn, bias) (inference, a ResnetBlock's shortcut NIN on the same parts): where the conv's operand pass can also
+    write the shortcut (hip_ops.block_pass_ok, f16f6) it does, handed back as b_f32["res_out"]; otherwise the key is left unset.
     b_f32["keep"] (training, layers with hip_ops.wgrad_wino_ok): the operand T is allocated on its own and handed back as
     b_f32["t_out"]; `act_s16` may then be None (nothing else reads the S16B activation of such a layer)."""
     P = S_out ** 3
@@ -200,8 +202,15 @@ def run_conv3(pw, act_s16, B, S_out, *, bias=None, bias_bstride=0, residual=None
             f8 = False                   # this conv was taken off the reduced-precision path (layer.md_bf16x3_sites: tools/audit_precision.py)
         # inference: an upsampled operand is written once per source row (the training forward keeps the full layout: md_wgrad_wino reads it)
         compact = (not b_f32.get("wino_only")) and ops.prep_compact_ok(ups, S_out, S_out, S_out, drop=b_f32.get("drop"), keep=bool(b_f32.get("keep")))
-        t = ops.wino_prep(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), ups, B, S_out, drop=b_f32.get("drop"),
-                          keep=bool(b_f32.get("keep")), f8=f8, eq=wino.eq() if f8 and hasattr(wino, "eq") else None, compact=compact)
+        nin = b_f32.get("nin")
+        if (nin is not None and f8 == "f6" and not compact and not ups and not b_f32.get("drop") and not b_f32.get("keep")
+                and not b_f32.get("wino_only") and ops.block_pass_ok(b_f32["parts"], nin[0].rows, B, S_out, S_out, S_out)):
+            # a block with a NIN shortcut: the shortcut comes out of the operand pass, which holds the block input anyway
+            t, b_f32["res_out"] = ops.wino_prep_nin(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), B, S_out,
+                                                    wino.eq() if hasattr(wino, "eq") else None, nin[0], nin[1])
+        else:
+            t = ops.wino_prep(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), ups, B, S_out, drop=b_f32.get("drop"),
+                              keep=bool(b_f32.get("keep")), f8=f8, eq=wino.eq() if f8 and hasattr(wino, "eq") else None, compact=compact)
         if b_f32.get("keep"):
             b_f32["t_out"] = t           # training: the Winograd weight gradient reads the operand again (tape)
         ops.conv3_wino(wino(f8) if f8 else wino(), t, B, S_out, bias=bias, bias_bstride=bias_bstride, residual=residual,
@@ -480,11 +489,16 @@ class ResnetBlockDDPM(HipLayer):
                     bias0, bias0_stride = ops.linear(temb, self.Dense_0.weight, self._bias0(), silu_in=True), self.out_ch
                 else:
                     bias0, bias0_stride = self.Conv_0.bias, 0
+            f0 = dict(parts=parts, ac=ac0, silu=True)
+            pwn = self.NIN_0.packed(P, hbm_bound=True) if need_nin else None
+            if need_nin and ops.BLOCK_PASS and pwn.kdim == cin and ops.nin_stream_ok(parts, self.out_ch, P):
+                f0["nin"] = (pwn, self.NIN_0.b)                     # Conv_0's operand pass may write the shortcut too
             h = run_conv3(pw0, None, B, S, bias=bias0, bias_bstride=bias0_stride, want_stats=True,
-                          b_f32=dict(parts=parts, ac=ac0, silu=True), wino=conv3_wino_packed(self, "w0", self.Conv_0, gn=g0))
+                          b_f32=f0, wino=conv3_wino_packed(self, "w0", self.Conv_0, gn=g0))
             if need_nin:
-                pwn = self.NIN_0.packed(P, hbm_bound=True)
-                if pwn.kdim == cin and ops.nin_stream_ok(parts, self.out_ch, P):   # weights resident in LDS, input streamed once
+                if f0.get("res_out") is not None:                   # one pass over the block input wrote operand and shortcut
+                    res = f0["res_out"]
+                elif pwn.kdim == cin and ops.nin_stream_ok(parts, self.out_ch, P):   # weights resident in LDS, input streamed once
                     res = ops.nin_f32(parts, pwn, self.NIN_0.b, B, P)
                 elif pwn.cfg in (ops.CFG_G1_128, ops.CFG_G1_128_N128) and pwn.kdim == cin:   # the shortcut GEMM splits the raw fp32 parts itself
                     res = run_gemm(pwn, None, B, P, bias=self.NIN_0.b, b_f32=dict(parts=parts, ac=None, silu=False))
