@@ -770,6 +770,60 @@ int md_sample_points(const float* verts, const int64_t* faces, const float* cdf,
 int md_sample_points_bwd(const float* grad_points, const float* weights, const int32_t* ptr, const int32_t* order,
                          int32_t batch, int32_t n_verts, int32_t n_samples, float* dverts, void* stream);
 
+/*
+ * Depth and silhouette rasteriser of the fitting loop (nvdiffrec/lib/render/render.py:287-329: dr.DepthPeeler, two layers, +
+ * dr.interpolate(v_pos) + the distance to the camera), csrc/raster.hip.  Purely additive: MD_ABI_VERSION stays 16.
+ *
+ * The rasterisation contract
+ *   pos_clip float32 [B][V][4] = (x, y, z, w) (16-byte aligned), faces int64 [F][3] shared by the views, resolution (H, W) with
+ *   H, W <= 2048, F < 2^24, B <= 64: anything else MD_ERR_UNSUPPORTED.  The kernels index with `faces` unchecked: the host checks
+ *   the range once (meshdiffusion_amd/render.py).
+ *   Snap: X = rint(((x / w) * 0.5 + 0.5) * (256 W)), Y likewise with H, zw = z / w; every fp32 operation rounded on its own
+ *   (correctly rounded divide, no contraction); X, Y clamped to +-2^22.
+ *   Skipped: a triangle with a vertex of w <= 0 or a non-finite coordinate (no clipping), or with integer doubled area
+ *   A2 = (X1-X0)(Y2-Y0) - (X2-X0)(Y1-Y0) == 0.  No back-face culling.
+ *   Coverage (exact integers): pixel (row i, column j) has the centre Q = (256 j + 128, 256 i + 128), row 0 is y = -1.  With the
+ *   triangle oriented so that A2 > 0, edge a -> b (d = b - a) has e = d.x (Q.y - a.y) - d.y (Q.x - a.x); covered iff all three
+ *   e >= 0, where e == 0 counts only if d.y < 0 or (d.y == 0 and d.x > 0).
+ *   Fragment depth: zf = sum_k (e_k / A2) zw_k in fp32 (e_k opposite vertex k); fragments with zf outside [-1, 1] are dropped.
+ *   Layers: by the key (zf, face index); layer 1 the smallest, layer 2 the second smallest; independent of the visiting order.
+ *   rast float32 [B][H][W][4] per layer: (u, v, zf, face index + 1), zeros where uncovered.  u, v: perspective-correct from the
+ *   unsnapped clip floats -- fx = (2j+1)/W - 1, fy = (2i+1)/H - 1, p_k = (x_k - fx w_k, y_k - fy w_k), a0 = p1 x p2, a1 = p2 x p0,
+ *   a2 = p0 x p1, u = a0 / (a0+a1+a2), v = a1 / (a0+a1+a2), not clamped; an attribute is u A0 + v A1 + (1-u-v) A2.
+ *   Depth buffers: gb_pos = that interpolation of the world vertices, depth = |gb_pos - campos|; uncovered: 20.0 (layer 1),
+ *   -1.0 (layer 2); mask = 1.0 where covered.
+ *   Gradient of both depth layers w.r.t. verts, ids fixed, through the attribute path AND the barycentric path (u, v <- pos_clip
+ *   <- verts through mvp); none for mvp / campos.
+ *
+ * md_raster_bin_count: counts int32 [B][F] = the 16x16-pixel tiles the bounding box of face f touches in view b (0: skipped or
+ *   off screen).
+ * md_raster_bin_emit: offsets int64 [B][F] = the exclusive prefix sum of counts, total = their sum (> 2^31 - 1:
+ *   MD_ERR_UNSUPPORTED); writes pair_tile int32 [total] = (b * tiles_y + ty) * tiles_x + tx and pair_face int32 [total].
+ * md_raster_tiles: tile_ptr int32 [B * tiles_y * tiles_x + 1], tile_faces int32 [total]: the pairs sorted by tile (CSR); writes
+ *   every element of rast1, rast2.
+ * md_raster_depth: verts float32 [V][3] (world space, shared by the views), campos float32 [B][3]; depth1/2, mask1/2 float32
+ *   [B][H][W].
+ * md_raster_depth_bwd: cov int32 [n_cov] = (b * 2 + layer) * H W + pixel of the covered entries (3 n_cov < 2^31), gd1 / gd2
+ *   float32 [B][H][W] = d L / d depth, mvp float32 [B][4][4] row-major (pos_clip = mvp (P, 1)); corner_grad float32 [n_cov][3][3]
+ *   workspace; (ptr int32 [V+1], order int32 [3 n_cov]) the CSR of the codes 3 * entry + corner sorted stably by
+ *   faces[id][corner]; dverts float32 [V][3], every element written.  A gather: no float atomics, bit-reproducible.
+ */
+int md_raster_bin_count(const float* pos_clip, const int64_t* faces, int32_t batch, int32_t n_verts, int32_t n_faces,
+                        int32_t H, int32_t W, int32_t* counts, void* stream);
+int md_raster_bin_emit(const float* pos_clip, const int64_t* faces, const int64_t* offsets, int32_t batch, int32_t n_verts,
+                       int32_t n_faces, int32_t H, int32_t W, int64_t total, int32_t* pair_tile, int32_t* pair_face,
+                       void* stream);
+int md_raster_tiles(const float* pos_clip, const int64_t* faces, const int32_t* tile_ptr, const int32_t* tile_faces,
+                    int32_t batch, int32_t n_verts, int32_t n_faces, int32_t H, int32_t W, float* rast1, float* rast2,
+                    void* stream);
+int md_raster_depth(const float* rast1, const float* rast2, const float* verts, const int64_t* faces, const float* campos,
+                    int32_t batch, int32_t n_verts, int32_t n_faces, int32_t H, int32_t W, float* depth1, float* depth2,
+                    float* mask1, float* mask2, void* stream);
+int md_raster_depth_bwd(const int32_t* cov, int32_t n_cov, const float* rast1, const float* rast2, const float* gd1,
+                        const float* gd2, const float* pos_clip, const float* verts, const int64_t* faces, const float* mvp,
+                        const float* campos, const int32_t* ptr, const int32_t* order, int32_t batch, int32_t n_verts,
+                        int32_t n_faces, int32_t H, int32_t W, float* corner_grad, float* dverts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

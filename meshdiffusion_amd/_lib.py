@@ -152,6 +152,12 @@ SIGNATURES = {
     "md_face_areas": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "md_sample_points": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "md_sample_points_bwd": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "md_raster_bin_count": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "md_raster_bin_emit": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I64, _P, _P, _P]),
+    "md_raster_tiles": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "md_raster_depth": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "md_raster_depth_bwd": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P,
+                                      _P]),
 }
 SDF_REG_SLABS = 64                                  # MD_SDF_REG_SLABS
 SDF_REG_WORKSPACE_BYTES = SDF_REG_SLABS * 24        # MD_SDF_REG_WORKSPACE_BYTES

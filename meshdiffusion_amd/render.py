@@ -1,0 +1,341 @@
+"""Depth and silhouette rendering for DMTet fitting on MI355X -- host side of csrc/raster.hip.
+
+The reference gets its depth buffers from nvdiffrast (nvdiffrec/lib/render/render.py:287-329): `xfm_points` -> two depth-peeled
+layers -> `interpolate(v_pos)` -> |gb_pos - campos|, and supervises the geometry with the depth terms of `DMTetGeometry.tick`
+(nvdiffrec/lib/geometry/dmtet.py:402-434) and the silhouette carve (:366-378).  This module is that path: `rasterize` and
+`render_depth` follow the rasterisation contract in the header comment of csrc/raster.hip, `depth_loss`, `make_targets`,
+`carve_outside_silhouette` and `fit_to_views` are the loop around it.  The kernels run on the GPU only: a CPU tensor is an
+error, not a fallback.  The camera helpers, `xfm_points`, `depth_loss` and the carve are plain torch and run anywhere.
+
+Not built: dr.antialias (so alpha / colour terms would give no geometry gradient), materials, lights,
+BSDFs, textures, spp > 1 / MSAA, clipping of triangles that cross w = 0, more than two layers, gradients for mvp / campos.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .hip_ops import _ptr, _stream
+
+TILE = 16                                # RS_TILE of csrc/raster.hip
+MAX_RES, MAX_VIEWS, MAX_FACES = 2048, 64, 2 ** 24 - 1
+
+
+# ---- camera matrices (nvdiffrec/lib/render/util.py:193-277: float32 tensors of numpy-double entries) ---------------------------
+def _mat(rows, device):
+    return torch.tensor(rows, dtype=torch.float32, device=device)
+
+
+def perspective(fovy=0.7854, aspect=1.0, n=0.1, f=1000.0, device=None):
+    """gluPerspective with y flipped (row 0 of the image is y = -1)."""
+    y = np.tan(fovy / 2)
+    return _mat([[1 / (y * aspect), 0, 0, 0], [0, 1 / -y, 0, 0], [0, 0, -(f + n) / (f - n), -(2 * f * n) / (f - n)],
+                 [0, 0, -1, 0]], device)
+
+
+def translate(x, y, z, device=None):
+    return _mat([[1, 0, 0, x], [0, 1, 0, y], [0, 0, 1, z], [0, 0, 0, 1]], device)
+
+
+def rotate_x(a, device=None):
+    s, c = np.sin(a), np.cos(a)
+    return _mat([[1, 0, 0, 0], [0, c, s, 0], [0, -s, c, 0], [0, 0, 0, 1]], device)
+
+
+def rotate_y(a, device=None):
+    s, c = np.sin(a), np.cos(a)
+    return _mat([[c, 0, s, 0], [0, 1, 0, 0], [-s, 0, c, 0], [0, 0, 0, 1]], device)
+
+
+@torch.no_grad()
+def random_rotation_translation(t, device=None):
+    """A random frame and a translation in [-t, t]^3, drawn from numpy's global stream in the reference's order (nine
+    normals, then three uniforms)."""
+    m = np.random.normal(size=[3, 3])
+    m[1] = np.cross(m[0], m[2])
+    m[2] = np.cross(m[0], m[1])
+    m = m / np.linalg.norm(m, axis=1, keepdims=True)
+    out = np.zeros((4, 4))
+    out[:3, :3] = m
+    out[3, 3] = 1.0
+    out[:3, 3] = np.random.uniform(-t, t, size=[3])
+    return torch.tensor(out, dtype=torch.float32, device=device)
+
+
+def xfm_points(points, matrix):
+    """points [1|B,V,3] (or [V,3]), matrix [B,4,4] -> [B,V,4] = matrix (p, 1) (the reference's ru.xfm_points).  Differentiable;
+    the four products are summed left to right elementwise, so the CPU and the GPU give the same bits."""
+    p = points[None] if points.dim() == 2 else points
+    if p.dim() != 3 or p.shape[-1] != 3 or matrix.dim() != 3 or matrix.shape[1:] != (4, 4):
+        raise ValueError(f"xfm_points: expected points [1|B,V,3] and matrix [B,4,4], got {tuple(points.shape)} and {tuple(matrix.shape)}")
+    if p.shape[0] not in (1, matrix.shape[0]):
+        raise ValueError("xfm_points: points need batch size 1 or that of the matrices")
+    m = matrix[:, None]
+    return ((p[..., 0:1] * m[..., 0] + p[..., 1:2] * m[..., 1]) + p[..., 2:3] * m[..., 2]) + m[..., 3]
+
+
+# ---- rasterisation -----------------------------------------------------------------------------------------------------------------
+def _gpu_only(t, what):
+    if not t.is_cuda:
+        raise _lib.MeshDiffusionHipError(f"{what} runs on the GPU only (no CPU fallback)")
+
+
+def _resolution(resolution):
+    H, W = (int(resolution), int(resolution)) if np.isscalar(resolution) else (int(resolution[0]), int(resolution[1]))
+    if H < 1 or W < 1:
+        raise ValueError(f"resolution must be positive, got {(H, W)}")
+    if H > MAX_RES or W > MAX_RES:
+        raise _lib.MeshDiffusionHipError(f"resolution {(H, W)} exceeds {MAX_RES} (MD_ERR_UNSUPPORTED)")
+    return H, W
+
+
+def _check_faces(faces, n_verts):
+    """faces int64 [F,3] contiguous on the device, F >= 0, every index in [0, n_verts): checked once, the kernels index unchecked."""
+    if faces.dim() != 2 or faces.shape[-1] != 3:
+        raise ValueError(f"expected faces [F,3], got {tuple(faces.shape)}")
+    if faces.shape[0] > MAX_FACES:
+        raise _lib.MeshDiffusionHipError("the rasteriser takes fewer than 2^24 faces (MD_ERR_UNSUPPORTED)")
+    f = faces.to(torch.int64).contiguous()
+    if f.shape[0] > 0:
+        lo, hi = torch.aminmax(f)
+        if int(lo) < 0 or int(hi) >= n_verts:
+            raise ValueError(f"faces name vertices outside [0, {n_verts})")
+    return f
+
+
+def _check_clip(pos_clip):
+    if pos_clip.dim() != 3 or pos_clip.shape[-1] != 4 or pos_clip.shape[0] < 1 or pos_clip.shape[1] < 1:
+        raise ValueError(f"expected pos_clip [B,V,4] with B, V >= 1, got {tuple(pos_clip.shape)}")
+    if pos_clip.shape[0] > MAX_VIEWS:
+        raise _lib.MeshDiffusionHipError(f"the rasteriser takes at most {MAX_VIEWS} views per call (MD_ERR_UNSUPPORTED)")
+
+
+def _bin(pc, f, H, W):
+    """The tile CSR of the triangles: (tile_ptr int32 [B * tiles + 1], tile_faces int32 [pairs]), or None when no triangle
+    touches a tile.  Two kernels with a torch.cumsum between them, then a stable torch sort by tile."""
+    lib = _lib.load()
+    B, V, F, dev = pc.shape[0], pc.shape[1], f.shape[0], pc.device
+    if F == 0:
+        return None
+    counts = torch.empty(B * F, dtype=torch.int32, device=dev)
+    _lib.check(lib.md_raster_bin_count(_ptr(pc), _ptr(f), B, V, F, H, W, _ptr(counts), _stream()), "md_raster_bin_count")
+    ends = torch.cumsum(counts, 0, dtype=torch.int64)
+    total = int(ends[-1])
+    if total > 2 ** 31 - 1:
+        raise _lib.MeshDiffusionHipError(f"{total} (tile, triangle) pairs exceed 2^31 - 1 (MD_ERR_UNSUPPORTED)")
+    if total == 0:
+        return None
+    offsets = (ends - counts).contiguous()
+    pair_tile = torch.empty(total, dtype=torch.int32, device=dev)
+    pair_face = torch.empty(total, dtype=torch.int32, device=dev)
+    _lib.check(lib.md_raster_bin_emit(_ptr(pc), _ptr(f), _ptr(offsets), B, V, F, H, W, total, _ptr(pair_tile), _ptr(pair_face),
+                                      _stream()), "md_raster_bin_emit")
+    n_tiles = B * ((H + TILE - 1) // TILE) * ((W + TILE - 1) // TILE)
+    sorted_tile, order = torch.sort(pair_tile, stable=True)
+    tile_faces = pair_face[order].contiguous()
+    tile_ptr = torch.searchsorted(sorted_tile, torch.arange(n_tiles + 1, dtype=torch.int32, device=dev)).to(torch.int32).contiguous()
+    return tile_ptr, tile_faces
+
+
+def _rasterize(pc, f, H, W):
+    """pc float32 [B,V,4] contiguous, f checked faces -> (rast1, rast2) float32 [B,H,W,4]."""
+    lib = _lib.load()
+    B, V, F, dev = pc.shape[0], pc.shape[1], f.shape[0], pc.device
+    csr = _bin(pc, f, H, W)
+    if csr is None:
+        return torch.zeros((B, H, W, 4), dtype=torch.float32, device=dev), torch.zeros((B, H, W, 4), dtype=torch.float32, device=dev)
+    rast1 = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
+    rast2 = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
+    _lib.check(lib.md_raster_tiles(_ptr(pc), _ptr(f), _ptr(csr[0]), _ptr(csr[1]), B, V, F, H, W, _ptr(rast1), _ptr(rast2),
+                                   _stream()), "md_raster_tiles")
+    return rast1, rast2
+
+
+def rasterize(pos_clip, faces, resolution, num_layers=2):
+    """The contract's `rast` layers of pos_clip float32 [B,V,4], faces [F,3] at resolution (H, W) (or one int): a list of
+    `num_layers` (1 or 2) float32 [B,H,W,4] tensors (u, v, zf, face index + 1), zeros where uncovered.  No gradient."""
+    _gpu_only(pos_clip, "rasterize")
+    if num_layers not in (1, 2):
+        raise NotImplementedError("rasterize: one or two layers")
+    _check_clip(pos_clip)
+    H, W = _resolution(resolution)
+    pc = pos_clip.detach().to(torch.float32).contiguous()
+    f = _check_faces(faces.to(pc.device), pc.shape[1])
+    return list(_rasterize(pc, f, H, W)[:num_layers])
+
+
+class _RenderDepthFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts, pos_clip, faces, mvp, campos, H, W):
+        lib = _lib.load()
+        B, V, F, dev = pos_clip.shape[0], verts.shape[0], faces.shape[0], verts.device
+        rast1, rast2 = _rasterize(pos_clip, faces, H, W)
+        depth1 = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev)
+        depth2, mask1, mask2 = torch.empty_like(depth1), torch.empty_like(depth1), torch.empty_like(depth1)
+        if F == 0:
+            depth1.fill_(20.0), depth2.fill_(-1.0), mask1.zero_(), mask2.zero_()
+        else:
+            _lib.check(lib.md_raster_depth(_ptr(rast1), _ptr(rast2), _ptr(verts), _ptr(faces), _ptr(campos), B, V, F, H, W,
+                                           _ptr(depth1), _ptr(depth2), _ptr(mask1), _ptr(mask2), _stream()), "md_raster_depth")
+        ctx.save_for_backward(verts, pos_clip, faces, mvp, campos, rast1, rast2)
+        ctx.res = (H, W)
+        ctx.mark_non_differentiable(mask1, mask2, rast1, rast2)
+        return depth1, depth2, mask1, mask2, rast1, rast2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g1, g2, *_unused):
+        lib = _lib.load()
+        verts, pos_clip, faces, mvp, campos, rast1, rast2 = ctx.saved_tensors
+        H, W = ctx.res
+        B, V, F, dev = pos_clip.shape[0], verts.shape[0], faces.shape[0], verts.device
+        g1 = torch.zeros((B, H, W), dtype=torch.float32, device=dev) if g1 is None else g1.to(torch.float32).reshape(B, H, W).contiguous()
+        g2 = torch.zeros((B, H, W), dtype=torch.float32, device=dev) if g2 is None else g2.to(torch.float32).reshape(B, H, W).contiguous()
+        ids = torch.stack([rast1[..., 3], rast2[..., 3]], 1).reshape(-1)        # [B,2,H,W]: the code of an entry is its flat index
+        cov = torch.nonzero(ids > 0)[:, 0]
+        N = cov.numel()
+        if 3 * N >= 2 ** 31:
+            raise _lib.MeshDiffusionHipError("render_depth backward: 3 x the covered (pixel, layer) entries must fit int32")
+        dverts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        if N == 0 or F == 0:
+            return dverts.zero_(), None, None, None, None, None, None
+        corner_vert = faces[ids[cov].to(torch.int64) - 1].reshape(-1)          # entry 3 n + corner names this vertex
+        vals, order = torch.sort(corner_vert, stable=True)
+        ptr = torch.searchsorted(vals, torch.arange(V + 1, dtype=torch.int64, device=dev)).to(torch.int32).contiguous()
+        order = order.to(torch.int32).contiguous()
+        cov = cov.to(torch.int32).contiguous()
+        corner_grad = torch.empty((N, 3, 3), dtype=torch.float32, device=dev)
+        _lib.check(lib.md_raster_depth_bwd(_ptr(cov), N, _ptr(rast1), _ptr(rast2), _ptr(g1), _ptr(g2), _ptr(pos_clip), _ptr(verts),
+                                           _ptr(faces), _ptr(mvp), _ptr(campos), _ptr(ptr), _ptr(order), B, V, F, H, W,
+                                           _ptr(corner_grad), _ptr(dverts), _stream()), "md_raster_depth_bwd")
+        return dverts, None, None, None, None, None, None
+
+
+def render_depth(verts, faces, mvp, campos, resolution):
+    """The depth part of the reference's render_mesh: world-space verts [V,3] (or [1,V,3]) shared by the B views mvp [B,4,4]
+    with camera centres campos [B,3] -> dict of
+      depth, depth_second   float32 [B,H,W,1]: |gb_pos - campos| of layer 1 / 2, 20.0 / -1.0 where uncovered; they carry a
+                            grad_fn when `verts` requires a gradient (ids held fixed; attribute and barycentric path)
+      mask, mask_second     float32 [B,H,W,1]: 1.0 where covered
+      rast, rast_second     float32 [B,H,W,4]: (u, v, zf, face index + 1)
+      rast_triangle_id      the sorted unique visible face ids of layer 1 (int64), or None when nothing is visible.
+    The rasterised tensor is exactly `xfm_points(verts[None], mvp)`."""
+    _gpu_only(verts, "render_depth")
+    v = verts[0] if verts.dim() == 3 and verts.shape[0] == 1 else verts
+    if v.dim() != 2 or v.shape[-1] != 3 or v.shape[0] < 1:
+        raise ValueError(f"render_depth: expected verts [V,3] or [1,V,3], got {tuple(verts.shape)}")
+    if mvp.dim() != 3 or mvp.shape[1:] != (4, 4) or campos.shape != (mvp.shape[0], 3):
+        raise ValueError(f"render_depth: expected mvp [B,4,4] and campos [B,3], got {tuple(mvp.shape)} and {tuple(campos.shape)}")
+    H, W = _resolution(resolution)
+    v = v.to(torch.float32).contiguous()
+    mvp = mvp.detach().to(device=v.device, dtype=torch.float32).contiguous()
+    campos = campos.detach().to(device=v.device, dtype=torch.float32).contiguous()
+    pos_clip = xfm_points(v.detach()[None], mvp).contiguous()
+    _check_clip(pos_clip)
+    f = _check_faces(faces.to(v.device), v.shape[0])
+    depth, depth2, mask, mask2, rast, rast2 = _RenderDepthFn.apply(v, pos_clip, f, mvp, campos, H, W)
+    tri = torch.unique(rast[..., 3])
+    tri = tri[tri > 0].to(torch.int64) - 1
+    return {"depth": depth, "depth_second": depth2, "mask": mask, "mask_second": mask2, "rast": rast, "rast_second": rast2,
+            "rast_triangle_id": tri if tri.numel() > 0 else None}
+
+
+# ---- losses and the fitting loop ---------------------------------------------------------------------------------------------------
+def depth_loss(buffers, target, iteration):
+    """The depth terms of DMTetGeometry.tick (dmtet.py:402-434) with no_depth_thin: elementwise torch.
+    buffers: `depth`, `depth_second`; target: `depth`, `depth_second`, `mask_cont`, all [B,H,W,1]."""
+    mask = (target["mask_cont"][..., 0] == 1.0).float().unsqueeze(-1)
+    valid = (target["depth_second"] >= 0).float()
+    prox = ((target["depth_second"] - target["depth"]).abs() >= 5e-3).float()
+    d1 = (buffers["depth"][..., :1] - target["depth"][..., :1]).abs() * mask * valid
+    d2 = (buffers["depth_second"][..., :1] - target["depth_second"][..., :1]).abs() * mask * valid * prox * 0.1
+    scale = 100.0 if iteration < 10000 else 1.0
+
+    def huber(d):
+        return torch.where(d < 1.0, d, d * d)
+    return (huber(d1).mean() + huber(d2).mean()) * scale
+
+
+@torch.no_grad()
+def make_targets(verts, faces, mvp, campos, resolution):
+    """Render the ground-truth mesh with the same rasteriser (the role of dataset_mesh.py:120): `depth`, `depth_second`,
+    `mask_cont` [B,H,W,1], and the cameras `mvp`, `campos`, `resolution`."""
+    out = render_depth(verts.detach(), faces, mvp, campos, resolution)
+    H, W = _resolution(resolution)
+    return {"depth": out["depth"], "depth_second": out["depth_second"], "mask_cont": out["mask"],
+            "mvp": mvp.detach().to(device=verts.device, dtype=torch.float32), "campos": campos.detach().to(device=verts.device, dtype=torch.float32),
+            "resolution": [H, W]}
+
+
+@torch.no_grad()
+def carve_outside_silhouette(geometry, target, kernel_size=11):
+    """The carve of tick (dmtet.py:366-378): project the deformed grid vertices, round to pixels, dilate `mask_cont` with a
+    `kernel_size` box; where a vertex lands on a pixel whose dilated mask is 0 in ANY view, sdf = 1e-2 and deform = 0.
+    x is scaled with the width and y with the height.  Returns the number of vertices carved."""
+    v = geometry.get_deformed().detach()
+    H, W = target["resolution"]
+    clip = xfm_points(v[None], target["mvp"])
+    ndc = clip[..., :2] / clip[..., 3:4]
+    px = torch.round((ndc[..., 0] * 0.5 + 0.5).clip(0, 1) * (W - 1)).long()
+    py = torch.round((ndc[..., 1] * 0.5 + 0.5).clip(0, 1) * (H - 1)).long()
+    m = target["mask_cont"][..., 0].unsqueeze(1)
+    box = torch.ones((1, 1, kernel_size, kernel_size), dtype=m.dtype, device=m.device) / (kernel_size * kernel_size)
+    dilated = torch.nn.functional.conv2d(m, box, stride=1, padding=kernel_size // 2)[:, 0]
+    outside = dilated == 0
+    carved = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
+    for k in range(outside.shape[0]):
+        carved |= outside[k, py[k], px[k]]
+    geometry.sdf.data[carved] = 1e-2
+    geometry.deform.data[carved] = 0.0
+    return int(carved.sum())
+
+
+def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, views_per_iter=None, generator=None,
+                 target_points=None, num_samples=50000, carve=True, callback=None, start_iteration=0):
+    """Fit a `DMTetGeometry` to rendered targets (`make_targets`) the way the reference's tick supervises geometry: per
+    iteration
+        [carve, for 200 < it < 2000 and it % 20 == 0] -> [deform *= 0.4, for it % 300 == 0 and it < 1790]
+        -> getMesh -> render_depth on `views_per_iter` views -> depth_loss + sdf_reg_loss(masked sdf) * weight * 0.1
+        [+ chamfer(sample_points(num_samples), target_points)] -> Adam step on (sdf, deform) -> clamp_deform.
+    views_per_iter: None = every view each iteration, else that many drawn without replacement (torch.randperm, `generator`).
+    `callback(it, loss, mesh)` after each step.  Returns the depth-loss values, float32 [iters] on the device."""
+    from .dmtet import sdf_reg_loss
+    from .pointcloud import chamfer_distance, sample_points, sdf_regularizer_weight
+    dev = geometry.sdf.device
+    _gpu_only(geometry.sdf, "fit_to_views")
+    n_views = targets["mvp"].shape[0]
+    pts = None if target_points is None else target_points.detach().to(device=dev, dtype=torch.float32).reshape(1, -1, 3).contiguous()
+    opt = torch.optim.Adam([geometry.sdf, geometry.deform], lr=lr)
+    history = []
+    for k in range(iters):
+        it = start_iteration + k
+        if views_per_iter is None or views_per_iter >= n_views:
+            tgt = targets
+        else:
+            sel = torch.randperm(n_views, generator=generator, device=generator.device if generator is not None else "cpu")
+            sel = sel[:views_per_iter].to(dev)
+            tgt = {key: (val[sel] if torch.is_tensor(val) and val.shape[0] == n_views else val) for key, val in targets.items()}
+        if carve and 200 < it < 2000 and it % 20 == 0:
+            carve_outside_silhouette(geometry, tgt)
+        if it % 300 == 0 and it < 1790:
+            with torch.no_grad():
+                geometry.deform.data[:] *= 0.4
+        opt.zero_grad(set_to_none=True)
+        mesh = geometry.getMesh()
+        if mesh.t_pos_idx.shape[0] == 0:
+            raise _lib.MeshDiffusionHipError(f"fit_to_views: the mesh of iteration {it} has no faces")
+        buffers = render_depth(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"])
+        loss = depth_loss(buffers, tgt, it)
+        sdf_mask = torch.zeros_like(geometry.sdf)
+        sdf_mask[mesh.valid_vert_idx] = 1.0
+        sdf_masked = geometry.sdf.detach() * sdf_mask + geometry.sdf * (1 - sdf_mask)
+        total = loss + sdf_reg_loss(sdf_masked, geometry.all_edges).mean() * sdf_regularizer_weight(it, start_iteration + iters, sdf_regularizer) * 0.1
+        if pts is not None:
+            pred = sample_points(mesh.v_pos[None], mesh.t_pos_idx, num_samples, generator=generator)[0]
+            total = total + chamfer_distance(pred, pts).mean()
+        total.backward()
+        opt.step()
+        geometry.clamp_deform()
+        history.append(loss.detach())
+        if callback is not None:
+            callback(it, history[-1], mesh)
+    return torch.stack(history) if history else torch.empty(0, device=dev)

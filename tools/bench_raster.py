@@ -1,0 +1,148 @@
+"""Depth rasteriser cost, one process, at 512 x 512 with B = 1 and 8 views on the sphere and the noise mesh of
+tests/raster_cases.py:
+  (a) forward, two layers (`rasterize`) and forward + backward (`render_depth` and the gradient of both depth layers), in ms;
+  (b) the split of (a) between the kernels (binning count / emit, tile kernel, depth, backward) and the torch glue around them
+      (cumsum, the stable sort by tile, searchsorted, the CSR of the backward);
+  (c) (pixel, triangle) coverage tests per second of the tile kernel: 256 x the (tile, triangle) pairs per launch;
+  (d) the baseline: the fp32 torch restatement of the contract (tests/raster_cases.py) on the same GPU, forward and
+      forward + backward, one repetition;
+  (e) one fit_to_views iteration on the shipped 64 grid (sphere start, torus target, 8 views at 512 x 512), next to the
+      chamfer iteration of tools/bench_pointcloud.py.
+Device events after warm-up; each figure is the median over rounds.
+    python tools/bench_raster.py [--res 512] [--rounds 5] [--reps 5] [--json PATH] [--no-baseline]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from bench_pc import timed  # noqa: E402
+
+
+def median_ms(fn, rounds, reps):
+    fn()
+    torch.cuda.synchronize()
+    return statistics.median(timed(fn, reps) for _ in range(rounds))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, default=512)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--no-baseline", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_raster.py needs a GPU: the HIP path has no CPU fallback")
+    import raster_cases as rc
+    from meshdiffusion_amd import _lib, render
+    from meshdiffusion_amd.dmtet import DMTetGeometry
+    from meshdiffusion_amd.hip_ops import _ptr, _stream
+    lib = _lib.load()
+    H = W = a.res
+    rec = {"res": a.res, "rounds": a.rounds, "reps": a.reps, "cases": {}}
+    for name in ("sphere", "noise"):
+        verts, faces = (t.cuda() for t in rc.mesh(name))
+        V, F = verts.shape[0], faces.shape[0]
+        for B in (1, 8):
+            angles = [0.7 + 2 * 3.141592653589793 * k / B for k in range(B)]
+            mvp, campos = (t.cuda() for t in rc.cameras(angles, H, W))
+            pc = render.xfm_points(verts[None], mvp).contiguous()
+            G = torch.randn(B, H, W, 1, device="cuda")
+
+            def fwd():
+                return render.rasterize(pc, faces, (H, W))
+
+            def fwd_bwd():
+                v = verts.detach().requires_grad_(True)
+                out = render.render_depth(v, faces, mvp, campos, (H, W))
+                ((out["depth"] * G).sum() + (out["depth_second"] * G).sum()).backward()
+                return v.grad
+
+            # the kernels alone, on buffers built once
+            counts = torch.empty(B * F, dtype=torch.int32, device="cuda")
+            k_count = lambda: _lib.check(lib.md_raster_bin_count(_ptr(pc), _ptr(faces), B, V, F, H, W, _ptr(counts), _stream()), "count")  # noqa: E731
+            k_count()
+            ends = torch.cumsum(counts, 0, dtype=torch.int64)
+            total = int(ends[-1])
+            offsets = (ends - counts).contiguous()
+            pt, pf = torch.empty(total, dtype=torch.int32, device="cuda"), torch.empty(total, dtype=torch.int32, device="cuda")
+            k_emit = lambda: _lib.check(lib.md_raster_bin_emit(_ptr(pc), _ptr(faces), _ptr(offsets), B, V, F, H, W, total, _ptr(pt), _ptr(pf), _stream()), "emit")  # noqa: E731
+            tile_ptr, tile_faces = render._bin(pc, faces, H, W)
+            r1 = torch.empty(B, H, W, 4, device="cuda")
+            r2 = torch.empty_like(r1)
+            k_tiles = lambda: _lib.check(lib.md_raster_tiles(_ptr(pc), _ptr(faces), _ptr(tile_ptr), _ptr(tile_faces), B, V, F, H, W, _ptr(r1), _ptr(r2), _stream()), "tiles")  # noqa: E731
+            k_tiles()
+            d1, d2, m1, m2 = (torch.empty(B, H, W, 1, device="cuda") for _ in range(4))
+            k_depth = lambda: _lib.check(lib.md_raster_depth(_ptr(r1), _ptr(r2), _ptr(verts), _ptr(faces), _ptr(campos), B, V, F, H, W, _ptr(d1), _ptr(d2), _ptr(m1), _ptr(m2), _stream()), "depth")  # noqa: E731
+            ids = torch.stack([r1[..., 3], r2[..., 3]], 1).reshape(-1)
+            cov = torch.nonzero(ids > 0)[:, 0]
+            N = cov.numel()
+            vals, order = torch.sort(faces[ids[cov].long() - 1].reshape(-1), stable=True)
+            ptr = torch.searchsorted(vals, torch.arange(V + 1, device="cuda")).to(torch.int32).contiguous()
+            order, cov32 = order.to(torch.int32).contiguous(), cov.to(torch.int32).contiguous()
+            cg, dv = torch.empty(N, 3, 3, device="cuda"), torch.empty(V, 3, device="cuda")
+            g1 = G.reshape(B, H, W).contiguous()
+            k_bwd = lambda: _lib.check(lib.md_raster_depth_bwd(_ptr(cov32), N, _ptr(r1), _ptr(r2), _ptr(g1), _ptr(g1), _ptr(pc), _ptr(verts), _ptr(faces), _ptr(mvp), _ptr(campos), _ptr(ptr), _ptr(order), B, V, F, H, W, _ptr(cg), _ptr(dv), _stream()), "bwd")  # noqa: E731
+
+            ms = {k: median_ms(f, a.rounds, a.reps) for k, f in (("forward", fwd), ("forward_backward", fwd_bwd), ("k_bin_count", k_count),
+                                                               ("k_bin_emit", k_emit), ("k_tiles", k_tiles), ("k_depth", k_depth),
+                                                               ("k_backward", k_bwd))}
+            k_fwd = ms["k_bin_count"] + ms["k_bin_emit"] + ms["k_tiles"]
+            k_all = k_fwd + ms["k_depth"] + ms["k_backward"]
+            tests = 256.0 * total / (ms["k_tiles"] * 1e-3)
+            line = (f"{name} V={V} F={F} B={B} {H}x{W}: forward {ms['forward']:.3f} ms (kernels {k_fwd:.3f}: count {ms['k_bin_count']:.3f} emit "
+                    f"{ms['k_bin_emit']:.3f} tiles {ms['k_tiles']:.3f}; torch glue {ms['forward'] - k_fwd:.3f}) | forward+backward "
+                    f"{ms['forward_backward']:.3f} ms (kernels {k_all:.3f}: depth {ms['k_depth']:.3f} backward {ms['k_backward']:.3f}; torch glue "
+                    f"{ms['forward_backward'] - k_all:.3f}) | {total} (tile, triangle) pairs, {tests / 1e9:.1f} G (pixel, triangle) tests/s | covered entries {N}")
+            if not a.no_baseline:
+                try:
+                    def base_fwd():
+                        return rc.rasterize_restated(pc, faces, H, W)["ids"]
+
+                    def base_fwd_bwd():
+                        return rc.grad_restated(verts, faces, mvp, campos, base_fwd(), torch.cat([G, G], 3).permute(0, 3, 1, 2), torch.float32)
+                    ms["baseline_forward"] = median_ms(base_fwd, 1, 1)
+                    ms["baseline_forward_backward"] = median_ms(base_fwd_bwd, 1, 1)
+                    line += (f" | fp32 torch restatement: forward {ms['baseline_forward']:.1f} ms (x{ms['baseline_forward'] / ms['forward']:.0f}) "
+                             f"forward+backward {ms['baseline_forward_backward']:.1f} ms (x{ms['baseline_forward_backward'] / ms['forward_backward']:.0f})")
+                except torch.cuda.OutOfMemoryError:
+                    line += " | fp32 torch restatement: out of memory at this size, not timed"
+                    torch.cuda.empty_cache()
+            print(line, flush=True)
+            rec["cases"][f"{name}_B{B}"] = dict({k: round(v, 4) for k, v in ms.items()}, pairs=total, tests_per_s=tests, covered=N, V=V, F=F)
+
+    # one fitting iteration: shipped grid, sphere start, torus target, 8 views
+    geo = DMTetGeometry(64, rc.MESH_SCALE, None, tets=rc.tet_grid(), deform_scale=2.0)
+    with torch.no_grad():
+        geo.sdf.copy_(rc.fit_initial_sdf(geo.verts))
+    tv, tf = (t.cuda() for t in rc.mesh("torus"))
+    for B, res in ((4, 64), (8, a.res)):
+        mvp, campos = (t.cuda() for t in rc.cameras([2 * 3.141592653589793 * k / B for k in range(B)], res, res))
+        targets = render.make_targets(tv, tf, mvp, campos, res)
+        state = {"it": 1}
+
+        def fit_iter():
+            render.fit_to_views(geo, targets, 1, lr=1e-4, carve=False, start_iteration=state["it"])
+            state["it"] += 1
+        t = median_ms(fit_iter, a.rounds, a.reps)
+        print(f"fit_to_views iteration, {B} views at {res}x{res} (marching tets + render_depth + depth loss + regulariser + Adam, a new "
+              f"optimiser each call): {t:.3f} ms  (the chamfer iteration of tools/bench_pointcloud.py: 3.2 ms)", flush=True)
+        rec[f"fit_iter_B{B}_{res}"] = round(t, 4)
+    print(json.dumps(rec), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

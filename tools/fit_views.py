@@ -1,0 +1,90 @@
+"""Fit a DMTet grid to a mesh under depth supervision, the way the reference's fit_dmtets.py supervises geometry: `.obj` ->
+depth / silhouette targets of --views cameras (rendered with the project's own rasteriser) -> DMTetGeometry fitted with the
+depth loss, the SDF regulariser, the silhouette carve and, with --points, the chamfer distance -> the `{'sdf', 'deform'}` dict
+that `mesh_export.dicts_to_grids` turns into a training grid.
+
+    python tools/fit_views.py --obj shape.obj --tet_path data/tets/64_tets_cropped.npz --views 16 --res 256 --out fitted/dmt_dict_00000.pt
+and then `mesh_export.dicts_to_grids(tet_vertices, "fitted", "grids", 64, [0])` writes grids/grid_00000.pt.
+
+The mesh is centred and scaled into the tet grid's volume (largest half-extent -> --fit_scale).  Camera k of N looks at the
+origin from distance --cam_radius: perspective(--fovy, 1, 0.1, 1000) @ translate(0, 0, -radius) @ rotate_x(elevation_k) @
+rotate_y(2 pi k / N), the elevations alternating between +-0.4.  The loop is meshdiffusion_amd.render.fit_to_views.  GPU only."""
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def orbit_cameras(n, radius, fovy, device):
+    """(mvp [n,4,4], campos [n,3]) of n cameras around the y axis."""
+    from meshdiffusion_amd import render
+    proj = render.perspective(fovy, 1.0, 0.1, 1000.0)
+    mvps, cams = [], []
+    for k in range(n):
+        mv = render.translate(0, 0, -radius) @ render.rotate_x(-0.4 if k % 2 == 0 else 0.4) @ render.rotate_y(2 * math.pi * k / n)
+        mvps.append(proj @ mv)
+        cams.append(torch.linalg.inv(mv)[:3, 3])
+    return torch.stack(mvps).to(device), torch.stack(cams).to(device)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--obj", required=True, help="triangle mesh to fit")
+    ap.add_argument("--tet_path", required=True, help="<R>_tets_cropped.npz (vertices, indices)")
+    ap.add_argument("--out", required=True, help="path of the dict to write, e.g. fitted/dmt_dict_00000.pt")
+    ap.add_argument("--views", type=int, default=16)
+    ap.add_argument("--res", type=int, default=256)
+    ap.add_argument("--views_per_iter", type=int, default=4)
+    ap.add_argument("--resolution", type=int, default=64, help="resolution of the tet grid")
+    ap.add_argument("--iters", type=int, default=2000)
+    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--sdf_regularizer", type=float, default=0.2)
+    ap.add_argument("--points", type=int, default=0, help="> 0: add the chamfer term with this many target points and samples")
+    ap.add_argument("--mesh_scale", type=float, default=2.1)
+    ap.add_argument("--deform_scale", type=float, default=2.0)
+    ap.add_argument("--fit_scale", type=float, default=0.8, help="largest half-extent of the normalised target")
+    ap.add_argument("--cam_radius", type=float, default=3.0)
+    ap.add_argument("--fovy", type=float, default=math.radians(45.0))
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--sphere_init", type=float, default=0.0, help="start from a sphere of this radius instead of the random SDF")
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("fit_views.py needs a GPU: the HIP path has no CPU fallback")
+    from meshdiffusion_amd import mesh_export, render
+    from meshdiffusion_amd.dmtet import DMTetGeometry
+    from meshdiffusion_amd.pointcloud import sample_points
+
+    torch.manual_seed(a.seed)
+    gen = torch.Generator(device="cuda").manual_seed(a.seed)
+    verts, faces = mesh_export.load_obj(a.obj)
+    v = torch.as_tensor(verts, dtype=torch.float32).cuda()
+    f = torch.as_tensor(faces).cuda()
+    lo, hi = v.min(0).values, v.max(0).values
+    v = (v - (lo + hi) / 2) * (a.fit_scale / float((hi - lo).max() / 2))
+    mvp, campos = orbit_cameras(a.views, a.cam_radius, a.fovy, "cuda")
+    targets = render.make_targets(v, f, mvp, campos, a.res)
+    points = sample_points(v[None], f, a.points, generator=gen)[0][0] if a.points > 0 else None
+    tet = np.load(a.tet_path)
+    geo = DMTetGeometry(a.resolution, a.mesh_scale, None, tets=(tet["vertices"], tet["indices"]), deform_scale=a.deform_scale)
+    if a.sphere_init > 0:
+        with torch.no_grad():
+            geo.sdf.copy_((a.sphere_init - geo.verts.norm(dim=1)).clamp(-1.0, 1.0))
+
+    def report(it, loss, mesh):
+        if it % 100 == 0 or it == a.iters - 1:
+            print(f"iter {it}: depth loss {float(loss):.6f}  V {mesh.v_pos.shape[0]} F {mesh.t_pos_idx.shape[0]}", flush=True)
+
+    render.fit_to_views(geo, targets, a.iters, lr=a.lr, sdf_regularizer=a.sdf_regularizer, views_per_iter=a.views_per_iter,
+                        generator=gen, target_points=points, num_samples=max(a.points, 1), callback=report)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    torch.save(geo.state_to_dict(), a.out)
+    print(f"wrote {a.out}")
+
+
+if __name__ == "__main__":
+    main()
