@@ -824,6 +824,60 @@ int md_raster_depth_bwd(const int32_t* cov, int32_t n_cov, const float* rast1, c
                         const float* campos, const int32_t* ptr, const int32_t* order, int32_t batch, int32_t n_verts,
                         int32_t n_faces, int32_t H, int32_t W, float* corner_grad, float* dverts, void* stream);
 
+/*
+ * Silhouette antialiasing of the fitting loop, in the manner of nvdiffrast's dr.antialias (nvdiffrec/lib/render/render.py:256-276),
+ * not equal to it; csrc/antialias.hip.  Purely additive: MD_ABI_VERSION stays 16.
+ *
+ * The antialiasing contract
+ *   color float32 [B][H][W][C], 1 <= C <= 8; rast float32 [B][H][W][4], one layer of the rasterisation contract: (u, v, zf,
+ *   face + 1), zeros where uncovered; pos_clip float32 [B][V][4]; faces int64 [F][3]; nbr int32 [F][3].  The limits on B, H, W, F
+ *   are those of the rasterisation contract, anything else MD_ERR_UNSUPPORTED; null or misaligned pointers and non-positive
+ *   sizes MD_ERR_BAD_ARG.  A rast id outside [0, F] makes every pair it takes part in inactive; it is never an index.
+ *   Neighbours: nbr[f][k] belongs to the edge opposite corner k of face f (vertices faces[f][(k+1)%3], faces[f][(k+2)%3], as an
+ *   unordered pair): the other face's opposite vertex if exactly two face corners of the mesh own that pair, else -1.
+ *   Pairs: every pixel with its right neighbour and with the pixel below it, inside the image.  Ids t0, t1, depths z0, z1 of the
+ *   first / second pixel: a candidate iff t0 != t1; the owning pixel P is the second if t0 == 0, the first if t1 == 0, otherwise
+ *   the first iff z0 < z1 (fp32 compare of the stored values); Q the other, T = P's triangle, s = +1 if Q follows P, else -1.
+ *   A triangle T with a vertex of w <= 0 or a non-finite coordinate has no edge.
+ *   Decisions (exact integers; snapped X, Y of the rasterisation contract, P's centre (Px, Py) = (256 j + 128, 256 i + 128)):
+ *   the edges of T in the order k = 0, 1, 2 (a = faces[T][(k+1)%3] -> b = faces[T][(k+2)%3], opposite corner o); the first that
+ *   passes all of the following is the pair's edge, without one the pair is inactive.
+ *     Silhouette: nbr < 0, or the neighbour vertex o' has w <= 0 or a non-finite coordinate, or
+ *       sign(cross(b-a, o-a)) sign(cross(b-a, o'-a)) >= 0 (int64).
+ *     Orientation: |Yb-Ya| >= |Xb-Xa| for a horizontal pair, |Xb-Xa| >= |Yb-Ya| for a vertical one.
+ *     Crossing: u = s (X - Px), v = Y - Py (X, Y swapped for a vertical pair): (va > 0) != (vb > 0), and with den = vb - va,
+ *       n = ua den - va (ub - ua): 0 <= n sign(den) <= 256 |den|.
+ *   Value (fp32, every operation rounded on its own, correctly rounded divide, no contraction; unsnapped floats, pixels relative
+ *   to P's centre): fu = s ((x / w - fx_P) W/2), fv = (y / w - fy_P) H/2 (roles swapped for a vertical pair);
+ *   t = clamp(fu_a - fv_a (fu_b - fu_a) / (fv_b - fv_a), 0, 1), a zero denominator makes the pair inactive; w = t - 0.5;
+ *   w >= 0: out[Q] += w (color[P] - color[Q]), else out[P] += (-w) (color[Q] - color[P]).  A pixel's result is
+ *   color + right pair + pair below + left pair + pair above, summed in that order.
+ *   Gradient: color (the operator is linear in it) and pos_clip (through t: x, y, w of the edge's two vertices, no z; zero where
+ *   the clamp is active).  No floating-point atomics: bit-reproducible.
+ *
+ * md_mesh_edge_neighbours: sorted_keys int64 [3 F] = the keys min(a, b) * V + max(a, b) of the corners f * 3 + k sorted stably,
+ *   order int64 [3 F] = the corner of each sorted entry; writes every element of nbr.
+ * md_antialias_pairs: writes pairs int32 [B][H][W][2][4] (16-byte aligned): per pixel the record of its right pair and of the
+ *   pair below, (va, vb, the bits of the float w, P is the first pixel); va = vb = -1 where inactive or outside the image.
+ * md_antialias_blend: out float32 [B][H][W][C], every element written.
+ * md_antialias_bwd_color: grad_out float32 [B][H][W][C] -> dcolor, every element written.
+ * md_antialias_bwd_pos: active int64 [n_active] = the flat indices ((b H + i) W + j) * 2 + direction of the active pairs
+ *   (2 n_active < 2^31, B V < 2^31 - 1); vert_grad float32 [n_active][2][3] workspace; (ptr int32 [B V + 1], order int32
+ *   [2 n_active]) the CSR of the codes 2 * entry + end sorted stably by b V + vertex; dpos_clip float32 [B][V][4] (16-byte
+ *   aligned), every element written, z component 0.
+ */
+int md_mesh_edge_neighbours(const int64_t* sorted_keys, const int64_t* order, const int64_t* faces, int32_t n_faces, int32_t* nbr,
+                            void* stream);
+int md_antialias_pairs(const float* rast, const float* pos_clip, const int64_t* faces, const int32_t* nbr, int32_t batch,
+                       int32_t n_verts, int32_t n_faces, int32_t H, int32_t W, int32_t* pairs, void* stream);
+int md_antialias_blend(const float* color, const int32_t* pairs, int32_t batch, int32_t H, int32_t W, int32_t C, float* out,
+                       void* stream);
+int md_antialias_bwd_color(const float* grad_out, const int32_t* pairs, int32_t batch, int32_t H, int32_t W, int32_t C,
+                           float* dcolor, void* stream);
+int md_antialias_bwd_pos(const int64_t* active, int32_t n_active, const float* color, const float* grad_out, const int32_t* pairs,
+                         const float* pos_clip, const int32_t* ptr, const int32_t* order, int32_t batch, int32_t n_verts, int32_t H,
+                         int32_t W, int32_t C, float* vert_grad, float* dpos_clip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

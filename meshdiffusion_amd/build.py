@@ -17,7 +17,7 @@ _SUFFIX = os.environ.get("MD_LIB_SUFFIX", "")
 OBJDIR = os.path.join(CSRC, "build" + _SUFFIX)
 LIB_PATH = os.path.join(HERE, f"libmeshdiffusion_hip{_SUFFIX}.so")
 ARCH = "gfx950"
-SOURCES = ["capi.hip", "gemm_conv.hip", "conv3_main.hip", "conv3_wino.hip", "conv3_s2.hip", "conv3_head.hip", "conv3_stem.hip", "pack_batch.hip", "wino_prep2.hip", "wino_eq.hip", "norm.hip", "elementwise.hip", "sde_steps.hip", "attention.hip", "nin_stream.hip", "block_pass.hip", "train.hip", "backward.hip", "wgrad.hip", "wgrad_wino.hip", "dmtet.hip", "dmtet_bwd.hip", "pointcloud.hip", "raster.hip"]
+SOURCES = ["capi.hip", "gemm_conv.hip", "conv3_main.hip", "conv3_wino.hip", "conv3_s2.hip", "conv3_head.hip", "conv3_stem.hip", "pack_batch.hip", "wino_prep2.hip", "wino_eq.hip", "norm.hip", "elementwise.hip", "sde_steps.hip", "attention.hip", "nin_stream.hip", "block_pass.hip", "train.hip", "backward.hip", "wgrad.hip", "wgrad_wino.hip", "dmtet.hip", "dmtet_bwd.hip", "pointcloud.hip", "raster.hip", "antialias.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", f"-I{INCLUDE}", f"-I{CSRC}",
          "-munsafe-fp-atomics", "-Wno-unused-result"]
 
@@ -43,7 +43,7 @@ def build(verbose=False, force=False):
     from concurrent.futures import ThreadPoolExecutor
     hipcc = _hipcc()
     os.makedirs(OBJDIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "md_common.h"), os.path.join(CSRC, "md_pack.h"), os.path.join(CSRC, "md_prep_f6.h"), os.path.join(INCLUDE, "meshdiffusion_hip.h")]
+    headers = [os.path.join(CSRC, "md_common.h"), os.path.join(CSRC, "md_pack.h"), os.path.join(CSRC, "md_prep_f6.h"), os.path.join(CSRC, "md_raster_snap.h"), os.path.join(INCLUDE, "meshdiffusion_hip.h")]
     flags = FLAGS + (["-DMD_BUILD_ABLATIONS"] if os.environ.get("MD_BUILD_ABLATIONS") == "1" else [])
     flags = flags + os.environ.get("MD_EXTRA_DEFINES", "").split()
     stamp = os.path.join(OBJDIR, "flags.txt")

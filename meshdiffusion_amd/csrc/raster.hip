@@ -40,13 +40,13 @@
 // GATHERS them over a CSR of (covered entry, corner) codes sorted stably by vertex id (the pattern of md_sample_points_bwd):
 // no floating-point atomics, two runs agree bit for bit.
 #include "md_common.h"
+#include "md_raster_snap.h"
 
 #pragma clang fp contract(off)
 
 static constexpr int RS_TILE = 16;                           // pixels per tile side
 static constexpr int RS_THREADS = RS_TILE * RS_TILE;         // one pixel per lane
 static constexpr int RS_CHUNK = 256;                         // triangle records per LDS chunk (16 KiB)
-static constexpr int RS_SNAP_MAX = 1 << 22;
 static constexpr uint64_t RS_NO_KEY = ~0ull;
 
 struct alignas(16) RsRecord {                                // one triangle, oriented so that A2 > 0; 64 bytes
@@ -62,15 +62,6 @@ struct RsTri {
   float zw[3];
   int64_t A2;
 };
-
-__device__ __forceinline__ bool rs_finite(float x) { return fabsf(x) < __builtin_inff(); }
-
-// the contract's snap of one coordinate: rint(((x / w) * 0.5 + 0.5) * scale), clamped to +-2^22
-__device__ __forceinline__ int rs_snap(float x, float w, float scale) {
-  const float t = __fadd_rn(__fmul_rn(__fdiv_rn(x, w), 0.5f), 0.5f);
-  const float r = rintf(__fmul_rn(t, scale));
-  return (int)fminf(fmaxf(r, -(float)RS_SNAP_MAX), (float)RS_SNAP_MAX);
-}
 
 // false: the triangle is skipped
 __device__ __forceinline__ bool rs_setup(const float* __restrict__ pc, const int64_t* __restrict__ faces, int64_t f, int H, int W,

@@ -1,14 +1,18 @@
-"""Depth and silhouette rendering for DMTet fitting on MI355X -- host side of csrc/raster.hip.
+"""Depth and silhouette rendering for DMTet fitting on MI355X -- host side of csrc/raster.hip and csrc/antialias.hip.
 
 The reference gets its depth buffers from nvdiffrast (nvdiffrec/lib/render/render.py:287-329): `xfm_points` -> two depth-peeled
 layers -> `interpolate(v_pos)` -> |gb_pos - campos|, and supervises the geometry with the depth terms of `DMTetGeometry.tick`
 (nvdiffrec/lib/geometry/dmtet.py:402-434) and the silhouette carve (:366-378).  This module is that path: `rasterize` and
 `render_depth` follow the rasterisation contract in the header comment of csrc/raster.hip, `depth_loss`, `make_targets`,
-`carve_outside_silhouette` and `fit_to_views` are the loop around it.  The kernels run on the GPU only: a CPU tensor is an
+`carve_outside_silhouette` and `fit_to_views` are the loop around it.  `edge_neighbours` and `antialias` follow the antialiasing
+contract in the header comment of csrc/antialias.hip: silhouette antialiasing in the manner of dr.antialias (render.py:256-276),
+not equal to it, with gradients for the colour and the clip-space vertices.  `render_depth(antialias=True)` adds the antialiased
+coverage of both layers and `silhouette_loss` is the coverage term of tick (dmtet.py:394,399), the one path from a silhouette to
+the vertices.  The kernels run on the GPU only: a CPU tensor is an
 error, not a fallback.  The camera helpers, `xfm_points`, `depth_loss` and the carve are plain torch and run anywhere.
 
-Not built: dr.antialias (so alpha / colour terms would give no geometry gradient), materials, lights,
-BSDFs, textures, spp > 1 / MSAA, clipping of triangles that cross w = 0, more than two layers, gradients for mvp / campos.
+Not built: materials, lights, BSDFs, textures and the colour terms of tick, spp > 1 / MSAA, clipping of
+triangles that cross w = 0, more than two layers, gradients for mvp / campos, a silhouette search beyond the covering triangle.
 """
 import numpy as np
 import torch
@@ -210,7 +214,123 @@ class _RenderDepthFn(torch.autograd.Function):
         return dverts, None, None, None, None, None, None
 
 
-def render_depth(verts, faces, mvp, campos, resolution):
+# ---- antialiasing ------------------------------------------------------------------------------------------------------------------
+MAX_CHANNELS = 8                         # AA_MAX_C of csrc/antialias.hip
+
+
+def edge_neighbours(faces, n_verts):
+    """nbr int32 [F,3] of the antialiasing contract: nbr[f][k] is the vertex opposite the edge (faces[f][(k+1)%3],
+    faces[f][(k+2)%3]) in the one other face that owns it, or -1 (boundary, or an edge of three or more faces).  A stable torch
+    sort of the 3 F edge keys, then one kernel."""
+    _gpu_only(faces, "edge_neighbours")
+    n_verts = int(n_verts)
+    if n_verts < 1:
+        raise ValueError(f"edge_neighbours: n_verts must be positive, got {n_verts}")
+    f = _check_faces(faces, n_verts)
+    F = f.shape[0]
+    nbr = torch.empty((F, 3), dtype=torch.int32, device=f.device)
+    if F == 0:
+        return nbr
+    a, b = f[:, [1, 2, 0]], f[:, [2, 0, 1]]
+    keys = (torch.minimum(a, b) * n_verts + torch.maximum(a, b)).reshape(-1)
+    keys, order = torch.sort(keys, stable=True)
+    _lib.check(_lib.load().md_mesh_edge_neighbours(_ptr(keys), _ptr(order), _ptr(f), F, _ptr(nbr), _stream()),
+               "md_mesh_edge_neighbours")
+    return nbr
+
+
+class _AntialiasFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, color, pos_clip, rast, faces, nbr):
+        lib = _lib.load()
+        B, H, W, C = color.shape
+        V, F = pos_clip.shape[1], faces.shape[0]
+        pairs = torch.empty((B, H, W, 2, 4), dtype=torch.int32, device=color.device)
+        if F == 0:                                                             # every id is above F: no pair is active
+            pairs[..., :2] = -1
+            pairs[..., 2:] = 0
+            out = color.clone()
+        else:
+            out = torch.empty_like(color)
+            _lib.check(lib.md_antialias_pairs(_ptr(rast), _ptr(pos_clip), _ptr(faces), _ptr(nbr), B, V, F, H, W, _ptr(pairs),
+                                              _stream()), "md_antialias_pairs")
+            _lib.check(lib.md_antialias_blend(_ptr(color), _ptr(pairs), B, H, W, C, _ptr(out), _stream()), "md_antialias_blend")
+        ctx.save_for_backward(color, pos_clip, pairs)
+        ctx.mark_non_differentiable(pairs)
+        return out, pairs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _unused):
+        lib = _lib.load()
+        color, pos_clip, pairs = ctx.saved_tensors
+        B, H, W, C = color.shape
+        V, dev = pos_clip.shape[1], color.device
+        g = g.to(torch.float32).contiguous()
+        dcolor = dpos = None
+        if ctx.needs_input_grad[0]:
+            dcolor = torch.empty_like(color)
+            _lib.check(lib.md_antialias_bwd_color(_ptr(g), _ptr(pairs), B, H, W, C, _ptr(dcolor), _stream()), "md_antialias_bwd_color")
+        if ctx.needs_input_grad[1]:
+            rec = pairs.view(-1, 4)
+            act = torch.nonzero(rec[:, 0] >= 0)[:, 0]                          # the flat index of a pair is its code
+            N = act.numel()
+            if 2 * N >= 2 ** 31 or B * V >= 2 ** 31 - 1:
+                raise _lib.MeshDiffusionHipError("antialias backward: 2 x the active pairs and B x V must fit int32")
+            dpos = torch.empty((B, V, 4), dtype=torch.float32, device=dev)
+            if N == 0:
+                dpos.zero_()
+            else:
+                view = torch.div(act, 2 * H * W, rounding_mode="floor")
+                end_vert = (view[:, None] * V + rec[act, :2].to(torch.int64)).reshape(-1)     # entry 2 n + end names this vertex
+                vals, order = torch.sort(end_vert, stable=True)
+                ptr = torch.searchsorted(vals, torch.arange(B * V + 1, dtype=torch.int64, device=dev)).to(torch.int32).contiguous()
+                order = order.to(torch.int32).contiguous()
+                vert_grad = torch.empty((N, 2, 3), dtype=torch.float32, device=dev)
+                _lib.check(lib.md_antialias_bwd_pos(_ptr(act), N, _ptr(color), _ptr(g), _ptr(pairs), _ptr(pos_clip), _ptr(ptr),
+                                                    _ptr(order), B, V, H, W, C, _ptr(vert_grad), _ptr(dpos), _stream()),
+                           "md_antialias_bwd_pos")
+        return dcolor, dpos, None, None, None
+
+
+def antialias(color, rast, pos_clip, faces, neighbours=None, return_pairs=False):
+    """Silhouette antialiasing of `color` float32 [B,H,W,C] (1 <= C <= 8) by the contract in the header comment of
+    csrc/antialias.hip, in the manner of dr.antialias: rast float32 [B,H,W,4] one layer of `rasterize`, pos_clip float32 [B,V,4],
+    faces [F,3], neighbours = `edge_neighbours(faces, V)` (built when None).  Returns float32 [B,H,W,C] with gradients for
+    `color` and `pos_clip` (x, y, w of the silhouette edges' vertices); rast, faces and neighbours get none.
+    return_pairs=True also returns the pair records int32 [B,H,W,2,4]: per pixel, for the pair with its right neighbour and the
+    pair with the pixel below, (va, vb, the bits of the float32 weight w, P is the pair's first pixel); va = vb = -1: inactive."""
+    _gpu_only(color, "antialias")
+    if color.dim() != 4 or color.shape[0] < 1 or color.shape[1] < 1 or color.shape[2] < 1:
+        raise ValueError(f"antialias: expected color [B,H,W,C], got {tuple(color.shape)}")
+    B, H, W, C = color.shape
+    if C < 1 or C > MAX_CHANNELS:
+        raise _lib.MeshDiffusionHipError(f"antialias takes 1 to {MAX_CHANNELS} channels, got {C} (MD_ERR_UNSUPPORTED)")
+    _resolution((H, W))
+    _check_clip(pos_clip)
+    if tuple(rast.shape) != (B, H, W, 4) or pos_clip.shape[0] != B:
+        raise ValueError(f"antialias: expected rast [{B},{H},{W},4] and pos_clip [{B},V,4], got {tuple(rast.shape)} and {tuple(pos_clip.shape)}")
+    dev, V = color.device, pos_clip.shape[1]
+    col = color.to(torch.float32).contiguous()
+    pc = pos_clip.to(device=dev, dtype=torch.float32).contiguous()
+    r = rast.detach().to(device=dev, dtype=torch.float32).contiguous()
+    f = _check_faces(faces.to(dev), V)
+    if neighbours is None:
+        nbr = edge_neighbours(f, V)
+    else:
+        nbr = neighbours.to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(nbr.shape) != (f.shape[0], 3):
+            raise ValueError(f"antialias: expected neighbours [{f.shape[0]},3], got {tuple(nbr.shape)}")
+        if nbr.numel() > 0 and int(nbr.max()) >= V:
+            raise ValueError(f"antialias: neighbours name vertices outside [0, {V})")
+    out, pairs = _AntialiasFn.apply(col, pc, r, f, nbr)
+    return (out, pairs) if return_pairs else out
+
+
+_antialias = antialias                   # render_depth and make_targets have a flag of that name
+
+
+def render_depth(verts, faces, mvp, campos, resolution, antialias=False):
     """The depth part of the reference's render_mesh: world-space verts [V,3] (or [1,V,3]) shared by the B views mvp [B,4,4]
     with camera centres campos [B,3] -> dict of
       depth, depth_second   float32 [B,H,W,1]: |gb_pos - campos| of layer 1 / 2, 20.0 / -1.0 where uncovered; they carry a
@@ -218,6 +338,9 @@ def render_depth(verts, faces, mvp, campos, resolution):
       mask, mask_second     float32 [B,H,W,1]: 1.0 where covered
       rast, rast_second     float32 [B,H,W,4]: (u, v, zf, face index + 1)
       rast_triangle_id      the sorted unique visible face ids of layer 1 (int64), or None when nothing is visible.
+    antialias=True adds
+      alpha, alpha_second   float32 [B,H,W,1]: `antialias(mask_k, rast_k, xfm_points(verts[None], mvp), faces)`, each layer with
+                            its own rast; they carry a grad_fn to `verts` through xfm_points.
     The rasterised tensor is exactly `xfm_points(verts[None], mvp)`."""
     _gpu_only(verts, "render_depth")
     v = verts[0] if verts.dim() == 3 and verts.shape[0] == 1 else verts
@@ -235,8 +358,14 @@ def render_depth(verts, faces, mvp, campos, resolution):
     depth, depth2, mask, mask2, rast, rast2 = _RenderDepthFn.apply(v, pos_clip, f, mvp, campos, H, W)
     tri = torch.unique(rast[..., 3])
     tri = tri[tri > 0].to(torch.int64) - 1
-    return {"depth": depth, "depth_second": depth2, "mask": mask, "mask_second": mask2, "rast": rast, "rast_second": rast2,
-            "rast_triangle_id": tri if tri.numel() > 0 else None}
+    out = {"depth": depth, "depth_second": depth2, "mask": mask, "mask_second": mask2, "rast": rast, "rast_second": rast2,
+           "rast_triangle_id": tri if tri.numel() > 0 else None}
+    if antialias:
+        clip = xfm_points(v[None], mvp)                                        # the bits of pos_clip, with the way back to verts
+        nbr = edge_neighbours(f, v.shape[0])
+        out["alpha"] = _antialias(mask, rast, clip, f, nbr)
+        out["alpha_second"] = _antialias(mask2, rast2, clip, f, nbr)
+    return out
 
 
 # ---- losses and the fitting loop ---------------------------------------------------------------------------------------------------
@@ -255,15 +384,24 @@ def depth_loss(buffers, target, iteration):
     return (huber(d1).mean() + huber(d2).mean()) * scale
 
 
+def silhouette_loss(buffers, target):
+    """The coverage term of DMTetGeometry.tick (dmtet.py:394,399): mse(alpha) + 0.1 mse(alpha_second), all [B,H,W,1]."""
+    mse = torch.nn.functional.mse_loss
+    return mse(buffers["alpha"], target["alpha"]) + 0.1 * mse(buffers["alpha_second"], target["alpha_second"])
+
+
 @torch.no_grad()
-def make_targets(verts, faces, mvp, campos, resolution):
+def make_targets(verts, faces, mvp, campos, resolution, antialias=False):
     """Render the ground-truth mesh with the same rasteriser (the role of dataset_mesh.py:120): `depth`, `depth_second`,
-    `mask_cont` [B,H,W,1], and the cameras `mvp`, `campos`, `resolution`."""
-    out = render_depth(verts.detach(), faces, mvp, campos, resolution)
+    `mask_cont` [B,H,W,1], and the cameras `mvp`, `campos`, `resolution`; antialias=True adds `alpha`, `alpha_second`."""
+    out = render_depth(verts.detach(), faces, mvp, campos, resolution, antialias=antialias)
     H, W = _resolution(resolution)
-    return {"depth": out["depth"], "depth_second": out["depth_second"], "mask_cont": out["mask"],
-            "mvp": mvp.detach().to(device=verts.device, dtype=torch.float32), "campos": campos.detach().to(device=verts.device, dtype=torch.float32),
-            "resolution": [H, W]}
+    tgt = {"depth": out["depth"], "depth_second": out["depth_second"], "mask_cont": out["mask"],
+           "mvp": mvp.detach().to(device=verts.device, dtype=torch.float32), "campos": campos.detach().to(device=verts.device, dtype=torch.float32),
+           "resolution": [H, W]}
+    if antialias:
+        tgt["alpha"], tgt["alpha_second"] = out["alpha"], out["alpha_second"]
+    return tgt
 
 
 @torch.no_grad()
@@ -290,22 +428,29 @@ def carve_outside_silhouette(geometry, target, kernel_size=11):
 
 
 def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, views_per_iter=None, generator=None,
-                 target_points=None, num_samples=50000, carve=True, callback=None, start_iteration=0):
+                 target_points=None, num_samples=50000, carve=True, callback=None, start_iteration=0, alpha_weight=0.0,
+                 return_terms=False):
     """Fit a `DMTetGeometry` to rendered targets (`make_targets`) the way the reference's tick supervises geometry: per
     iteration
         [carve, for 200 < it < 2000 and it % 20 == 0] -> [deform *= 0.4, for it % 300 == 0 and it < 1790]
         -> getMesh -> render_depth on `views_per_iter` views -> depth_loss + sdf_reg_loss(masked sdf) * weight * 0.1
+        [+ alpha_weight * silhouette_loss, for alpha_weight > 0; the reference's weight is 1.0]
         [+ chamfer(sample_points(num_samples), target_points)] -> Adam step on (sdf, deform) -> clamp_deform.
     views_per_iter: None = every view each iteration, else that many drawn without replacement (torch.randperm, `generator`).
-    `callback(it, loss, mesh)` after each step.  Returns the depth-loss values, float32 [iters] on the device."""
+    `callback(it, loss, mesh)` after each step.  Returns the depth-loss values, float32 [iters] on the device; with
+    return_terms=True the dict {"depth": [iters], "alpha": [iters]} of both terms.  alpha_weight > 0 and return_terms need
+    targets made with `make_targets(..., antialias=True)`."""
     from .dmtet import sdf_reg_loss
     from .pointcloud import chamfer_distance, sample_points, sdf_regularizer_weight
     dev = geometry.sdf.device
     _gpu_only(geometry.sdf, "fit_to_views")
     n_views = targets["mvp"].shape[0]
+    with_alpha = alpha_weight > 0 or return_terms
+    if with_alpha and not ("alpha" in targets and "alpha_second" in targets):
+        raise ValueError("fit_to_views: the alpha term needs targets made with make_targets(..., antialias=True)")
     pts = None if target_points is None else target_points.detach().to(device=dev, dtype=torch.float32).reshape(1, -1, 3).contiguous()
     opt = torch.optim.Adam([geometry.sdf, geometry.deform], lr=lr)
-    history = []
+    history, alpha_history = [], []
     for k in range(iters):
         it = start_iteration + k
         if views_per_iter is None or views_per_iter >= n_views:
@@ -323,12 +468,17 @@ def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, view
         mesh = geometry.getMesh()
         if mesh.t_pos_idx.shape[0] == 0:
             raise _lib.MeshDiffusionHipError(f"fit_to_views: the mesh of iteration {it} has no faces")
-        buffers = render_depth(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"])
+        buffers = render_depth(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"], antialias=with_alpha)
         loss = depth_loss(buffers, tgt, it)
         sdf_mask = torch.zeros_like(geometry.sdf)
         sdf_mask[mesh.valid_vert_idx] = 1.0
         sdf_masked = geometry.sdf.detach() * sdf_mask + geometry.sdf * (1 - sdf_mask)
         total = loss + sdf_reg_loss(sdf_masked, geometry.all_edges).mean() * sdf_regularizer_weight(it, start_iteration + iters, sdf_regularizer) * 0.1
+        if with_alpha:
+            alpha = silhouette_loss(buffers, tgt)
+            alpha_history.append(alpha.detach())
+            if alpha_weight > 0:
+                total = total + alpha * alpha_weight
         if pts is not None:
             pred = sample_points(mesh.v_pos[None], mesh.t_pos_idx, num_samples, generator=generator)[0]
             total = total + chamfer_distance(pred, pts).mean()
@@ -338,4 +488,7 @@ def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, view
         history.append(loss.detach())
         if callback is not None:
             callback(it, history[-1], mesh)
-    return torch.stack(history) if history else torch.empty(0, device=dev)
+    depth_terms = torch.stack(history) if history else torch.empty(0, device=dev)
+    if return_terms:
+        return {"depth": depth_terms, "alpha": torch.stack(alpha_history) if alpha_history else torch.empty(0, device=dev)}
+    return depth_terms

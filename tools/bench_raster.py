@@ -6,6 +6,9 @@ tests/raster_cases.py:
   (c) (pixel, triangle) coverage tests per second of the tile kernel: 256 x the (tile, triangle) pairs per launch;
   (d) the baseline: the fp32 torch restatement of the contract (tests/raster_cases.py) on the same GPU, forward and
       forward + backward, one repetition;
+  (f) at B = 8: `antialias` of the layer-1 coverage mask, forward and forward + backward (color and pos_clip), next to the fp32
+      torch restatement of tests/antialias_cases.py on the same GPU in interleaved rounds; `edge_neighbours`; `render_depth`
+      forward + backward with and without antialias=True; the device kernels launched per call (torch.profiler);
   (e) one fit_to_views iteration on the shipped 64 grid (sphere start, torus target, 8 views at 512 x 512), next to the
       chamfer iteration of tools/bench_pointcloud.py.
 Device events after warm-up; each figure is the median over rounds.
@@ -32,6 +35,82 @@ def median_ms(fn, rounds, reps):
     return statistics.median(timed(fn, reps) for _ in range(rounds))
 
 
+def interleaved_ms(fns, rounds, reps):
+    """Medians of several callables timed in interleaved rounds (a, b, a, b, ...), so that drift hits all alike."""
+    for f in fns:
+        f()
+    torch.cuda.synchronize()
+    samples = [[] for _ in fns]
+    for _ in range(rounds):
+        for k, f in enumerate(fns):
+            samples[k].append(timed(f, reps))
+    return [statistics.median(x) for x in samples]
+
+
+def launches(fn):
+    """Device kernels launched by one call, or -1 when the profiler is not available."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "mem" not in e.name.lower())
+    except Exception:
+        return -1
+
+
+def bench_antialias(name, verts, faces, mvp, campos, pc, H, W, a, rec):
+    import antialias_cases as ac
+    from meshdiffusion_amd import render
+    B, V = pc.shape[0], verts.shape[0]
+    rast = render.rasterize(pc, faces, (H, W))[0]
+    nbr = render.edge_neighbours(faces, V)
+    mask = (rast[..., 3:4] > 0).float()
+    G = torch.randn(B, H, W, 1, device="cuda")
+    _, pairs = render.antialias(mask, rast, pc, faces, nbr, return_pairs=True)
+    active = int((pairs[..., 0] >= 0).sum())
+    cand = int((rast[:, :, :-1, 3] != rast[:, :, 1:, 3]).sum() + (rast[:, :-1, :, 3] != rast[:, 1:, :, 3]).sum())
+
+    def fwd():
+        return render.antialias(mask, rast, pc, faces, nbr)
+
+    def fwd_bwd():
+        c, p = mask.clone().requires_grad_(True), pc.clone().requires_grad_(True)
+        (render.antialias(c, rast, p, faces, nbr) * G).sum().backward()
+        return p.grad
+
+    def base_fwd():
+        return ac.antialias_restated(mask, rast, pc, faces, nbr, torch.float32)
+
+    def base_fwd_bwd():
+        return ac.grads_restated(mask, rast, pc, faces, nbr, G, torch.float32)[2]
+
+    def depth(aa):
+        def run():
+            v = verts.detach().requires_grad_(True)
+            out = render.render_depth(v, faces, mvp, campos, (H, W), antialias=aa)
+            loss = (out["depth"] * G).sum() + (out["depth_second"] * G).sum()
+            if aa:
+                loss = loss + (out["alpha"] * G).sum() + (out["alpha_second"] * G).sum()
+            loss.backward()
+            return v.grad
+        return run
+
+    t = interleaved_ms([fwd, base_fwd, fwd_bwd, base_fwd_bwd], a.rounds, a.reps)
+    t_nbr, t_plain, t_aa = interleaved_ms([lambda: render.edge_neighbours(faces, V), depth(False), depth(True)], a.rounds, a.reps)
+    n = [launches(f) for f in (fwd, fwd_bwd, lambda: render.edge_neighbours(faces, V), depth(False), depth(True))]
+    print(f"antialias {name} V={V} F={faces.shape[0]} B={B} {H}x{W} C=1: candidate pairs {cand} active {active} | forward {t[0]:.3f} ms "
+          f"({n[0]} launches; fp32 torch restatement {t[1]:.1f} ms, x{t[1] / t[0]:.0f}) | forward+backward {t[2]:.3f} ms ({n[1]} launches; "
+          f"restatement {t[3]:.1f} ms, x{t[3] / t[2]:.0f}) | edge_neighbours {t_nbr:.3f} ms ({n[2]} launches) | render_depth forward+backward "
+          f"{t_plain:.3f} ms ({n[3]} launches), with antialias=True {t_aa:.3f} ms ({n[4]} launches)", flush=True)
+    rec["cases"][f"antialias_{name}_B{B}"] = dict(forward=round(t[0], 4), baseline_forward=round(t[1], 4), forward_backward=round(t[2], 4),
+                                                 baseline_forward_backward=round(t[3], 4), edge_neighbours=round(t_nbr, 4),
+                                                 render_depth=round(t_plain, 4), render_depth_antialias=round(t_aa, 4), launches=n,
+                                                 candidates=cand, active=active)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, default=512)
@@ -39,6 +118,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--json", default=None)
     ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--only-antialias", action="store_true", help="skip the rasteriser's own rows and the fit iteration")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_raster.py needs a GPU: the HIP path has no CPU fallback")
@@ -57,6 +137,10 @@ def main():
             mvp, campos = (t.cuda() for t in rc.cameras(angles, H, W))
             pc = render.xfm_points(verts[None], mvp).contiguous()
             G = torch.randn(B, H, W, 1, device="cuda")
+            if B == 8:
+                bench_antialias(name, verts, faces, mvp, campos, pc, H, W, a, rec)
+            if a.only_antialias:
+                continue
 
             def fwd():
                 return render.rasterize(pc, faces, (H, W))
@@ -125,7 +209,7 @@ def main():
     with torch.no_grad():
         geo.sdf.copy_(rc.fit_initial_sdf(geo.verts))
     tv, tf = (t.cuda() for t in rc.mesh("torus"))
-    for B, res in ((4, 64), (8, a.res)):
+    for B, res in (() if a.only_antialias else ((4, 64), (8, a.res))):
         mvp, campos = (t.cuda() for t in rc.cameras([2 * 3.141592653589793 * k / B for k in range(B)], res, res))
         targets = render.make_targets(tv, tf, mvp, campos, res)
         state = {"it": 1}

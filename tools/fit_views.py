@@ -1,7 +1,7 @@
 """Fit a DMTet grid to a mesh under depth supervision, the way the reference's fit_dmtets.py supervises geometry: `.obj` ->
 depth / silhouette targets of --views cameras (rendered with the project's own rasteriser) -> DMTetGeometry fitted with the
-depth loss, the SDF regulariser, the silhouette carve and, with --points, the chamfer distance -> the `{'sdf', 'deform'}` dict
-that `mesh_export.dicts_to_grids` turns into a training grid.
+depth loss, the SDF regulariser, the silhouette carve, with --alpha_weight the antialiased coverage term and, with --points,
+the chamfer distance -> the `{'sdf', 'deform'}` dict that `mesh_export.dicts_to_grids` turns into a training grid.
 
     python tools/fit_views.py --obj shape.obj --tet_path data/tets/64_tets_cropped.npz --views 16 --res 256 --out fitted/dmt_dict_00000.pt
 and then `mesh_export.dicts_to_grids(tet_vertices, "fitted", "grids", 64, [0])` writes grids/grid_00000.pt.
@@ -45,6 +45,8 @@ def main(argv=None):
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--sdf_regularizer", type=float, default=0.2)
     ap.add_argument("--points", type=int, default=0, help="> 0: add the chamfer term with this many target points and samples")
+    ap.add_argument("--alpha_weight", type=float, default=0.0,
+                    help="> 0: add this weight times the antialiased coverage term (the reference's weight is 1.0)")
     ap.add_argument("--mesh_scale", type=float, default=2.1)
     ap.add_argument("--deform_scale", type=float, default=2.0)
     ap.add_argument("--fit_scale", type=float, default=0.8, help="largest half-extent of the normalised target")
@@ -67,7 +69,7 @@ def main(argv=None):
     lo, hi = v.min(0).values, v.max(0).values
     v = (v - (lo + hi) / 2) * (a.fit_scale / float((hi - lo).max() / 2))
     mvp, campos = orbit_cameras(a.views, a.cam_radius, a.fovy, "cuda")
-    targets = render.make_targets(v, f, mvp, campos, a.res)
+    targets = render.make_targets(v, f, mvp, campos, a.res, antialias=a.alpha_weight > 0)
     points = sample_points(v[None], f, a.points, generator=gen)[0][0] if a.points > 0 else None
     tet = np.load(a.tet_path)
     geo = DMTetGeometry(a.resolution, a.mesh_scale, None, tets=(tet["vertices"], tet["indices"]), deform_scale=a.deform_scale)
@@ -80,7 +82,8 @@ def main(argv=None):
             print(f"iter {it}: depth loss {float(loss):.6f}  V {mesh.v_pos.shape[0]} F {mesh.t_pos_idx.shape[0]}", flush=True)
 
     render.fit_to_views(geo, targets, a.iters, lr=a.lr, sdf_regularizer=a.sdf_regularizer, views_per_iter=a.views_per_iter,
-                        generator=gen, target_points=points, num_samples=max(a.points, 1), callback=report)
+                        generator=gen, target_points=points, num_samples=max(a.points, 1), callback=report,
+                        alpha_weight=a.alpha_weight)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     torch.save(geo.state_to_dict(), a.out)
     print(f"wrote {a.out}")
