@@ -878,6 +878,53 @@ int md_antialias_bwd_pos(const int64_t* active, int32_t n_active, const float* c
                          const float* pos_clip, const int32_t* ptr, const int32_t* order, int32_t batch, int32_t n_verts, int32_t H,
                          int32_t W, int32_t C, float* vert_grad, float* dpos_clip, void* stream);
 
+/* ---- attribute interpolation, barycentric gradients, differentiable vertex normals (csrc/interp.hip) ----
+ * THE INTERPOLATION CONTRACT (the header comment of csrc/interp.hip has it in full; tests/interp_cases.py restates it)
+ *   rast float32 [B][H][W][4] one layer of the rasteriser (16-byte aligned); attr float32 [Ba][N][C], Ba = 1 or B, 1 <= C <= 8;
+ *   tri int64 [F][3] with indices into N (8-byte aligned; tri[f] = (f, f, f), N = F for face-constant attributes).  The limits on
+ *   B, H, W, F are those of the rasterisation contract, anything else is MD_ERR_UNSUPPORTED.
+ *   Value: a pixel with 1 <= id = rast.w <= F gets out[c] = (u A0[c] + v A1[c]) + t A2[c], t = (1 - u) - v, A_k =
+ *   attr[tri[id-1][k]]; every other pixel gets zeros; an id above F is never an index.
+ *   d attr: w_k g of corner k of every covered pixel, summed per destination row in ascending order of the code 3 * entry +
+ *   corner (entry: the rank of the pixel among the covered pixels in flat (b, i, j) order; Ba == 1 sums over the views).
+ *   d rast: du = sum_c g[c] (A0[c] - A2[c]), dv = sum_c g[c] (A1[c] - A2[c]) in channels 0, 1; everything else zero.
+ *   Barycentric backward: (du, dv) -> d pos_clip by the formulas of md_raster_depth_bwd, gathered per (view, vertex) in
+ *   ascending code order; z gets none.  No floating-point atomics anywhere: bit-reproducible.
+ *   Sums: every sum over codes of this contract (d attr, d pos_clip, the vertex normals' s_v, d verts) is a compensated (Kahan)
+ *   fp32 sum in ascending code order, every operation rounded on its own and none contracted: sum = 0, lost = 0; per term x:
+ *   y = x - lost, t = sum + y, lost = (t - sum) - y, sum = t.  The result is `sum`.
+ *
+ * md_interpolate: out float32 [B][H][W][C], every element written.
+ * md_interpolate_bwd: cov int32 [n_cov] = the flat pixel indices (b H + i) W + j of the covered pixels, ascending (3 n_cov <
+ *   2^31, Ba N < 2^31 - 1); corner_grad float32 [n_cov][3][C] workspace; (ptr int32 [Ba N + 1], order int32 [3 n_cov]) the CSR of
+ *   the codes sorted stably by (Ba == 1 ? 0 : b) N + tri[id-1][corner]; dattr float32 [Ba][N][C] and drast float32 [B][H][W][4]
+ *   (16-byte aligned) are each written in full when not null; one of them may be null, and its launch or store is skipped.
+ * md_raster_bary_bwd: drast float32 [B][H][W][4] holding (du, dv) in channels 0, 1; corner_grad float32 [n_cov][3][3]
+ *   workspace receiving (d x, d y, d w); (ptr int32 [B V + 1], order int32 [3 n_cov]) the CSR of the codes sorted stably by
+ *   b V + faces[id-1][corner]; dpos_clip float32 [B][V][4] (16-byte aligned), every element written, z component 0.
+ * md_vertex_normals_det: fn_f = cross(v1 - v0, v2 - v0) -> f_nrm float32 [F][3]; s_v = the sum of fn_f over the corners that name
+ *   v in ascending order of the code 3 f + k, over (ptr int32 [V + 1], order int32 [3 F]), the CSR of the codes sorted stably by
+ *   vertex; s_v . s_v <= 1e-20 replaces s_v by (0, 0, 1); v_nrm = s_v / sqrt(max(s_v . s_v, 1e-20)); v_len float32 [V] =
+ *   that square root, 0 for a replaced vertex.
+ * md_vertex_normals_bwd: d s_v = (g - n (n . g)) / |s_v| (zero for a replaced vertex), d fn_f = its sum over the face's corners,
+ *   d a = b x d fn, d b = d fn x a for a = v1 - v0, b = v2 - v0; face_grad float32 [F][3][3] workspace; dverts float32 [V][3],
+ *   every element written, gathered over the same CSR.
+ */
+int md_interpolate(const float* rast, const float* attr, const int64_t* tri, int32_t batch, int32_t attr_batch, int32_t n_rows,
+                   int32_t C, int32_t n_faces, int32_t H, int32_t W, float* out, void* stream);
+int md_interpolate_bwd(const int32_t* cov, int32_t n_cov, const float* rast, const float* grad_out, const float* attr,
+                       const int64_t* tri, const int32_t* ptr, const int32_t* order, int32_t batch, int32_t attr_batch,
+                       int32_t n_rows, int32_t C, int32_t n_faces, int32_t H, int32_t W, float* corner_grad, float* dattr,
+                       float* drast, void* stream);
+int md_raster_bary_bwd(const int32_t* cov, int32_t n_cov, const float* rast, const float* drast, const float* pos_clip,
+                       const int64_t* faces, const int32_t* ptr, const int32_t* order, int32_t batch, int32_t n_verts,
+                       int32_t n_faces, int32_t H, int32_t W, float* corner_grad, float* dpos_clip, void* stream);
+int md_vertex_normals_det(const float* verts, const int64_t* faces, const int32_t* ptr, const int32_t* order, int32_t n_verts,
+                          int32_t n_faces, float* v_nrm, float* f_nrm, float* v_len, void* stream);
+int md_vertex_normals_bwd(const float* verts, const int64_t* faces, const int32_t* ptr, const int32_t* order, const float* v_nrm,
+                          const float* v_len, const float* grad_v_nrm, int32_t n_verts, int32_t n_faces, float* face_grad,
+                          float* dverts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,11 @@ SIGNATURES = {
     "md_antialias_blend": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "md_antialias_bwd_color": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "md_antialias_bwd_pos": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "md_interpolate": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "md_interpolate_bwd": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "md_raster_bary_bwd": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "md_vertex_normals_det": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "md_vertex_normals_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
 }
 SDF_REG_SLABS = 64                                  # MD_SDF_REG_SLABS
 SDF_REG_WORKSPACE_BYTES = SDF_REG_SLABS * 24        # MD_SDF_REG_WORKSPACE_BYTES

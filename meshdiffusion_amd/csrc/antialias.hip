@@ -46,7 +46,7 @@
 
 #pragma clang fp contract(off)
 
-static constexpr int AA_MAX_C = 8;
+static constexpr int AA_MAX_C = RS_MAX_CHANNELS;
 
 struct alignas(16) AaPair {                                  // one pixel pair; va < 0: inactive
   int32_t va, vb;                                            // the edge's vertices
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(256) void md_mesh_edge_neighbours_kernel(const int6
 }
 
 static bool aa_shape_ok(int32_t batch, int32_t n_faces, int32_t H, int32_t W) {
-  return batch <= 64 && H <= 2048 && W <= 2048 && n_faces < (1 << 24);
+  return rs_limits_ok(batch, n_faces, H, W);
 }
 
 extern "C" int md_mesh_edge_neighbours(const int64_t* sorted_keys, const int64_t* order, const int64_t* faces, int32_t n_faces,

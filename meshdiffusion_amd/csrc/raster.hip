@@ -242,7 +242,7 @@ __global__ __launch_bounds__(RS_THREADS) void md_raster_tiles_kernel(const float
 }
 
 static bool rs_shape_ok(int32_t batch, int32_t n_verts, int32_t n_faces, int32_t H, int32_t W) {
-  return batch <= 64 && H <= 2048 && W <= 2048 && n_faces < (1 << 24) && n_verts > 0;
+  return rs_limits_ok(batch, n_faces, H, W) && n_verts > 0;
 }
 
 extern "C" int md_raster_bin_count(const float* pos_clip, const int64_t* faces, int32_t batch, int32_t n_verts, int32_t n_faces,

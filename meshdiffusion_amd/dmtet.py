@@ -443,11 +443,14 @@ class DMTetGeometry(torch.nn.Module):
             return self.verts + 2 / (self.grid_res * 2) * torch.tanh(deform) * self.deform_scale
         return self.verts + 2 / (self.grid_res * 2) * deform * self.deform_scale
 
-    def getMesh(self, material=None):
+    def getMesh(self, material=None, normals_grad=False):
         """Named like the reference's Mesh: v_pos (differentiable), t_pos_idx, v_tex, t_tex_idx, v_nrm / t_nrm_idx (smooth
-        normals, detached), valid_vert_idx."""
+        normals, detached; with normals_grad=True from `vertex_normals` and attached to the graph), valid_vert_idx."""
         verts, faces, uvs, uv_idx, _tet_gidx, valid_vert_idx = self.marching_tets(self.get_deformed(), self.sdf, self.indices)
-        v_nrm = auto_normals(verts.detach(), faces)[0] if verts.shape[0] > 0 else torch.zeros_like(verts)
+        if normals_grad and verts.shape[0] > 0:
+            v_nrm = vertex_normals(verts, faces)[0]
+        else:
+            v_nrm = auto_normals(verts.detach(), faces)[0] if verts.shape[0] > 0 else torch.zeros_like(verts)
         return types.SimpleNamespace(v_pos=verts, t_pos_idx=faces, v_tex=uvs, t_tex_idx=uv_idx, v_nrm=v_nrm, t_nrm_idx=faces,
                                      material=material, valid_vert_idx=valid_vert_idx)
 
@@ -471,4 +474,60 @@ def auto_normals(verts, faces):
     _lib.check(lib.md_vertex_normals(C.c_void_p(v.data_ptr()), C.c_void_p(f.data_ptr()), v.shape[0], f.shape[0],
                                      C.c_void_p(v_nrm.data_ptr()), C.c_void_p(f_nrm.data_ptr()),
                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)), "md_vertex_normals")
+    return v_nrm, f_nrm
+
+
+class _VertexNormalsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts, faces, ptr, order):
+        lib = _lib.load()
+        V, F = verts.shape[0], faces.shape[0]
+        v_nrm = torch.empty_like(verts)
+        f_nrm = torch.empty((F, 3), dtype=torch.float32, device=verts.device)
+        v_len = torch.empty(V, dtype=torch.float32, device=verts.device)
+        _lib.check(lib.md_vertex_normals_det(_ptr(verts), _ptr(faces), _ptr(ptr), _ptr(order), V, F, _ptr(v_nrm), _ptr(f_nrm),
+                                             _ptr(v_len), _stream()), "md_vertex_normals_det")
+        ctx.save_for_backward(verts, faces, ptr, order, v_nrm, v_len)
+        return v_nrm
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        verts, faces, ptr, order, v_nrm, v_len = ctx.saved_tensors
+        V, F = verts.shape[0], faces.shape[0]
+        g = g.to(torch.float32).contiguous()
+        face_grad = torch.empty((F, 3, 3), dtype=torch.float32, device=verts.device)
+        dverts = torch.empty_like(verts)
+        _lib.check(lib.md_vertex_normals_bwd(_ptr(verts), _ptr(faces), _ptr(ptr), _ptr(order), _ptr(v_nrm), _ptr(v_len), _ptr(g),
+                                             V, F, _ptr(face_grad), _ptr(dverts), _stream()), "md_vertex_normals_bwd")
+        return dverts, None, None, None
+
+
+def vertex_normals(verts, faces):
+    """Smooth vertex normals under autograd, by the interpolation contract in the header comment of csrc/interp.hip (mesh.py:
+    200-229): verts float32 [V,3], faces [F,3] -> (v_nrm float32 [V,3], f_nrm float32 [F,3] unnormalised).  fn_f = cross(v1 - v0,
+    v2 - v0); a vertex's normal sums the fn of the corners that name it in ascending order of 3 f + k, a gather over the static
+    face-corner CSR, so two runs agree bit for bit (the atomic `auto_normals` cannot promise that); a sum with s . s <= 1e-20, a
+    vertex no face names included, becomes (0, 0, 1) with a zero gradient.  v_nrm is differentiable w.r.t. verts through
+    md_vertex_normals_bwd, f_nrm through plain torch."""
+    if not verts.is_cuda:
+        raise _lib.MeshDiffusionHipError("vertex_normals runs on the GPU only (no CPU fallback)")
+    if verts.dim() != 2 or verts.shape[-1] != 3 or verts.shape[0] < 1 or faces.dim() != 2 or faces.shape[-1] != 3:
+        raise ValueError(f"vertex_normals: expected verts [V,3] and faces [F,3], got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    v = verts.to(torch.float32).contiguous()
+    f = faces.to(device=v.device, dtype=torch.int64).contiguous()
+    V, F = v.shape[0], f.shape[0]
+    if F >= 2 ** 24:
+        raise _lib.MeshDiffusionHipError("vertex_normals takes fewer than 2^24 faces (MD_ERR_UNSUPPORTED)")
+    if F == 0:
+        up = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float32, device=v.device)
+        return up.expand(V, 3).contiguous(), torch.zeros((0, 3), dtype=torch.float32, device=v.device)
+    lo, hi = torch.aminmax(f)
+    if int(lo) < 0 or int(hi) >= V:
+        raise ValueError(f"faces name vertices outside [0, {V})")
+    vals, order = torch.sort(f.reshape(-1), stable=True)                       # corner code 3 f + k, by vertex
+    ptr = torch.searchsorted(vals, torch.arange(V + 1, dtype=torch.int64, device=v.device)).to(torch.int32).contiguous()
+    v_nrm = _VertexNormalsFn.apply(v, f, ptr, order.to(torch.int32).contiguous())
+    f_nrm = torch.linalg.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
     return v_nrm, f_nrm

@@ -8,11 +8,15 @@ layers -> `interpolate(v_pos)` -> |gb_pos - campos|, and supervises the geometry
 contract in the header comment of csrc/antialias.hip: silhouette antialiasing in the manner of dr.antialias (render.py:256-276),
 not equal to it, with gradients for the colour and the clip-space vertices.  `render_depth(antialias=True)` adds the antialiased
 coverage of both layers and `silhouette_loss` is the coverage term of tick (dmtet.py:394,399), the one path from a silhouette to
-the vertices.  The kernels run on the GPU only: a CPU tensor is an
-error, not a fallback.  The camera helpers, `xfm_points`, `depth_loss` and the carve are plain torch and run anywhere.
+the vertices.  `interpolate`, `rasterize(grad=True)` and `dmtet.vertex_normals` follow the interpolation contract in the header
+comment of csrc/interp.hip: dr.interpolate, the `rast` gradient of dr.rasterize and auto_normals under autograd.  On top of them
+`render_buffers` is the reference's `bsdf == 'normal'` renderer (render.py:105-106, 177-264) and `image_loss` / `color_loss` the
+colour term of tick (dmtet.py:391-400).  The kernels run on the GPU only: a CPU tensor is an
+error, not a fallback.  The camera helpers, `xfm_points`, `shading_normal`, the losses and the carve are plain torch and run
+anywhere.
 
-Not built: materials, lights, BSDFs, textures and the colour terms of tick, spp > 1 / MSAA, clipping of
-triangles that cross w = 0, more than two layers, gradients for mvp / campos, a silhouette search beyond the covering triangle.
+Not built: materials, lights, textures, spp > 1 / MSAA, clipping of triangles that cross w = 0, more than
+two layers, gradients for mvp / campos and zf, a silhouette search beyond the covering triangle.
 """
 import numpy as np
 import torch
@@ -22,6 +26,7 @@ from .hip_ops import _ptr, _stream
 
 TILE = 16                                # RS_TILE of csrc/raster.hip
 MAX_RES, MAX_VIEWS, MAX_FACES = 2048, 64, 2 ** 24 - 1
+MAX_CHANNELS = 8                         # AA_MAX_C of csrc/antialias.hip
 
 
 # ---- camera matrices (nvdiffrec/lib/render/util.py:193-277: float32 tensors of numpy-double entries) ---------------------------
@@ -154,25 +159,196 @@ def _rasterize(pc, f, H, W):
     return rast1, rast2
 
 
-def rasterize(pos_clip, faces, resolution, num_layers=2):
+class _LayerPlan:
+    """What the backward passes over one `rast` layer share: the covered list and the CSRs of the gathers, each built at the
+    first backward that needs it (`nonzero`, a stable sort, `searchsorted`)."""
+
+    def __init__(self, rast, n_faces):
+        self.rast, self.F = rast, n_faces                                      # rast detached, float32, contiguous
+        self._cov, self._csr = None, {}
+
+    def cov(self):
+        """(int64, int32) flat indices (b H + i) W + j of the pixels with 1 <= id <= F, ascending."""
+        if self._cov is None:
+            ids = self.rast[..., 3].reshape(-1)
+            cov = torch.nonzero((ids >= 1) & (ids <= self.F))[:, 0]
+            if 3 * cov.numel() >= 2 ** 31:
+                raise _lib.MeshDiffusionHipError("3 x the covered pixels of a layer must fit int32 (MD_ERR_UNSUPPORTED)")
+            self._cov = (cov, cov.to(torch.int32).contiguous())
+        return self._cov
+
+    def csr(self, tri, n_rows, per_view):
+        """(ptr int32 [rows + 1], order int32 [3 n_cov]) of the codes 3 * entry + corner sorted stably by the row they name:
+        tri[id - 1][corner], plus view * n_rows when every view has rows of its own."""
+        key = (tri.data_ptr(), n_rows, per_view)                               # the entry holds `tri`, so the address stays its own
+        if key not in self._csr or self._csr[key][2]._version != tri._version:
+            B, H, W, _ = self.rast.shape
+            rows = n_rows * (B if per_view else 1)
+            if rows >= 2 ** 31 - 1:
+                raise _lib.MeshDiffusionHipError("the destination rows of a gather must fit int32 (MD_ERR_UNSUPPORTED)")
+            cov = self.cov()[0]
+            dest = tri[self.rast[..., 3].reshape(-1)[cov].to(torch.int64) - 1]
+            if per_view:
+                dest = dest + (torch.div(cov, H * W, rounding_mode="floor") * n_rows)[:, None]
+            vals, order = torch.sort(dest.reshape(-1), stable=True)
+            ptr = torch.searchsorted(vals, torch.arange(rows + 1, dtype=torch.int64, device=vals.device))
+            self._csr[key] = (ptr.to(torch.int32).contiguous(), order.to(torch.int32).contiguous(), tri)
+        return self._csr[key][:2]
+
+
+class _RasterizeFn(torch.autograd.Function):
+    """The two layers of `plans` (rasterised from pos_clip already) with md_raster_bary_bwd as the backward of their (u, v)
+    w.r.t. pos_clip."""
+
+    @staticmethod
+    def forward(ctx, pos_clip, faces, plans):
+        ctx.plans = plans
+        ctx.save_for_backward(pos_clip, faces, plans[0].rast, plans[1].rast)
+        ctx.set_materialize_grads(False)
+        return plans[0].rast.view_as(plans[0].rast), plans[1].rast.view_as(plans[1].rast)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g1, g2):
+        lib = _lib.load()
+        pos_clip, faces, rast1, rast2 = ctx.saved_tensors
+        B, V, F = pos_clip.shape[0], pos_clip.shape[1], faces.shape[0]
+        total = None
+        for plan, rast, g in zip(ctx.plans, (rast1, rast2), (g1, g2)):
+            if g is None or F == 0:
+                continue
+            _, H, W, _ = rast.shape
+            cov = plan.cov()[1]
+            N = cov.numel()
+            if N == 0:
+                continue
+            ptr, order = plan.csr(faces, V, True)
+            g = g.to(torch.float32).contiguous()
+            corner_grad = torch.empty((N, 3, 3), dtype=torch.float32, device=g.device)
+            dpos = torch.empty((B, V, 4), dtype=torch.float32, device=g.device)
+            _lib.check(lib.md_raster_bary_bwd(_ptr(cov), N, _ptr(rast), _ptr(g), _ptr(pos_clip), _ptr(faces), _ptr(ptr),
+                                              _ptr(order), B, V, F, H, W, _ptr(corner_grad), _ptr(dpos), _stream()),
+                       "md_raster_bary_bwd")
+            total = dpos if total is None else total + dpos
+        return (torch.zeros_like(pos_clip) if total is None else total), None, None
+
+
+def _rasterize_grad(pc, f, H, W):
+    """(layers, plans): the two rast layers of pc float32 [B,V,4] with a grad_fn to it, and the `_LayerPlan` of each."""
+    plans = [_LayerPlan(r, f.shape[0]) for r in _rasterize(pc.detach(), f, H, W)]
+    return _RasterizeFn.apply(pc, f, plans), plans
+
+
+def rasterize(pos_clip, faces, resolution, num_layers=2, grad=False):
     """The contract's `rast` layers of pos_clip float32 [B,V,4], faces [F,3] at resolution (H, W) (or one int): a list of
-    `num_layers` (1 or 2) float32 [B,H,W,4] tensors (u, v, zf, face index + 1), zeros where uncovered.  No gradient."""
+    `num_layers` (1 or 2) float32 [B,H,W,4] tensors (u, v, zf, face index + 1), zeros where uncovered.  No gradient, unless
+    grad=True: then the layers (the same bits) carry a grad_fn to `pos_clip` for u and v (ids held fixed; zf and the id get
+    none, and neither does z), by the barycentric backward of the interpolation contract (csrc/interp.hip)."""
     _gpu_only(pos_clip, "rasterize")
     if num_layers not in (1, 2):
         raise NotImplementedError("rasterize: one or two layers")
     _check_clip(pos_clip)
     H, W = _resolution(resolution)
+    if grad:
+        pc = pos_clip.to(torch.float32).contiguous()
+        f = _check_faces(faces.to(pc.device), pc.shape[1])
+        return list(_rasterize_grad(pc, f, H, W)[0][:num_layers])
     pc = pos_clip.detach().to(torch.float32).contiguous()
     f = _check_faces(faces.to(pc.device), pc.shape[1])
     return list(_rasterize(pc, f, H, W)[:num_layers])
 
 
+class _InterpolateFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, attr, rast, tri, plan, rast_grad):
+        lib = _lib.load()
+        B, H, W, _ = rast.shape
+        Ba, N, C = attr.shape
+        F = tri.shape[0]
+        if F == 0:
+            out = torch.zeros((B, H, W, C), dtype=torch.float32, device=rast.device)
+        else:
+            out = torch.empty((B, H, W, C), dtype=torch.float32, device=rast.device)
+            _lib.check(lib.md_interpolate(_ptr(rast), _ptr(attr), _ptr(tri), B, Ba, N, C, F, H, W, _ptr(out), _stream()),
+                       "md_interpolate")
+        ctx.plan, ctx.rast_grad = plan, rast_grad
+        ctx.save_for_backward(attr, tri, rast)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        attr, tri, rast = ctx.saved_tensors
+        plan = ctx.plan                                                        # the covered list and the CSRs of rast's layer
+        B, H, W, _ = rast.shape
+        Ba, N, C = attr.shape
+        F = tri.shape[0]
+        need_attr, need_rast = ctx.needs_input_grad[0], ctx.rast_grad and ctx.needs_input_grad[1]
+        dattr = torch.empty_like(attr) if need_attr else None
+        drast = torch.empty_like(rast) if need_rast else None
+        n_cov = plan.cov()[1].numel() if F > 0 and (need_attr or need_rast) else 0
+        if n_cov == 0:
+            return (None if dattr is None else dattr.zero_()), (None if drast is None else drast.zero_()), None, None, None
+        cov = plan.cov()[1]
+        g = g.to(torch.float32).contiguous()
+        ptr = order = corner_grad = None
+        if need_attr:
+            ptr, order = plan.csr(tri, N, Ba != 1)
+            corner_grad = torch.empty((n_cov, 3, C), dtype=torch.float32, device=g.device)
+        _lib.check(lib.md_interpolate_bwd(_ptr(cov), n_cov, _ptr(rast), _ptr(g), _ptr(attr), _ptr(tri), _ptr(ptr), _ptr(order),
+                                          B, Ba, N, C, F, H, W, _ptr(corner_grad), _ptr(dattr), _ptr(drast), _stream()),
+                   "md_interpolate_bwd")
+        return dattr, drast, None, None, None
+
+
+def _check_tri(tri, n_rows):
+    try:
+        return _check_faces(tri, n_rows)
+    except ValueError as e:
+        raise ValueError(str(e).replace("faces", "tri").replace("vertices", "attribute rows")) from None
+
+
+def interpolate(attr, rast, tri, rast_grad=False, _plan=None):
+    """dr.interpolate by the interpolation contract in the header comment of csrc/interp.hip: attr float32 [N,C], [1,N,C] (shared
+    by the views) or [B,N,C], 1 <= C <= 8; rast float32 [B,H,W,4] one layer of `rasterize`; tri [F,3] with indices into N (for a
+    face-constant attribute tri[f] = (f, f, f) and N = F).  Returns float32 [B,H,W,C]: (u A0 + v A1) + (1 - u - v) A2 where
+    1 <= id <= F, zeros elsewhere, with a gradient for `attr`, and with rast_grad=True and a `rast` that requires one
+    (`rasterize(grad=True)`) for u and v of `rast` too.  Shapes, C and the range of tri are checked once here; the kernels
+    index unchecked.  Deterministic: two runs agree bit for bit, backward included."""
+    _gpu_only(rast, "interpolate")
+    _gpu_only(attr, "interpolate")
+    a = attr[None] if attr.dim() == 2 else attr
+    if rast.dim() != 4 or rast.shape[-1] != 4 or rast.shape[0] < 1 or rast.shape[1] < 1 or rast.shape[2] < 1:
+        raise ValueError(f"interpolate: expected rast [B,H,W,4], got {tuple(rast.shape)}")
+    B, H, W, _ = rast.shape
+    if a.dim() != 3 or a.shape[0] not in (1, B) or a.shape[1] < 1:
+        raise ValueError(f"interpolate: expected attr [N,C], [1,N,C] or [{B},N,C], got {tuple(attr.shape)}")
+    C = a.shape[2]
+    if C < 1 or C > MAX_CHANNELS:
+        raise _lib.MeshDiffusionHipError(f"interpolate takes 1 to {MAX_CHANNELS} channels, got {C} (MD_ERR_UNSUPPORTED)")
+    if B > MAX_VIEWS:
+        raise _lib.MeshDiffusionHipError(f"interpolate takes at most {MAX_VIEWS} views per call (MD_ERR_UNSUPPORTED)")
+    _resolution((H, W))
+    dev = rast.device
+    a = a.to(device=dev, dtype=torch.float32).contiguous()
+    t = _check_tri(tri.to(dev), a.shape[1])
+    r = rast.to(torch.float32).contiguous()
+    if not rast_grad:
+        r = r.detach()
+    if _plan is None:
+        _plan = _LayerPlan(r.detach(), t.shape[0])
+    elif _plan.F != t.shape[0] or _plan.rast.shape != r.shape:
+        raise ValueError("interpolate: the plan belongs to another layer")
+    return _InterpolateFn.apply(a, r, t, _plan, bool(rast_grad))
+
+
 class _RenderDepthFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, verts, pos_clip, faces, mvp, campos, H, W):
+    def forward(ctx, verts, pos_clip, faces, mvp, campos, H, W, layers=None):
         lib = _lib.load()
         B, V, F, dev = pos_clip.shape[0], verts.shape[0], faces.shape[0], verts.device
-        rast1, rast2 = _rasterize(pos_clip, faces, H, W)
+        rast1, rast2 = _rasterize(pos_clip, faces, H, W) if layers is None else layers     # layers: these, rasterised already
         depth1 = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev)
         depth2, mask1, mask2 = torch.empty_like(depth1), torch.empty_like(depth1), torch.empty_like(depth1)
         if F == 0:
@@ -201,7 +377,7 @@ class _RenderDepthFn(torch.autograd.Function):
             raise _lib.MeshDiffusionHipError("render_depth backward: 3 x the covered (pixel, layer) entries must fit int32")
         dverts = torch.empty((V, 3), dtype=torch.float32, device=dev)
         if N == 0 or F == 0:
-            return dverts.zero_(), None, None, None, None, None, None
+            return dverts.zero_(), None, None, None, None, None, None, None
         corner_vert = faces[ids[cov].to(torch.int64) - 1].reshape(-1)          # entry 3 n + corner names this vertex
         vals, order = torch.sort(corner_vert, stable=True)
         ptr = torch.searchsorted(vals, torch.arange(V + 1, dtype=torch.int64, device=dev)).to(torch.int32).contiguous()
@@ -211,13 +387,10 @@ class _RenderDepthFn(torch.autograd.Function):
         _lib.check(lib.md_raster_depth_bwd(_ptr(cov), N, _ptr(rast1), _ptr(rast2), _ptr(g1), _ptr(g2), _ptr(pos_clip), _ptr(verts),
                                            _ptr(faces), _ptr(mvp), _ptr(campos), _ptr(ptr), _ptr(order), B, V, F, H, W,
                                            _ptr(corner_grad), _ptr(dverts), _stream()), "md_raster_depth_bwd")
-        return dverts, None, None, None, None, None, None
+        return dverts, None, None, None, None, None, None, None
 
 
 # ---- antialiasing ------------------------------------------------------------------------------------------------------------------
-MAX_CHANNELS = 8                         # AA_MAX_C of csrc/antialias.hip
-
-
 def edge_neighbours(faces, n_verts):
     """nbr int32 [F,3] of the antialiasing contract: nbr[f][k] is the vertex opposite the edge (faces[f][(k+1)%3],
     faces[f][(k+2)%3]) in the one other face that owns it, or -1 (boundary, or an edge of three or more faces).  A stable torch
@@ -368,6 +541,101 @@ def render_depth(verts, faces, mvp, campos, resolution, antialias=False):
     return out
 
 
+# ---- the bsdf == 'normal' renderer -------------------------------------------------------------------------------------------------
+NORMAL_THRESHOLD = 0.1                   # renderutils/bsdf.py:13
+
+
+def _dot(a, b):
+    return torch.sum(a * b, -1, keepdim=True)
+
+
+def _shading_normal(gb_pos, campos, gb_normal, gb_geo_normal):
+    """(shading normal, flipped geometric normal)."""
+    if campos.dim() == 2:
+        campos = campos[:, None, None, :]
+    smooth = torch.nn.functional.normalize(gb_normal, dim=-1)
+    view = torch.nn.functional.normalize(campos - gb_pos, dim=-1)
+    front = _dot(gb_geo_normal, view) > 0
+    smooth = torch.where(front, smooth, -smooth)
+    geo = torch.where(front, gb_geo_normal, -gb_geo_normal)
+    t = torch.clamp(_dot(view, smooth) / NORMAL_THRESHOLD, min=0, max=1)
+    return torch.lerp(geo, smooth, t), geo
+
+
+def shading_normal(gb_pos, campos, gb_normal, gb_geo_normal):
+    """The reference's prepare_shading_normal with no tangent, two_sided_shading=True, use_python=True (renderutils/bsdf.py:
+    28-54): normalise the smooth normal and the view vector campos - gb_pos, flip both normals where geo . view <= 0, then bend
+    with t = clamp(view . smooth / 0.1, 0, 1): lerp(geo, smooth, t).  gb_* [B,H,W,3], campos [B,3] or broadcastable.  Plain torch."""
+    return _shading_normal(gb_pos, campos, gb_normal, gb_geo_normal)[0]
+
+
+def render_buffers(verts, faces, mvp, campos, resolution, v_nrm=None):
+    """The reference's render_mesh with `bsdf == 'normal'` on a zero background (render.py:105-106, 177-329): everything
+    `render_depth(verts, faces, mvp, campos, resolution, antialias=True)` returns, with equal bits, plus for layer 1 and, under
+    names ending in `_second`, for layer 2
+      pos          float32 [B,H,W,3]: the interpolated world position; uncovered pixels hold 20.0 (layer 2: -1.0)
+      geo_normal   float32 [B,H,W,3]: the interpolation of safe_normalize(f_nrm) with tri = (f, f, f), flipped towards the
+                   camera as `shading_normal` flips it; zeros where uncovered
+      normal       float32 [B,H,W,3]: `shading_normal` of the interpolated vertex normals, not antialiased; zeros where uncovered
+      shaded       float32 [B,H,W,4]: `antialias(cat(((normal + 1) / 2) * mask, mask))` with the layer's own rast; channel 3
+                   equals `alpha`.
+    `shaded_second` is layer 2's own image; the reference's `shaded_second` repeats layer 1 (render.py:325).
+    v_nrm [V,3]: the vertex normals to shade with (`DMTetGeometry.getMesh(normals_grad=True).v_nrm`); None: `dmtet.vertex_normals
+    (verts, faces)`.  Gradients reach `verts` through the attribute path, the barycentric path (`rasterize(grad=True)` on
+    `xfm_points(verts)`), the vertex normals and the antialiasing.  The rast, tri and CSRs of a layer are built once and shared
+    by its interpolations."""
+    from .dmtet import vertex_normals
+    _gpu_only(verts, "render_buffers")
+    v = verts[0] if verts.dim() == 3 and verts.shape[0] == 1 else verts
+    if v.dim() != 2 or v.shape[-1] != 3 or v.shape[0] < 1:
+        raise ValueError(f"render_buffers: expected verts [V,3] or [1,V,3], got {tuple(verts.shape)}")
+    if mvp.dim() != 3 or mvp.shape[1:] != (4, 4) or campos.shape != (mvp.shape[0], 3):
+        raise ValueError(f"render_buffers: expected mvp [B,4,4] and campos [B,3], got {tuple(mvp.shape)} and {tuple(campos.shape)}")
+    H, W = _resolution(resolution)
+    v = v.to(torch.float32).contiguous()
+    dev, V = v.device, v.shape[0]
+    mvp = mvp.detach().to(device=dev, dtype=torch.float32).contiguous()
+    campos = campos.detach().to(device=dev, dtype=torch.float32).contiguous()
+    clip = xfm_points(v[None], mvp).contiguous()                               # the rasterised bits, with the way back to verts
+    _check_clip(clip)
+    f = _check_faces(faces.to(dev), V)
+    F = f.shape[0]
+    if v_nrm is None:
+        v_nrm, f_nrm = vertex_normals(v, f)
+    else:
+        if tuple(v_nrm.shape) != (V, 3):
+            raise ValueError(f"render_buffers: expected v_nrm [{V},3], got {tuple(v_nrm.shape)}")
+        v_nrm = v_nrm.to(device=dev, dtype=torch.float32)
+        f_nrm = torch.linalg.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    layers, plans = _rasterize_grad(clip, f, H, W)
+    depth, depth2, mask, mask2, rast, rast2 = _RenderDepthFn.apply(v, clip.detach(), f, mvp, campos, H, W,
+                                                                   (plans[0].rast, plans[1].rast))
+    tri = torch.unique(rast[..., 3])
+    tri = tri[tri > 0].to(torch.int64) - 1
+    out = {"depth": depth, "depth_second": depth2, "mask": mask, "mask_second": mask2, "rast": rast, "rast_second": rast2,
+           "rast_triangle_id": tri if tri.numel() > 0 else None}
+    nbr = edge_neighbours(f, V)
+    out["alpha"] = _antialias(mask, rast, clip, f, nbr)
+    out["alpha_second"] = _antialias(mask2, rast2, clip, f, nbr)
+    vert_attr = torch.cat([v, v_nrm], -1)                                      # position and smooth normal in one pass
+    geo_attr = f_nrm / torch.sqrt(torch.clamp(_dot(f_nrm, f_nrm), min=1e-20))  # the reference's safe_normalize
+    fff = torch.arange(F, dtype=torch.int64, device=dev)[:, None].expand(F, 3).contiguous()
+    for k, (r_grad, plan, m, bg, tail) in enumerate(((layers[0], plans[0], mask, 20.0, ""), (layers[1], plans[1], mask2, -1.0, "_second"))):
+        gb = interpolate(vert_attr, r_grad, f, rast_grad=True, _plan=plan)
+        if F > 0:
+            gb_geo = interpolate(geo_attr, plan.rast, fff, _plan=plan)         # face-constant: du = dv = 0
+        else:
+            gb_geo = torch.zeros_like(gb[..., :3])
+        covered = m > 0
+        normal, geo = _shading_normal(gb[..., :3], campos, gb[..., 3:], gb_geo)
+        zero = torch.zeros_like(normal)
+        normal, geo = torch.where(covered, normal, zero), torch.where(covered, geo, zero)
+        out["pos" + tail] = torch.where(covered, gb[..., :3], torch.full_like(zero, bg))
+        out["geo_normal" + tail], out["normal" + tail] = geo, normal
+        out["shaded" + tail] = _antialias(torch.cat([((normal + 1) / 2) * m, m], -1), plan.rast, clip, f, nbr)
+    return out
+
+
 # ---- losses and the fitting loop ---------------------------------------------------------------------------------------------------
 def depth_loss(buffers, target, iteration):
     """The depth terms of DMTetGeometry.tick (dmtet.py:402-434) with no_depth_thin: elementwise torch.
@@ -390,17 +658,56 @@ def silhouette_loss(buffers, target):
     return mse(buffers["alpha"], target["alpha"]) + 0.1 * mse(buffers["alpha_second"], target["alpha_second"])
 
 
+IMAGE_LOSSES = ("smape", "mse", "logl1", "logl2", "relmse")
+
+
+def _tonemap_srgb(f):
+    return torch.where(f > 0.0031308, torch.pow(torch.clamp(f, min=0.0031308), 1.0 / 2.4) * 1.055 - 0.055, 12.92 * f)
+
+
+def image_loss(img, ref, kind):
+    """The reference's createLoss(kind)(img, ref) (fit_dmtets.py:65-77, renderutils/loss.py): `smape`, `mse`, `relmse` on the
+    images as they are, `logl1` / `logl2` the L1 / MSE of tonemap_srgb(log(clamp(x, 0, 65535) + 1)).  Plain torch."""
+    if kind not in IMAGE_LOSSES:
+        raise ValueError(f"image_loss: kind must be one of {IMAGE_LOSSES}, got {kind!r}")
+    if kind in ("logl1", "logl2"):
+        img = _tonemap_srgb(torch.log(torch.clamp(img, min=0, max=65535) + 1))
+        ref = _tonemap_srgb(torch.log(torch.clamp(ref, min=0, max=65535) + 1))
+    if kind in ("mse", "logl2"):
+        return torch.nn.functional.mse_loss(img, ref)
+    if kind == "smape":
+        return torch.mean(torch.abs(img - ref) / (torch.abs(img) + torch.abs(ref) + 0.01))
+    if kind == "relmse":
+        return torch.mean((img - ref) * (img - ref) / (img * img + ref * ref + 0.1))
+    return torch.nn.functional.l1_loss(img, ref)
+
+
+def color_loss(buffers, target, kind="logl1"):
+    """The colour term of DMTetGeometry.tick (dmtet.py:395,400): image_loss(shaded rgb x ref alpha, ref rgb x ref alpha) of layer
+    1 plus 0.1 times that of `shaded_second` / `img_second`.  The alpha terms of those lines are `silhouette_loss`."""
+    ref, ref2 = target["img"], target["img_second"]
+    return (image_loss(buffers["shaded"][..., 0:3] * ref[..., 3:], ref[..., 0:3] * ref[..., 3:], kind)
+            + 0.1 * image_loss(buffers["shaded_second"][..., 0:3] * ref2[..., 3:], ref2[..., 0:3] * ref2[..., 3:], kind))
+
+
 @torch.no_grad()
-def make_targets(verts, faces, mvp, campos, resolution, antialias=False):
+def make_targets(verts, faces, mvp, campos, resolution, antialias=False, shaded=False):
     """Render the ground-truth mesh with the same rasteriser (the role of dataset_mesh.py:120): `depth`, `depth_second`,
-    `mask_cont` [B,H,W,1], and the cameras `mvp`, `campos`, `resolution`; antialias=True adds `alpha`, `alpha_second`."""
-    out = render_depth(verts.detach(), faces, mvp, campos, resolution, antialias=antialias)
+    `mask_cont` [B,H,W,1], and the cameras `mvp`, `campos`, `resolution`; antialias=True adds `alpha`, `alpha_second`;
+    shaded=True implies it and adds `img`, `img_second` [B,H,W,4], the `shaded` buffers of `render_buffers`."""
+    antialias = antialias or shaded
+    if shaded:
+        out = render_buffers(verts.detach(), faces, mvp, campos, resolution)
+    else:
+        out = render_depth(verts.detach(), faces, mvp, campos, resolution, antialias=antialias)
     H, W = _resolution(resolution)
     tgt = {"depth": out["depth"], "depth_second": out["depth_second"], "mask_cont": out["mask"],
            "mvp": mvp.detach().to(device=verts.device, dtype=torch.float32), "campos": campos.detach().to(device=verts.device, dtype=torch.float32),
            "resolution": [H, W]}
     if antialias:
         tgt["alpha"], tgt["alpha_second"] = out["alpha"], out["alpha_second"]
+    if shaded:
+        tgt["img"], tgt["img_second"] = out["shaded"], out["shaded_second"]
     return tgt
 
 
@@ -429,17 +736,20 @@ def carve_outside_silhouette(geometry, target, kernel_size=11):
 
 def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, views_per_iter=None, generator=None,
                  target_points=None, num_samples=50000, carve=True, callback=None, start_iteration=0, alpha_weight=0.0,
-                 return_terms=False):
+                 return_terms=False, color_weight=0.0, color_loss_kind="logl1"):
     """Fit a `DMTetGeometry` to rendered targets (`make_targets`) the way the reference's tick supervises geometry: per
     iteration
         [carve, for 200 < it < 2000 and it % 20 == 0] -> [deform *= 0.4, for it % 300 == 0 and it < 1790]
         -> getMesh -> render_depth on `views_per_iter` views -> depth_loss + sdf_reg_loss(masked sdf) * weight * 0.1
         [+ alpha_weight * silhouette_loss, for alpha_weight > 0; the reference's weight is 1.0]
+        [+ color_weight * color_loss(color_loss_kind), for color_weight > 0: the mesh then comes from getMesh(normals_grad=True)
+           and is rendered with render_buffers; the reference's weight is 1.0 and its loss logl1]
         [+ chamfer(sample_points(num_samples), target_points)] -> Adam step on (sdf, deform) -> clamp_deform.
     views_per_iter: None = every view each iteration, else that many drawn without replacement (torch.randperm, `generator`).
     `callback(it, loss, mesh)` after each step.  Returns the depth-loss values, float32 [iters] on the device; with
     return_terms=True the dict {"depth": [iters], "alpha": [iters]} of both terms.  alpha_weight > 0 and return_terms need
-    targets made with `make_targets(..., antialias=True)`."""
+    targets made with `make_targets(..., antialias=True)`; color_weight > 0 needs `make_targets(..., shaded=True)` and adds
+    "color": [iters] to the dict of return_terms."""
     from .dmtet import sdf_reg_loss
     from .pointcloud import chamfer_distance, sample_points, sdf_regularizer_weight
     dev = geometry.sdf.device
@@ -448,9 +758,12 @@ def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, view
     with_alpha = alpha_weight > 0 or return_terms
     if with_alpha and not ("alpha" in targets and "alpha_second" in targets):
         raise ValueError("fit_to_views: the alpha term needs targets made with make_targets(..., antialias=True)")
+    with_color = color_weight > 0
+    if with_color and not ("img" in targets and "img_second" in targets):
+        raise ValueError("fit_to_views: the colour term needs targets made with make_targets(..., shaded=True)")
     pts = None if target_points is None else target_points.detach().to(device=dev, dtype=torch.float32).reshape(1, -1, 3).contiguous()
     opt = torch.optim.Adam([geometry.sdf, geometry.deform], lr=lr)
-    history, alpha_history = [], []
+    history, alpha_history, color_history = [], [], []
     for k in range(iters):
         it = start_iteration + k
         if views_per_iter is None or views_per_iter >= n_views:
@@ -465,10 +778,13 @@ def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, view
             with torch.no_grad():
                 geometry.deform.data[:] *= 0.4
         opt.zero_grad(set_to_none=True)
-        mesh = geometry.getMesh()
+        mesh = geometry.getMesh(normals_grad=True) if with_color else geometry.getMesh()
         if mesh.t_pos_idx.shape[0] == 0:
             raise _lib.MeshDiffusionHipError(f"fit_to_views: the mesh of iteration {it} has no faces")
-        buffers = render_depth(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"], antialias=with_alpha)
+        if with_color:
+            buffers = render_buffers(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"], v_nrm=mesh.v_nrm)
+        else:
+            buffers = render_depth(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"], antialias=with_alpha)
         loss = depth_loss(buffers, tgt, it)
         sdf_mask = torch.zeros_like(geometry.sdf)
         sdf_mask[mesh.valid_vert_idx] = 1.0
@@ -479,6 +795,10 @@ def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, view
             alpha_history.append(alpha.detach())
             if alpha_weight > 0:
                 total = total + alpha * alpha_weight
+        if with_color:
+            color = color_loss(buffers, tgt, color_loss_kind)
+            color_history.append(color.detach())
+            total = total + color * color_weight
         if pts is not None:
             pred = sample_points(mesh.v_pos[None], mesh.t_pos_idx, num_samples, generator=generator)[0]
             total = total + chamfer_distance(pred, pts).mean()
@@ -490,5 +810,8 @@ def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, view
             callback(it, history[-1], mesh)
     depth_terms = torch.stack(history) if history else torch.empty(0, device=dev)
     if return_terms:
-        return {"depth": depth_terms, "alpha": torch.stack(alpha_history) if alpha_history else torch.empty(0, device=dev)}
+        terms = {"depth": depth_terms, "alpha": torch.stack(alpha_history) if alpha_history else torch.empty(0, device=dev)}
+        if with_color:
+            terms["color"] = torch.stack(color_history) if color_history else torch.empty(0, device=dev)
+        return terms
     return depth_terms

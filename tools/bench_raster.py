@@ -9,6 +9,10 @@ tests/raster_cases.py:
   (f) at B = 8: `antialias` of the layer-1 coverage mask, forward and forward + backward (color and pos_clip), next to the fp32
       torch restatement of tests/antialias_cases.py on the same GPU in interleaved rounds; `edge_neighbours`; `render_depth`
       forward + backward with and without antialias=True; the device kernels launched per call (torch.profiler);
+  (g) at B = 8: `render_buffers` (the bsdf == 'normal' renderer: interpolation, vertex normals, shading normal, two antialiased
+      images) forward and forward + backward next to `render_depth(antialias=True)` at equal shapes in interleaved rounds, and
+      the split of its device time between the library's own kernels and the torch glue (elementwise chain, sorts, CSRs) with
+      the launches of each (torch.profiler);
   (e) one fit_to_views iteration on the shipped 64 grid (sphere start, torus target, 8 views at 512 x 512), next to the
       chamfer iteration of tools/bench_pointcloud.py.
 Device events after warm-up; each figure is the median over rounds.
@@ -59,6 +63,76 @@ def launches(fn):
         return sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "mem" not in e.name.lower())
     except Exception:
         return -1
+
+
+def device_split(fn):
+    """(own kernels ms, own launches, torch glue ms, glue launches) of one call by torch.profiler: device time of the library's
+    kernels (every one is named md_<...>_kernel) against every other device kernel; copies and memsets are left out.  None,
+    with the reason printed, when the profiler cannot be used."""
+    import re
+    try:
+        from torch.profiler import ProfilerActivity, profile
+    except ImportError as e:
+        print(f"device_split: torch.profiler is not available ({e}); no split of kernel time against glue", flush=True)
+        return None
+    fn()
+    torch.cuda.synchronize()
+    try:
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+    except RuntimeError as e:
+        print(f"device_split: the profiler failed ({e}); no split of kernel time against glue", flush=True)
+        return None
+    own, glue = [0.0, 0], [0.0, 0]
+    for e in prof.events():
+        if e.device_type != torch.autograd.DeviceType.CUDA or e.name.startswith(("Memcpy", "Memset")):
+            continue
+        acc = own if re.search(r"\bmd_\w+_kernel\b", e.name) else glue
+        acc[0] += e.device_time_total / 1000.0
+        acc[1] += 1
+    return own[0], own[1], glue[0], glue[1]
+
+
+def bench_buffers(name, verts, faces, mvp, campos, H, W, a, rec):
+    from meshdiffusion_amd import render
+    B = mvp.shape[0]
+    G1 = torch.randn(B, H, W, 1, device="cuda")
+    G3, G4 = torch.randn(B, H, W, 3, device="cuda"), torch.randn(B, H, W, 4, device="cuda")
+
+    def depth_fwd():
+        with torch.no_grad():
+            return render.render_depth(verts, faces, mvp, campos, (H, W), antialias=True)
+
+    def depth_fwd_bwd():
+        v = verts.detach().requires_grad_(True)
+        out = render.render_depth(v, faces, mvp, campos, (H, W), antialias=True)
+        ((out["depth"] * G1).sum() + (out["depth_second"] * G1).sum() + (out["alpha"] * G1).sum() + (out["alpha_second"] * G1).sum()).backward()
+        return v.grad
+
+    def buf_fwd():
+        with torch.no_grad():
+            return render.render_buffers(verts, faces, mvp, campos, (H, W))
+
+    def buf_fwd_bwd():
+        v = verts.detach().requires_grad_(True)
+        out = render.render_buffers(v, faces, mvp, campos, (H, W))
+        ((out["depth"] * G1).sum() + (out["depth_second"] * G1).sum() + (out["shaded"] * G4).sum() + (out["shaded_second"] * G4).sum()
+         + (out["normal"] * G3).sum() + (out["pos"] * G3).sum()).backward()
+        return v.grad
+
+    t = interleaved_ms([depth_fwd, buf_fwd, depth_fwd_bwd, buf_fwd_bwd], a.rounds, a.reps)
+    split = [device_split(f) for f in (buf_fwd, buf_fwd_bwd, depth_fwd_bwd)]
+    line = (f"render_buffers {name} V={verts.shape[0]} F={faces.shape[0]} B={B} {H}x{W}: forward {t[1]:.3f} ms (render_depth(antialias=True) "
+            f"{t[0]:.3f} ms, x{t[1] / t[0]:.2f}) | forward+backward {t[3]:.3f} ms (render_depth(antialias=True) {t[2]:.3f} ms, x{t[3] / t[2]:.2f})")
+    for label, sp in zip(("forward", "forward+backward", "render_depth(antialias=True) forward+backward"), split):
+        if sp is not None:
+            line += (f" | {label} device time: own kernels {sp[0]:.3f} ms in {sp[1]} launches, torch glue {sp[2]:.3f} ms in {sp[3]} launches "
+                     f"({100 * sp[2] / max(sp[0] + sp[2], 1e-9):.0f} % glue)")
+    print(line, flush=True)
+    rec["cases"][f"buffers_{name}_B{B}"] = dict(render_depth_aa_forward=round(t[0], 4), forward=round(t[1], 4),
+                                               render_depth_aa_forward_backward=round(t[2], 4), forward_backward=round(t[3], 4),
+                                               device_split=split)
 
 
 def bench_antialias(name, verts, faces, mvp, campos, pc, H, W, a, rec):
@@ -119,6 +193,7 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--no-baseline", action="store_true")
     ap.add_argument("--only-antialias", action="store_true", help="skip the rasteriser's own rows and the fit iteration")
+    ap.add_argument("--only-buffers", action="store_true", help="only the render_buffers rows (g)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_raster.py needs a GPU: the HIP path has no CPU fallback")
@@ -137,9 +212,11 @@ def main():
             mvp, campos = (t.cuda() for t in rc.cameras(angles, H, W))
             pc = render.xfm_points(verts[None], mvp).contiguous()
             G = torch.randn(B, H, W, 1, device="cuda")
-            if B == 8:
+            if B == 8 and not a.only_buffers:
                 bench_antialias(name, verts, faces, mvp, campos, pc, H, W, a, rec)
-            if a.only_antialias:
+            if B == 8 and not a.only_antialias:
+                bench_buffers(name, verts, faces, mvp, campos, H, W, a, rec)
+            if a.only_antialias or a.only_buffers:
                 continue
 
             def fwd():
@@ -209,7 +286,7 @@ def main():
     with torch.no_grad():
         geo.sdf.copy_(rc.fit_initial_sdf(geo.verts))
     tv, tf = (t.cuda() for t in rc.mesh("torus"))
-    for B, res in (() if a.only_antialias else ((4, 64), (8, a.res))):
+    for B, res in (() if a.only_antialias or a.only_buffers else ((4, 64), (8, a.res))):
         mvp, campos = (t.cuda() for t in rc.cameras([2 * 3.141592653589793 * k / B for k in range(B)], res, res))
         targets = render.make_targets(tv, tf, mvp, campos, res)
         state = {"it": 1}

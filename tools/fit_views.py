@@ -1,10 +1,12 @@
 """Fit a DMTet grid to a mesh under depth supervision, the way the reference's fit_dmtets.py supervises geometry: `.obj` ->
 depth / silhouette targets of --views cameras (rendered with the project's own rasteriser) -> DMTetGeometry fitted with the
-depth loss, the SDF regulariser, the silhouette carve, with --alpha_weight the antialiased coverage term and, with --points,
-the chamfer distance -> the `{'sdf', 'deform'}` dict that `mesh_export.dicts_to_grids` turns into a training grid.
+depth loss, the SDF regulariser, the silhouette carve, with --alpha_weight the antialiased coverage term, with --color_weight
+the colour term of the normal-shaded image and, with --points, the chamfer distance -> the `{'sdf', 'deform'}` dict that `mesh_export.dicts_to_grids` turns into a training grid.
 
     python tools/fit_views.py --obj shape.obj --tet_path data/tets/64_tets_cropped.npz --views 16 --res 256 --out fitted/dmt_dict_00000.pt
 and then `mesh_export.dicts_to_grids(tet_vertices, "fitted", "grids", 64, [0])` writes grids/grid_00000.pt.
+    python tools/fit_views.py ... --alpha_weight 1 --color_weight 1 --dump_normals fitted/normals
+adds the reference's image terms and writes the normal map of every view after the fit.
 
 The mesh is centred and scaled into the tet grid's volume (largest half-extent -> --fit_scale).  Camera k of N looks at the
 origin from distance --cam_radius: perspective(--fovy, 1, 0.1, 1000) @ translate(0, 0, -radius) @ rotate_x(elevation_k) @
@@ -47,6 +49,10 @@ def main(argv=None):
     ap.add_argument("--points", type=int, default=0, help="> 0: add the chamfer term with this many target points and samples")
     ap.add_argument("--alpha_weight", type=float, default=0.0,
                     help="> 0: add this weight times the antialiased coverage term (the reference's weight is 1.0)")
+    ap.add_argument("--color_weight", type=float, default=0.0,
+                    help="> 0: add this weight times the colour term of the bsdf == 'normal' image (the reference's weight is 1.0)")
+    ap.add_argument("--dump_normals", default=None, metavar="DIR",
+                    help="write the final `shaded` view k (the normal map over the antialiased coverage) as DIR/view_<k>.npy")
     ap.add_argument("--mesh_scale", type=float, default=2.1)
     ap.add_argument("--deform_scale", type=float, default=2.0)
     ap.add_argument("--fit_scale", type=float, default=0.8, help="largest half-extent of the normalised target")
@@ -69,7 +75,7 @@ def main(argv=None):
     lo, hi = v.min(0).values, v.max(0).values
     v = (v - (lo + hi) / 2) * (a.fit_scale / float((hi - lo).max() / 2))
     mvp, campos = orbit_cameras(a.views, a.cam_radius, a.fovy, "cuda")
-    targets = render.make_targets(v, f, mvp, campos, a.res, antialias=a.alpha_weight > 0)
+    targets = render.make_targets(v, f, mvp, campos, a.res, antialias=a.alpha_weight > 0, shaded=a.color_weight > 0)
     points = sample_points(v[None], f, a.points, generator=gen)[0][0] if a.points > 0 else None
     tet = np.load(a.tet_path)
     geo = DMTetGeometry(a.resolution, a.mesh_scale, None, tets=(tet["vertices"], tet["indices"]), deform_scale=a.deform_scale)
@@ -83,7 +89,15 @@ def main(argv=None):
 
     render.fit_to_views(geo, targets, a.iters, lr=a.lr, sdf_regularizer=a.sdf_regularizer, views_per_iter=a.views_per_iter,
                         generator=gen, target_points=points, num_samples=max(a.points, 1), callback=report,
-                        alpha_weight=a.alpha_weight)
+                        alpha_weight=a.alpha_weight, color_weight=a.color_weight)
+    if a.dump_normals:
+        os.makedirs(a.dump_normals, exist_ok=True)
+        with torch.no_grad():
+            mesh = geo.getMesh()
+            shaded = render.render_buffers(mesh.v_pos, mesh.t_pos_idx, mvp, campos, a.res)["shaded"].cpu().numpy()
+        for k in range(shaded.shape[0]):
+            np.save(os.path.join(a.dump_normals, f"view_{k:03d}.npy"), shaded[k])
+        print(f"wrote {shaded.shape[0]} views to {a.dump_normals}")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     torch.save(geo.state_to_dict(), a.out)
     print(f"wrote {a.out}")
