@@ -925,6 +925,40 @@ int md_vertex_normals_bwd(const float* verts, const int64_t* faces, const int32_
                           const float* v_len, const float* grad_v_nrm, int32_t n_verts, int32_t n_faces, float* face_grad,
                           float* dverts, void* stream);
 
+/*
+ * The fixed-topology second pass of the DMTet fit (nvdiffrec/fit_dmtets.py:758-793, dmtet_fixedtopo.py:176-288, regularizer.py:
+ * 41-60), csrc/fixedtopo.hip.  Purely additive: MD_ABI_VERSION stays 16, no existing entry point changes.
+ *
+ * THE FIXED-TOPOLOGY CONTRACT (the header comment of csrc/fixedtopo.hip has it in full; tests/fixedtopo_cases.py restates it)
+ *   Plan: edge int32 [Vm][2] (8-byte aligned) = the grid endpoints (a, b) of mesh vertex i, the crossing edges of the sorted edge
+ *   table in ascending edge id (md_marching_tets's numbering); grid-vertex CSR ptr int32 [N+1], inc int32 [2 Vm] of the codes
+ *   2 * mesh vertex + endpoint, ascending inside a grid vertex; face-corner CSR ptr int32 [V+1], order int32 [3 F] of the codes
+ *   3 f + k sorted stably by vertex (that of md_vertex_normals_det).  An index outside its table is skipped, never read.
+ *   Sizes are int64: non-positive MD_ERR_BAD_ARG; N, V, 2 Vm beyond int32 or F >= 2^24 MD_ERR_UNSUPPORTED; null or misaligned
+ *   pointers MD_ERR_BAD_ARG.  fp32, no contraction, no floating-point atomics: two runs agree bit for bit.
+ * md_fixedtopo_verts: verts float32 [Vm][3] = pos[a] * (-sb / den) + pos[b] * (sa / den), den = sa - sb, the expressions of
+ *   md_marching_tets in its order: bit-equal to it on the same pos float32 [N][3], sdf float32 [N].
+ * md_fixedtopo_verts_bwd: dpos float32 [N][3] = per grid vertex the plain fp32 sum, in ascending code order, of grad_verts[i] * the
+ *   forward's weight: bit-equal to the dpos of md_marching_tets_bwd; zeros where a vertex has no codes.  No gradient for sdf.
+ * md_laplace_umbrella: y = x - base (base may be NULL); term float32 [V][3] = the compensated sum over the corners (f, k) of v, in
+ *   ascending code order, of (y[f[(k+1)%3]] - y_v) + (y[f[(k+2)%3]] - y_v), divided by max(2 corners, 1); loss float32 [1] =
+ *   mean(term^2) over 3 V from fp64 partial sums at MD_LAPLACE_SLABS fixed slabs of `workspace` (MD_LAPLACE_WORKSPACE_BYTES,
+ *   8-byte aligned) added by one wave in a fixed order; it stays on the device.
+ * md_laplace_umbrella_bwd: q float32 [V][3] workspace = ((2 / (3 V)) grad_out[0]) * term / max(2 corners, 1); dx float32 [V][3] =
+ *   the compensated sum over the corners of v of (q[f[(k+1)%3]] + q[f[(k+2)%3]]) - 2 q_v, every element written, exactly 0 for a
+ *   vertex no face names.  grad_out is a device pointer.
+ */
+#define MD_LAPLACE_SLABS 64
+#define MD_LAPLACE_WORKSPACE_BYTES (MD_LAPLACE_SLABS * 8)
+int md_fixedtopo_verts(const float* pos, const float* sdf, const int32_t* edge, int64_t n_verts, int64_t n_mesh_verts, float* verts,
+                       void* stream);
+int md_fixedtopo_verts_bwd(const float* grad_verts, const float* sdf, const int32_t* edge, const int32_t* ptr, const int32_t* inc,
+                           int64_t n_verts, int64_t n_mesh_verts, float* dpos, void* stream);
+int md_laplace_umbrella(const float* x, const float* base, const int64_t* faces, const int32_t* ptr, const int32_t* order,
+                        int64_t n_verts, int64_t n_faces, float* term, void* workspace, float* loss, void* stream);
+int md_laplace_umbrella_bwd(const float* term, const int64_t* faces, const int32_t* ptr, const int32_t* order, const float* grad_out,
+                            int64_t n_verts, int64_t n_faces, float* q, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,7 +168,13 @@ SIGNATURES = {
     "md_raster_bary_bwd": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "md_vertex_normals_det": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     "md_vertex_normals_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "md_fixedtopo_verts": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P]),
+    "md_fixedtopo_verts_bwd": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
+    "md_laplace_umbrella": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "md_laplace_umbrella_bwd": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
 }
+LAPLACE_SLABS = 64                                  # MD_LAPLACE_SLABS
+LAPLACE_WORKSPACE_BYTES = LAPLACE_SLABS * 8         # MD_LAPLACE_WORKSPACE_BYTES
 SDF_REG_SLABS = 64                                  # MD_SDF_REG_SLABS
 SDF_REG_WORKSPACE_BYTES = SDF_REG_SLABS * 24        # MD_SDF_REG_WORKSPACE_BYTES
 

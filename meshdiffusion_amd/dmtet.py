@@ -12,6 +12,10 @@ The vertex interpolation is differentiable as in the reference (only its topolog
 when `pos` or `sdf` requires a gradient, `verts` carries a grad_fn whose backward is md_marching_tets_bwd, one gather
 launch over a static incidence list (no atomics: bit-reproducible).  `sdf_reg_loss` (dmtet.py:169-175) and the part of
 `DMTetGeometry` (dmtet.py:203-304) that needs no renderer complete the fitting loop fit -> dict -> training grid.
+
+The fixed-topology second pass (fit_dmtets.py:758-793): `FixedTopoPlan` keeps what depends on the sign of the SDF alone (faces, the
+crossing edges, the CSRs, the edge neighbours) and moves the vertices with md_fixedtopo_verts / md_fixedtopo_verts_bwd, by the
+contract in the header comment of csrc/fixedtopo.hip; `DMTetGeometryFixedTopo` (dmtet_fixedtopo.py:176-288) is the geometry on it.
 """
 import ctypes as C
 import os
@@ -459,6 +463,170 @@ class DMTetGeometry(torch.nn.Module):
         return {"sdf": self.sdf.detach().cpu(), "deform": self.deform.detach().cpu()}
 
 
+# ---- the fixed-topology second pass -------------------------------------------------------------------------------------------------
+class _FixedTopoVertsFn(torch.autograd.Function):
+    """md_fixedtopo_verts with md_fixedtopo_verts_bwd as the backward of `verts` w.r.t. pos; the frozen SDF gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, pos, sdf, plan):
+        lib = _lib.load()
+        verts = torch.empty((plan.n_mesh_verts, 3), dtype=torch.float32, device=pos.device)
+        _lib.check(lib.md_fixedtopo_verts(_ptr(pos), _ptr(sdf), _ptr(plan.edge), pos.shape[0], plan.n_mesh_verts, _ptr(verts),
+                                          _stream()), "md_fixedtopo_verts")
+        ctx.plan = plan
+        ctx.save_for_backward(sdf)
+        return verts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        sdf, = ctx.saved_tensors
+        plan = ctx.plan
+        g = g.to(torch.float32).contiguous()
+        dpos = torch.empty((sdf.shape[0], 3), dtype=torch.float32, device=g.device)
+        _lib.check(lib.md_fixedtopo_verts_bwd(_ptr(g), _ptr(sdf), _ptr(plan.edge), _ptr(plan.inc_ptr), _ptr(plan.inc), sdf.shape[0],
+                                              plan.n_mesh_verts, _ptr(dpos), _stream()), "md_fixedtopo_verts_bwd")
+        return dpos, None, None
+
+
+class FixedTopoPlan:
+    """Everything about the mesh of one tet grid that depends on the SIGN of the SDF alone, by the fixed-topology contract in the
+    header comment of csrc/fixedtopo.hip: built once from one run of the existing marching tetrahedra (under no_grad), then
+    `verts(pos, sdf)` moves the vertices with one launch and no topology search, no counts and no device-to-host read.
+      faces int64 [F,3], uvs, uv_idx, face_tet int64 [F], valid_vert_idx    what `DMTet()` returns for this sign
+      edge int32 [Vm,2]                       the grid endpoints of each mesh vertex: the crossing edges in ascending edge id
+      inc_ptr int32 [N+1], inc int32 [2 Vm]   grid-vertex CSR of the codes 2 * mesh vertex + endpoint (`build_incidence(edge, N)`)
+      corner_csr                              `face_corner_csr(faces, Vm)`, for `vertex_normals(csr=)` and the Laplacian
+      neighbours int32 [F,3]                  `render.edge_neighbours(faces, Vm)`, for `render_depth / render_buffers(neighbours=)`
+    tables: the grid's `TetTables`; pos float32 [N,3], sdf float32 [N] on the GPU (only the sign of sdf matters)."""
+
+    def __init__(self, tables, pos, sdf):
+        from .render import edge_neighbours
+        if not (torch.is_tensor(pos) and pos.is_cuda and torch.is_tensor(sdf) and sdf.is_cuda):
+            raise _lib.MeshDiffusionHipError("FixedTopoPlan runs on the GPU only (no CPU fallback)")
+        if pos.dim() != 2 or pos.shape[-1] != 3 or sdf.dim() != 1 or sdf.shape[0] != pos.shape[0]:
+            raise ValueError(f"FixedTopoPlan: expected pos [N,3] and sdf [N], got {tuple(pos.shape)} and {tuple(sdf.shape)}")
+        with torch.no_grad():
+            pos = pos.detach().to(torch.float32).contiguous()
+            sdf = sdf.detach().to(torch.float32).contiguous()
+            meshes, cnt = marching_tets_batch(pos[None], sdf[None], tables)
+            verts, faces, face_tet = meshes[0]
+            if verts.shape[0] == 0 or faces.shape[0] == 0:
+                raise _lib.MeshDiffusionHipError("FixedTopoPlan: the sign field has no surface")
+            self.tables, self.n_grid_verts, self.n_mesh_verts = tables, pos.shape[0], verts.shape[0]
+            self.faces = faces.clone()                                         # not views into the call's 2 T rows
+            self.face_tet = face_tet.long().clone()
+            self.uvs, self.uv_idx = _map_uv(face_tet, int(cnt[0, 2]), tables.n_tets, pos.device)
+            self.valid_vert_idx = tables.tets64[torch.unique(face_tet)].long().unique()
+            e = tables.edges.long()
+            pos_sign = sdf > 0
+            self.edge = tables.edges[pos_sign[e[:, 0]] != pos_sign[e[:, 1]]].contiguous()          # ascending edge id
+            if self.edge.shape[0] != self.n_mesh_verts:
+                raise _lib.MeshDiffusionHipError("FixedTopoPlan: the crossing edges do not match the marching-tets vertices")
+            self.inc_ptr, self.inc = build_incidence(self.edge, self.n_grid_verts)
+            self.corner_csr = face_corner_csr(self.faces, self.n_mesh_verts)
+            self.neighbours = edge_neighbours(self.faces, self.n_mesh_verts)
+            self.initial_verts = verts.clone()
+
+    def verts(self, pos, sdf):
+        """verts float32 [Vm,3] of pos [N,3], sdf [N] whose signs are the plan's: bit-equal to `marching_tets_batch` on the same
+        inputs; differentiable w.r.t. pos (bit-equal to the existing backward), no gradient for sdf."""
+        if not (pos.is_cuda and sdf.is_cuda):
+            raise _lib.MeshDiffusionHipError("FixedTopoPlan.verts runs on the GPU only (no CPU fallback)")
+        if tuple(pos.shape) != (self.n_grid_verts, 3) or tuple(sdf.shape) != (self.n_grid_verts,):
+            raise ValueError(f"FixedTopoPlan.verts: expected pos [{self.n_grid_verts},3] and sdf [{self.n_grid_verts}], got "
+                             f"{tuple(pos.shape)} and {tuple(sdf.shape)}")
+        return _FixedTopoVertsFn.apply(pos.to(torch.float32).contiguous(), sdf.detach().to(torch.float32).contiguous(), self)
+
+
+def fixed_sign(sdf):
+    """The frozen sign of pass 2 (dmtet_fixedtopo.py:194-195): sign(sdf + 1e-8) with zeros set to +1.  Plain torch."""
+    s = torch.sign(sdf.detach() + 1e-8).float()
+    s[s == 0] = 1.0
+    return s
+
+
+class DMTetGeometryFixedTopo(torch.nn.Module):
+    """The reference's DMTetGeometryFixedTopo (dmtet_fixedtopo.py:176-288) without its renderer: pass 2 of the fit.  The sign of
+    `dmt_geometry.sdf` is frozen (`sdf_sign`, zeros -> +1), `sdf_abs` = 1 is frozen too, and `deform` -- taken over from pass 1;
+    the caller rescales it by first_stage_deform / second_stage_deform as fit_dmtets.py:770 does -- is the only trainable tensor.
+    The `FixedTopoPlan` is built at construction (`plan`), so `getMesh` runs no topology search; assigning `geo.sdf_sign = s`
+    rebuilds it.  tets=(vertices, indices) or None to take the grid of `dmt_geometry`.  No EMA copies, no material."""
+
+    def __init__(self, dmt_geometry, grid_res, scale, FLAGS=None, deform_scale=1.0, tets=None, **kwargs):
+        super().__init__()
+        self.FLAGS, self.grid_res, self.scale, self.deform_scale, self.tanh = FLAGS, grid_res, scale, deform_scale, False
+        dev = dmt_geometry.sdf.device
+        if not dev.type == "cuda":
+            raise _lib.MeshDiffusionHipError("DMTetGeometryFixedTopo runs on the GPU only (no CPU fallback)")
+        self.marching_tets = DMTet()
+        if tets is None:
+            self.tet_vertices, self.indices = dmt_geometry.tet_vertices, dmt_geometry.indices.to(dev)
+        else:
+            self.tet_vertices = torch.as_tensor(np.asarray(tets[0]), dtype=torch.float32)
+            self.indices = torch.as_tensor(np.asarray(tets[1]), dtype=torch.long).to(dev)
+        self.verts = self.tet_vertices.to(dev) * scale
+        self.generate_edges()
+        self._parameters["sdf_sign"] = torch.nn.Parameter(fixed_sign(dmt_geometry.sdf.data), requires_grad=False)
+        self.sdf_abs = torch.nn.Parameter(torch.ones_like(dmt_geometry.sdf.data), requires_grad=False)
+        self.deform = torch.nn.Parameter(dmt_geometry.deform.data.clone(), requires_grad=True)
+        self._build_plan()
+
+    def __setattr__(self, name, value):
+        if name == "sdf_sign" and "sdf_sign" in self._parameters:               # a new sign is a new topology
+            with torch.no_grad():
+                self._parameters["sdf_sign"].copy_(fixed_sign(torch.as_tensor(value).to(self._parameters["sdf_sign"].device)))
+            self._build_plan()
+            return
+        super().__setattr__(name, value)
+
+    def _build_plan(self):
+        with torch.no_grad():
+            self._sdf = (self.sdf_sign * self.sdf_abs.abs()).contiguous()
+            self.plan = FixedTopoPlan(self.marching_tets.tables_for(self.indices), self.get_deformed(), self._sdf)
+        self.initial_guess_v_pos = self.plan.initial_verts
+
+    generate_edges = DMTetGeometry.generate_edges
+    getAABB = DMTetGeometry.getAABB
+    getTetCenters = DMTetGeometry.getTetCenters
+    get_deformed = DMTetGeometry.get_deformed
+
+    def set_init_v_pos(self):
+        """The vertices the Laplacian measures the displacement from (dmtet_fixedtopo.py:207-211): those of the current deform."""
+        with torch.no_grad():
+            self.initial_guess_v_pos = self.plan.verts(self.get_deformed(), self._sdf)
+
+    def getValidTetIdx(self):
+        return self.plan.face_tet
+
+    def getValidVertsIdx(self):
+        return self.plan.valid_vert_idx
+
+    def clamp_deform(self):
+        if not self.tanh:
+            self.deform.data[:] = self.deform.data.clamp(-0.99, 0.99)
+
+    def getMesh(self, material=None, normals_grad=False):
+        """The namespace of `DMTetGeometry.getMesh`, through the plan: one launch for the vertices, the plan's faces and uvs."""
+        plan = self.plan
+        verts = plan.verts(self.get_deformed(), self._sdf)
+        if normals_grad:
+            v_nrm = vertex_normals(verts, plan.faces, csr=plan.corner_csr)[0]
+        else:
+            v_nrm = auto_normals(verts.detach(), plan.faces)[0]
+        return types.SimpleNamespace(v_pos=verts, t_pos_idx=plan.faces, v_tex=plan.uvs, t_tex_idx=plan.uv_idx, v_nrm=v_nrm,
+                                     t_nrm_idx=plan.faces, material=material, valid_vert_idx=plan.valid_vert_idx)
+
+    def state_to_dict(self):
+        """The dict fit_dmtets.py:784-793 saves under tets/: the sign, the deformation masked to the vertices of the surface
+        tets, and the unmasked deformation."""
+        vert_mask = torch.zeros_like(self.sdf_sign).long().view(-1, 1)
+        vert_mask[self.getValidVertsIdx()] = 1
+        return {"sdf": self.sdf_sign.detach().cpu(), "deform": (self.deform.detach() * vert_mask).cpu(),
+                "deform_unmasked": self.deform.detach().cpu()}
+
+
 def auto_normals(verts, faces):
     """Smooth vertex normals of a mesh (nvdiffrec/lib/render/mesh.py:200-229, the call at nvdiffrec/eval.py:422 on the
     marching-tets output): returns (v_nrm float32 [V,3], f_nrm float32 [F,3] unnormalised) -- md_vertex_normals."""
@@ -504,13 +672,31 @@ class _VertexNormalsFn(torch.autograd.Function):
         return dverts, None, None, None
 
 
-def vertex_normals(verts, faces):
+def face_corner_csr(faces, n_verts):
+    """(ptr int32 [V+1], order int32 [3F]) of the corner codes 3 f + k sorted stably by the vertex they name: the CSR of
+    `vertex_normals` and `render.laplace_regularizer_const`.  faces int64 [F,3] with every index in [0, V), not checked here."""
+    vals, order = torch.sort(faces.reshape(-1), stable=True)                   # corner code 3 f + k, by vertex
+    ptr = torch.searchsorted(vals, torch.arange(n_verts + 1, dtype=torch.int64, device=faces.device)).to(torch.int32).contiguous()
+    return ptr, order.to(torch.int32).contiguous()
+
+
+def _check_corner_csr(csr, n_verts, n_faces, device, what):
+    ptr, order = csr
+    if tuple(ptr.shape) != (n_verts + 1,) or tuple(order.shape) != (3 * n_faces,):
+        raise ValueError(f"{what}: expected a face-corner CSR of shapes [{n_verts + 1}] and [{3 * n_faces}], got "
+                         f"{tuple(ptr.shape)} and {tuple(order.shape)}")
+    return (ptr.to(device=device, dtype=torch.int32).contiguous(), order.to(device=device, dtype=torch.int32).contiguous())
+
+
+def vertex_normals(verts, faces, csr=None):
     """Smooth vertex normals under autograd, by the interpolation contract in the header comment of csrc/interp.hip (mesh.py:
     200-229): verts float32 [V,3], faces [F,3] -> (v_nrm float32 [V,3], f_nrm float32 [F,3] unnormalised).  fn_f = cross(v1 - v0,
     v2 - v0); a vertex's normal sums the fn of the corners that name it in ascending order of 3 f + k, a gather over the static
     face-corner CSR, so two runs agree bit for bit (the atomic `auto_normals` cannot promise that); a sum with s . s <= 1e-20, a
     vertex no face names included, becomes (0, 0, 1) with a zero gradient.  v_nrm is differentiable w.r.t. verts through
-    md_vertex_normals_bwd, f_nrm through plain torch."""
+    md_vertex_normals_bwd, f_nrm through plain torch.
+    csr: the `face_corner_csr(faces, V)` of a mesh whose faces do not change (`FixedTopoPlan.corner_csr`); None builds it, and
+    checks the range of `faces`, as every call did before the keyword existed.  The bits are the same either way."""
     if not verts.is_cuda:
         raise _lib.MeshDiffusionHipError("vertex_normals runs on the GPU only (no CPU fallback)")
     if verts.dim() != 2 or verts.shape[-1] != 3 or verts.shape[0] < 1 or faces.dim() != 2 or faces.shape[-1] != 3:
@@ -523,11 +709,13 @@ def vertex_normals(verts, faces):
     if F == 0:
         up = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float32, device=v.device)
         return up.expand(V, 3).contiguous(), torch.zeros((0, 3), dtype=torch.float32, device=v.device)
-    lo, hi = torch.aminmax(f)
-    if int(lo) < 0 or int(hi) >= V:
-        raise ValueError(f"faces name vertices outside [0, {V})")
-    vals, order = torch.sort(f.reshape(-1), stable=True)                       # corner code 3 f + k, by vertex
-    ptr = torch.searchsorted(vals, torch.arange(V + 1, dtype=torch.int64, device=v.device)).to(torch.int32).contiguous()
-    v_nrm = _VertexNormalsFn.apply(v, f, ptr, order.to(torch.int32).contiguous())
+    if csr is None:
+        lo, hi = torch.aminmax(f)
+        if int(lo) < 0 or int(hi) >= V:
+            raise ValueError(f"faces name vertices outside [0, {V})")
+        ptr, order = face_corner_csr(f, V)
+    else:
+        ptr, order = _check_corner_csr(csr, V, F, v.device, "vertex_normals")
+    v_nrm = _VertexNormalsFn.apply(v, f, ptr, order)
     f_nrm = torch.linalg.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
     return v_nrm, f_nrm

@@ -11,7 +11,9 @@ coverage of both layers and `silhouette_loss` is the coverage term of tick (dmte
 the vertices.  `interpolate`, `rasterize(grad=True)` and `dmtet.vertex_normals` follow the interpolation contract in the header
 comment of csrc/interp.hip: dr.interpolate, the `rast` gradient of dr.rasterize and auto_normals under autograd.  On top of them
 `render_buffers` is the reference's `bsdf == 'normal'` renderer (render.py:105-106, 177-264) and `image_loss` / `color_loss` the
-colour term of tick (dmtet.py:391-400).  The kernels run on the GPU only: a CPU tensor is an
+colour term of tick (dmtet.py:391-400).  `laplace_regularizer_const`, `depth_loss_fixedtopo` and `fit_fixed_topology` are pass 2 of
+the reference's fit (fit_dmtets.py:758-793) on a `dmtet.DMTetGeometryFixedTopo`, by the fixed-topology contract in the header
+comment of csrc/fixedtopo.hip.  The kernels run on the GPU only: a CPU tensor is an
 error, not a fallback.  The camera helpers, `xfm_points`, `shading_normal`, the losses and the carve are plain torch and run
 anywhere.
 
@@ -503,7 +505,7 @@ def antialias(color, rast, pos_clip, faces, neighbours=None, return_pairs=False)
 _antialias = antialias                   # render_depth and make_targets have a flag of that name
 
 
-def render_depth(verts, faces, mvp, campos, resolution, antialias=False):
+def render_depth(verts, faces, mvp, campos, resolution, antialias=False, neighbours=None):
     """The depth part of the reference's render_mesh: world-space verts [V,3] (or [1,V,3]) shared by the B views mvp [B,4,4]
     with camera centres campos [B,3] -> dict of
       depth, depth_second   float32 [B,H,W,1]: |gb_pos - campos| of layer 1 / 2, 20.0 / -1.0 where uncovered; they carry a
@@ -513,7 +515,9 @@ def render_depth(verts, faces, mvp, campos, resolution, antialias=False):
       rast_triangle_id      the sorted unique visible face ids of layer 1 (int64), or None when nothing is visible.
     antialias=True adds
       alpha, alpha_second   float32 [B,H,W,1]: `antialias(mask_k, rast_k, xfm_points(verts[None], mvp), faces)`, each layer with
-                            its own rast; they carry a grad_fn to `verts` through xfm_points.
+                            its own rast; they carry a grad_fn to `verts` through xfm_points.  neighbours: the prebuilt
+                            `edge_neighbours(faces, V)` of a mesh whose faces do not change (`FixedTopoPlan.neighbours`); None
+                            builds them, as before the keyword existed.  The bits are the same either way.
     The rasterised tensor is exactly `xfm_points(verts[None], mvp)`."""
     _gpu_only(verts, "render_depth")
     v = verts[0] if verts.dim() == 3 and verts.shape[0] == 1 else verts
@@ -535,7 +539,7 @@ def render_depth(verts, faces, mvp, campos, resolution, antialias=False):
            "rast_triangle_id": tri if tri.numel() > 0 else None}
     if antialias:
         clip = xfm_points(v[None], mvp)                                        # the bits of pos_clip, with the way back to verts
-        nbr = edge_neighbours(f, v.shape[0])
+        nbr = edge_neighbours(f, v.shape[0]) if neighbours is None else neighbours
         out["alpha"] = _antialias(mask, rast, clip, f, nbr)
         out["alpha_second"] = _antialias(mask2, rast2, clip, f, nbr)
     return out
@@ -569,7 +573,7 @@ def shading_normal(gb_pos, campos, gb_normal, gb_geo_normal):
     return _shading_normal(gb_pos, campos, gb_normal, gb_geo_normal)[0]
 
 
-def render_buffers(verts, faces, mvp, campos, resolution, v_nrm=None):
+def render_buffers(verts, faces, mvp, campos, resolution, v_nrm=None, neighbours=None, corner_csr=None):
     """The reference's render_mesh with `bsdf == 'normal'` on a zero background (render.py:105-106, 177-329): everything
     `render_depth(verts, faces, mvp, campos, resolution, antialias=True)` returns, with equal bits, plus for layer 1 and, under
     names ending in `_second`, for layer 2
@@ -583,7 +587,8 @@ def render_buffers(verts, faces, mvp, campos, resolution, v_nrm=None):
     v_nrm [V,3]: the vertex normals to shade with (`DMTetGeometry.getMesh(normals_grad=True).v_nrm`); None: `dmtet.vertex_normals
     (verts, faces)`.  Gradients reach `verts` through the attribute path, the barycentric path (`rasterize(grad=True)` on
     `xfm_points(verts)`), the vertex normals and the antialiasing.  The rast, tri and CSRs of a layer are built once and shared
-    by its interpolations."""
+    by its interpolations.  neighbours / corner_csr: the prebuilt `edge_neighbours(faces, V)` and `dmtet.face_corner_csr(faces, V)`
+    of a mesh whose faces do not change (`FixedTopoPlan`); None builds them, as before the keywords existed, with the same bits."""
     from .dmtet import vertex_normals
     _gpu_only(verts, "render_buffers")
     v = verts[0] if verts.dim() == 3 and verts.shape[0] == 1 else verts
@@ -601,7 +606,7 @@ def render_buffers(verts, faces, mvp, campos, resolution, v_nrm=None):
     f = _check_faces(faces.to(dev), V)
     F = f.shape[0]
     if v_nrm is None:
-        v_nrm, f_nrm = vertex_normals(v, f)
+        v_nrm, f_nrm = vertex_normals(v, f, csr=corner_csr)
     else:
         if tuple(v_nrm.shape) != (V, 3):
             raise ValueError(f"render_buffers: expected v_nrm [{V},3], got {tuple(v_nrm.shape)}")
@@ -614,7 +619,7 @@ def render_buffers(verts, faces, mvp, campos, resolution, v_nrm=None):
     tri = tri[tri > 0].to(torch.int64) - 1
     out = {"depth": depth, "depth_second": depth2, "mask": mask, "mask_second": mask2, "rast": rast, "rast_second": rast2,
            "rast_triangle_id": tri if tri.numel() > 0 else None}
-    nbr = edge_neighbours(f, V)
+    nbr = edge_neighbours(f, V) if neighbours is None else neighbours
     out["alpha"] = _antialias(mask, rast, clip, f, nbr)
     out["alpha_second"] = _antialias(mask2, rast2, clip, f, nbr)
     vert_attr = torch.cat([v, v_nrm], -1)                                      # position and smooth normal in one pass
@@ -815,3 +820,161 @@ def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, view
             terms["color"] = torch.stack(color_history) if color_history else torch.empty(0, device=dev)
         return terms
     return depth_terms
+
+
+# ---- the fixed-topology second pass (fit_dmtets.py:758-793) --------------------------------------------------------------------------
+class _LaplaceUmbrellaFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, base, faces, ptr, order):
+        lib = _lib.load()
+        V, F, dev = x.shape[0], faces.shape[0], x.device
+        term = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.LAPLACE_WORKSPACE_BYTES // 8, dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        _lib.check(lib.md_laplace_umbrella(_ptr(x), _ptr(base), _ptr(faces), _ptr(ptr), _ptr(order), V, F, _ptr(term), _ptr(ws),
+                                           _ptr(loss), _stream()), "md_laplace_umbrella")
+        ctx.save_for_backward(term, faces, ptr, order)
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        term, faces, ptr, order = ctx.saved_tensors
+        V, F = term.shape[0], faces.shape[0]
+        g = g.to(torch.float32).reshape(1).contiguous()
+        q, dx = torch.empty_like(term), torch.empty_like(term)
+        _lib.check(lib.md_laplace_umbrella_bwd(_ptr(term), _ptr(faces), _ptr(ptr), _ptr(order), _ptr(g), V, F, _ptr(q), _ptr(dx),
+                                               _stream()), "md_laplace_umbrella_bwd")
+        return dx, None, None, None, None
+
+
+def laplace_regularizer_const(v_pos, t_pos_idx, base=None, corner_csr=None):
+    """The reference's umbrella Laplacian (regularizer.py:41-60) of y = v_pos - base by the fixed-topology contract in the header
+    comment of csrc/fixedtopo.hip: mean over the 3 V components of (sum over the corners naming v of (y_next - y_v) + (y_prev - y_v)
+    / max(2 corners, 1))^2, a float32 scalar on the device, differentiable w.r.t. v_pos (`base` gets no gradient).  The reference
+    passes the difference v_pos - initial_guess_v_pos; here it is formed inside the kernel.  Gathers in a fixed order instead of
+    six scatter_add_: two runs agree bit for bit.  corner_csr: the prebuilt `dmtet.face_corner_csr(t_pos_idx, V)`
+    (`FixedTopoPlan.corner_csr`); None builds it and checks the range of the faces."""
+    from .dmtet import _check_corner_csr, face_corner_csr
+    _gpu_only(v_pos, "laplace_regularizer_const")
+    if v_pos.dim() != 2 or v_pos.shape[-1] != 3 or v_pos.shape[0] < 1:
+        raise ValueError(f"laplace_regularizer_const: expected v_pos [V,3], got {tuple(v_pos.shape)}")
+    if base is not None and tuple(base.shape) != tuple(v_pos.shape):
+        raise ValueError(f"laplace_regularizer_const: expected base {tuple(v_pos.shape)}, got {tuple(base.shape)}")
+    if t_pos_idx.dim() != 2 or t_pos_idx.shape[-1] != 3 or t_pos_idx.shape[0] < 1:
+        raise ValueError(f"laplace_regularizer_const: expected t_pos_idx [F,3] with F >= 1, got {tuple(t_pos_idx.shape)}")
+    x = v_pos.to(torch.float32).contiguous()
+    V, dev = x.shape[0], x.device
+    b = None if base is None else base.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if corner_csr is None:
+        f = _check_faces(t_pos_idx.to(dev), V)
+        ptr, order = face_corner_csr(f, V)
+    else:
+        if t_pos_idx.shape[0] > MAX_FACES:
+            raise _lib.MeshDiffusionHipError("laplace_regularizer_const takes fewer than 2^24 faces (MD_ERR_UNSUPPORTED)")
+        f = t_pos_idx.to(device=dev, dtype=torch.int64).contiguous()
+        ptr, order = _check_corner_csr(corner_csr, V, f.shape[0], dev, "laplace_regularizer_const")
+    return _LaplaceUmbrellaFn.apply(x, b, f, ptr, order)
+
+
+def depth_loss_fixedtopo(buffers, target):
+    """The depth term of DMTetGeometryFixedTopo.tick (dmtet_fixedtopo.py:326-337) as written there: the line that forms the
+    layer-1 difference (:333) is overwritten by the next one (:334), so the term is the SECOND layer only,
+        d = |depth_second - target depth_second| * mask * [target depth_second >= 0] * [|target depth_second - target depth| >= 5e-3] * 0.1,
+    Huber at 1 (d below 1, d^2 from there), mean, times 100; `buffers['depth']` does not enter.  Kept, not fixed.  The mask is
+    `target['mask_cont'][..., 0]` (the reference's `target['mask']`) as it is.  Elementwise torch."""
+    mask = target["mask_cont"][..., 0].unsqueeze(-1)
+    valid = ((target["depth_second"] >= 0).float() * ((target["depth_second"] - target["depth"]).abs() >= 5e-3).float()).detach()
+    d = (buffers["depth_second"][..., :1] - target["depth_second"][..., :1]).abs() * mask * valid * 1e-1
+    l1 = (d < 1.0).float()
+    return (l1 * d + (1 - l1) * d.pow(2)).mean() * 100.0
+
+
+def lr_schedule_fixedtopo(it, warmup_iter=100):
+    """fit_dmtets.py:396-399: it / warmup below warmup_iter, then 10^(-0.0002 (it - warmup))."""
+    if it < warmup_iter:
+        return it / warmup_iter
+    return max(0.0, 10 ** (-(it - warmup_iter) * 0.0002))
+
+
+def fit_fixed_topology(geometry, targets, iters, *, lr=0.01, laplace_scale=10000.0, warmup_iter=100, views_per_iter=None,
+                       generator=None, target_points=None, num_samples=50000, callback=None, alpha_weight=0.0,
+                       return_terms=False, color_weight=0.0, color_loss_kind="logl1"):
+    """Pass 2 of the reference's fit (fit_dmtets.py:758-793, DMTetGeometryFixedTopo.tick): fine-tune the `deform` of a
+    `dmtet.DMTetGeometryFixedTopo` on its frozen topology.  Per iteration
+        getMesh (through the plan) -> render_depth, or render_buffers when color_weight > 0, on `views_per_iter` views, with the
+        plan's neighbours and corner CSR -> depth_loss_fixedtopo
+        [+ laplace_regularizer_const(v_pos, faces, base=initial_guess_v_pos) * laplace_scale * (1 - it / iters) * 1e-2, for laplace_scale > 0]
+        [+ alpha_weight * mse(alpha), layer 1 only (:318)] [+ color_weight * image_loss(color_loss_kind), layer 1 only (:319-322)]
+        [+ chamfer(sample_points(num_samples), target_points)]
+        -> Adam step on deform, LambdaLR(lr_schedule_fixedtopo) step -> clamp_deform.
+    `callback(it, loss, mesh)` after each step.  Returns the depth terms, float32 [iters] on the device; with return_terms=True
+    the dict {"depth", "laplace", "alpha"[, "color"]} of the unweighted terms per iteration (device tensors; the Laplacian and
+    alpha terms are then computed even at weight 0, and added to the loss only above it).  The alpha term needs targets made
+    with `make_targets(..., antialias=True)`, the colour term `make_targets(..., shaded=True)`."""
+    from .pointcloud import chamfer_distance, sample_points
+    _gpu_only(geometry.deform, "fit_fixed_topology")
+    dev = geometry.deform.device
+    n_views = targets["mvp"].shape[0]
+    with_alpha = alpha_weight > 0 or return_terms
+    if with_alpha and "alpha" not in targets:
+        raise ValueError("fit_fixed_topology: the alpha term needs targets made with make_targets(..., antialias=True)")
+    with_color = color_weight > 0
+    if with_color and "img" not in targets:
+        raise ValueError("fit_fixed_topology: the colour term needs targets made with make_targets(..., shaded=True)")
+    with_laplace = laplace_scale > 0 or return_terms
+    pts = None if target_points is None else target_points.detach().to(device=dev, dtype=torch.float32).reshape(1, -1, 3).contiguous()
+    opt = torch.optim.Adam([geometry.deform], lr=lr)
+    sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda it: lr_schedule_fixedtopo(it, warmup_iter))
+    hist = {"depth": [], "laplace": [], "alpha": [], "color": []}
+    for it in range(iters):
+        if views_per_iter is None or views_per_iter >= n_views:
+            tgt = targets
+        else:
+            sel = torch.randperm(n_views, generator=generator, device=generator.device if generator is not None else "cpu")
+            sel = sel[:views_per_iter].to(dev)
+            tgt = {key: (val[sel] if torch.is_tensor(val) and val.shape[0] == n_views else val) for key, val in targets.items()}
+        opt.zero_grad(set_to_none=True)
+        plan = geometry.plan
+        mesh = geometry.getMesh(normals_grad=True) if with_color else geometry.getMesh()
+        if with_color:
+            buffers = render_buffers(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"], v_nrm=mesh.v_nrm,
+                                     neighbours=plan.neighbours, corner_csr=plan.corner_csr)
+        else:
+            buffers = render_depth(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"], antialias=with_alpha,
+                                   neighbours=plan.neighbours)
+        loss = depth_loss_fixedtopo(buffers, tgt)
+        total = loss
+        if with_laplace:
+            lap = laplace_regularizer_const(mesh.v_pos, mesh.t_pos_idx, base=geometry.initial_guess_v_pos, corner_csr=plan.corner_csr)
+            hist["laplace"].append(lap.detach())
+            if laplace_scale > 0:
+                total = total + lap * (laplace_scale * (1 - it / iters) * 1e-2)
+        if with_alpha:
+            alpha = torch.nn.functional.mse_loss(buffers["alpha"], tgt["alpha"])
+            hist["alpha"].append(alpha.detach())
+            if alpha_weight > 0:
+                total = total + alpha * alpha_weight
+        if with_color:
+            ref = tgt["img"]
+            color = image_loss(buffers["shaded"][..., 0:3] * ref[..., 3:], ref[..., 0:3] * ref[..., 3:], color_loss_kind)
+            hist["color"].append(color.detach())
+            total = total + color * color_weight
+        if pts is not None:
+            pred = sample_points(mesh.v_pos[None], mesh.t_pos_idx, num_samples, generator=generator)[0]
+            total = total + chamfer_distance(pred, pts).mean()
+        total.backward()
+        opt.step()
+        sched.step()
+        geometry.clamp_deform()
+        hist["depth"].append(loss.detach())
+        if callback is not None:
+            callback(it, hist["depth"][-1], mesh)
+
+    def stacked(xs):
+        return torch.stack(xs) if xs else torch.empty(0, device=dev)
+    if return_terms:
+        keys = ("depth", "laplace", "alpha") + (("color",) if with_color else ())
+        return {k: stacked(hist[k]) for k in keys}
+    return stacked(hist["depth"])

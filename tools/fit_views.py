@@ -7,6 +7,11 @@ the colour term of the normal-shaded image and, with --points, the chamfer dista
 and then `mesh_export.dicts_to_grids(tet_vertices, "fitted", "grids", 64, [0])` writes grids/grid_00000.pt.
     python tools/fit_views.py ... --alpha_weight 1 --color_weight 1 --dump_normals fitted/normals
 adds the reference's image terms and writes the normal map of every view after the fit.
+    python tools/fit_views.py ... --pass2_iters 500 --out fitted/tets/dmt_dict_00000.pt
+adds the reference's second pass (fit_dmtets.py:758-793): the pass-1 dict goes to fitted/tets/tets_pre/dmt_dict_00000.pt, then the
+sign of the SDF is frozen, `deform` is fine-tuned on the fixed topology with the umbrella Laplacian
+(meshdiffusion_amd.render.fit_fixed_topology), and --out receives `{'sdf': +-1, 'deform': masked, 'deform_unmasked'}`, the dict
+the reference trains its diffusion model on.
 
 The mesh is centred and scaled into the tet grid's volume (largest half-extent -> --fit_scale).  Camera k of N looks at the
 origin from distance --cam_radius: perspective(--fovy, 1, 0.1, 1000) @ translate(0, 0, -radius) @ rotate_x(elevation_k) @
@@ -60,6 +65,12 @@ def main(argv=None):
     ap.add_argument("--fovy", type=float, default=math.radians(45.0))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--sphere_init", type=float, default=0.0, help="start from a sphere of this radius instead of the random SDF")
+    ap.add_argument("--pass2_iters", type=int, default=0,
+                    help="> 0: after the fit, this many iterations of the fixed-topology second pass; the pass-1 dict goes to tets_pre/ next to --out")
+    ap.add_argument("--pass2_lr", type=float, default=0.01)
+    ap.add_argument("--laplace_scale", type=float, default=10000.0)
+    ap.add_argument("--second_stage_deform", type=float, default=None,
+                    help="deform_scale of the second pass (default: --deform_scale); deform is rescaled by deform_scale / this")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("fit_views.py needs a GPU: the HIP path has no CPU fallback")
@@ -99,6 +110,27 @@ def main(argv=None):
             np.save(os.path.join(a.dump_normals, f"view_{k:03d}.npy"), shaded[k])
         print(f"wrote {shaded.shape[0]} views to {a.dump_normals}")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.pass2_iters > 0:
+        from meshdiffusion_amd.dmtet import DMTetGeometryFixedTopo
+        pre = os.path.join(os.path.dirname(os.path.abspath(a.out)), "tets_pre", os.path.basename(a.out))
+        os.makedirs(os.path.dirname(pre), exist_ok=True)
+        torch.save(geo.state_to_dict(), pre)
+        print(f"wrote {pre}")
+        second = a.deform_scale if a.second_stage_deform is None else a.second_stage_deform
+        fixed = DMTetGeometryFixedTopo(geo, a.resolution, a.mesh_scale, deform_scale=second)
+        with torch.no_grad():
+            fixed.deform.data[:] = fixed.deform * a.deform_scale / second        # fit_dmtets.py:770
+        fixed.set_init_v_pos()
+
+        def report2(it, loss, mesh):
+            if it % 100 == 0 or it == a.pass2_iters - 1:
+                print(f"pass 2 iter {it}: depth loss {float(loss):.6f}  V {mesh.v_pos.shape[0]} F {mesh.t_pos_idx.shape[0]}", flush=True)
+
+        render.fit_fixed_topology(fixed, targets, a.pass2_iters, lr=a.pass2_lr, laplace_scale=a.laplace_scale,
+                                  views_per_iter=a.views_per_iter, generator=gen, target_points=points,
+                                  num_samples=max(a.points, 1), callback=report2, alpha_weight=a.alpha_weight,
+                                  color_weight=a.color_weight)
+        geo = fixed
     torch.save(geo.state_to_dict(), a.out)
     print(f"wrote {a.out}")
 
