@@ -39,9 +39,10 @@
 // 16-byte record per pair (va, vb, w, P is first); a pair with t0 == t1, which is almost every pair, writes the inactive record
 // before any vertex is loaded.  md_antialias_blend / md_antialias_bwd_color: one thread per pixel gathers its four pairs.
 // md_antialias_bwd_pos: one thread per active pair writes the (x, y, w) gradients of the edge's two vertices; one thread per
-// (view, vertex) then GATHERS them over a CSR sorted stably by vertex (the pattern of md_raster_depth_bwd).  No floating-point
-// atomics anywhere: two runs agree bit for bit.
+// (view, vertex) then GATHERS the codes 2 * entry + end, a plain fp32 sum, over a CSR sorted stably by b V + vertex
+// (csrc/md_gather.h, md_csr_gather_kernel<3, false, true>).  No floating-point atomics anywhere: two runs agree bit for bit.
 #include "md_common.h"
+#include "md_gather.h"
 #include "md_raster_snap.h"
 
 #pragma clang fp contract(off)
@@ -290,26 +291,6 @@ __global__ __launch_bounds__(256) void md_antialias_bwd_pair_kernel(const int64_
   for (int k = 0; k < 6; ++k) dst[k] = out[k];
 }
 
-// dpos_clip[b][v] = sum of vert_grad[code] over the codes 2 * entry + end that name (b, v): (ptr int32 [B V + 1], order int32
-// [2 N]) is the CSR of the codes sorted stably by b V + vertex.  A gather in a fixed order: no atomics.
-__global__ __launch_bounds__(256) void md_antialias_bwd_gather_kernel(const float* __restrict__ vert_grad,
-                                                                      const int32_t* __restrict__ ptr,
-                                                                      const int32_t* __restrict__ order, int64_t BV, int64_t n_codes,
-                                                                      float* __restrict__ dpos) {
-  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (v >= BV) return;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-  const int j1 = ptr[v + 1];
-  for (int j = ptr[v]; j < j1; ++j) {
-    if (j < 0 || j >= n_codes) break;                        // never with the CSR of the host
-    const int32_t code = order[j];
-    if (code < 0 || code >= n_codes) continue;
-    const float* c = vert_grad + (int64_t)code * 3;
-    a0 += c[0]; a1 += c[1]; a2 += c[2];
-  }
-  *reinterpret_cast<float4*>(dpos + v * 4) = make_float4(a0, a1, 0.f, a2);
-}
-
 // sorted entry n of the 3 F corner keys: the run it sits in has exactly two entries -> the other corner's vertex
 __global__ __launch_bounds__(256) void md_mesh_edge_neighbours_kernel(const int64_t* __restrict__ keys,
                                                                       const int64_t* __restrict__ order,
@@ -412,8 +393,7 @@ extern "C" int md_antialias_bwd_pos(const int64_t* active, int32_t n_active, con
     hipLaunchKernelGGL(md_antialias_bwd_pair_kernel, dim3((unsigned)((n_active + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        active, (int)n_active, color, grad_out, reinterpret_cast<const AaPair*>(pairs), pos_clip, (int)n_verts,
                        (int)H, (int)W, (int)C, (int64_t)batch * H * W * 2, vert_grad);
-  hipLaunchKernelGGL(md_antialias_bwd_gather_kernel, dim3((unsigned)((BV + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     vert_grad, ptr, order, BV, (int64_t)n_active * 2, dpos_clip);
+  md_csr_gather<3, false, true>(vert_grad, ptr, order, BV, (int64_t)n_active * 2, dpos_clip, (hipStream_t)stream);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }

@@ -34,20 +34,15 @@
 //
 // Kernels.  Latency- and HBM-bound gathers over short rows (valence ~6 on a marching-tets mesh, at most 14 codes per grid vertex):
 // one thread per row, 256-thread workgroups, coalesced ptr reads, no LDS, no floating-point atomics, plain stores: two runs
-// agree bit for bit.
+// agree bit for bit.  Every row computes a term per code, so the row loops stay here; the compensated step is md_kahan_add of
+// csrc/md_gather.h.
 #include "md_common.h"
+#include "md_gather.h"
 
 #pragma clang fp contract(off)
 
 static constexpr int FT_THREADS = 256;
 static_assert(MD_LAPLACE_SLABS == 64, "the final reduction takes one slab per lane of a wave64");
-
-__device__ __forceinline__ void ft_add(float& sum, float& lost, float x) {
-  const float y = x - lost;
-  const float t = sum + y;
-  lost = (t - sum) - y;
-  sum = t;
-}
 
 // ---- vertices ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(FT_THREADS) void md_ft_verts_kernel(const float* __restrict__ pos, const float* __restrict__ sdf,
@@ -130,7 +125,7 @@ __global__ __launch_bounds__(FT_THREADS) void md_ft_laplace_term_kernel(const fl
     ft_load_y(x, base, i1, y1);
     ft_load_y(x, base, i2, y2);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) ft_add(s[c], lost[c], (y1[c] - yv[c]) + (y2[c] - yv[c]));
+    for (int c = 0; c < 3; ++c) md_kahan_add(s[c], lost[c], (y1[c] - yv[c]) + (y2[c] - yv[c]));
   }
   const float n = fmaxf(2.f * (float)max(j1 - j0, 0), 1.f);
   float* dst = term + (int64_t)v * 3;
@@ -184,7 +179,7 @@ __global__ __launch_bounds__(FT_THREADS) void md_ft_laplace_bwd_kernel(const flo
     int64_t i1, i2;
     if (!ft_others(faces, order[j], V, F, i1, i2)) continue;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) ft_add(s[c], lost[c], (q[i1 * 3 + c] + q[i2 * 3 + c]) - qv2[c]);
+    for (int c = 0; c < 3; ++c) md_kahan_add(s[c], lost[c], (q[i1 * 3 + c] + q[i2 * 3 + c]) - qv2[c]);
   }
   float* dst = dx + (int64_t)v * 3;
   dst[0] = s[0]; dst[1] = s[1]; dst[2] = s[2];

@@ -31,11 +31,12 @@
 //              Backward: d s_v = (g - n (n . g)) / |s_v|, zero for a replaced vertex; d fn_f = the sum of d s over the face's
 //              corners k = 0, 1, 2; with a = v1 - v0, b = v2 - v0: d a = b x d fn, d b = d fn x a, d v0 = -d a - d b.
 //
-// Kernels.  Every reduction is a GATHER in a fixed order over a CSR of codes sorted stably by destination (the pattern of
-// md_raster_depth_bwd_gather_kernel): one thread per covered entry (or face) writes its per-corner gradients, one thread per
-// destination row then sums them, compensated (ip_add), in that order.  No floating-point atomics anywhere: two runs agree bit
-// for bit.  md_interpolate: one thread per pixel, one 16-byte rast load, C unrolled at compile time.
+// Kernels.  Every reduction is a GATHER in a fixed order over a CSR of codes sorted stably by destination (csrc/md_gather.h):
+// one thread per covered entry (or face) writes its per-corner gradients, one thread per destination row then sums them,
+// compensated (md_kahan_add), in that order: md_csr_gather_kernel<W, true, .>.  No floating-point atomics anywhere: two runs
+// agree bit for bit.  md_interpolate: one thread per pixel, one 16-byte rast load, C unrolled at compile time.
 #include "md_common.h"
+#include "md_gather.h"
 #include "md_raster_snap.h"
 
 #pragma clang fp contract(off)
@@ -114,67 +115,8 @@ __global__ __launch_bounds__(256) void md_interpolate_bwd_pix_kernel(const int32
   }
 }
 
-// One step of a compensated (Kahan) sum: the order of the terms is the contract's, `lost` carries the low bits a plain fp32 add
-// drops, so a row of a thousand codes is as accurate as a row of three.  No contraction, no reassociation: still bit-reproducible.
-__device__ __forceinline__ void ip_add(float& sum, float& lost, float x) {
-  const float y = x - lost;
-  const float t = sum + y;
-  lost = (t - sum) - y;
-  sum = t;
-}
-
-// dst[row] = the sum of src[code] (W floats each) over the codes of the row: (ptr int32 [rows + 1], order int32 [n_codes]) is the
-// CSR of the codes sorted stably by row.  A gather in a fixed order: no atomics.  STRIDE is the row pitch of dst (4 for
-// pos_clip: x, y, 0, w).
-template <int W, int STRIDE>
-__device__ __forceinline__ void ip_gather_row(const float* __restrict__ src, const int32_t* __restrict__ ptr,
-                                              const int32_t* __restrict__ order, int64_t row, int64_t n_codes, float (&acc)[W]) {
-#pragma unroll
-  for (int c = 0; c < W; ++c) acc[c] = 0.f;
-  float lost[W];
-#pragma unroll
-  for (int c = 0; c < W; ++c) lost[c] = 0.f;
-  const int j1 = ptr[row + 1];
-  for (int j = ptr[row]; j < j1; ++j) {
-    if (j < 0 || j >= n_codes) break;                        // never with the CSR of the host
-    const int32_t code = order[j];
-    if (code < 0 || code >= n_codes) continue;
-    const float* s = src + (int64_t)code * W;
-#pragma unroll
-    for (int c = 0; c < W; ++c) ip_add(acc[c], lost[c], s[c]);
-  }
-}
-
-template <int C>
-__global__ __launch_bounds__(256) void md_interpolate_bwd_gather_kernel(const float* __restrict__ corner_grad,
-                                                                        const int32_t* __restrict__ ptr,
-                                                                        const int32_t* __restrict__ order, int64_t rows,
-                                                                        int64_t n_codes, float* __restrict__ dattr) {
-  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (row >= rows) return;
-  float acc[C];
-  ip_gather_row<C, C>(corner_grad, ptr, order, row, n_codes, acc);
-#pragma unroll
-  for (int c = 0; c < C; ++c) dattr[row * C + c] = acc[c];
-}
-
-// the rows are (view, vertex) or vertices; three floats per code
-__global__ __launch_bounds__(256) void md_gather3_kernel(const float* __restrict__ src, const int32_t* __restrict__ ptr,
-                                                         const int32_t* __restrict__ order, int64_t rows, int64_t n_codes,
-                                                         int as_clip, float* __restrict__ dst) {
-  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (row >= rows) return;
-  float acc[3];
-  ip_gather_row<3, 3>(src, ptr, order, row, n_codes, acc);
-  if (as_clip) {
-    *reinterpret_cast<float4*>(dst + row * 4) = make_float4(acc[0], acc[1], 0.f, acc[2]);
-  } else {
-    dst[row * 3] = acc[0]; dst[row * 3 + 1] = acc[1]; dst[row * 3 + 2] = acc[2];
-  }
-}
-
 // Entry n names the covered pixel cov[n] = b H W + pixel; corner_grad float32 [N][3][3] receives (d x, d y, d w) of the three
-// corners: the barycentric path of md_raster_depth_bwd_pix_kernel, fed (du, dv) from drast.
+// corners: rs_bary_bwd (csrc/md_raster_snap.h), the barycentric path of md_raster_depth_bwd_pix_kernel, fed (du, dv) from drast.
 __global__ __launch_bounds__(256) void md_raster_bary_bwd_pix_kernel(const int32_t* __restrict__ cov, int N,
                                                                      const float* __restrict__ rast, const float* __restrict__ drast,
                                                                      const float* __restrict__ pos_clip,
@@ -204,25 +146,13 @@ __global__ __launch_bounds__(256) void md_raster_bary_bwd_pix_kernel(const int32
       const float fx = (float)(2 * j + 1) / (float)W - 1.f, fy = (float)(2 * i + 1) / (float)H - 1.f;
 #pragma unroll
       for (int k = 0; k < 3; ++k) { px[k] = px[k] - fx * wc[k]; py[k] = py[k] - fy * wc[k]; }
-      const float a0 = px[1] * py[2] - py[1] * px[2];
-      const float a1 = px[2] * py[0] - py[2] * px[0];
-      const float a2 = px[0] * py[1] - py[0] * px[1];
-      const float S = (a0 + a1) + a2;
-      const float da0 = (du * (1.f - u) - dv * v) / S;
-      const float da1 = (dv * (1.f - v) - du * u) / S;
-      const float da2 = (-du * u - dv * v) / S;
-      float dpx[3], dpy[3];
-      dpx[0] = da2 * py[1] - da1 * py[2];
-      dpy[0] = da1 * px[2] - da2 * px[1];
-      dpx[1] = da0 * py[2] - da2 * py[0];
-      dpy[1] = da2 * px[0] - da0 * px[2];
-      dpx[2] = da1 * py[0] - da0 * py[1];
-      dpy[2] = da0 * px[1] - da1 * px[0];
+      float dpx[3], dpy[3], dw[3];
+      rs_bary_bwd(px, py, u, v, du, dv, fx, fy, dpx, dpy, dw);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         out[k][0] = dpx[k];
         out[k][1] = dpy[k];
-        out[k][2] = -fx * dpx[k] - fy * dpy[k];
+        out[k][2] = dw[k];
       }
     }
   }
@@ -262,7 +192,7 @@ __global__ __launch_bounds__(256) void md_vertex_normals_gather_kernel(const flo
     const int32_t code = order[j];
     if (code < 0 || code >= n_codes) continue;
     const float* fn = f_nrm + (int64_t)(code / 3) * 3;
-    ip_add(s0, l0, fn[0]); ip_add(s1, l1, fn[1]); ip_add(s2, l2, fn[2]);
+    md_kahan_add(s0, l0, fn[0]); md_kahan_add(s1, l1, fn[1]); md_kahan_add(s2, l2, fn[2]);
   }
   const float d = (s0 * s0 + s1 * s1) + s2 * s2;
   float len = 0.f, n0 = 0.f, n1 = 0.f, n2 = 1.f;
@@ -371,8 +301,7 @@ extern "C" int md_interpolate_bwd(const int32_t* cov, int32_t n_cov, const float
                                         (hipStream_t)stream, cov, (int)n_cov, rast, grad_out, attr, tri, bstride, (int)n_faces,
                                         (int)(H * W), n_pix, dattr ? corner_grad : (float*)nullptr, drast));
   if (dattr)
-    IP_DISPATCH_C(C, hipLaunchKernelGGL(md_interpolate_bwd_gather_kernel<K>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
-                                        (hipStream_t)stream, corner_grad, ptr, order, rows, (int64_t)n_cov * 3, dattr));
+    IP_DISPATCH_C(C, (md_csr_gather<K, true, false>(corner_grad, ptr, order, rows, (int64_t)n_cov * 3, dattr, (hipStream_t)stream)));
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }
@@ -392,8 +321,7 @@ extern "C" int md_raster_bary_bwd(const int32_t* cov, int32_t n_cov, const float
     hipLaunchKernelGGL(md_raster_bary_bwd_pix_kernel, dim3((unsigned)((n_cov + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cov,
                        (int)n_cov, rast, drast, pos_clip, faces, (int)n_verts, (int)n_faces, (int)H, (int)W,
                        (int64_t)batch * H * W, corner_grad);
-  hipLaunchKernelGGL(md_gather3_kernel, dim3((unsigned)((BV + 255) / 256)), dim3(256), 0, (hipStream_t)stream, corner_grad, ptr,
-                     order, BV, (int64_t)n_cov * 3, 1, dpos_clip);
+  md_csr_gather<3, true, true>(corner_grad, ptr, order, BV, (int64_t)n_cov * 3, dpos_clip, (hipStream_t)stream);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }
@@ -423,8 +351,7 @@ extern "C" int md_vertex_normals_bwd(const float* verts, const int64_t* faces, c
   MD_HIP_CLEAR_ERROR();
   hipLaunchKernelGGL(md_vertex_normals_bwd_face_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      verts, faces, v_nrm, v_len, grad_v_nrm, (int)n_faces, face_grad);
-  hipLaunchKernelGGL(md_gather3_kernel, dim3((unsigned)((n_verts + 255) / 256)), dim3(256), 0, (hipStream_t)stream, face_grad, ptr,
-                     order, (int64_t)n_verts, (int64_t)n_faces * 3, 0, dverts);
+  md_csr_gather<3, true, false>(face_grad, ptr, order, n_verts, (int64_t)n_faces * 3, dverts, (hipStream_t)stream);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }

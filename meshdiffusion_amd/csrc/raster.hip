@@ -37,9 +37,10 @@
 //     key = sortable(zf) << 32 | face index
 // and finally computes u, v of the two winners from the unsnapped floats and writes both layers with 16-byte stores.
 // Backward: one thread per covered (pixel, layer) writes its three per-corner position gradients; one thread per vertex then
-// GATHERS them over a CSR of (covered entry, corner) codes sorted stably by vertex id (the pattern of md_sample_points_bwd):
-// no floating-point atomics, two runs agree bit for bit.
+// GATHERS them, a plain fp32 sum, over a CSR of (covered entry, corner) codes sorted stably by vertex id (csrc/md_gather.h,
+// md_csr_gather_kernel<3, false, false>): no floating-point atomics, two runs agree bit for bit.
 #include "md_common.h"
+#include "md_gather.h"
 #include "md_raster_snap.h"
 
 #pragma clang fp contract(off)
@@ -380,10 +381,6 @@ __global__ __launch_bounds__(256) void md_raster_depth_bwd_pix_kernel(
     const float fx = (float)(2 * j + 1) / (float)W - 1.f, fy = (float)(2 * i + 1) / (float)H - 1.f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { px[k] = px[k] - fx * wc[k]; py[k] = py[k] - fy * wc[k]; }
-    const float a0 = px[1] * py[2] - py[1] * px[2];
-    const float a1 = px[2] * py[0] - py[2] * px[0];
-    const float a2 = px[0] * py[1] - py[0] * px[1];
-    const float S = (a0 + a1) + a2;
     float D[3], dgb[3], s = 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -399,46 +396,19 @@ __global__ __launch_bounds__(256) void md_raster_depth_bwd_pix_kernel(
       du += dgb[c] * (P[0][c] - P[2][c]);
       dv += dgb[c] * (P[1][c] - P[2][c]);
     }
-    const float da0 = (du * (1.f - u) - dv * v) / S;
-    const float da1 = (dv * (1.f - v) - du * u) / S;
-    const float da2 = (-du * u - dv * v) / S;
-    float dpx[3], dpy[3];
-    dpx[0] = da2 * py[1] - da1 * py[2];
-    dpy[0] = da1 * px[2] - da2 * px[1];
-    dpx[1] = da0 * py[2] - da2 * py[0];
-    dpy[1] = da2 * px[0] - da0 * px[2];
-    dpx[2] = da1 * py[0] - da0 * py[1];
-    dpy[2] = da0 * px[1] - da1 * px[0];
+    float dpx[3], dpy[3], dw[3];
+    rs_bary_bwd(px, py, u, v, du, dv, fx, fy, dpx, dpy, dw);
     const float wk[3] = {u, v, t};
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float dw = -fx * dpx[k] - fy * dpy[k];
+    for (int k = 0; k < 3; ++k)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) out[k][c] = wk[k] * dgb[c] + ((M[c] * dpx[k] + M[4 + c] * dpy[k]) + M[12 + c] * dw);
-    }
+      for (int c = 0; c < 3; ++c) out[k][c] = wk[k] * dgb[c] + ((M[c] * dpx[k] + M[4 + c] * dpy[k]) + M[12 + c] * dw[k]);
   }
   float* dst = corner_grad + (int64_t)n * 9;
 #pragma unroll
   for (int k = 0; k < 3; ++k)
 #pragma unroll
     for (int c = 0; c < 3; ++c) dst[k * 3 + c] = out[k][c];
-}
-
-// dverts[v] = sum of corner_grad[code] over the codes 3 * entry + corner that name v: (ptr int32 [V+1], order int32 [3N]) is
-// the CSR of the codes sorted stably by vertex id.  A gather in a fixed order: no atomics.
-__global__ __launch_bounds__(256) void md_raster_depth_bwd_gather_kernel(const float* __restrict__ corner_grad,
-                                                                         const int32_t* __restrict__ ptr,
-                                                                         const int32_t* __restrict__ order, int V,
-                                                                         float* __restrict__ dverts) {
-  const int v = blockIdx.x * 256 + threadIdx.x;
-  if (v >= V) return;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-  const int j1 = ptr[v + 1];
-  for (int j = ptr[v]; j < j1; ++j) {
-    const float* c = corner_grad + (int64_t)order[j] * 3;
-    a0 += c[0]; a1 += c[1]; a2 += c[2];
-  }
-  dverts[(int64_t)v * 3] = a0; dverts[(int64_t)v * 3 + 1] = a1; dverts[(int64_t)v * 3 + 2] = a2;
 }
 
 extern "C" int md_raster_depth_bwd(const int32_t* cov, int32_t n_cov, const float* rast1, const float* rast2, const float* gd1,
@@ -458,8 +428,7 @@ extern "C" int md_raster_depth_bwd(const int32_t* cov, int32_t n_cov, const floa
     hipLaunchKernelGGL(md_raster_depth_bwd_pix_kernel, dim3((unsigned)((n_cov + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        cov, (int)n_cov, rast1, rast2, gd1, gd2, pos_clip, verts, faces, mvp, campos, (int)n_verts, (int)H, (int)W,
                        corner_grad);
-  hipLaunchKernelGGL(md_raster_depth_bwd_gather_kernel, dim3((unsigned)((n_verts + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, corner_grad, ptr, order, (int)n_verts, dverts);
+  md_csr_gather<3, false, false>(corner_grad, ptr, order, n_verts, (int64_t)n_cov * 3, dverts, (hipStream_t)stream);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }

@@ -17,7 +17,6 @@ The fixed-topology second pass (fit_dmtets.py:758-793): `FixedTopoPlan` keeps wh
 crossing edges, the CSRs, the edge neighbours) and moves the vertices with md_fixedtopo_verts / md_fixedtopo_verts_bwd, by the
 contract in the header comment of csrc/fixedtopo.hip; `DMTetGeometryFixedTopo` (dmtet_fixedtopo.py:176-288) is the geometry on it.
 """
-import ctypes as C
 import os
 import types
 
@@ -25,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._csr import csr_by_row
 from .hip_ops import _ptr, _stream
 
 BASE_TET_EDGES = (0, 1, 0, 2, 0, 3, 1, 2, 1, 3, 2, 3)
@@ -312,9 +312,6 @@ class GridMesher:
         pos, sdf = self.inputs(grids)
         meshes, _ = marching_tets_batch(pos, sdf, self.tables)
         return meshes
-
-
-_ = C
 
 
 # ---- regulariser and geometry of the fitting loop -------------------------------------------------
@@ -630,8 +627,6 @@ class DMTetGeometryFixedTopo(torch.nn.Module):
 def auto_normals(verts, faces):
     """Smooth vertex normals of a mesh (nvdiffrec/lib/render/mesh.py:200-229, the call at nvdiffrec/eval.py:422 on the
     marching-tets output): returns (v_nrm float32 [V,3], f_nrm float32 [F,3] unnormalised) -- md_vertex_normals."""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
     if not verts.is_cuda:
         raise _lib.MeshDiffusionHipError("auto_normals runs on the GPU only")
@@ -639,9 +634,8 @@ def auto_normals(verts, faces):
     f = faces.to(torch.int64).contiguous()
     v_nrm = torch.empty_like(v)
     f_nrm = torch.empty((f.shape[0], 3), dtype=torch.float32, device=v.device)
-    _lib.check(lib.md_vertex_normals(C.c_void_p(v.data_ptr()), C.c_void_p(f.data_ptr()), v.shape[0], f.shape[0],
-                                     C.c_void_p(v_nrm.data_ptr()), C.c_void_p(f_nrm.data_ptr()),
-                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)), "md_vertex_normals")
+    _lib.check(lib.md_vertex_normals(_ptr(v), _ptr(f), v.shape[0], f.shape[0], _ptr(v_nrm), _ptr(f_nrm), _stream()),
+               "md_vertex_normals")
     return v_nrm, f_nrm
 
 
@@ -675,9 +669,7 @@ class _VertexNormalsFn(torch.autograd.Function):
 def face_corner_csr(faces, n_verts):
     """(ptr int32 [V+1], order int32 [3F]) of the corner codes 3 f + k sorted stably by the vertex they name: the CSR of
     `vertex_normals` and `render.laplace_regularizer_const`.  faces int64 [F,3] with every index in [0, V), not checked here."""
-    vals, order = torch.sort(faces.reshape(-1), stable=True)                   # corner code 3 f + k, by vertex
-    ptr = torch.searchsorted(vals, torch.arange(n_verts + 1, dtype=torch.int64, device=faces.device)).to(torch.int32).contiguous()
-    return ptr, order.to(torch.int32).contiguous()
+    return csr_by_row(faces.reshape(-1), n_verts)
 
 
 def _check_corner_csr(csr, n_verts, n_faces, device, what):

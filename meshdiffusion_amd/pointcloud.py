@@ -14,6 +14,7 @@ indices); the summation is the kernel, so two backward passes agree bit for bit.
 import torch
 
 from . import _lib
+from ._csr import csr_by_row
 from .hip_ops import _ptr, _stream
 
 
@@ -56,12 +57,8 @@ def sided_distance(p1, p2, skip_same_index=False):
 
 def _csr(idx, n_targets):
     """CSR of a dynamic index table idx int64 [B,K] with values in [0, n_targets): (ptr int32 [B,n_targets+1], order int32
-    [B,K] = the positions sorted stably by their value).  Torch plumbing on the device."""
-    B = idx.shape[0]
-    vals, order = torch.sort(idx, dim=1, stable=True)
-    bounds = torch.arange(n_targets + 1, dtype=torch.int64, device=idx.device).expand(B, -1).contiguous()
-    ptr = torch.searchsorted(vals.contiguous(), bounds)
-    return ptr.to(torch.int32).contiguous(), order.to(torch.int32).contiguous()
+    [B,K] = the positions sorted stably by their value)."""
+    return csr_by_row(idx, n_targets)
 
 
 class _ChamferFn(torch.autograd.Function):

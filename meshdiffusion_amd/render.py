@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._csr import csr_by_row
 from .hip_ops import _ptr, _stream
 
 TILE = 16                                # RS_TILE of csrc/raster.hip
@@ -141,10 +142,8 @@ def _bin(pc, f, H, W):
     _lib.check(lib.md_raster_bin_emit(_ptr(pc), _ptr(f), _ptr(offsets), B, V, F, H, W, total, _ptr(pair_tile), _ptr(pair_face),
                                       _stream()), "md_raster_bin_emit")
     n_tiles = B * ((H + TILE - 1) // TILE) * ((W + TILE - 1) // TILE)
-    sorted_tile, order = torch.sort(pair_tile, stable=True)
-    tile_faces = pair_face[order].contiguous()
-    tile_ptr = torch.searchsorted(sorted_tile, torch.arange(n_tiles + 1, dtype=torch.int32, device=dev)).to(torch.int32).contiguous()
-    return tile_ptr, tile_faces
+    tile_ptr, order = csr_by_row(pair_tile, n_tiles)
+    return tile_ptr, pair_face[order].contiguous()
 
 
 def _rasterize(pc, f, H, W):
@@ -185,16 +184,11 @@ class _LayerPlan:
         key = (tri.data_ptr(), n_rows, per_view)                               # the entry holds `tri`, so the address stays its own
         if key not in self._csr or self._csr[key][2]._version != tri._version:
             B, H, W, _ = self.rast.shape
-            rows = n_rows * (B if per_view else 1)
-            if rows >= 2 ** 31 - 1:
-                raise _lib.MeshDiffusionHipError("the destination rows of a gather must fit int32 (MD_ERR_UNSUPPORTED)")
             cov = self.cov()[0]
             dest = tri[self.rast[..., 3].reshape(-1)[cov].to(torch.int64) - 1]
             if per_view:
                 dest = dest + (torch.div(cov, H * W, rounding_mode="floor") * n_rows)[:, None]
-            vals, order = torch.sort(dest.reshape(-1), stable=True)
-            ptr = torch.searchsorted(vals, torch.arange(rows + 1, dtype=torch.int64, device=vals.device))
-            self._csr[key] = (ptr.to(torch.int32).contiguous(), order.to(torch.int32).contiguous(), tri)
+            self._csr[key] = csr_by_row(dest.reshape(-1), n_rows * (B if per_view else 1)) + (tri,)
         return self._csr[key][:2]
 
 
@@ -375,15 +369,10 @@ class _RenderDepthFn(torch.autograd.Function):
         ids = torch.stack([rast1[..., 3], rast2[..., 3]], 1).reshape(-1)        # [B,2,H,W]: the code of an entry is its flat index
         cov = torch.nonzero(ids > 0)[:, 0]
         N = cov.numel()
-        if 3 * N >= 2 ** 31:
-            raise _lib.MeshDiffusionHipError("render_depth backward: 3 x the covered (pixel, layer) entries must fit int32")
         dverts = torch.empty((V, 3), dtype=torch.float32, device=dev)
         if N == 0 or F == 0:
             return dverts.zero_(), None, None, None, None, None, None, None
-        corner_vert = faces[ids[cov].to(torch.int64) - 1].reshape(-1)          # entry 3 n + corner names this vertex
-        vals, order = torch.sort(corner_vert, stable=True)
-        ptr = torch.searchsorted(vals, torch.arange(V + 1, dtype=torch.int64, device=dev)).to(torch.int32).contiguous()
-        order = order.to(torch.int32).contiguous()
+        ptr, order = csr_by_row(faces[ids[cov].to(torch.int64) - 1].reshape(-1), V)     # entry 3 n + corner names this vertex
         cov = cov.to(torch.int32).contiguous()
         corner_grad = torch.empty((N, 3, 3), dtype=torch.float32, device=dev)
         _lib.check(lib.md_raster_depth_bwd(_ptr(cov), N, _ptr(rast1), _ptr(rast2), _ptr(g1), _ptr(g2), _ptr(pos_clip), _ptr(verts),
@@ -450,17 +439,13 @@ class _AntialiasFn(torch.autograd.Function):
             rec = pairs.view(-1, 4)
             act = torch.nonzero(rec[:, 0] >= 0)[:, 0]                          # the flat index of a pair is its code
             N = act.numel()
-            if 2 * N >= 2 ** 31 or B * V >= 2 ** 31 - 1:
-                raise _lib.MeshDiffusionHipError("antialias backward: 2 x the active pairs and B x V must fit int32")
             dpos = torch.empty((B, V, 4), dtype=torch.float32, device=dev)
             if N == 0:
                 dpos.zero_()
             else:
                 view = torch.div(act, 2 * H * W, rounding_mode="floor")
                 end_vert = (view[:, None] * V + rec[act, :2].to(torch.int64)).reshape(-1)     # entry 2 n + end names this vertex
-                vals, order = torch.sort(end_vert, stable=True)
-                ptr = torch.searchsorted(vals, torch.arange(B * V + 1, dtype=torch.int64, device=dev)).to(torch.int32).contiguous()
-                order = order.to(torch.int32).contiguous()
+                ptr, order = csr_by_row(end_vert, B * V)
                 vert_grad = torch.empty((N, 2, 3), dtype=torch.float32, device=dev)
                 _lib.check(lib.md_antialias_bwd_pos(_ptr(act), N, _ptr(color), _ptr(g), _ptr(pairs), _ptr(pos_clip), _ptr(ptr),
                                                     _ptr(order), B, V, H, W, C, _ptr(vert_grad), _ptr(dpos), _stream()),
@@ -505,6 +490,36 @@ def antialias(color, rast, pos_clip, faces, neighbours=None, return_pairs=False)
 _antialias = antialias                   # render_depth and make_targets have a flag of that name
 
 
+def _render_args(what, verts, mvp, campos, resolution):
+    """What render_depth and render_buffers check and convert alike: (v float32 [V,3] contiguous, mvp and campos
+    detached float32 on v's device, H, W)."""
+    _gpu_only(verts, what)
+    v = verts[0] if verts.dim() == 3 and verts.shape[0] == 1 else verts
+    if v.dim() != 2 or v.shape[-1] != 3 or v.shape[0] < 1:
+        raise ValueError(f"{what}: expected verts [V,3] or [1,V,3], got {tuple(verts.shape)}")
+    if mvp.dim() != 3 or mvp.shape[1:] != (4, 4) or campos.shape != (mvp.shape[0], 3):
+        raise ValueError(f"{what}: expected mvp [B,4,4] and campos [B,3], got {tuple(mvp.shape)} and {tuple(campos.shape)}")
+    H, W = _resolution(resolution)
+    v = v.to(torch.float32).contiguous()
+    mvp = mvp.detach().to(device=v.device, dtype=torch.float32).contiguous()
+    campos = campos.detach().to(device=v.device, dtype=torch.float32).contiguous()
+    return v, mvp, campos, H, W
+
+
+def _depth_buffers(rendered, clip=None, f=None, nbr=None):
+    """The dict both renderers share, from the six outputs of _RenderDepthFn: depth, mask and rast of both layers and
+    rast_triangle_id; with `clip` (pos_clip with the way back to verts) also alpha and alpha_second."""
+    depth, depth2, mask, mask2, rast, rast2 = rendered
+    tri = torch.unique(rast[..., 3])
+    tri = tri[tri > 0].to(torch.int64) - 1
+    out = {"depth": depth, "depth_second": depth2, "mask": mask, "mask_second": mask2, "rast": rast, "rast_second": rast2,
+           "rast_triangle_id": tri if tri.numel() > 0 else None}
+    if clip is not None:
+        out["alpha"] = _antialias(mask, rast, clip, f, nbr)
+        out["alpha_second"] = _antialias(mask2, rast2, clip, f, nbr)
+    return out
+
+
 def render_depth(verts, faces, mvp, campos, resolution, antialias=False, neighbours=None):
     """The depth part of the reference's render_mesh: world-space verts [V,3] (or [1,V,3]) shared by the B views mvp [B,4,4]
     with camera centres campos [B,3] -> dict of
@@ -519,30 +534,15 @@ def render_depth(verts, faces, mvp, campos, resolution, antialias=False, neighbo
                             `edge_neighbours(faces, V)` of a mesh whose faces do not change (`FixedTopoPlan.neighbours`); None
                             builds them, as before the keyword existed.  The bits are the same either way.
     The rasterised tensor is exactly `xfm_points(verts[None], mvp)`."""
-    _gpu_only(verts, "render_depth")
-    v = verts[0] if verts.dim() == 3 and verts.shape[0] == 1 else verts
-    if v.dim() != 2 or v.shape[-1] != 3 or v.shape[0] < 1:
-        raise ValueError(f"render_depth: expected verts [V,3] or [1,V,3], got {tuple(verts.shape)}")
-    if mvp.dim() != 3 or mvp.shape[1:] != (4, 4) or campos.shape != (mvp.shape[0], 3):
-        raise ValueError(f"render_depth: expected mvp [B,4,4] and campos [B,3], got {tuple(mvp.shape)} and {tuple(campos.shape)}")
-    H, W = _resolution(resolution)
-    v = v.to(torch.float32).contiguous()
-    mvp = mvp.detach().to(device=v.device, dtype=torch.float32).contiguous()
-    campos = campos.detach().to(device=v.device, dtype=torch.float32).contiguous()
+    v, mvp, campos, H, W = _render_args("render_depth", verts, mvp, campos, resolution)
     pos_clip = xfm_points(v.detach()[None], mvp).contiguous()
     _check_clip(pos_clip)
     f = _check_faces(faces.to(v.device), v.shape[0])
-    depth, depth2, mask, mask2, rast, rast2 = _RenderDepthFn.apply(v, pos_clip, f, mvp, campos, H, W)
-    tri = torch.unique(rast[..., 3])
-    tri = tri[tri > 0].to(torch.int64) - 1
-    out = {"depth": depth, "depth_second": depth2, "mask": mask, "mask_second": mask2, "rast": rast, "rast_second": rast2,
-           "rast_triangle_id": tri if tri.numel() > 0 else None}
-    if antialias:
-        clip = xfm_points(v[None], mvp)                                        # the bits of pos_clip, with the way back to verts
-        nbr = edge_neighbours(f, v.shape[0]) if neighbours is None else neighbours
-        out["alpha"] = _antialias(mask, rast, clip, f, nbr)
-        out["alpha_second"] = _antialias(mask2, rast2, clip, f, nbr)
-    return out
+    rendered = _RenderDepthFn.apply(v, pos_clip, f, mvp, campos, H, W)
+    if not antialias:
+        return _depth_buffers(rendered)
+    clip = xfm_points(v[None], mvp)                                            # the bits of pos_clip, with the way back to verts
+    return _depth_buffers(rendered, clip, f, edge_neighbours(f, v.shape[0]) if neighbours is None else neighbours)
 
 
 # ---- the bsdf == 'normal' renderer -------------------------------------------------------------------------------------------------
@@ -590,17 +590,8 @@ def render_buffers(verts, faces, mvp, campos, resolution, v_nrm=None, neighbours
     by its interpolations.  neighbours / corner_csr: the prebuilt `edge_neighbours(faces, V)` and `dmtet.face_corner_csr(faces, V)`
     of a mesh whose faces do not change (`FixedTopoPlan`); None builds them, as before the keywords existed, with the same bits."""
     from .dmtet import vertex_normals
-    _gpu_only(verts, "render_buffers")
-    v = verts[0] if verts.dim() == 3 and verts.shape[0] == 1 else verts
-    if v.dim() != 2 or v.shape[-1] != 3 or v.shape[0] < 1:
-        raise ValueError(f"render_buffers: expected verts [V,3] or [1,V,3], got {tuple(verts.shape)}")
-    if mvp.dim() != 3 or mvp.shape[1:] != (4, 4) or campos.shape != (mvp.shape[0], 3):
-        raise ValueError(f"render_buffers: expected mvp [B,4,4] and campos [B,3], got {tuple(mvp.shape)} and {tuple(campos.shape)}")
-    H, W = _resolution(resolution)
-    v = v.to(torch.float32).contiguous()
+    v, mvp, campos, H, W = _render_args("render_buffers", verts, mvp, campos, resolution)
     dev, V = v.device, v.shape[0]
-    mvp = mvp.detach().to(device=dev, dtype=torch.float32).contiguous()
-    campos = campos.detach().to(device=dev, dtype=torch.float32).contiguous()
     clip = xfm_points(v[None], mvp).contiguous()                               # the rasterised bits, with the way back to verts
     _check_clip(clip)
     f = _check_faces(faces.to(dev), V)
@@ -613,15 +604,10 @@ def render_buffers(verts, faces, mvp, campos, resolution, v_nrm=None, neighbours
         v_nrm = v_nrm.to(device=dev, dtype=torch.float32)
         f_nrm = torch.linalg.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
     layers, plans = _rasterize_grad(clip, f, H, W)
-    depth, depth2, mask, mask2, rast, rast2 = _RenderDepthFn.apply(v, clip.detach(), f, mvp, campos, H, W,
-                                                                   (plans[0].rast, plans[1].rast))
-    tri = torch.unique(rast[..., 3])
-    tri = tri[tri > 0].to(torch.int64) - 1
-    out = {"depth": depth, "depth_second": depth2, "mask": mask, "mask_second": mask2, "rast": rast, "rast_second": rast2,
-           "rast_triangle_id": tri if tri.numel() > 0 else None}
+    rendered = _RenderDepthFn.apply(v, clip.detach(), f, mvp, campos, H, W, (plans[0].rast, plans[1].rast))
     nbr = edge_neighbours(f, V) if neighbours is None else neighbours
-    out["alpha"] = _antialias(mask, rast, clip, f, nbr)
-    out["alpha_second"] = _antialias(mask2, rast2, clip, f, nbr)
+    out = _depth_buffers(rendered, clip, f, nbr)
+    mask, mask2 = out["mask"], out["mask_second"]
     vert_attr = torch.cat([v, v_nrm], -1)                                      # position and smooth normal in one pass
     geo_attr = f_nrm / torch.sqrt(torch.clamp(_dot(f_nrm, f_nrm), min=1e-20))  # the reference's safe_normalize
     fff = torch.arange(F, dtype=torch.int64, device=dev)[:, None].expand(F, 3).contiguous()
@@ -739,6 +725,15 @@ def carve_outside_silhouette(geometry, target, kernel_size=11):
     return int(carved.sum())
 
 
+def _select_views(targets, n_views, views_per_iter, generator, dev):
+    """The targets of one iteration: all of them, or `views_per_iter` views drawn without replacement (one torch.randperm)."""
+    if views_per_iter is None or views_per_iter >= n_views:
+        return targets
+    sel = torch.randperm(n_views, generator=generator, device=generator.device if generator is not None else "cpu")
+    sel = sel[:views_per_iter].to(dev)
+    return {key: (val[sel] if torch.is_tensor(val) and val.shape[0] == n_views else val) for key, val in targets.items()}
+
+
 def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, views_per_iter=None, generator=None,
                  target_points=None, num_samples=50000, carve=True, callback=None, start_iteration=0, alpha_weight=0.0,
                  return_terms=False, color_weight=0.0, color_loss_kind="logl1"):
@@ -771,12 +766,7 @@ def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, view
     history, alpha_history, color_history = [], [], []
     for k in range(iters):
         it = start_iteration + k
-        if views_per_iter is None or views_per_iter >= n_views:
-            tgt = targets
-        else:
-            sel = torch.randperm(n_views, generator=generator, device=generator.device if generator is not None else "cpu")
-            sel = sel[:views_per_iter].to(dev)
-            tgt = {key: (val[sel] if torch.is_tensor(val) and val.shape[0] == n_views else val) for key, val in targets.items()}
+        tgt = _select_views(targets, n_views, views_per_iter, generator, dev)
         if carve and 200 < it < 2000 and it % 20 == 0:
             carve_outside_silhouette(geometry, tgt)
         if it % 300 == 0 and it < 1790:
@@ -929,12 +919,7 @@ def fit_fixed_topology(geometry, targets, iters, *, lr=0.01, laplace_scale=10000
     sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda it: lr_schedule_fixedtopo(it, warmup_iter))
     hist = {"depth": [], "laplace": [], "alpha": [], "color": []}
     for it in range(iters):
-        if views_per_iter is None or views_per_iter >= n_views:
-            tgt = targets
-        else:
-            sel = torch.randperm(n_views, generator=generator, device=generator.device if generator is not None else "cpu")
-            sel = sel[:views_per_iter].to(dev)
-            tgt = {key: (val[sel] if torch.is_tensor(val) and val.shape[0] == n_views else val) for key, val in targets.items()}
+        tgt = _select_views(targets, n_views, views_per_iter, generator, dev)
         opt.zero_grad(set_to_none=True)
         plan = geometry.plan
         mesh = geometry.getMesh(normals_grad=True) if with_color else geometry.getMesh()
