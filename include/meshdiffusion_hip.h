@@ -959,6 +959,34 @@ int md_laplace_umbrella(const float* x, const float* base, const int64_t* faces,
 int md_laplace_umbrella_bwd(const float* term, const int64_t* faces, const int32_t* ptr, const int32_t* order, const float* grad_out,
                             int64_t n_verts, int64_t n_faces, float* q, float* dx, void* stream);
 
+/*
+ * Visible-tet labelling of the single-view fit (nvdiffrec/lib/render/render.py:346-407 with get_visible_tets, fit_singleview.py:
+ * 795-820), csrc/visibility.hip.  Purely additive: MD_ABI_VERSION stays 16, no existing entry point changes.
+ *
+ * THE VISIBILITY CONTRACT (the header comment of csrc/visibility.hip has it in full; tests/visibility_cases.py restates it)
+ *   rast float32 [B][H][W][4] (16-byte aligned) is layer 1 of the rasterisation contract.  D = zf where the id is not 0, else 100.
+ *   Dmin = the minimum of D over the (2 r + 1)^2 window clipped to the image, 0 <= r <= 15.  A tet centre p is projected as
+ *   c = mvp (p, 1) (products summed left to right), n = c.xyz / c.w, q_k = rint((n_k / 2 + 0.5) * S_k), S = (W-1, H-1, H-1), each
+ *   fp32 operation rounded on its own; it is valid iff every q_k lies in [0, S_k] (compared in float), c is finite and c.w > 0, and
+ *   visible iff valid and (Dmin[q_y][q_x] >= n.z or Dmin[q_y][q_x] == 100).  1 <= B <= 64, 1 <= H, W <= 2048, r > 15:
+ *   MD_ERR_UNSUPPORTED beyond; counts are int64, non-positive MD_ERR_BAD_ARG, beyond int32 (faces: 2^24) MD_ERR_UNSUPPORTED; null or
+ *   misaligned pointers MD_ERR_BAD_ARG.  No atomics: every label store writes the same value, two runs agree bit for bit.
+ * md_window_min: dmin float32 [B][H][W].
+ * md_tet_visibility: visible uint8 [B][T] (0 / 1) from dmin, centres float32 [T][3], mvp float32 [B][4][4]; every element written.
+ * md_rast_mark_tets: rast_tet uint8 [T], zeroed by the caller: 1 where a pixel has 1 <= id <= F and face_tet[id - 1] (int64 [F]) is
+ *   this tet; ids above F and tets outside [0, T) are skipped.
+ * md_tets_mark_verts: vis float32 [N] and vis_rast uint8 [N], zeroed by the caller: vis[v] = 1.0 where a tet visible in any of the
+ *   `batch` views names v (indices int64 [T][4]), vis_rast[v] = 1 where such a tet or one with rast_tet[t] != 0 does (rast_tet may be
+ *   NULL: none); vertices outside [0, N) are skipped.
+ */
+int md_window_min(const float* rast, int32_t batch, int32_t H, int32_t W, int32_t radius, float* dmin, void* stream);
+int md_tet_visibility(const float* dmin, const float* centres, const float* mvp, int32_t batch, int64_t n_tets, int32_t H, int32_t W,
+                      uint8_t* visible, void* stream);
+int md_rast_mark_tets(const float* rast, const int64_t* face_tet, int32_t batch, int32_t H, int32_t W, int64_t n_faces,
+                      int64_t n_tets, uint8_t* rast_tet, void* stream);
+int md_tets_mark_verts(const uint8_t* visible, const uint8_t* rast_tet, const int64_t* indices, int32_t batch, int64_t n_tets,
+                       int64_t n_verts, float* vis, uint8_t* vis_rast, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

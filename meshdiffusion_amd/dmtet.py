@@ -455,6 +455,11 @@ class DMTetGeometry(torch.nn.Module):
         return types.SimpleNamespace(v_pos=verts, t_pos_idx=faces, v_tex=uvs, t_tex_idx=uv_idx, v_nrm=v_nrm, t_nrm_idx=faces,
                                      material=material, valid_vert_idx=valid_vert_idx)
 
+    def init_with_gt_surface(self, gt_verts, surface_faces, campos):
+        """dmtet_singleview.py:421-435: sdf = 1.0 on the camera's side of the nearest visible face (`singleview.init_with_gt_surface`)."""
+        from .singleview import init_with_gt_surface
+        return init_with_gt_surface(self, gt_verts, surface_faces, campos)
+
     def state_to_dict(self):
         """The `{'sdf', 'deform'}` dict fit_dmtets.py saves and mesh_export.dicts_to_grids reads."""
         return {"sdf": self.sdf.detach().cpu(), "deform": self.deform.detach().cpu()}

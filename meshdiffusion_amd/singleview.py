@@ -1,0 +1,282 @@
+"""The single-view fit and its visible-tet labelling on MI355X -- host side of csrc/visibility.hip.
+
+The reference's second generation mode, `cond_gen`, reads a dict `{'sdf', 'deform', 'vis', 'vis_rast'}`: the last thing
+nvdiffrec/fit_singleview.py writes (:783-827) after a single-view RGBD fit (`dmtet_singleview.DMTetGeometry.tick`), the
+fixed-topology pass and a labelling of every tetrahedron as seen or occluded from that view (lib/render/render.py:346-407 with
+`get_visible_tets=True`), spread to the grid vertices.  This module is that path:
+
+  window_min_depth, visible_tets, label_vertices   the visibility contract in the header comment of csrc/visibility.hip; the
+                                kernels run on the GPU only: a CPU tensor is an error, not a fallback
+  single_view_partial           geometry + one view (or several: their union) -> the dict, on the CPU
+  init_with_gt_surface          dmtet_singleview.py:421-435, the nearest visible face through `pointcloud._nn` (md_nn_sided)
+  carve_single_view             the carve of the single-view tick (:447-458), plain torch
+  fit_single_view               the reference's loop (fit_singleview.py:489-502) around that tick (:438-516)
+
+tools/fit_singleview.py is the command line around them.
+"""
+import torch
+
+from . import _lib
+from .hip_ops import _ptr, _stream
+from .render import MAX_RES, MAX_VIEWS, _gpu_only, image_loss, rasterize, render_buffers, render_depth, xfm_points
+
+MAX_RADIUS = 15                          # VS_MAX_RADIUS of csrc/visibility.hip
+EMPTY_DEPTH = 100.0                      # VS_EMPTY
+
+
+# ---- the visibility contract -------------------------------------------------------------------------------------------------------
+def _check_rast(rast, what):
+    """rast float32 [B,H,W,4] within the rasteriser's limits -> (contiguous float32 rast, B, H, W)."""
+    if not torch.is_tensor(rast) or rast.dim() != 4 or rast.shape[-1] != 4 or min(rast.shape[:3]) < 1:
+        raise ValueError(f"{what}: expected rast [B,H,W,4], got {tuple(rast.shape) if torch.is_tensor(rast) else type(rast)}")
+    _gpu_only(rast, what)
+    B, H, W, _ = rast.shape
+    if B > MAX_VIEWS or H > MAX_RES or W > MAX_RES:
+        raise _lib.MeshDiffusionHipError(f"{what}: at most {MAX_VIEWS} views of {MAX_RES} x {MAX_RES} pixels (MD_ERR_UNSUPPORTED)")
+    return rast.detach().to(torch.float32).contiguous(), B, H, W
+
+
+def _check_radius(radius, what):
+    r = int(radius)
+    if r != radius or r < 0:
+        raise ValueError(f"{what}: radius must be a non-negative integer, got {radius!r}")
+    if r > MAX_RADIUS:
+        raise _lib.MeshDiffusionHipError(f"{what}: radius {r} exceeds {MAX_RADIUS} (MD_ERR_UNSUPPORTED)")
+    return r
+
+
+def _window_min(rast, B, H, W, r):
+    dmin = torch.empty((B, H, W), dtype=torch.float32, device=rast.device)
+    _lib.check(_lib.load().md_window_min(_ptr(rast), B, H, W, r, _ptr(dmin), _stream()), "md_window_min")
+    return dmin
+
+
+def window_min_depth(rast, radius=7):
+    """Dmin of the visibility contract: rast float32 [B,H,W,4], layer 1 of `rasterize` -> float32 [B,H,W], the minimum over the
+    (2 radius + 1)^2 window, clipped to the image, of zf where a triangle covers the pixel and 100.0 where none does: the
+    reference's -max_pool2d(-corrected_rast_depth, 2 r + 1, 1, r).  0 <= radius <= 15 (the reference's depth_search_range is 7)."""
+    r = _check_radius(radius, "window_min_depth")
+    rast, B, H, W = _check_rast(rast, "window_min_depth")
+    return _window_min(rast, B, H, W, r)
+
+
+def visible_tets(rast, centres, mvp, radius=7):
+    """visible bool [B,T] of the visibility contract: tet t is visible in view b iff its centre (centres float32 [T,3], world
+    space: `geometry.getTetCenters()`), projected with mvp [B,4,4] and rounded to a pixel and a depth step, lies inside the clip
+    cube and not behind the window minimum of `rast` (layer 1 of `rasterize`) at that pixel.  A centre with w <= 0 or a non-finite
+    clip coordinate is not visible (the reference projects it through the camera)."""
+    r = _check_radius(radius, "visible_tets")
+    rast, B, H, W = _check_rast(rast, "visible_tets")
+    if not torch.is_tensor(centres) or centres.dim() != 2 or centres.shape[-1] != 3 or centres.shape[0] < 1:
+        raise ValueError(f"visible_tets: expected centres [T,3] with T >= 1, got {tuple(centres.shape)}")
+    if not torch.is_tensor(mvp) or tuple(mvp.shape) != (B, 4, 4):
+        raise ValueError(f"visible_tets: expected mvp [{B},4,4], got {tuple(mvp.shape)}")
+    _gpu_only(centres, "visible_tets")
+    dev, T = rast.device, centres.shape[0]
+    c = centres.detach().to(device=dev, dtype=torch.float32).contiguous()
+    m = mvp.detach().to(device=dev, dtype=torch.float32).contiguous()
+    dmin = _window_min(rast, B, H, W, r)
+    visible = torch.empty((B, T), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().md_tet_visibility(_ptr(dmin), _ptr(c), _ptr(m), B, T, H, W, _ptr(visible), _stream()), "md_tet_visibility")
+    return visible.view(torch.bool)
+
+
+def _check_index_table(t, shape_tail, hi, what, name):
+    """An int64 index table with every entry in [0, hi): checked once here, the kernels skip what lies outside."""
+    if not torch.is_tensor(t) or t.dim() != len(shape_tail) + 1 or tuple(t.shape[1:]) != shape_tail:
+        raise ValueError(f"{what}: expected {name} [n{''.join(',' + str(s) for s in shape_tail)}], got {tuple(t.shape)}")
+    t = t.to(torch.int64).contiguous()
+    if t.numel() > 0:
+        lo, top = torch.aminmax(t)
+        if int(lo) < 0 or int(top) >= hi:
+            raise ValueError(f"{what}: {name} names entries outside [0, {hi})")
+    return t
+
+
+def label_vertices(visible, rast, face_tet, indices, n_verts):
+    """The labels of the visibility contract: visible bool [B,T] (`visible_tets`), rast float32 [B,H,W,4] the layer it came from,
+    face_tet int64 [F] the tet of each face of the rasterised mesh (`geometry.getValidTetIdx()`), indices int64 [T,4] the grid's
+    tets, n_verts = N -> (vis float32 [N] of 0 / 1, vis_rast bool [N]): the grid vertices of the tets visible in any view, and of
+    those or the tets that own a pixel of layer 1.  These are the dtypes of the reference's dict (fit_singleview.py:812-820)."""
+    what = "label_vertices"
+    rast, B, H, W = _check_rast(rast, what)
+    if not torch.is_tensor(visible) or visible.dim() != 2 or visible.shape[0] != B or visible.shape[1] < 1:
+        raise ValueError(f"{what}: expected visible [{B},T] with T >= 1, got {tuple(visible.shape)}")
+    _gpu_only(visible, what)
+    N, T, dev = int(n_verts), visible.shape[1], rast.device
+    if N < 1:
+        raise ValueError(f"{what}: n_verts must be positive, got {n_verts}")
+    if N > 2 ** 31 - 1 or T > 2 ** 31 - 1:
+        raise _lib.MeshDiffusionHipError(f"{what}: the counts of tets and vertices must fit int32 (MD_ERR_UNSUPPORTED)")
+    idx = _check_index_table(indices.to(dev), (4,), N, what, "indices")
+    if idx.shape[0] != T:
+        raise ValueError(f"{what}: visible has {T} tets, indices {idx.shape[0]}")
+    ft = _check_index_table(face_tet.to(dev), (), T, what, "face_tet")
+    F = ft.shape[0]
+    if F >= 2 ** 24:
+        raise _lib.MeshDiffusionHipError(f"{what}: the rasteriser takes fewer than 2^24 faces (MD_ERR_UNSUPPORTED)")
+    lib = _lib.load()
+    vis_u8 = visible.to(torch.uint8).contiguous() if visible.dtype != torch.bool else visible.contiguous().view(torch.uint8)
+    rast_tet = None
+    if F > 0:
+        rast_tet = torch.zeros(T, dtype=torch.uint8, device=dev)
+        _lib.check(lib.md_rast_mark_tets(_ptr(rast), _ptr(ft), B, H, W, F, T, _ptr(rast_tet), _stream()), "md_rast_mark_tets")
+    vis = torch.zeros(N, dtype=torch.float32, device=dev)
+    vis_rast = torch.zeros(N, dtype=torch.uint8, device=dev)
+    _lib.check(lib.md_tets_mark_verts(_ptr(vis_u8), None if rast_tet is None else _ptr(rast_tet), _ptr(idx), B, T, N, _ptr(vis),
+                                      _ptr(vis_rast), _stream()), "md_tets_mark_verts")
+    return vis, vis_rast.view(torch.bool)
+
+
+@torch.no_grad()
+def single_view_partial(geometry, target, radius=7):
+    """The dict `evaler.cond_gen` reads (`config.eval.partial_dmtet_path`), as fit_singleview.py:795-827 makes it, from a
+    `DMTetGeometry` or a `DMTetGeometryFixedTopo` and a target of `make_targets` (its `mvp` and `resolution`):
+        getMesh -> rasterize (layer 1) -> getTetCenters -> visible_tets -> label_vertices with getValidTetIdx() as face_tet.
+    Returns CPU tensors {'sdf' float32 [N] (`sdf_sign` for the fixed-topology geometry, as the reference saves it), 'deform'
+    float32 [N,3], 'vis' float32 [N] of 0 / 1, 'vis_rast' bool [N]}.  More than one view in `target` gives the union over them."""
+    _gpu_only(geometry.deform, "single_view_partial")
+    mesh = geometry.getMesh()
+    mvp = target["mvp"].detach().to(device=mesh.v_pos.device, dtype=torch.float32)
+    if mesh.t_pos_idx.shape[0] == 0:
+        raise _lib.MeshDiffusionHipError("single_view_partial: the mesh has no faces")
+    clip = xfm_points(mesh.v_pos.detach()[None], mvp).contiguous()
+    rast = rasterize(clip, mesh.t_pos_idx, target["resolution"], num_layers=1)[0]
+    visible = visible_tets(rast, geometry.getTetCenters().detach(), mvp, radius)
+    vis, vis_rast = label_vertices(visible, rast, geometry.getValidTetIdx(), geometry.indices, geometry.verts.shape[0])
+    sdf = geometry.sdf_sign if hasattr(geometry, "sdf_sign") else geometry.sdf
+    return {"sdf": sdf.detach().float().cpu(), "deform": geometry.deform.detach().cpu(), "vis": vis.cpu(), "vis_rast": vis_rast.cpu()}
+
+
+# ---- the single-view tick ----------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def init_with_gt_surface(geometry, gt_verts, surface_faces, campos):
+    """dmtet_singleview.py:421-435: every grid vertex that lies on the camera's side of its nearest visible face of the
+    ground-truth mesh gets sdf = 1.0.  gt_verts [V,3], surface_faces int64 [Fs,3] the faces the view sees (the `rast_triangle_id`
+    faces of `render_depth`), campos [3].  Nearest = the nearest face CENTRE, through md_nn_sided (direct-form fp32 distances, ties
+    to the lowest index); the face normal (v0 - v1) x (v0 - v2) is flipped towards the camera (kept where normal . (campos -
+    centre) >= 0); a vertex is outside where (vertex - centre) . normal > 0.  No gradient.  Returns the number of vertices set."""
+    from .pointcloud import _nn
+    _gpu_only(geometry.sdf, "init_with_gt_surface")
+    dev = geometry.sdf.device
+    if surface_faces.dim() != 2 or surface_faces.shape[-1] != 3 or surface_faces.shape[0] < 1:
+        raise ValueError(f"init_with_gt_surface: expected surface_faces [Fs,3] with Fs >= 1, got {tuple(surface_faces.shape)}")
+    gv = gt_verts.detach().to(device=dev, dtype=torch.float32)
+    fv = gv[surface_faces.to(dev).long()]                                      # [Fs,3,3]
+    centres = fv.mean(dim=1)
+    v_pos = geometry.get_deformed().detach().to(torch.float32)
+    idx = _nn(v_pos[None].contiguous(), centres[None].contiguous())[1][0]
+    displacement = v_pos - centres[idx]
+    view_dirs = campos.detach().to(device=dev, dtype=torch.float32).reshape(1, 3) - centres
+    normals = torch.linalg.cross(fv[:, 0] - fv[:, 1], fv[:, 0] - fv[:, 2])
+    mask = ((normals * view_dirs).sum(dim=-1, keepdim=True) >= 0).float()
+    normals = normals * mask - normals * (1 - mask)
+    outside = (displacement * normals[idx]).sum(dim=-1) > 0
+    geometry.sdf.data[outside] = 1.0
+    return int(outside.sum())
+
+
+@torch.no_grad()
+def carve_single_view(geometry, target):
+    """The carve of the single-view tick (dmtet_singleview.py:447-458): project the deformed grid vertices, clip the unit
+    coordinates to [0, 1], scale and TRUNCATE them to pixels (`.long()`: no rounding, no dilation); where a vertex lands on a
+    pixel whose `mask_cont` is 0 in a view, sdf = |sdf|.clamp(0, 1), view after view.  x is scaled with the width and y with
+    the height (the reference asserts a square image).  Plain torch.  Returns the number of vertices carved."""
+    v = geometry.get_deformed().detach()
+    H, W = target["resolution"]
+    clip = xfm_points(v[None], target["mvp"])
+    ndc = clip[..., :2] / clip[..., 3:4]
+    px = ((ndc[..., 0] * 0.5 + 0.5).clip(0, 1) * (W - 1)).long()
+    py = ((ndc[..., 1] * 0.5 + 0.5).clip(0, 1) * (H - 1)).long()
+    empty = target["mask_cont"][..., 0] == 0
+    carved = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
+    for k in range(empty.shape[0]):
+        m = empty[k, py[k], px[k]]
+        geometry.sdf.data[m] = geometry.sdf.data[m].abs().clamp(0.0, 1.0)
+        carved |= m
+    return int(carved.sum())
+
+
+def depth_loss_single_view(buffers, target):
+    """The depth term of the single-view tick (dmtet_singleview.py:474-490): layer 1 only,
+        d = |depth - target depth| * [mask_cont == 1] * [target depth_second >= 0] * [|target depth_second - target depth| >= 5e-3],
+    Huber at 1 (d below 1, d^2 from there), mean, times 100.  Elementwise torch."""
+    mask = (target["mask_cont"][..., 0] == 1.0).float().unsqueeze(-1)
+    valid = ((target["depth_second"] >= 0).float() * ((target["depth_second"] - target["depth"]).abs() >= 5e-3).float()).detach()
+    d = (buffers["depth"][..., :1] - target["depth"][..., :1]).abs() * mask * valid
+    l1 = (d < 1.0).float()
+    return (l1 * d + (1 - l1) * d.pow(2)).mean() * 100.0
+
+
+def fit_single_view(geometry, target, iters, *, lr=0.01, sdf_regularizer=0.2, target_points=None, gt_mesh=None, num_samples=50000,
+                    generator=None, color_loss_kind="logl1", callback=None, start_iteration=0, total_iters=None):
+    """Fit a `DMTetGeometry` to ONE view the way the reference's single-view loop does (fit_singleview.py:489-502 around
+    dmtet_singleview.DMTetGeometry.tick, :438-516).  target: `make_targets(..., shaded=True)` of the view.  Per iteration `it`
+        [init_with_gt_surface, for it < 300 and it % 10 == 0, with the faces of gt_mesh = (verts, faces) that the view sees: the
+         `rast_triangle_id` of `render_depth` on it, found once]
+        -> deform.requires_grad = (it >= 100) -> [carve_single_view, for 200 < it < 2000 and it % 20 == 0]
+        -> [deform *= 0.4, for it % 300 == 0 and it < 1790] -> getMesh(normals_grad=True) -> render_buffers
+        -> mse(alpha) + image_loss(shaded rgb x ref alpha, ref rgb x ref alpha) of layer 1 + depth_loss_single_view
+           + sdf_reg_loss(masked sdf) * weight * 2.5 [+ chamfer(sample_points(num_samples), target_points)]
+        -> Adam step on (sdf, deform) -> clamp_deform.
+    The regulariser's weight falls from `sdf_regularizer` to 0.01 over the first quarter of `total_iters` (default:
+    start_iteration + iters).  `callback(it, depth term, mesh)` after each step.  Returns the per-iteration terms as
+    `fit_to_views(return_terms=True)` does: {"depth", "alpha", "color"}, float32 [iters] each on the device.
+    Not built: the reference's `kd_grad` and `occlusion` regularisers (they need materials), `msaa`, and its random background
+    (the targets and the prediction are rendered on a zero background)."""
+    from .dmtet import sdf_reg_loss
+    from .pointcloud import chamfer_distance, sample_points, sdf_regularizer_weight
+    _gpu_only(geometry.sdf, "fit_single_view")
+    dev = geometry.sdf.device
+    for key in ("img", "alpha", "depth", "depth_second", "mask_cont", "mvp", "campos", "resolution"):
+        if key not in target:
+            raise ValueError(f"fit_single_view: the target has no {key!r}; make it with make_targets(..., shaded=True)")
+    total_iters = start_iteration + iters if total_iters is None else total_iters
+    pts = None if target_points is None else target_points.detach().to(device=dev, dtype=torch.float32).reshape(1, -1, 3).contiguous()
+    surface_faces = gt_verts = None
+    if gt_mesh is not None:
+        gt_verts = gt_mesh[0].detach().to(device=dev, dtype=torch.float32)
+        gt_faces = gt_mesh[1].to(dev).long()
+        with torch.no_grad():
+            seen = render_depth(gt_verts, gt_faces, target["mvp"], target["campos"], target["resolution"])["rast_triangle_id"]
+        surface_faces = None if seen is None else gt_faces[seen]
+    opt = torch.optim.Adam([geometry.sdf, geometry.deform], lr=lr)
+    hist = {"depth": [], "alpha": [], "color": []}
+    ref = target["img"]
+    try:
+        for k in range(iters):
+            it = start_iteration + k
+            if surface_faces is not None and it < 300 and it % 10 == 0:
+                init_with_gt_surface(geometry, gt_verts, surface_faces, target["campos"][0])
+            geometry.deform.requires_grad_(it >= 100)
+            if 200 < it < 2000 and it % 20 == 0:
+                carve_single_view(geometry, target)
+            if it % 300 == 0 and it < 1790:
+                with torch.no_grad():
+                    geometry.deform.data[:] *= 0.4
+            opt.zero_grad(set_to_none=True)
+            mesh = geometry.getMesh(normals_grad=True)
+            if mesh.t_pos_idx.shape[0] == 0:
+                raise _lib.MeshDiffusionHipError(f"fit_single_view: the mesh of iteration {it} has no faces")
+            buffers = render_buffers(mesh.v_pos, mesh.t_pos_idx, target["mvp"], target["campos"], target["resolution"], v_nrm=mesh.v_nrm)
+            alpha = torch.nn.functional.mse_loss(buffers["shaded"][..., 3:], ref[..., 3:])
+            color = image_loss(buffers["shaded"][..., 0:3] * ref[..., 3:], ref[..., 0:3] * ref[..., 3:], color_loss_kind)
+            depth = depth_loss_single_view(buffers, target)
+            sdf_mask = torch.zeros_like(geometry.sdf)
+            sdf_mask[mesh.valid_vert_idx] = 1.0
+            sdf_masked = geometry.sdf.detach() * sdf_mask + geometry.sdf * (1 - sdf_mask)
+            reg = sdf_reg_loss(sdf_masked, geometry.all_edges).mean() * sdf_regularizer_weight(it, total_iters, sdf_regularizer) * 2.5
+            total = alpha + color + depth + reg
+            if pts is not None:
+                pred = sample_points(mesh.v_pos[None], mesh.t_pos_idx, num_samples, generator=generator)[0]
+                total = total + chamfer_distance(pred, pts).mean()
+            total.backward()
+            opt.step()
+            geometry.clamp_deform()
+            for name, val in (("depth", depth), ("alpha", alpha), ("color", color)):
+                hist[name].append(val.detach())
+            if callback is not None:
+                callback(it, hist["depth"][-1], mesh)
+    finally:
+        geometry.deform.requires_grad_(True)
+    return {name: (torch.stack(v) if v else torch.empty(0, device=dev)) for name, v in hist.items()}
