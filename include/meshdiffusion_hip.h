@@ -987,6 +987,24 @@ int md_rast_mark_tets(const float* rast, const int64_t* face_tet, int32_t batch,
 int md_tets_mark_verts(const uint8_t* visible, const uint8_t* rast_tet, const int64_t* indices, int32_t batch, int64_t n_tets,
                        int64_t n_verts, float* vis, uint8_t* vis_rast, void* stream);
 
+/*
+ * Generation metrics (MMD / COV / 1-NNA under the chamfer distance), csrc/shape_metrics.hip: the all-pairs matrix of sided mean
+ * squared distances between two sets of point clouds.  The reference has no counterpart.  Purely additive: MD_ABI_VERSION stays
+ * 16, no existing entry point changes.
+ *
+ * md_sided_mean_matrix: x float32 [nx][p][3], y float32 [ny][q][3] -> out float32 [nx][ny] (every element written),
+ *     out[i][j] = (1/p) * sum_a min_b |x[i][a] - y[j][b]|^2.
+ *   The chamfer distance of a pair is out_xy[i][j] + out_yx[j][i]; x == y is allowed (the union matrix of one set is S + S^T).
+ *   Arithmetic as md_nn_sided: distances in the direct form dz*dz + (dy*dy + dx*dx) in fp32 (never the expanded form, no
+ *   matrix-core instruction); the per-point minima are summed in float64 in a fixed order (lane, wave, workgroup), divided by p
+ *   and rounded once to fp32.  No atomics, no workspace, one launch; the result does not depend on how the launch is cut up and
+ *   two runs agree bit for bit.  Non-finite coordinates: out[i][j] is torch's d2.min(dim=1).values.mean() on the direct-form fp32
+ *   distances (a NaN distance, inf - inf included, wins its row's minimum and makes the mean NaN).
+ *   Null pointers or sizes < 1: MD_ERR_BAD_ARG.  nx is the x dimension of a grid of 256-lane workgroups, whose threads along x must
+ *   stay below 2^32: nx >= 2^24 is MD_ERR_UNSUPPORTED.  The runs of y clouds per x cloud (at most 2048) are its y dimension.
+ */
+int md_sided_mean_matrix(const float* x, const float* y, int32_t nx, int32_t ny, int32_t p, int32_t q, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,73 @@
+"""MMD / COV / 1-NNA (chamfer distance) of a set of generated shapes against a reference set.
+
+    python tools/eval_shapes.py --samples meshes/ --ref reference_meshes/ [--points 2048] [--normalize bbox] [--out metrics.json]
+    python tools/eval_shapes.py --samples out/0.npy --tet_path 64_tets_cropped.npz --ref reference_meshes/
+
+--samples and --ref are directories of `.obj` files (read in sorted order), or --samples the sampler's `.npy` of grids, which
+goes through marching tetrahedra (`GridMesher`, needs --tet_path).  Every mesh is sampled at --points surface points
+(`meshdiffusion_amd.metrics.clouds_from_meshes`; one device generator seeded with --seed draws for the samples, then for the
+references), normalised (`normalize_clouds`) and handed to `shape_metrics`.  Meshes without faces are left out and counted.
+Prints one JSON line: the figures of `shape_metrics`, `skipped_sample`, `skipped_ref` and wall `seconds`.  GPU only."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def load_meshes(path, tet_path=None, batch=32):
+    """A directory of .obj files, or a .npy of grids [M,4,R,R,R] -> list of (verts, faces)."""
+    from meshdiffusion_amd import mesh_export
+    if os.path.isdir(path):
+        names = sorted(n for n in os.listdir(path) if n.lower().endswith(".obj"))
+        if not names:
+            raise SystemExit(f"eval_shapes.py: no .obj files in {path}")
+        return [mesh_export.load_obj(os.path.join(path, n)) for n in names]
+    if not path.endswith(".npy"):
+        raise SystemExit(f"eval_shapes.py: {path} is neither a directory of .obj files nor a .npy of grids")
+    if tet_path is None:
+        raise SystemExit("eval_shapes.py: a .npy of grids needs --tet_path")
+    from meshdiffusion_amd.dmtet import GridMesher
+    grids, tet = np.load(path), np.load(tet_path)
+    mesher = GridMesher(tet["vertices"], tet["indices"], grids.shape[-1])
+    meshes = []
+    for lo in range(0, grids.shape[0], batch):
+        meshes += [(v.detach(), f) for v, f, _face_tet in mesher(torch.from_numpy(grids[lo:lo + batch]))]
+    return meshes
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--samples", required=True, help="directory of .obj files, or the sampler's .npy of grids")
+    ap.add_argument("--tet_path", default=None, help="<R>_tets_cropped.npz (vertices, indices), for a .npy of grids")
+    ap.add_argument("--ref", required=True, help="directory of reference .obj files")
+    ap.add_argument("--points", type=int, default=2048)
+    ap.add_argument("--normalize", choices=("bbox", "none"), default="bbox")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default=None, help="also write the JSON record here")
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_shapes.py needs a GPU: the HIP path has no CPU fallback")
+    from meshdiffusion_amd.metrics import clouds_from_meshes, normalize_clouds, shape_metrics
+
+    t0 = time.time()
+    gen = torch.Generator(device="cuda").manual_seed(a.seed)
+    s, skipped_s = clouds_from_meshes(load_meshes(a.samples, a.tet_path), a.points, generator=gen, skip_empty=True)
+    r, skipped_r = clouds_from_meshes(load_meshes(a.ref), a.points, generator=gen, skip_empty=True)
+    rec = shape_metrics(normalize_clouds(s, a.normalize), normalize_clouds(r, a.normalize))
+    torch.cuda.synchronize()
+    rec.update(skipped_sample=len(skipped_s), skipped_ref=len(skipped_r), seconds=round(time.time() - t0, 3))
+    print(json.dumps(rec), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rec, f)
+
+
+if __name__ == "__main__":
+    main()
