@@ -1005,6 +1005,33 @@ int md_tets_mark_verts(const uint8_t* visible, const uint8_t* rast_tet, const in
  */
 int md_sided_mean_matrix(const float* x, const float* y, int32_t nx, int32_t ny, int32_t p, int32_t q, float* out, void* stream);
 
+/*
+ * Generation metrics under the earth mover's distance, csrc/emd.hip: the all-pairs matrix
+ *     out[i][j] = (1/p) * min over permutations pi of sum_k |x[i][k] - y[j][pi(k)]|        (Euclidean distance, not its square)
+ * of two sets of clouds of the same size p.  The reference has no counterpart.  Purely additive: MD_ABI_VERSION stays 16.
+ *
+ * THE EMD CONTRACT (the header comment of csrc/emd.hip has it in full; tests/emd_cases.py restates it and derives the bars)
+ *   Distance: fp32, direct form sqrtf(dz*dz + (dy*dy + dx*dx)), no contraction, correctly rounded square root.
+ *   Integer:  q = rint(d / quantum); quantum is a positive power of two, one per call, so the entries of a matrix are comparable.
+ *   Solver:   the integer assignment problem on q is solved exactly, by a forward Jacobi auction with eps-scaling on the costs
+ *             q (p + 1) whose last phase runs at eps = 1; prices and bids are 64-bit integers.  Ties for a bidder's best object go to
+ *             the lowest index, an object takes its highest bid, ties to the lowest bidder.
+ *   Output:   out = (float)((double)total * quantum / p), total the optimal integer cost -- unique where the assignment is not, so
+ *             out depends neither on the bidding order nor on the launch, two runs agree bit for bit, and
+ *             md_emd_matrix(x, y)[i][j] == md_emd_matrix(y, x)[j][i] bit for bit.
+ *   status[i][j]: 0 solved; 1 the pair reached max_rounds bidding rounds (out NaN, total -1, perm -1; the other pairs of the launch
+ *             are unaffected); 2 some d / quantum >= 2^21: the quantum is too small for the data (NaN likewise); 3 a NaN or infinite
+ *             coordinate in either cloud (NaN, no bidding).
+ *   triangular != 0 (needs x == y and nx == ny): only the pairs i < j are solved and written to [i][j] and [j][i] (perm[j][i] is the
+ *             inverse permutation); the diagonal is exactly 0 with status 0 and the identity (a non-finite cloud: status 3 there too).
+ *   total, rounds (bidding rounds run) and perm (perm[i][j][k] = the point of y[j] matched to point k of x[i]) may be null.
+ *   One workgroup per pair, both clouds in LDS: p <= 2048, nx * ny < 2^31 and 2^-126 <= quantum <= 2^126, else MD_ERR_UNSUPPORTED.
+ *   Null x, y, out or status, sizes < 1, max_rounds < 1, a quantum that is not a positive finite power of two, triangular with
+ *   x != y or nx != ny: MD_ERR_BAD_ARG.
+ */
+int md_emd_matrix(const float* x, const float* y, int32_t nx, int32_t ny, int32_t p, float quantum, int32_t max_rounds,
+                  int32_t triangular, float* out, int32_t* status, int64_t* total, int32_t* rounds, int32_t* perm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,7 @@ SIGNATURES = {
     "md_rast_mark_tets": (C.c_int, [_P, _P, _I32, _I32, _I32, _I64, _I64, _P, _P]),
     "md_tets_mark_verts": (C.c_int, [_P, _P, _P, _I32, _I64, _I64, _P, _P, _P]),
     "md_sided_mean_matrix": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
+    "md_emd_matrix": (C.c_int, [_P, _P, _I32, _I32, _I32, _F, _I32, _I32, _P, _P, _P, _P, _P, _P]),
 }
 LAPLACE_SLABS = 64                                  # MD_LAPLACE_SLABS
 LAPLACE_WORKSPACE_BYTES = LAPLACE_SLABS * 8         # MD_LAPLACE_WORKSPACE_BYTES

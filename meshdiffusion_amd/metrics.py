@@ -14,7 +14,14 @@ docstrings below, and the oracle of the tests is a float64 restatement of the sa
 The hot path is the matrix of chamfer distances between EVERY pair of clouds (`chamfer_matrix`, one launch of
 md_sided_mean_matrix for a union); everything after it is torch on an [S+R, S+R] matrix.  GPU only, like pointcloud.py: a CPU
 tensor is an error, not a fallback.
+
+The same three figures under the earth mover's distance EMD(a, b) = (1/P) min over permutations pi of sum_i |a_i - b_pi(i)|
+(Euclidean distance; clouds of equal size) come from `emd_matrix` (csrc/emd.hip: one workgroup per pair solves the assignment
+problem exactly on distances quantised to integers), and `jsd` is the Jensen-Shannon divergence of the two sets' occupancy of
+a voxel grid.  `shape_metrics(..., emd=True, jsd=True)` adds them.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -100,13 +107,129 @@ def one_nna(d_ss, d_sr, d_rr):
     return float(right.mean()), float(right[:S].mean()), float(right[S:].mean())
 
 
-def shape_metrics(sample_clouds, ref_clouds):
+EMD_MAX_POINTS = 2048                                       # EMD_MAX_P of csrc/emd.hip: both clouds of a pair live in LDS
+EMD_PERM_PAIRS = 4096                                       # return_info: the matchings are returned for at most this many pairs
+
+
+def emd_quantum(*clouds, bits=20):
+    """The power of two 2^(ceil(log2 diag) - bits) as a Python float, diag being the diagonal of the bounding box of ALL the
+    clouds passed ([...,3] tensors, any device): every distance between two of their points is then at most 2^bits quanta.  A
+    zero diagonal gives 2^-bits.  Plain torch."""
+    if not clouds:
+        raise ValueError("emd_quantum: no clouds")
+    pts = [c.detach().reshape(-1, 3).to(torch.float64) for c in clouds]
+    lo = torch.stack([c.min(dim=0).values for c in pts]).min(dim=0).values
+    hi = torch.stack([c.max(dim=0).values for c in pts]).max(dim=0).values
+    diag = float((hi - lo).square().sum().sqrt())
+    if not math.isfinite(diag):
+        raise ValueError("emd_quantum: a non-finite coordinate")
+    if diag == 0:
+        return 2.0 ** -bits
+    m, e = math.frexp(diag)                                 # diag = m 2^e with 0.5 <= m < 1
+    return 2.0 ** ((e - 1 if m == 0.5 else e) - bits)
+
+
+def emd_matrix(x, y=None, quantum=None, max_rounds=None, return_info=False):
+    """Earth mover's distance matrix float32 [Nx,Ny] of x [Nx,P,3] against y [Ny,P,3]: md_emd_matrix, one workgroup per pair.
+    Distances are fp32 in the direct form, quantised to rint(d / quantum) and the integer assignment problem is solved exactly
+    (forward auction, eps-scaling, 64-bit integer prices): out = total * quantum / P, so the result does not depend on the
+    launch, two runs agree bit for bit and emd_matrix(x, y) == emd_matrix(y, x).t().  `quantum` is a power of two, by default
+    `emd_quantum(x, y)` (20 bits); pass one value to every call whose entries are to be compared.  `max_rounds` bounds the
+    bidding rounds of a pair (default 256 P + 4096; at P = 64 that is 20480, 7.1 times the worst count in tests/emd_cases.py, 2867).
+
+    y=None or y is x: the triangular launch -- the pairs i < j only, exactly symmetric, an exactly zero diagonal.
+    A cloud with a NaN or infinite coordinate gives NaN in its pairs (status 3) and nothing else.  A pair that runs out of
+    rounds (status 1) or whose distances exceed 2^21 quanta (status 2) raises MeshDiffusionHipError -- unless return_info,
+    which returns (out, {"status", "total", "rounds", "perm", "quantum"}) as they are: int32 [Nx,Ny], int64 [Nx,Ny] (the optimal
+    integer cost, -1 where there is none), int32 [Nx,Ny] (bidding rounds run) and int32 [Nx,Ny,P] (perm[i,j,k] = the point of
+    y[j] matched to point k of x[i]; None beyond 4096 pairs).  P > 2048 and P != Q are ValueErrors.  Not differentiable."""
+    tri = y is None or y is x
+    # the shapes first, so that they are refused the same way wherever the tensors live
+    for t in (x,) if tri else (x, y):
+        if t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"emd_matrix: expected [N,P,3] point clouds with N, P >= 1, got {tuple(t.shape)}")
+    if not tri and y.shape[1] != x.shape[1]:
+        raise ValueError(f"emd_matrix: the clouds of both sets need the same number of points, got {x.shape[1]} and {y.shape[1]}")
+    if x.shape[1] > EMD_MAX_POINTS:
+        raise ValueError(f"emd_matrix: at most {EMD_MAX_POINTS} points per cloud, got {x.shape[1]}")
+    xc = _clouds(x, "emd_matrix")
+    yc = xc if tri else _clouds(y, "emd_matrix")
+    if yc.device != xc.device:
+        raise ValueError("emd_matrix: both sets of clouds need the same device")
+    P = xc.shape[1]
+    nx, ny = xc.shape[0], yc.shape[0]
+    if quantum is None:
+        finite = [c[torch.isfinite(c).all(dim=2).all(dim=1)] for c in ((xc,) if tri else (xc, yc))]
+        finite = [c for c in finite if c.shape[0]]
+        quantum = emd_quantum(*finite) if finite else 2.0 ** -20
+    quantum = float(quantum)
+    if max_rounds is None:
+        max_rounds = 256 * P + 4096
+    lib = _lib.load()
+    dev = xc.device
+    out = torch.empty((nx, ny), dtype=torch.float32, device=dev)
+    status = torch.empty((nx, ny), dtype=torch.int32, device=dev)
+    total = torch.empty((nx, ny), dtype=torch.int64, device=dev) if return_info else None
+    rounds = torch.empty((nx, ny), dtype=torch.int32, device=dev) if return_info else None
+    perm = torch.empty((nx, ny, P), dtype=torch.int32, device=dev) if return_info and nx * ny <= EMD_PERM_PAIRS else None
+    _lib.check(lib.md_emd_matrix(_ptr(xc), _ptr(yc), nx, ny, P, quantum, int(max_rounds), 1 if tri else 0, _ptr(out), _ptr(status),
+                                 _ptr(total), _ptr(rounds), _ptr(perm), _stream()), "md_emd_matrix")
+    if return_info:
+        return out, {"status": status, "total": total, "rounds": rounds, "perm": perm, "quantum": quantum}
+    failed = torch.nonzero((status == 1) | (status == 2))
+    if failed.shape[0]:
+        i, j = (int(v) for v in failed[0])
+        if int(status[i, j]) == 1:
+            raise _lib.MeshDiffusionHipError(f"emd_matrix: pair ({i}, {j}) was not solved within max_rounds={int(max_rounds)} bidding "
+                                             f"rounds: raise max_rounds")
+        raise _lib.MeshDiffusionHipError(f"emd_matrix: pair ({i}, {j}) has distances beyond 2^21 quanta of quantum={quantum!r}: pass a "
+                                         f"larger quantum (emd_quantum of all the clouds)")
+    return out
+
+
+def jsd(sample_clouds, ref_clouds, resolution=28):
+    """Jensen-Shannon divergence, in bits, between the occupancy histograms of two SETS of clouds [N,P,3] on a resolution^3 grid
+    over [-0.5, 0.5]^3 (the range of `normalize_clouds(..., "bbox")`): every point of every cloud of a set is counted into the
+    cell clamp(floor((c + 0.5) * resolution), 0, resolution - 1) per axis, each histogram is divided by its total, and
+        JSD = H((P + Q) / 2) - (H(P) + H(Q)) / 2,      H = the entropy with base-2 logarithms,
+    which lies in [0, 1]: 0 for equal histograms, 1 for disjoint ones.  Plain torch in float64 on the device of the inputs; a
+    non-finite coordinate is a ValueError."""
+    res = int(resolution)
+    if res < 1:
+        raise ValueError(f"jsd: resolution must be at least 1, got {resolution}")
+    hist = []
+    for name, c in (("sample_clouds", sample_clouds), ("ref_clouds", ref_clouds)):
+        if c.dim() < 2 or c.shape[-1] != 3 or c.numel() == 0:
+            raise ValueError(f"jsd: {name}: expected [...,P,3] point clouds, got {tuple(c.shape)}")
+        pts = c.detach().reshape(-1, 3).to(torch.float64)
+        if not bool(torch.isfinite(pts).all()):
+            raise ValueError(f"jsd: {name} holds a non-finite coordinate")
+        cell = torch.floor((pts + 0.5) * res).clamp_(0, res - 1).to(torch.int64)
+        flat = (cell[:, 0] * res + cell[:, 1]) * res + cell[:, 2]
+        h = torch.bincount(flat, minlength=res ** 3).to(torch.float64)
+        hist.append(h / h.sum())
+    if hist[0].device != hist[1].device:
+        raise ValueError("jsd: both sets of clouds need the same device")
+
+    def entropy(h):
+        nz = h[h > 0]
+        return -(nz * torch.log2(nz)).sum()
+
+    return float(entropy((hist[0] + hist[1]) / 2) - (entropy(hist[0]) + entropy(hist[1])) / 2)
+
+
+def shape_metrics(sample_clouds, ref_clouds, emd=False, jsd=False):
     """MMD / COV / 1-NNA under the chamfer distance of samples [S,P,3] against references [R,Q,3].  One kernel call on the
     concatenation when P == Q, three `chamfer_matrix` calls otherwise.  Returns {"mmd_cd", "cov_cd", "1nna_cd",
     "1nna_cd_sample", "1nna_cd_ref", "n_sample", "n_ref", "points"} (`points` = [P, Q]).  A cloud with a non-finite
-    coordinate makes its whole row of the matrix non-finite; the first such cloud is named in a ValueError."""
+    coordinate makes its whole row of the matrix non-finite; the first such cloud is named in a ValueError.
+    emd=True (needs P == Q <= 2048) adds "mmd_emd", "cov_emd", "1nna_emd", "1nna_emd_sample", "1nna_emd_ref" from ONE triangular
+    `emd_matrix` of the concatenation, and "emd_quantum", the `emd_quantum` of both sets it was computed with.  jsd=True adds
+    "jsd" (`jsd` at its default resolution)."""
     s, r = _clouds(sample_clouds, "shape_metrics"), _clouds(ref_clouds, "shape_metrics")
     S, R = s.shape[0], r.shape[0]
+    if emd and s.shape[1] != r.shape[1]:
+        raise ValueError(f"shape_metrics: emd=True needs the same number of points on both sides, got {s.shape[1]} and {r.shape[1]}")
     if s.shape[1] == r.shape[1]:
         d = chamfer_matrix(torch.cat([s, r], dim=0))
     else:
@@ -121,8 +244,21 @@ def shape_metrics(sample_clouds, ref_clouds):
     d_ss, d_sr, d_rr = d[:S, :S], d[:S, S:], d[S:, S:]
     mmd, cov = mmd_cov(d_sr)
     acc, acc_s, acc_r = one_nna(d_ss, d_sr, d_rr)
-    return {"mmd_cd": mmd, "cov_cd": cov, "1nna_cd": acc, "1nna_cd_sample": acc_s, "1nna_cd_ref": acc_r, "n_sample": S,
-            "n_ref": R, "points": [int(s.shape[1]), int(r.shape[1])]}
+    rec = {"mmd_cd": mmd, "cov_cd": cov, "1nna_cd": acc, "1nna_cd_sample": acc_s, "1nna_cd_ref": acc_r, "n_sample": S,
+           "n_ref": R, "points": [int(s.shape[1]), int(r.shape[1])]}
+    if emd:
+        quantum = emd_quantum(s, r)
+        e = emd_matrix(torch.cat([s, r], dim=0), quantum=quantum)
+        mmd, cov = mmd_cov(e[:S, S:])
+        acc, acc_s, acc_r = one_nna(e[:S, :S], e[:S, S:], e[S:, S:])
+        rec.update({"mmd_emd": mmd, "cov_emd": cov, "1nna_emd": acc, "1nna_emd_sample": acc_s, "1nna_emd_ref": acc_r,
+                    "emd_quantum": quantum})
+    if jsd:
+        rec["jsd"] = _jsd(s, r)
+    return rec
+
+
+_jsd = jsd                                                  # `shape_metrics` has a flag of that name
 
 
 def normalize_clouds(points, mode="bbox"):

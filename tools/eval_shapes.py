@@ -1,12 +1,15 @@
-"""MMD / COV / 1-NNA (chamfer distance) of a set of generated shapes against a reference set.
+"""MMD / COV / 1-NNA (chamfer distance; with --emd the earth mover's distance too) and JSD of generated shapes against a reference set.
 
     python tools/eval_shapes.py --samples meshes/ --ref reference_meshes/ [--points 2048] [--normalize bbox] [--out metrics.json]
+    python tools/eval_shapes.py --samples meshes/ --ref reference_meshes/ --emd --jsd
     python tools/eval_shapes.py --samples out/0.npy --tet_path 64_tets_cropped.npz --ref reference_meshes/
 
 --samples and --ref are directories of `.obj` files (read in sorted order), or --samples the sampler's `.npy` of grids, which
 goes through marching tetrahedra (`GridMesher`, needs --tet_path).  Every mesh is sampled at --points surface points
 (`meshdiffusion_amd.metrics.clouds_from_meshes`; one device generator seeded with --seed draws for the samples, then for the
 references), normalised (`normalize_clouds`) and handed to `shape_metrics`.  Meshes without faces are left out and counted.
+--emd adds MMD / COV / 1-NNA under the earth mover's distance (`emd_matrix`, at most 2048 points), --jsd the Jensen-Shannon
+divergence of the two sets' occupancy of a 28^3 grid over [-0.5, 0.5]^3, which is where --normalize bbox puts the clouds.
 Prints one JSON line: the figures of `shape_metrics`, `skipped_sample`, `skipped_ref` and wall `seconds`.  GPU only."""
 import argparse
 import json
@@ -49,6 +52,8 @@ def main(argv=None):
     ap.add_argument("--points", type=int, default=2048)
     ap.add_argument("--normalize", choices=("bbox", "none"), default="bbox")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--emd", action="store_true", help="also MMD / COV / 1-NNA under the earth mover's distance")
+    ap.add_argument("--jsd", action="store_true", help="also the Jensen-Shannon divergence of the occupancy grids")
     ap.add_argument("--out", default=None, help="also write the JSON record here")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -59,7 +64,8 @@ def main(argv=None):
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
     s, skipped_s = clouds_from_meshes(load_meshes(a.samples, a.tet_path), a.points, generator=gen, skip_empty=True)
     r, skipped_r = clouds_from_meshes(load_meshes(a.ref), a.points, generator=gen, skip_empty=True)
-    rec = shape_metrics(normalize_clouds(s, a.normalize), normalize_clouds(r, a.normalize))
+    extra = {k: True for k in ("emd", "jsd") if getattr(a, k)}                 # without them: the call and the record of before
+    rec = shape_metrics(normalize_clouds(s, a.normalize), normalize_clouds(r, a.normalize), **extra)
     torch.cuda.synchronize()
     rec.update(skipped_sample=len(skipped_s), skipped_ref=len(skipped_r), seconds=round(time.time() - t0, 3))
     print(json.dumps(rec), flush=True)
