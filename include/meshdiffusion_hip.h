@@ -1032,6 +1032,45 @@ int md_sided_mean_matrix(const float* x, const float* y, int32_t nx, int32_t ny,
 int md_emd_matrix(const float* x, const float* y, int32_t nx, int32_t ny, int32_t p, float quantum, int32_t max_rounds,
                   int32_t triangular, float* out, int32_t* status, int64_t* total, int32_t* rounds, int32_t* perm, void* stream);
 
+/*
+ * Post-processing of generated meshes (the tail of nvdiffrec/eval.py:421-456: a diffuse quick-look image and a clean-up), csrc/
+ * meshpost.hip.  In the manner of that tail, not bit-equal to MeshLab or nvdiffrast.  Purely additive: MD_ABI_VERSION stays 16, no
+ * existing entry point changes.
+ *
+ * THE MESH POST-PROCESSING CONTRACT (the header comment of csrc/meshpost.hip has it in full; tests/meshpost_cases.py restates it)
+ *   A mesh batch is concatenated: verts float32 [V][3], faces int64 [F][3] (8-byte aligned) of global vertex ids; meshes laid end to
+ *   end share no edge, so no entry point needs their number.  fp32, no contraction, no floating-point atomics (integer atomicMin /
+ *   atomicAdd only): two runs agree bit for bit.  Null or misaligned pointers and non-positive sizes MD_ERR_BAD_ARG; V, 2 V (smoothing:
+ *   the codes), n_codes or 3 F beyond int32 MD_ERR_UNSUPPORTED.  An index outside its table is absent, never read.  Nothing is
+ *   allocated: the caller passes the scratch.
+ * md_mesh_smooth: ptr int32 [V+1], adj int32 [n_codes = 2 E] is the neighbour CSR of the undirected edge table, codes
+ *   2 * neighbour + (1 if the edge belongs to exactly one face), ascending inside a row.  `steps` >= 0 umbrella steps, step i with
+ *   w = lam (i even, or mu NaN = unset) or mu (Taubin): a vertex whose row holds a boundary code keeps only the boundary codes; n
+ *   codes left: n == 0 keeps the vertex's bits, else x' = x + w (s / (float)n - x), s the compensated sum of the neighbours in row
+ *   order.  One launch per step, all issued by this call; `verts` is never written and may alias neither `out` nor `scratch`
+ *   (float32 [V][3], needed for steps >= 2); the result is in `out`; steps == 0 copies.  lam not finite, mu neither finite nor NaN:
+ *   MD_ERR_BAD_ARG.
+ * md_mesh_components: label int32 [V] = the smallest vertex index connected to v through faces (a degenerate face connects too, a
+ *   vertex no face names is its own component), by hook-and-compress rounds (one thread per face atomicMin's the smallest of its
+ *   three roots into the other two, one thread per vertex compresses) until a round lowers no label; `workspace`
+ *   (MD_MESH_COMPONENTS_WORKSPACE_BYTES, 4-byte aligned) holds the device flag, read with one 4-byte copy per round, so the call
+ *   synchronises the stream.  More than MD_MESHPOST_MAX_ROUNDS rounds: MD_ERR_UNSUPPORTED, never an unbounded loop.  comp_faces int32
+ *   [V]: at index label the number of faces whose first vertex carries it, 0 elsewhere.  *rounds (host, may be NULL) = the rounds run.
+ * md_shade_diffuse: rast float32 [B][H][W][4] (16-byte aligned) one layer of the rasterisation contract, campos float32 [B][3], sh
+ *   float32 [9][3] radiance coefficients in the real spherical harmonics of bands 0-2, kd float32 [3] -> out float32 [B][H][W][4]
+ *   (16-byte aligned): where 1 <= id <= F, rgb = kd * max(e, 0) and alpha 1, e the irradiance over pi at the geometric normal of
+ *   face id - 1 turned towards campos (a uniform environment of radiance 1 gives kd); four zeros elsewhere.  B <= 64, H, W <= 2048,
+ *   F < 2^24, else MD_ERR_UNSUPPORTED.  Forward only.
+ */
+#define MD_MESHPOST_MAX_ROUNDS 64
+#define MD_MESH_COMPONENTS_WORKSPACE_BYTES 16
+int md_mesh_smooth(const float* verts, const int32_t* ptr, const int32_t* adj, int64_t n_verts, int64_t n_codes, int32_t steps,
+                   float lam, float mu, float* out, float* scratch, void* stream);
+int md_mesh_components(const int64_t* faces, int64_t n_verts, int64_t n_faces, int32_t* label, int32_t* comp_faces, void* workspace,
+                       int32_t* rounds, void* stream);
+int md_shade_diffuse(const float* rast, const float* verts, const int64_t* faces, const float* campos, const float* sh,
+                     const float* kd, int32_t batch, int64_t n_verts, int64_t n_faces, int32_t H, int32_t W, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,7 +178,12 @@ SIGNATURES = {
     "md_tets_mark_verts": (C.c_int, [_P, _P, _P, _I32, _I64, _I64, _P, _P, _P]),
     "md_sided_mean_matrix": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "md_emd_matrix": (C.c_int, [_P, _P, _I32, _I32, _I32, _F, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "md_mesh_smooth": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _F, _F, _P, _P, _P]),
+    "md_mesh_components": (C.c_int, [_P, _I64, _I64, _P, _P, _P, C.POINTER(C.c_int32), _P]),
+    "md_shade_diffuse": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I64, _I64, _I32, _I32, _P, _P]),
 }
+MESHPOST_MAX_ROUNDS = 64                            # MD_MESHPOST_MAX_ROUNDS
+MESH_COMPONENTS_WORKSPACE_BYTES = 16                # MD_MESH_COMPONENTS_WORKSPACE_BYTES
 LAPLACE_SLABS = 64                                  # MD_LAPLACE_SLABS
 LAPLACE_WORKSPACE_BYTES = LAPLACE_SLABS * 8         # MD_LAPLACE_WORKSPACE_BYTES
 SDF_REG_SLABS = 64                                  # MD_SDF_REG_SLABS

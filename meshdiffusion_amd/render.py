@@ -13,11 +13,16 @@ comment of csrc/interp.hip: dr.interpolate, the `rast` gradient of dr.rasterize 
 `render_buffers` is the reference's `bsdf == 'normal'` renderer (render.py:105-106, 177-264) and `image_loss` / `color_loss` the
 colour term of tick (dmtet.py:391-400).  `laplace_regularizer_const`, `depth_loss_fixedtopo` and `fit_fixed_topology` are pass 2 of
 the reference's fit (fit_dmtets.py:758-793) on a `dmtet.DMTetGeometryFixedTopo`, by the fixed-topology contract in the header
-comment of csrc/fixedtopo.hip.  The kernels run on the GPU only: a CPU tensor is an
-error, not a fallback.  The camera helpers, `xfm_points`, `shading_normal`, the losses and the carve are plain torch and run
-anywhere.
+comment of csrc/fixedtopo.hip.  `shade_diffuse` and `render_preview` are the quick-look image the reference renders of every sampled
+mesh (nvdiffrec/eval.py:421-438: `bsdf == 'diffuse'`, kd = (0.75, 0.3, 0.6), an environment light, the two-sided geometric normal)
+by the shading part of the mesh post-processing contract in the header comment of csrc/meshpost.hip: in the manner of that image,
+not equal to it -- the environment comes in as nine spherical-harmonic coefficients (`sh9_from_latlong`, `default_light`), which
+stand in for the reference's cosine-convolved cube map, and `preview_camera` is its `rotate_scene`.  The kernels run on the GPU
+only: a CPU tensor is an error, not a fallback.  The camera helpers, `xfm_points`, `shading_normal`, the losses and the carve are plain torch and run
+anywhere; `sh9_from_latlong` and `default_light` are numpy on the host.
 
-Not built: materials, lights, textures, spp > 1 / MSAA, clipping of triangles that cross w = 0, more than
+Not built: materials beyond one diffuse colour, specular / PBR shading, cube maps and `.hdr` loading,
+camera-space lights, gradients of the preview, textures, spp > 1 / MSAA, clipping of triangles that cross w = 0, more than
 two layers, gradients for mvp / campos and zf, a silhouette search beyond the covering triangle.
 """
 import numpy as np
@@ -963,3 +968,161 @@ def fit_fixed_topology(geometry, targets, iters, *, lr=0.01, laplace_scale=10000
         keys = ("depth", "laplace", "alpha") + (("color",) if with_color else ())
         return {k: stacked(hist[k]) for k in keys}
     return stacked(hist["depth"])
+
+
+# ---- the diffuse preview (nvdiffrec/eval.py:421-438) ---------------------------------------------------------------------------------
+SH_BAND_WEIGHTS = (1.0, 2 / 3, 2 / 3, 2 / 3, 0.25, 0.25, 0.25, 0.25, 0.25)     # A_l / pi of the cosine lobe, bands 0, 1, 2
+PREVIEW_KD = (0.75, 0.3, 0.6)                                                   # eval.py:426
+LIGHT_RES = (64, 128)
+
+
+def sh_basis(d):
+    """The nine real spherical harmonics of bands 0-2 at unit directions d [...,3] (numpy float64) -> [...,9], ordered (0,0),
+    (1,-1), (1,0), (1,1), (2,-2) .. (2,2), with the six-digit constants of the contract (csrc/meshpost.hip)."""
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    return np.stack([np.full_like(x, 0.282095), 0.488603 * y, 0.488603 * z, 0.488603 * x, 1.092548 * x * y, 1.092548 * y * z,
+                     0.315392 * (3 * z * z - 1), 1.092548 * x * z, 0.546274 * (x * x - y * y)], -1)
+
+
+def latlong_directions(h, w):
+    """(directions float64 [h,w,3], solid angles float64 [h,w]) of the texel centres of a lat-long map in the reference's
+    convention (nvdiffrec/lib/render/util.py:116-117: tu = atan2(x, -z) / 2 pi + 1/2, tv = acos(y) / pi)."""
+    theta = (np.arange(h, dtype=np.float64) + 0.5) / h * np.pi
+    phi = ((np.arange(w, dtype=np.float64) + 0.5) / w - 0.5) * 2 * np.pi
+    st, ct = np.sin(theta)[:, None], np.cos(theta)[:, None]
+    d = np.stack([st * np.sin(phi)[None], np.broadcast_to(ct, (h, w)), -st * np.cos(phi)[None]], -1)
+    return d, np.broadcast_to(st * (np.pi / h) * (2 * np.pi / w), (h, w))
+
+
+def sh9_from_latlong(env):
+    """env [h,w,3] (array or tensor), a lat-long radiance map -> float32 numpy [9,3]: L_k = the integral of env * Y_k over the sphere
+    by a midpoint quadrature over the texel centres with sin(theta) weights, in float64 on the host.  `shade_diffuse` turns these
+    into irradiance over pi, sum_k A_k L_k Y_k(n): a white map gives 1 (to the quadrature's error, 2e-4 at 64 x 128)."""
+    e = np.asarray(env.detach().cpu() if torch.is_tensor(env) else env, dtype=np.float64)
+    if e.ndim != 3 or e.shape[2] != 3 or e.shape[0] < 1 or e.shape[1] < 1:
+        raise ValueError(f"sh9_from_latlong: expected env [h,w,3], got {e.shape}")
+    d, dw = latlong_directions(e.shape[0], e.shape[1])
+    return np.einsum("hwk,hwc,hw->kc", sh_basis(d), e, dw).astype(np.float32)
+
+
+def default_sky(d):
+    """The analytic sky of `default_light` at unit directions d [...,3] (numpy) -> radiance [...,3]:
+        L(d) = ground + (sky - ground) * (0.5 + 0.5 d.y) + sun * max(0, d . s)^2,
+    ground = (0.30, 0.28, 0.26), sky = (0.95, 1.00, 1.10), sun = (0.90, 0.85, 0.75), s = (1, 2, 1) / sqrt(6)."""
+    ground, sky, sun = np.array([0.30, 0.28, 0.26]), np.array([0.95, 1.00, 1.10]), np.array([0.90, 0.85, 0.75])
+    s = np.array([1.0, 2.0, 1.0]) / np.sqrt(6.0)
+    up = (0.5 + 0.5 * d[..., 1])[..., None]
+    return ground + (sky - ground) * up + sun * (np.maximum(d @ s, 0.0) ** 2)[..., None]
+
+
+_CONSTANTS = {}
+
+
+def default_light():
+    """The light of `render_preview`: `sh9_from_latlong` of `default_sky` (a ground-to-sky gradient along y plus a soft key light
+    from the upper front right) sampled on a 64 x 128 lat-long map.  float32 numpy [9,3], deterministic (computed once, a copy per
+    call).  The reference's `.hdr` probe is not shipped; any lat-long `.npy` goes through `sh9_from_latlong` instead."""
+    if "light" not in _CONSTANTS:
+        _CONSTANTS["light"] = sh9_from_latlong(default_sky(latlong_directions(*LIGHT_RES)[0]))
+    return _CONSTANTS["light"].copy()
+
+
+def _device_constant(values, device):
+    """A float32 device tensor of a small host array (kd, the background, a light) or of the default light (values None),
+    uploaded once per device and value: a preview per mesh of a batch should not pay a host-to-device copy for each."""
+    host = _CONSTANTS["light"] if values is None and "light" in _CONSTANTS else None
+    if host is None:
+        host = default_light() if values is None else np.ascontiguousarray(values, dtype=np.float32)
+    key = (host.tobytes(), host.shape, str(device))
+    if key not in _CONSTANTS:
+        if len(_CONSTANTS) > 64:                                               # colours come and go; the table stays small
+            _CONSTANTS.clear()
+        _CONSTANTS[key] = torch.from_numpy(host.copy()).to(device)
+    return _CONSTANTS[key]
+
+
+def preview_camera(angle_ind, resolution, radius=3.0, fovy=np.deg2rad(45.0), near=0.1, far=1000.0, device=None):
+    """The reference's rotate_scene (eval.py:182-201): mv = translate(0, 0, -radius) @ (rotate_x(-0.4) @ rotate_y(angle_ind / 50 *
+    2 pi)), mvp = perspective(fovy, W / H, near, far) @ mv, campos = inv(mv)[:3, 3].  Returns (mvp [1,4,4], campos [1,3]) float32."""
+    H, W = _resolution(resolution)
+    mv = translate(0, 0, -radius) @ (rotate_x(-0.4) @ rotate_y((angle_ind / 50) * np.pi * 2))
+    mvp = perspective(fovy, W / H, near, far) @ mv
+    campos = torch.linalg.inv(mv)[:3, 3]
+    return mvp[None].to(device).contiguous(), campos[None].to(device).contiguous()
+
+
+def shade_diffuse(rast, verts, faces, campos, sh, kd):
+    """The shading kernel of the mesh post-processing contract (csrc/meshpost.hip): rast float32 [B,H,W,4] one layer of `rasterize`,
+    verts [V,3], faces [F,3], campos [B,3], sh [9,3] (`sh9_from_latlong`), kd [3] -> float32 [B,H,W,4]: kd * max(irradiance / pi, 0)
+    at the geometric normal turned towards the camera and alpha 1 where 1 <= id <= F, four zeros elsewhere.  Forward only."""
+    _gpu_only(rast, "shade_diffuse")
+    _gpu_only(verts, "shade_diffuse")
+    if rast.dim() != 4 or rast.shape[-1] != 4 or min(rast.shape[:3]) < 1:
+        raise ValueError(f"shade_diffuse: expected rast [B,H,W,4], got {tuple(rast.shape)}")
+    B, H, W, _ = rast.shape
+    if B > MAX_VIEWS:
+        raise _lib.MeshDiffusionHipError(f"shade_diffuse takes at most {MAX_VIEWS} views per call (MD_ERR_UNSUPPORTED)")
+    _resolution((H, W))
+    if verts.dim() != 2 or verts.shape[-1] != 3:
+        raise ValueError(f"shade_diffuse: expected verts [V,3], got {tuple(verts.shape)}")
+    dev = rast.device
+    v = verts.detach().to(device=dev, dtype=torch.float32).contiguous()
+    f = _check_faces(faces.to(dev), v.shape[0])
+    cam = torch.as_tensor(campos).detach().to(device=dev, dtype=torch.float32).contiguous()
+    s = torch.as_tensor(sh).detach().to(device=dev, dtype=torch.float32).contiguous()
+    k = torch.as_tensor(kd).detach().to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(cam.shape) != (B, 3) or tuple(s.shape) != (9, 3) or tuple(k.shape) != (3,):
+        raise ValueError(f"shade_diffuse: expected campos [{B},3], sh [9,3] and kd [3], got {tuple(cam.shape)}, {tuple(s.shape)} and {tuple(k.shape)}")
+    return _shade_diffuse(rast.detach().to(torch.float32).contiguous(), v, f, cam, s, k)
+
+
+def _shade_diffuse(r, v, f, cam, s, k):
+    """shade_diffuse on checked, contiguous float32 / int64 device tensors."""
+    B, H, W, _ = r.shape
+    if f.shape[0] == 0 or v.shape[0] == 0:                                      # every id is above F
+        return torch.zeros((B, H, W, 4), dtype=torch.float32, device=r.device)
+    out = torch.empty((B, H, W, 4), dtype=torch.float32, device=r.device)
+    _lib.check(_lib.load().md_shade_diffuse(_ptr(r), _ptr(v), _ptr(f), _ptr(cam), _ptr(s), _ptr(k), B, v.shape[0], f.shape[0], H, W,
+                                            _ptr(out), _stream()), "md_shade_diffuse")
+    return out
+
+
+@torch.no_grad()
+def render_preview(verts, faces, mvp, campos, resolution, *, kd=PREVIEW_KD, light=None, background=(1.0, 1.0, 1.0), antialias=True):
+    """The quick-look image of eval.py:435-438: float32 [B,H,W,3] in [0, 1].  `rasterize` layer 1 of xfm_points(verts, mvp) ->
+    `shade_diffuse` (light: sh [9,3], None = `default_light()`) -> the existing `antialias` on the four channels -> rgb + (1 - alpha)
+    * background -> the reference's rgb_to_srgb -> clamp.  An empty mesh gives the background."""
+    _gpu_only(verts, "render_preview")
+    H, W = _resolution(resolution)
+    dev = verts.device
+    if mvp.dim() != 3 or mvp.shape[1:] != (4, 4) or tuple(campos.shape) != (mvp.shape[0], 3):
+        raise ValueError(f"render_preview: expected mvp [B,4,4] and campos [B,3], got {tuple(mvp.shape)} and {tuple(campos.shape)}")
+    B = mvp.shape[0]
+    if B > MAX_VIEWS:
+        raise _lib.MeshDiffusionHipError(f"render_preview takes at most {MAX_VIEWS} views per call (MD_ERR_UNSUPPORTED)")
+
+    def constant(x, shape):
+        if torch.is_tensor(x):
+            t = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            t = _device_constant(x, dev)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"render_preview: expected a constant of shape {shape}, got {tuple(t.shape)}")
+        return t
+
+    bg = constant(background, (3,))
+    if verts.shape[0] == 0 or faces.shape[0] == 0:
+        rgb = bg.expand(B, H, W, 3)
+    else:
+        v = verts.detach().to(torch.float32).contiguous()
+        f = _check_faces(faces.to(dev), v.shape[0])                            # once for the rasteriser and the shading
+        m = mvp.detach().to(device=dev, dtype=torch.float32).contiguous()
+        cam = campos.detach().to(device=dev, dtype=torch.float32).contiguous()
+        clip = xfm_points(v[None], m).contiguous()
+        _check_clip(clip)
+        rast = _rasterize(clip, f, H, W)[0]
+        col = _shade_diffuse(rast, v, f, cam, constant(light, (9, 3)), constant(kd, (3,)))
+        if antialias:
+            col = _AntialiasFn.apply(col, clip, rast, f, edge_neighbours(f, v.shape[0]))[0]
+        rgb = col[..., 0:3] + (1 - col[..., 3:4]) * bg
+    return torch.clamp(_tonemap_srgb(rgb), 0.0, 1.0).contiguous()
