@@ -9,9 +9,9 @@
 // fp32 values.  After the MFMAs it
 //   activates them (a x + c, SiLU, equaliser; a / c / eq come from LDS tables: the sample's a / c in a wave-private copy,
 //   because the waves of a workgroup never synchronise and may stand in different samples),
-//   takes the activated values of positions j - 1 and j + 1 from the neighbouring lanes (ds_bpermute); lanes j = 0 / 31 take
+//   takes the activated values of positions j - 1 and j + 1 from the neighbouring lanes (DPP wave shifts); lanes j = 0 / 31 take
 //   them from the HALO: per group of 4 steps, lane L < 32 loads 16 bytes of the position in front of / behind the segment
-//   (L = step, channel group, end, half) and activates them once -- zero where that position lies outside the row,
+//   (L = step, channel group, end, half) and activates them once (pulled with ds_bpermute) -- zero where that position lies outside the row,
 //   forms the two frequencies of its position's parity on its own 8 channels (even position of a pair: f0, f1; odd: f2, f3),
 //   swaps one of them with the lane holding the other channel group of the same position (v_permlane32_swap): every lane now
 //   has ONE frequency f = 2 (j & 1) + h of pair j >> 1 with all 16 channels of the K block,
@@ -40,6 +40,14 @@ __device__ __forceinline__ void bp_store(uint64_t base, uint32_t off, uint4 v) {
 }
 __device__ __forceinline__ float bp_pull(int addr, float v) {      // v of lane addr / 4
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, v)));
+}
+// v of lane - 1 / lane + 1 by a DPP wave shift (wave_shr:1 / wave_shl:1: over all 64 lanes; lane 0 / lane 63 get zero): one
+// v_mov_b32_dpp, no LDS-pipe round trip and no lgkmcnt wait.  (The consumer is a select, which the compiler does not give a DPP source.)
+__device__ __forceinline__ float bp_from_prev(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float bp_from_next(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
 }
 }  // namespace
 
@@ -72,8 +80,8 @@ __global__ __launch_bounds__(BP_THREADS) void md_block_pass_kernel(const uint4* 
   const bool has_l = xr > 0, has_r = xr < W - 1;                  // the neighbour lies inside the row
   const bool first = j == 0, last = j == 31;                      // ... and outside the wave's segment: the halo
   const bool take_l = has_l && !first, take_r = has_r && !last, use_h = (first && has_l) || (last && has_r);
+  const bool no_l = !take_l, no_r = !take_r;
   const bool odd = j & 1;
-  const int a_l = ((lane - 1) & 63) * 4, a_r = ((lane + 1) & 63) * 4;
   // halo holder L = lane & 31 (lanes < 32 load): step hk of the group, channel group hh of its K block, end hend, 16-byte half hq
   const int hk = (lane >> 3) & 3, hh = (lane >> 2) & 1, hend = (lane >> 1) & 1, hq = lane & 1;
   const bool seg_l = ((wid * 32) & (W - 1)) != 0, seg_r = ((wid * 32 + 32) & (W - 1)) != 0;      // wave-uniform: that end has a halo
@@ -153,8 +161,10 @@ __global__ __launch_bounds__(BP_THREADS) void md_block_pass_kernel(const uint4* 
       // the neighbour inside the segment, else the halo value where that end of the segment has one, else zero (the conv pads the
       // ACTIVATED tensor).  One `edge` serves both sides: a lane is the first or the last of its segment, and W is even
       const float edge = use_h ? hl : 0.f;
-      const float pl = bp_pull(a_l, own), pr = bp_pull(a_r, own);      // by ALL lanes: a lane outside the exchange is still a source
-      const float l = take_l ? pl : edge, r = take_r ? pr : edge;
+      // lane = 32 h + j: a lane that takes pl (j > 0) / pr (j < 31) finds its neighbour in lane - 1 / lane + 1 of its own half; what
+      // the wave-wide shift brings to lanes 0, 31, 32 and 63 is never selected
+      const float pl = bp_from_prev(own), pr = bp_from_next(own);
+      const float l = no_l ? edge : pl, r = no_r ? edge : pr;
       // even position of its pair: own = d1, l = d0, r = d2 -> f0, f1; odd: own = d2, l = d1, r = d3 -> f2, f3 (f3 = d1 - d3 = l - r)
       const float lr = md_wino_bt(0, l, 0.f, r, 0.f);
       const float f1 = md_wino_bt(1, 0.f, own, r, 0.f);

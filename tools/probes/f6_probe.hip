@@ -3,6 +3,7 @@
 // What the "f16f6" Winograd conv (csrc/conv3_wino.hip, FMT = 2) relies on, each checked against a host computation in double:
 //  1. v_cvt_scalef32_2xpk16_fp6_f32 (32 floats -> 32 e2m3 codes in 6 registers): rounding, saturation, what the scale operand does, and
 //     -- through v_cvt_scalef32_pk32_f32_fp6, the decoder -- which of the 32 positions each of the two 16-float sources lands on;
+//     1b (`f6_probe scale`, alone): the convert at scale 2^k against a multiply by 2^-k in front of the convert at scale 1.0;
 //  2. v_mfma_scale_f32_32x32x64_f8f6f4 with both operands in e2m3 (cbsz = blgp = 2): a lane's 6 registers are the 32 k of its half
 //     (lanes 0-31: k 0..31, lanes 32-63: k 32..63), and EVERY LANE'S OWN scale byte (E8M0, byte 0 of the scale register) scales its
 //     own 32-value block: A block (row lane & 31, k half lane >> 5), B block (column lane & 31, k half lane >> 5);
@@ -50,6 +51,64 @@ __global__ void enc_dec_kernel(const float* x, float* y, unsigned* codes, float 
   for (int q = 0; q < 6; ++q) codes[l * 6 + q] = c[q];
   const f32x32 d = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(c, dec_scale);
   for (int i = 0; i < 32; ++i) y[l * 32 + i] = d[i];
+}
+
+// ---- 1b. the scale operand against a multiply in front of the convert -------------------------------------------------
+// md_split_f16f6 multiplies the block's 32 values by inv = 2^-k and converts at scale 1.0.  Does the convert at scale 2^k give the same
+// six words?  One wave per k; lane l, value i = x[l * 32 + i] (the same inputs for every k, see main).
+__global__ void scale_kernel(const float* x, unsigned* by_mul, unsigned* by_scale, int k0) {
+  const int l = threadIdx.x, k = k0 + (int)blockIdx.x;
+  const float scale = __uint_as_float((unsigned)(127 + k) << 23), inv = __uint_as_float((unsigned)(127 - k) << 23);
+  f32x16 s0, s1, m0, m1;
+  for (int i = 0; i < 16; ++i) {
+    s0[i] = x[(blockIdx.x * 64 + l) * 32 + i]; s1[i] = x[(blockIdx.x * 64 + l) * 32 + 16 + i];
+    m0[i] = s0[i] * inv; m1[i] = s1[i] * inv;
+  }
+  const u32x6 a = cvt_2xpk16_fp6(m0, m1, 1.0f), b = cvt_2xpk16_fp6(s0, s1, scale);
+  for (int q = 0; q < 6; ++q) { by_mul[(blockIdx.x * 64 + l) * 6 + q] = a[q]; by_scale[(blockIdx.x * 64 + l) * 6 + q] = b[q]; }
+}
+
+static int scale_sweep(int k0, int k1) {
+  // per k: lane 0 = the operand passes' special values as they are (they meet every block scale); lanes 1-7 = the e2m3 rounding and
+  // saturation edges times 2^k; the other lanes = random values in (-8, 8) 2^k, every fourth one a remainder-sized value 2^-11 of that
+  const int nk = k1 - k0 + 1;
+  std::vector<float> x((size_t)nk * 64 * 32);
+  const float inf = INFINITY;
+  const float special[32] = {NAN, -NAN, inf, -inf, 65504.f, -65504.f, 65519.996f, 65520.f, 1e30f, -1e30f, 0.f, -0.f, 1e-40f, -1e-40f, 1.4e-45f,
+                             1.17549435e-38f, 3.4028235e38f, -3.4028235e38f, 1.f, -1.f, 7.5f, 7.75f, 8.f, 0.0625f, 0.1875f, 1e-9f, 448.f, 60000.f,
+                             2048.f, 6e-8f, 1e-20f, 1e20f};
+  const float edge[28] = {7.5f, 7.75f, 7.9999995f, 8.f, 7.25f, 7.74f, 7.76f, 0.0625f, 0.06250001f, 0.0624f, 0.1875f, 0.3125f, 0.9375f, 1.0625f,
+                          1.9375f, 2.125f, 2.375f, 3.875f, 4.25f, 4.75f, 12.f, 100.f, 0.03125f, 1e-3f, 1e-6f, 3.f, 5.f, 6.f};
+  for (int kk = 0; kk < nk; ++kk) {
+    float* xk = x.data() + (size_t)kk * 64 * 32;
+    for (int i = 0; i < 32; ++i) xk[i] = special[i];
+    for (int l = 1; l < 8; ++l)
+      for (int i = 0; i < 32; ++i) {
+        const int e = ((l - 1) * 32 + i) % 56;
+        xk[l * 32 + i] = std::ldexp(e < 28 ? edge[e] : -edge[e - 28], k0 + kk);
+      }
+    for (int l = 8; l < 64; ++l)
+      for (int i = 0; i < 32; ++i) {
+        const double r = (rand() / (double)RAND_MAX * 2 - 1) * 8.0;
+        xk[l * 32 + i] = (float)std::ldexp((i & 3) == 3 ? r / 2048.0 : r, k0 + kk);
+      }
+  }
+  float* dx; unsigned *da, *db;
+  CK(hipMalloc(&dx, x.size() * 4)); CK(hipMalloc(&da, (size_t)nk * 64 * 6 * 4)); CK(hipMalloc(&db, (size_t)nk * 64 * 6 * 4));
+  CK(hipMemcpy(dx, x.data(), x.size() * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(scale_kernel, dim3(nk), dim3(64), 0, 0, dx, da, db, k0);
+  std::vector<unsigned> a((size_t)nk * 64 * 6), b(a.size());
+  CK(hipMemcpy(a.data(), da, a.size() * 4, hipMemcpyDeviceToHost));
+  CK(hipMemcpy(b.data(), db, b.size() * 4, hipMemcpyDeviceToHost));
+  int bad = 0;
+  for (size_t w = 0; w < a.size(); ++w)
+    if (a[w] != b[w]) {
+      if (bad < 8) printf("  k = %d lane %d word %d: multiply-then-convert %08x, convert at scale 2^k %08x\n", k0 + (int)(w / 384), (int)(w / 6 % 64), (int)(w % 6), a[w], b[w]);
+      ++bad;
+    }
+  printf("convert at scale 2^k against multiply by 2^-k + convert at scale 1, k = %d .. %d: %d of %zu words differ\n", k0, k1, bad, a.size());
+  CK(hipFree(dx)); CK(hipFree(da)); CK(hipFree(db));
+  return bad;
 }
 
 // ---- 2. MFMA semantics ------------------------------------------------------------------------------------------------
@@ -113,8 +172,12 @@ __global__ __launch_bounds__(256) void thr_kernel(const uint4* src, float* sink,
   if (s == 123.456f) sink[tid] = s;
 }
 
-int main() {
+int main(int argc, char** argv) {
   srand(3);
+  if (argc > 1 && argv[1][0] == 's') {      // `f6_probe scale`: the scale-operand sweep alone (the exponents of the issue, then those a block can have)
+    const int bad = scale_sweep(-20, 20) + scale_sweep(-109, -21) + scale_sweep(21, 126);
+    return bad ? 2 : 0;
+  }
   // ---------------- 1. encode / decode ----------------
   {
     std::vector<float> x(64 * 32), y(64 * 32);
