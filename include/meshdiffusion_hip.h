@@ -1071,6 +1071,66 @@ int md_mesh_components(const int64_t* faces, int64_t n_verts, int64_t n_faces, i
 int md_shade_diffuse(const float* rast, const float* verts, const int64_t* faces, const float* campos, const float* sh,
                      const float* kd, int32_t batch, int64_t n_verts, int64_t n_faces, int32_t H, int32_t W, float* out, void* stream);
 
+/*
+ * Isotropic remeshing of generated meshes (the meshing_isotropic_explicit_remeshing of nvdiffrec/eval.py:449-456), csrc/remesh.hip.
+ * In the manner of MeshLab's filter, not bit-equal to it.  Purely additive: MD_ABI_VERSION stays 16.
+ *
+ * THE REMESHING CONTRACT (the header comment of csrc/remesh.hip has it in full; tests/remesh_cases.py restates it in float32 numpy)
+ *   One iteration = split, collapse rounds, flip rounds, relax, driven by meshdiffusion_amd/postprocess.py remesh, which rebuilds
+ *   the tables between launch groups: the edge table lo, hi, mult int64 [E] sorted by (lo, hi); the neighbour CSR ptr int32 [V+1],
+ *   adj int32 [2 E] (neighbour = code >> 1, ascending); the corner CSR cptr int32 [V+1], corner int32 [3 F] (codes 3 f + k,
+ *   ascending); vflag int32 [V] (bit 0: on an edge of one face; bit 1: on an edge of three or more faces or named by a face that
+ *   names a vertex twice; non-zero = fixed); vert_mesh int32 [V] and lo2 / hi2 float32 [M], the squares of 4/5 and 4/3 of the
+ *   target length of each mesh.  Every decision is a function of the state before the launch: two runs agree bit for bit.  fp32,
+ *   no contraction, predicates without sqrt or division, integer atomicMin / atomicAdd only.  Null or misaligned pointers (int64
+ *   and the 64-bit priority words: 8 bytes) and non-positive sizes MD_ERR_BAD_ARG; V, 2 E or 3 F beyond int32 MD_ERR_UNSUPPORTED.
+ *   An index outside its table is absent, never read.  Nothing is allocated and no entry point synchronises.
+ * md_remesh_split_mark: mark int32 [E] = len2 > hi2[mesh of lo], mid float32 [E][3] = the midpoint of every edge.
+ * md_remesh_split_count: count int32 [F] = 1 + the marked edges of a face (1 for a face that names a vertex twice).
+ * md_remesh_split_emit: rank int32 [E] = the exclusive cumsum of mark (marked edge e becomes vertex V + rank[e]), offset int32 [F] =
+ *   the exclusive cumsum of count -> out_faces int64 [F_out][3], the children of face f at offset[f], by the fixed patterns.
+ * md_remesh_collapse_candidates: cand int32 [E], prio uint64 [E] = (float bits of len2) << 32 | e (all ones: no candidate).
+ * md_remesh_collapse_claim: atomicMin of prio into word uint64 [V] (set to all ones by the caller) over N(a) u N(b).
+ * md_remesh_collapse_apply: a candidate all of whose words hold its prio writes verts[a] = midpoint, remap[b] = a (remap int32 [V],
+ *   set to the identity by the caller) and adds one to *counter (device int32, zeroed by the caller).
+ * md_remesh_flip_candidates: cos2 = cos^2 of the flip angle in [0, 1]; info int32 [E][4] = (face (a,b,c), face (b,a,d), c, d) or -1;
+ *   a flip that would lower the smallest of the six angles of its two faces is no candidate; prio = (16 - gain) << 32 | e.  md_remesh_flip_claim: atomicMin over a, b, c, d.  md_remesh_flip_apply: a winner rewrites its two
+ *   face slots with (a,d,c) and (d,b,c) in place and adds one to *counter.
+ * md_remesh_relax: out float32 [V][3] (not verts) = x + lam (d - n (n . d)), d the umbrella mean minus x, n the normalised sum of
+ *   the incident face normals; a fixed vertex or one without neighbours keeps its bits.  lam must be finite.
+ */
+#define MD_REMESH_COLLAPSE_ROUNDS 8
+#define MD_REMESH_FLIP_ROUNDS 4
+#define MD_REMESH_MAX_ITERS 32
+int md_remesh_split_mark(const float* verts, const int64_t* lo, const int64_t* hi, const int32_t* vert_mesh, const float* hi2,
+                         int64_t n_verts, int64_t n_edges, int64_t n_meshes, int32_t* mark, float* mid, void* stream);
+int md_remesh_split_count(const int64_t* faces, const int64_t* lo, const int64_t* hi, const int32_t* mark, int64_t n_verts,
+                          int64_t n_edges, int64_t n_faces, int32_t* count, void* stream);
+int md_remesh_split_emit(const float* verts, const int64_t* faces, const int64_t* lo, const int64_t* hi, const int32_t* mark,
+                         const int32_t* rank, const int32_t* offset, int64_t n_verts, int64_t n_edges, int64_t n_faces,
+                         int64_t n_faces_out, int64_t* out_faces, void* stream);
+int md_remesh_collapse_candidates(const float* verts, const int64_t* faces, const int64_t* lo, const int64_t* hi, const int64_t* mult,
+                                  const int32_t* ptr, const int32_t* adj, const int32_t* cptr, const int32_t* corner,
+                                  const int32_t* vflag, const int32_t* vert_mesh, const float* lo2, const float* hi2, int64_t n_verts,
+                                  int64_t n_edges, int64_t n_faces, int64_t n_meshes, int32_t* cand, uint64_t* prio, void* stream);
+int md_remesh_collapse_claim(const int64_t* lo, const int64_t* hi, const int32_t* ptr, const int32_t* adj, const int32_t* cand,
+                             const uint64_t* prio, int64_t n_verts, int64_t n_edges, uint64_t* word, void* stream);
+int md_remesh_collapse_apply(const int64_t* lo, const int64_t* hi, const int32_t* ptr, const int32_t* adj, const int32_t* cand,
+                             const uint64_t* prio, uint64_t* word, int64_t n_verts, int64_t n_edges, float* verts, int32_t* remap,
+                             int32_t* counter, void* stream);
+int md_remesh_flip_candidates(const float* verts, const int64_t* faces, const int64_t* lo, const int64_t* hi, const int64_t* mult,
+                              const int32_t* ptr, const int32_t* cptr, const int32_t* corner, const int32_t* vflag, float cos2,
+                              int64_t n_verts, int64_t n_edges, int64_t n_faces, int32_t* cand, uint64_t* prio, int32_t* info,
+                              void* stream);
+int md_remesh_flip_claim(const int64_t* lo, const int64_t* hi, const int32_t* cand, const uint64_t* prio, const int32_t* info,
+                         int64_t n_verts, int64_t n_edges, uint64_t* word, void* stream);
+int md_remesh_flip_apply(const int64_t* lo, const int64_t* hi, const int32_t* cand, const uint64_t* prio, const int32_t* info,
+                         const uint64_t* word, int64_t n_verts, int64_t n_edges, int64_t n_faces, int64_t* faces, int32_t* counter,
+                         void* stream);
+int md_remesh_relax(const float* verts, const int64_t* faces, const int32_t* ptr, const int32_t* adj, const int32_t* cptr,
+                    const int32_t* corner, const int32_t* vflag, int64_t n_verts, int64_t n_edges, int64_t n_faces, float lam,
+                    float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

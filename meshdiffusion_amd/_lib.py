@@ -181,7 +181,20 @@ SIGNATURES = {
     "md_mesh_smooth": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _F, _F, _P, _P, _P]),
     "md_mesh_components": (C.c_int, [_P, _I64, _I64, _P, _P, _P, C.POINTER(C.c_int32), _P]),
     "md_shade_diffuse": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I64, _I64, _I32, _I32, _P, _P]),
+    "md_remesh_split_mark": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "md_remesh_split_count": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P]),
+    "md_remesh_split_emit": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "md_remesh_collapse_candidates": (C.c_int, [_P] * 13 + [_I64, _I64, _I64, _I64, _P, _P, _P]),
+    "md_remesh_collapse_claim": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
+    "md_remesh_collapse_apply": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "md_remesh_flip_candidates": (C.c_int, [_P] * 9 + [_F, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "md_remesh_flip_claim": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
+    "md_remesh_flip_apply": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "md_remesh_relax": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _F, _P, _P]),
 }
+REMESH_COLLAPSE_ROUNDS = 8                          # MD_REMESH_COLLAPSE_ROUNDS
+REMESH_FLIP_ROUNDS = 4                              # MD_REMESH_FLIP_ROUNDS
+REMESH_MAX_ITERS = 32                               # MD_REMESH_MAX_ITERS
 MESHPOST_MAX_ROUNDS = 64                            # MD_MESHPOST_MAX_ROUNDS
 MESH_COMPONENTS_WORKSPACE_BYTES = 16                # MD_MESH_COMPONENTS_WORKSPACE_BYTES
 LAPLACE_SLABS = 64                                  # MD_LAPLACE_SLABS

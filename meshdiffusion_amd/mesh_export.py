@@ -9,8 +9,8 @@ either side of the hot path, without nvdiffrast / pytor
   an environment light; `render.render_preview`) to `{idx:06d}.png`, and `smooth_steps` / `min_component_*` / `keep_largest`
   run the clean-up of `postprocess.postprocess` (eval.py:449-456) on the whole batch before the `.obj` is written.  Both are
   built in the manner of the reference under the mesh post-processing contract (csrc/meshpost.hip), not bit-equal to
-  pymeshlab or nvdiffrast: umbrella smoothing and a floater filter, no isotropic remeshing, nine spherical-harmonic
-  coefficients for the environment.
+  pymeshlab or nvdiffrast: umbrella smoothing, a floater filter, nine spherical-harmonic coefficients for the environment, and
+  with `remesh_iters` > 0 the isotropic remeshing of the remeshing contract (csrc/remesh.hip) before and after the smoothing.
 * `save_png` / `load_png`: 8-bit RGB PNG with the standard library's zlib and struct only, quantised with rint(x * 255) as the
   reference's `util.save_image` does.
 * `save_obj`: the plain "v x y z" / "f i j k" (1-based) subset of the format `pytorch3d.io.save_obj` writes
@@ -142,13 +142,15 @@ def load_png(path):
 
 def samples_to_obj(samples, tet_vertices, tet_indices, out_dir, resolution=None, batch=32, device="cuda", start_index=0,
                    with_normals=False, smooth_steps=0, lam=0.5, mu=None, min_component_faces=0, min_component_fraction=0.0,
-                   keep_largest=False, preview_dir=None, angle_ind=0, preview_res=512, preview_raw=True):
+                   keep_largest=False, preview_dir=None, angle_ind=0, preview_res=512, preview_raw=True, remesh_iters=0,
+                   remesh_target_scale=1.0):
     """samples: array [M,4,R,R,R] (or a path to the sampler's .npy).  Writes {out_dir}/{i:06d}.obj, returns their paths.
     with_normals: also write the smooth vertex normals the reference computes right after extraction
     (eval.py:422 `mesh.auto_normals`; its own OBJ export, eval.py:436-440, drops them); with a clean-up they are those of the
     cleaned mesh.
     smooth_steps, lam, mu, min_component_faces, min_component_fraction, keep_largest: the clean-up of `postprocess.postprocess`,
     run on each batch of meshes in one set of launches before the files are written (all off by default).
+    remesh_iters, remesh_target_scale: `postprocess.remesh` before and after the smoothing, as the reference's tail does (0 = off).
     preview_dir: also write {preview_dir}/{i:06d}.png, `render.render_preview` at `preview_camera(angle_ind, preview_res)` of the
     raw mesh, as the reference renders before its clean-up, or with preview_raw=False of the cleaned mesh."""
     if isinstance(samples, (str, os.PathLike)):
@@ -157,7 +159,7 @@ def samples_to_obj(samples, tet_vertices, tet_indices, out_dir, resolution=None,
     R = int(resolution or samples.shape[-1])
     mesher = GridMesher(tet_vertices, tet_indices, R, device=device)
     os.makedirs(out_dir, exist_ok=True)
-    clean = smooth_steps > 0 or min_component_faces > 0 or min_component_fraction > 0 or keep_largest
+    clean = smooth_steps > 0 or min_component_faces > 0 or min_component_fraction > 0 or keep_largest or remesh_iters > 0
     if preview_dir is not None:
         from .render import preview_camera, render_preview
         os.makedirs(preview_dir, exist_ok=True)
@@ -169,7 +171,8 @@ def samples_to_obj(samples, tet_vertices, tet_indices, out_dir, resolution=None,
         if clean:
             from .postprocess import postprocess
             cleaned = postprocess(meshes, smooth_steps=smooth_steps, lam=lam, mu=mu, min_component_faces=min_component_faces,
-                                  min_component_fraction=min_component_fraction, keep_largest=keep_largest)
+                                  min_component_fraction=min_component_fraction, keep_largest=keep_largest, remesh_iters=remesh_iters,
+                                  remesh_target_scale=remesh_target_scale)
         for k, (verts, faces, _face_tet) in enumerate(meshes):
             if preview_dir is not None:
                 pv, pf = (verts, faces) if preview_raw or cleaned is None else cleaned[k]
@@ -225,6 +228,8 @@ def main(argv=None):
     ap.add_argument("--min_component_faces", type=int, default=0, help="drop connected components with fewer faces")
     ap.add_argument("--min_component_fraction", type=float, default=0.0, help="drop components below this fraction of the mesh's largest")
     ap.add_argument("--keep_largest", action="store_true", help="keep only the largest connected component of each mesh")
+    ap.add_argument("--remesh_iters", type=int, default=0, help="isotropic remeshing iterations before and after the smoothing (0 = off)")
+    ap.add_argument("--remesh_target_scale", type=float, default=1.0, help="target edge length as a multiple of each mesh's mean edge length")
     ap.add_argument("--preview_dir", default=None, help="directory for a diffuse quick-look PNG of each mesh")
     ap.add_argument("--angle_ind", type=int, default=0, help="camera pose of the preview, 0..50 around the object")
     ap.add_argument("--preview_res", type=int, default=512)
@@ -234,7 +239,8 @@ def main(argv=None):
     paths = samples_to_obj(a.sample_path, tet["vertices"], tet["indices"], a.out, batch=a.batch, with_normals=a.normals,
                            smooth_steps=a.num_smooth_steps, lam=a.lam, mu=a.mu, min_component_faces=a.min_component_faces,
                            min_component_fraction=a.min_component_fraction, keep_largest=a.keep_largest, preview_dir=a.preview_dir,
-                           angle_ind=a.angle_ind, preview_res=a.preview_res, preview_raw=not a.preview_post)
+                           angle_ind=a.angle_ind, preview_res=a.preview_res, preview_raw=not a.preview_post, remesh_iters=a.remesh_iters,
+                           remesh_target_scale=a.remesh_target_scale)
     print(f"wrote {len(paths)} meshes to {a.out}" + (f" and their previews to {a.preview_dir}" if a.preview_dir else ""))
 
 

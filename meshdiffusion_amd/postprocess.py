@@ -3,14 +3,17 @@ umbrella (Laplacian / Taubin) smoothing, batched over the meshes of one marching
 
 The reference cleans each sampled mesh with pymeshlab at the end of nvdiffrec/eval.py (:449-456: isotropic remeshing and
 `apply_coord_laplacian_smoothing(stepsmoothnum=--num_smooth_steps)`).  This module is built in the manner of that step under the
-mesh post-processing contract in the header comment of csrc/meshpost.hip, not bit-equal to MeshLab: no remeshing, uniform
-(umbrella) weights, and a filter for the small disconnected shells that the sign noise of a sampled SDF leaves behind.  The
+mesh post-processing contract in the header comment of csrc/meshpost.hip, not bit-equal to MeshLab: uniform (umbrella) weights, a
+filter for the small disconnected shells that the sign noise of a sampled SDF leaves behind, and `remesh`, the isotropic remeshing
+(split, collapse, flip, relax) of the remeshing contract in the header comment of csrc/remesh.hip -- without re-projection onto the
+input surface, feature edges, adaptive sizing or cotangent weights.  The
 kernels run on the GPU only: a CPU tensor is an error, not a fallback.  The edge table, the compaction and the split / concat of a
 batch are torch plumbing.  Nothing here has a gradient: it runs after generation, not inside a fit.
 """
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -188,9 +191,220 @@ def split_meshes(verts, faces, vert_mesh, n_meshes):
     return out
 
 
-def postprocess(meshes, *, smooth_steps=0, lam=0.5, mu=None, min_component_faces=0, min_component_fraction=0.0, keep_largest=False):
-    """The clean-up of a whole batch (a list of (verts, faces, ...) or a `dmtet.MeshBatch`) in one set of launches: the floater
-    filter first (when min_component_faces > 0, min_component_fraction > 0 or keep_largest), then `smooth_steps` smoothing steps.
+def _repeated(f):
+    return (f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 2] == f[:, 0])
+
+
+def _remesh_tables(f, V):
+    """The tables of the remeshing contract from the faces of the moment: (lo, hi, mult int64 [E], ptr int32 [V+1], adj int32 [2 E],
+    cptr int32 [V+1], corner int32 [3 F], vflag int32 [V]).  Torch plumbing."""
+    lo, hi, mult, ptr, adj = mesh_edges(f, V)
+    cptr, corner = csr_by_row(f.reshape(-1), V)
+    vflag = torch.zeros(V, dtype=torch.int32, device=f.device)
+    for sel, bit in ((mult == 1, 1), (mult >= 3, 2)):
+        vflag[lo[sel]] |= bit
+        vflag[hi[sel]] |= bit
+    vflag[f[_repeated(f)].reshape(-1)] |= 2
+    return lo.contiguous(), hi.contiguous(), mult.contiguous(), ptr, adj, cptr, corner, vflag
+
+
+def remesh_default_target(verts, faces, vert_mesh, n_meshes):
+    """float32 numpy [M]: the mean edge length of each mesh (1 for a mesh without edges) -- float64 lengths from the fp32
+    coordinates on the device, then on the host the sequential float64 sum in table order, so that two runs agree bit for bit."""
+    V = verts.shape[0]
+    lo, hi, _, _, _ = mesh_edges(faces, V)
+    x = verts.to(torch.float64)
+    d = x[hi] - x[lo]
+    ln = torch.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).cpu().numpy()
+    em = vert_mesh.to(torch.int64)[lo].cpu().numpy()
+    s = np.bincount(em, weights=ln, minlength=n_meshes)
+    n = np.bincount(em, minlength=n_meshes)
+    return np.where(n > 0, s / np.maximum(n, 1), 1.0).astype(np.float32)
+
+
+def remesh_split(x, f, vm, hi2, lib=None):
+    """One split pass of the remeshing contract on checked device tensors: (verts', faces', vert_mesh', marked edges)."""
+    lib = lib or _lib.load()
+    V, F, M, dev = x.shape[0], f.shape[0], hi2.shape[0], x.device
+    lo, hi, mult, ptr, adj, cptr, corner, vflag = _remesh_tables(f, V)
+    E = lo.shape[0]
+    if E == 0:
+        return x, f, vm, 0
+    mark = torch.empty(E, dtype=torch.int32, device=dev)
+    mid = torch.empty(E, 3, dtype=torch.float32, device=dev)
+    _lib.check(lib.md_remesh_split_mark(_ptr(x), _ptr(lo), _ptr(hi), _ptr(vm), _ptr(hi2), V, E, M, _ptr(mark), _ptr(mid), _stream()),
+               "md_remesh_split_mark")
+    n = int(mark.sum())
+    if n == 0:
+        return x, f, vm, 0
+    if V + n > INT32_MAX:
+        raise _lib.MeshDiffusionHipError("remesh: V must fit int32 after the split (MD_ERR_UNSUPPORTED)")
+    rank = (torch.cumsum(mark, 0) - mark).to(torch.int32)
+    count = torch.empty(F, dtype=torch.int32, device=dev)
+    _lib.check(lib.md_remesh_split_count(_ptr(f), _ptr(lo), _ptr(hi), _ptr(mark), V, E, F, _ptr(count), _stream()), "md_remesh_split_count")
+    total = torch.cumsum(count.to(torch.int64), 0)
+    F_out = int(total[-1])
+    if 3 * F_out > INT32_MAX:
+        raise _lib.MeshDiffusionHipError("remesh: 3 F must fit int32 after the split (MD_ERR_UNSUPPORTED)")
+    offset = (total - count).to(torch.int32)
+    out = torch.empty(F_out, 3, dtype=torch.int64, device=dev)
+    _lib.check(lib.md_remesh_split_emit(_ptr(x), _ptr(f), _ptr(lo), _ptr(hi), _ptr(mark), _ptr(rank), _ptr(offset), V, E, F, F_out,
+                                        _ptr(out), _stream()), "md_remesh_split_emit")
+    sel = mark.bool()
+    x2, vm2 = torch.cat([x, mid[sel]]), torch.cat([vm, vm[lo[sel]]])
+    if M > 1:                                                                    # vertices stay grouped by mesh
+        order = torch.sort(vm2, stable=True).indices
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(order.shape[0], device=dev)
+        x2, vm2, out = x2[order], vm2[order], inv[out]
+    return x2.contiguous(), out.contiguous(), vm2.contiguous(), n
+
+
+def remesh_collapse_round(x, f, vm, lo2, hi2, lib=None):
+    """One collapse round of the remeshing contract: (verts', faces', vert_mesh', winners).  `x` is not written."""
+    lib = lib or _lib.load()
+    V, F, M, dev = x.shape[0], f.shape[0], hi2.shape[0], x.device
+    lo, hi, mult, ptr, adj, cptr, corner, vflag = _remesh_tables(f, V)
+    E = lo.shape[0]
+    if E == 0:
+        return x, f, vm, 0
+    cand = torch.empty(E, dtype=torch.int32, device=dev)
+    prio = torch.empty(E, dtype=torch.int64, device=dev)
+    word = torch.full((V,), -1, dtype=torch.int64, device=dev)                  # all ones
+    remap = torch.arange(V, dtype=torch.int32, device=dev)
+    counter = torch.zeros(1, dtype=torch.int32, device=dev)
+    new = x.clone()
+    st = _stream()
+    _lib.check(lib.md_remesh_collapse_candidates(_ptr(x), _ptr(f), _ptr(lo), _ptr(hi), _ptr(mult), _ptr(ptr), _ptr(adj), _ptr(cptr),
+                                                 _ptr(corner), _ptr(vflag), _ptr(vm), _ptr(lo2), _ptr(hi2), V, E, F, M, _ptr(cand),
+                                                 _ptr(prio), st), "md_remesh_collapse_candidates")
+    _lib.check(lib.md_remesh_collapse_claim(_ptr(lo), _ptr(hi), _ptr(ptr), _ptr(adj), _ptr(cand), _ptr(prio), V, E, _ptr(word), st),
+               "md_remesh_collapse_claim")
+    _lib.check(lib.md_remesh_collapse_apply(_ptr(lo), _ptr(hi), _ptr(ptr), _ptr(adj), _ptr(cand), _ptr(prio), _ptr(word), V, E, _ptr(new),
+                                            _ptr(remap), _ptr(counter), st), "md_remesh_collapse_apply")
+    n = int(counter)                                                            # the one 4-byte copy of a round
+    if n == 0:
+        return x, f, vm, 0
+    remap = remap.to(torch.int64)
+    f2 = remap[f]
+    f2 = f2[~_repeated(f2) | _repeated(f)]
+    keep = remap == torch.arange(V, device=dev)
+    newid = torch.cumsum(keep.to(torch.int64), 0) - 1
+    return new[keep].contiguous(), newid[f2].contiguous(), vm[keep].contiguous(), n
+
+
+def remesh_flip_round(x, f, cos2, lib=None):
+    """One flip round of the remeshing contract: (faces', winners).  `f` is not written."""
+    lib = lib or _lib.load()
+    V, F, dev = x.shape[0], f.shape[0], x.device
+    lo, hi, mult, ptr, adj, cptr, corner, vflag = _remesh_tables(f, V)
+    E = lo.shape[0]
+    if E == 0:
+        return f, 0
+    cand = torch.empty(E, dtype=torch.int32, device=dev)
+    prio = torch.empty(E, dtype=torch.int64, device=dev)
+    info = torch.empty(E, 4, dtype=torch.int32, device=dev)
+    word = torch.full((V,), -1, dtype=torch.int64, device=dev)
+    counter = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = f.clone()
+    st = _stream()
+    _lib.check(lib.md_remesh_flip_candidates(_ptr(x), _ptr(f), _ptr(lo), _ptr(hi), _ptr(mult), _ptr(ptr), _ptr(cptr), _ptr(corner),
+                                             _ptr(vflag), float(cos2), V, E, F, _ptr(cand), _ptr(prio), _ptr(info), st),
+               "md_remesh_flip_candidates")
+    _lib.check(lib.md_remesh_flip_claim(_ptr(lo), _ptr(hi), _ptr(cand), _ptr(prio), _ptr(info), V, E, _ptr(word), st), "md_remesh_flip_claim")
+    _lib.check(lib.md_remesh_flip_apply(_ptr(lo), _ptr(hi), _ptr(cand), _ptr(prio), _ptr(info), _ptr(word), V, E, F, _ptr(out),
+                                        _ptr(counter), st), "md_remesh_flip_apply")
+    n = int(counter)
+    return (out if n else f), n
+
+
+def remesh_relax(x, f, lam=0.5, lib=None):
+    """The relax pass of the remeshing contract: a new tensor."""
+    lib = lib or _lib.load()
+    V, F = x.shape[0], f.shape[0]
+    lo, hi, mult, ptr, adj, cptr, corner, vflag = _remesh_tables(f, V)
+    E = lo.shape[0]
+    if E == 0:
+        return x.clone()
+    out = torch.empty_like(x)
+    _lib.check(lib.md_remesh_relax(_ptr(x), _ptr(f), _ptr(ptr), _ptr(adj), _ptr(cptr), _ptr(corner), _ptr(vflag), V, E, F, float(lam),
+                                   _ptr(out), _stream()), "md_remesh_relax")
+    return out
+
+
+def remesh_bands(target):
+    """(lo2, hi2) float32 numpy [M] of float32 targets: (4/5 L)^2 and (4/3 L)^2 in float64, rounded once."""
+    t = np.asarray(target, dtype=np.float32).astype(np.float64)
+    return ((0.8 * t) ** 2).astype(np.float32), ((4.0 / 3.0 * t) ** 2).astype(np.float32)
+
+
+def remesh(verts, faces, *, iters=3, target_len=None, target_scale=1.0, relax=0.5, flip_angle=30.0, vert_mesh=None):
+    """Isotropic remeshing of a (concatenated) mesh by the remeshing contract (csrc/remesh.hip): `iters` iterations of split (edges
+    longer than 4/3 L), collapse (shorter than 4/5 L), flip (towards valence six) and tangential relaxation (weight `relax`, 0 = off).
+    L per mesh = (target_len float or [M], default the mesh's own mean edge length) * target_scale.  vert_mesh int [V] names the mesh
+    of a vertex (None: one mesh), ascending.  Returns (verts' float32 [V',3], faces' int64 [F',3], vert_mesh' int32 [V'], info) with
+    info = dict(target float32 numpy [M], iterations = [dict(splits, collapses, flips, collapse_rounds, flip_rounds), ...]).  GPU
+    only; the inputs are never written; two runs agree bit for bit.  Reaching a round cap is not an error."""
+    _gpu_only(verts, "remesh")
+    if verts.dim() != 2 or verts.shape[-1] != 3:
+        raise ValueError(f"remesh: expected verts [V,3], got {tuple(verts.shape)}")
+    iters = int(iters)
+    if iters < 0 or iters > _lib.REMESH_MAX_ITERS:
+        raise ValueError(f"remesh: iters must be in [0, {_lib.REMESH_MAX_ITERS}], got {iters}")
+    relax, flip_angle, target_scale = float(relax), float(flip_angle), float(target_scale)
+    if not math.isfinite(relax) or not 0.0 <= flip_angle <= 90.0 or not (math.isfinite(target_scale) and target_scale > 0):
+        raise ValueError("remesh: relax must be finite, flip_angle in [0, 90] degrees, target_scale finite and > 0")
+    dev = verts.device
+    x = verts.detach().to(torch.float32).contiguous().clone()
+    V = x.shape[0]
+    f = _check_faces(faces.to(dev), V, "remesh").clone()
+    if vert_mesh is None:
+        vm = torch.zeros(V, dtype=torch.int32, device=dev)
+    else:
+        vm = vert_mesh.to(device=dev, dtype=torch.int32).contiguous().clone()
+        if tuple(vm.shape) != (V,) or (V > 1 and (int(vm.min()) < 0 or bool((vm[1:] < vm[:-1]).any()))):
+            raise ValueError(f"remesh: expected vert_mesh [{V}] of ascending mesh numbers >= 0")
+    M = int(vm.max()) + 1 if V > 0 else 1
+    if target_len is None:
+        base = remesh_default_target(x, f, vm, M) if V > 0 and f.shape[0] > 0 else np.ones(M, np.float32)
+    else:
+        t = target_len.detach().cpu().numpy() if torch.is_tensor(target_len) else np.asarray(target_len)
+        if t.ndim > 1 or (t.ndim == 1 and t.shape[0] != M):
+            raise ValueError(f"remesh: expected one target length or [{M}], got {t.shape}")
+        base = np.broadcast_to(t.astype(np.float32), (M,))
+    target = (base.astype(np.float64) * target_scale).astype(np.float32)
+    if not (np.isfinite(target).all() and (target > 0).all()):
+        raise ValueError("remesh: every target length must be finite and > 0")
+    lo2, hi2 = (torch.as_tensor(a, device=dev) for a in remesh_bands(target))
+    cos2 = float(np.float32(math.cos(math.radians(flip_angle)) ** 2))
+    lib = _lib.load()
+    info = []
+    for _ in range(iters if V > 0 and f.shape[0] > 0 else 0):
+        rec = dict(splits=0, collapses=0, flips=0, collapse_rounds=0, flip_rounds=0)
+        x, f, vm, rec["splits"] = remesh_split(x, f, vm, hi2, lib)
+        for _r in range(_lib.REMESH_COLLAPSE_ROUNDS):
+            x, f, vm, n = remesh_collapse_round(x, f, vm, lo2, hi2, lib)
+            rec["collapse_rounds"] += 1
+            rec["collapses"] += n
+            if n == 0:
+                break
+        for _r in range(_lib.REMESH_FLIP_ROUNDS):
+            f, n = remesh_flip_round(x, f, cos2, lib)
+            rec["flip_rounds"] += 1
+            rec["flips"] += n
+            if n == 0:
+                break
+        if relax != 0.0:
+            x = remesh_relax(x, f, relax, lib)
+        info.append(rec)
+    return x, f, vm, dict(target=target, iterations=info)
+
+
+def postprocess(meshes, *, smooth_steps=0, lam=0.5, mu=None, min_component_faces=0, min_component_fraction=0.0, keep_largest=False,
+                remesh_iters=0, remesh_target_scale=1.0):
+    """The clean-up of a whole batch (a list of (verts, faces, ...) or a `dmtet.MeshBatch`) in one set of launches, in the
+    reference's order: the floater filter first (when min_component_faces > 0, min_component_fraction > 0 or keep_largest), then,
+    with remesh_iters > 0, `remesh`, then `smooth_steps` smoothing steps, then `remesh` again.
     Returns a list of (verts float32 [V_m,3], faces int64 [F_m,3]).  With every keyword at its default the meshes come back as they
     are."""
     verts, faces, vert_mesh = concat_meshes(meshes)
@@ -201,6 +415,10 @@ def postprocess(meshes, *, smooth_steps=0, lam=0.5, mu=None, min_component_faces
         verts, faces, vert_map, _ = drop_floaters(verts, faces, min_faces=min_component_faces, min_fraction=min_component_fraction,
                                                   keep_largest=keep_largest, vert_mesh=vert_mesh)
         vert_mesh = vert_mesh[vert_map >= 0]
+    if remesh_iters > 0 and verts.shape[0] > 0:
+        verts, faces, vert_mesh, _ = remesh(verts, faces, iters=remesh_iters, target_scale=remesh_target_scale, vert_mesh=vert_mesh)
     if smooth_steps > 0 and verts.shape[0] > 0:
         verts = smooth(verts, faces, smooth_steps, lam, mu)
+    if remesh_iters > 0 and verts.shape[0] > 0:
+        verts, faces, vert_mesh, _ = remesh(verts, faces, iters=remesh_iters, target_scale=remesh_target_scale, vert_mesh=vert_mesh)
     return split_meshes(verts, faces, vert_mesh, n)
