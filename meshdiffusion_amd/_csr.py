@@ -19,3 +19,18 @@ def csr_by_row(dest, n_rows):
         bounds = bounds.expand(dest.shape[0], -1).contiguous()
     ptr = torch.searchsorted(vals.contiguous(), bounds)
     return ptr.to(torch.int32).contiguous(), order.to(torch.int32).contiguous()
+
+
+def check_faces(faces, n_verts, what, limits=None, not_triangles=ValueError):
+    """faces [F,3] -> int64 contiguous with every index in [0, n_verts): checked once, with one aminmax, on the tensor's own device.
+    `limits(F)` raises what the caller refuses beyond that, after the shape check and before the conversion; `what` heads the messages."""
+    if faces.dim() != 2 or faces.shape[-1] != 3:
+        raise not_triangles(f"{what}: expected faces [F,3], got {tuple(faces.shape)}")
+    if limits is not None:
+        limits(faces.shape[0])
+    f = faces.to(torch.int64).contiguous()
+    if f.shape[0] > 0:
+        lo, hi = torch.aminmax(f)
+        if int(lo) < 0 or int(hi) >= n_verts:
+            raise ValueError(f"{what}: faces name vertices outside [0, {n_verts})")
+    return f

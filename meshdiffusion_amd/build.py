@@ -43,7 +43,7 @@ def build(verbose=False, force=False):
     from concurrent.futures import ThreadPoolExecutor
     hipcc = _hipcc()
     os.makedirs(OBJDIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "md_common.h"), os.path.join(CSRC, "md_pack.h"), os.path.join(CSRC, "md_prep_f6.h"), os.path.join(CSRC, "md_raster_snap.h"), os.path.join(CSRC, "md_gather.h"), os.path.join(INCLUDE, "meshdiffusion_hip.h")]
+    headers = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(INCLUDE, "meshdiffusion_hip.h")]
     flags = FLAGS + (["-DMD_BUILD_ABLATIONS"] if os.environ.get("MD_BUILD_ABLATIONS") == "1" else [])
     flags = flags + os.environ.get("MD_EXTRA_DEFINES", "").split()
     stamp = os.path.join(OBJDIR, "flags.txt")

@@ -41,7 +41,7 @@
 // md_antialias_bwd_pos: one thread per active pair writes the (x, y, w) gradients of the edge's two vertices; one thread per
 // (view, vertex) then GATHERS the codes 2 * entry + end, a plain fp32 sum, over a CSR sorted stably by b V + vertex
 // (csrc/md_gather.h, md_csr_gather_kernel<3, false, true>).  No floating-point atomics anywhere: two runs agree bit for bit.
-#include "md_common.h"
+#include "md_args.h"
 #include "md_gather.h"
 #include "md_raster_snap.h"
 
@@ -319,28 +319,20 @@ static bool aa_shape_ok(int32_t batch, int32_t n_faces, int32_t H, int32_t W) {
 
 extern "C" int md_mesh_edge_neighbours(const int64_t* sorted_keys, const int64_t* order, const int64_t* faces, int32_t n_faces,
                                        int32_t* nbr, void* stream) {
-  if (!sorted_keys || !order || !faces || !nbr || n_faces <= 0) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)sorted_keys & 7) || ((uintptr_t)order & 7) || ((uintptr_t)faces & 7) || ((uintptr_t)nbr & 3)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<8>(sorted_keys, order, faces) || md_any_bad<4>(nbr) || n_faces <= 0) return MD_ERR_BAD_ARG;
   if (n_faces >= (1 << 24)) return MD_ERR_UNSUPPORTED;
   const int64_t n = (int64_t)n_faces * 3;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_mesh_edge_neighbours_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     sorted_keys, order, faces, n, nbr);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  MD_LAUNCH_1D(md_mesh_edge_neighbours_kernel, n, 256, sorted_keys, order, faces, n, nbr);
 }
 
 extern "C" int md_antialias_pairs(const float* rast, const float* pos_clip, const int64_t* faces, const int32_t* nbr,
                                   int32_t batch, int32_t n_verts, int32_t n_faces, int32_t H, int32_t W, int32_t* pairs,
                                   void* stream) {
-  if (!rast || !pos_clip || !faces || !nbr || !pairs || batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0)
-    return MD_ERR_BAD_ARG;
-  if (((uintptr_t)rast & 15) || ((uintptr_t)pos_clip & 15) || ((uintptr_t)faces & 7) || ((uintptr_t)nbr & 3) ||
-      ((uintptr_t)pairs & 15))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<16>(rast, pos_clip, pairs) || md_any_bad<8>(faces) || md_any_bad<4>(nbr)) return MD_ERR_BAD_ARG;
+  if (batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0) return MD_ERR_BAD_ARG;
   if (!aa_shape_ok(batch, n_faces, H, W)) return MD_ERR_UNSUPPORTED;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_antialias_pairs_kernel, dim3((unsigned)((H * W + 255) / 256), (unsigned)batch), dim3(256), 0,
+  hipLaunchKernelGGL(md_antialias_pairs_kernel, dim3(md_blocks(H * W, 256), (unsigned)batch), dim3(256), 0,
                      (hipStream_t)stream, rast, pos_clip, faces, nbr, (int)n_verts, (int)n_faces, (int)H, (int)W,
                      reinterpret_cast<AaPair*>(pairs));
   MD_HIP_CHECK_LAUNCH();
@@ -348,8 +340,7 @@ extern "C" int md_antialias_pairs(const float* rast, const float* pos_clip, cons
 }
 
 static int aa_image_args(const void* a, const void* pairs, const void* out, int32_t batch, int32_t H, int32_t W, int32_t C) {
-  if (!a || !pairs || !out || batch <= 0 || H <= 0 || W <= 0) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)a & 3) || ((uintptr_t)pairs & 15) || ((uintptr_t)out & 3)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(a, out) || md_any_bad<16>(pairs) || batch <= 0 || H <= 0 || W <= 0) return MD_ERR_BAD_ARG;
   if (C < 1 || C > AA_MAX_C || !aa_shape_ok(batch, 0, H, W)) return MD_ERR_UNSUPPORTED;
   return MD_OK;
 }
@@ -359,7 +350,7 @@ extern "C" int md_antialias_blend(const float* color, const int32_t* pairs, int3
   const int rc = aa_image_args(color, pairs, out, batch, H, W, C);
   if (rc != MD_OK) return rc;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_antialias_blend_kernel, dim3((unsigned)((H * W + 255) / 256), (unsigned)batch), dim3(256), 0,
+  hipLaunchKernelGGL(md_antialias_blend_kernel, dim3(md_blocks(H * W, 256), (unsigned)batch), dim3(256), 0,
                      (hipStream_t)stream, color, reinterpret_cast<const AaPair*>(pairs), (int)H, (int)W, (int)C, out);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
@@ -370,7 +361,7 @@ extern "C" int md_antialias_bwd_color(const float* grad_out, const int32_t* pair
   const int rc = aa_image_args(grad_out, pairs, dcolor, batch, H, W, C);
   if (rc != MD_OK) return rc;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_antialias_bwd_color_kernel, dim3((unsigned)((H * W + 255) / 256), (unsigned)batch), dim3(256), 0,
+  hipLaunchKernelGGL(md_antialias_bwd_color_kernel, dim3(md_blocks(H * W, 256), (unsigned)batch), dim3(256), 0,
                      (hipStream_t)stream, grad_out, reinterpret_cast<const AaPair*>(pairs), (int)H, (int)W, (int)C, dcolor);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
@@ -380,17 +371,15 @@ extern "C" int md_antialias_bwd_pos(const int64_t* active, int32_t n_active, con
                                     const int32_t* pairs, const float* pos_clip, const int32_t* ptr, const int32_t* order,
                                     int32_t batch, int32_t n_verts, int32_t H, int32_t W, int32_t C, float* vert_grad,
                                     float* dpos_clip, void* stream) {
-  if (!dpos_clip || !ptr || batch <= 0 || n_verts <= 0 || H <= 0 || W <= 0 || n_active < 0) return MD_ERR_BAD_ARG;
-  if (n_active > 0 && (!active || !color || !grad_out || !pairs || !pos_clip || !order || !vert_grad)) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)pos_clip & 15) || ((uintptr_t)dpos_clip & 15) || ((uintptr_t)pairs & 15) || ((uintptr_t)active & 7))
+  if (md_any_bad<16>(dpos_clip) || md_any_bad<1>(ptr) || batch <= 0 || n_verts <= 0 || H <= 0 || W <= 0 || n_active < 0)
     return MD_ERR_BAD_ARG;
-  if (C < 1 || C > AA_MAX_C || !aa_shape_ok(batch, 0, H, W) || (int64_t)batch * n_verts >= 0x7fffffffLL ||
-      (int64_t)n_active * 2 > 0x7fffffffLL)
-    return MD_ERR_UNSUPPORTED;
+  if (n_active > 0 && md_any_bad<1>(active, color, grad_out, pairs, pos_clip, order, vert_grad)) return MD_ERR_BAD_ARG;
+  if (md_any_misaligned<16>(pos_clip, pairs) || md_any_misaligned<8>(active)) return MD_ERR_BAD_ARG;
   const int64_t BV = (int64_t)batch * n_verts;
+  if (C < 1 || C > AA_MAX_C || !aa_shape_ok(batch, 0, H, W) || !md_fits_i32(BV + 1, (int64_t)n_active * 2)) return MD_ERR_UNSUPPORTED;
   MD_HIP_CLEAR_ERROR();
   if (n_active > 0)
-    hipLaunchKernelGGL(md_antialias_bwd_pair_kernel, dim3((unsigned)((n_active + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(md_antialias_bwd_pair_kernel, dim3(md_blocks(n_active, 256)), dim3(256), 0, (hipStream_t)stream,
                        active, (int)n_active, color, grad_out, reinterpret_cast<const AaPair*>(pairs), pos_clip, (int)n_verts,
                        (int)H, (int)W, (int)C, (int64_t)batch * H * W * 2, vert_grad);
   md_csr_gather<3, false, true>(vert_grad, ptr, order, BV, (int64_t)n_active * 2, dpos_clip, (hipStream_t)stream);

@@ -11,7 +11,7 @@
 // faces are emitted 1-triangle tets first (tet order), then 2-triangle tets, like the
 // reference's torch.cat.  Prefix sums: wave-level ballots + popcounts (wave64) inside a chunk, the chunk offsets from the
 // scan kernel -- every number is an integer, so the result does not depend on how the work is cut.
-#include "md_common.h"
+#include "md_args.h"
 
 #pragma clang fp contract(off)
 
@@ -234,12 +234,12 @@ extern "C" int md_marching_tets(const float* pos, const float* sdf, const int32_
                                 int32_t n_verts, int32_t n_edges, int32_t n_tets, float* verts,
                                 int64_t* faces, int64_t* face_tet, int32_t* counts, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
-  if (!pos || !sdf || !tets || !edges || !tet_edges || !verts || !faces || !counts || !workspace ||
+  if (md_any_bad<1>(pos, sdf, tets, edges, tet_edges, verts, faces, counts, workspace) ||
       n_meshes <= 0 || n_verts <= 0 || n_edges <= 0 || n_tets <= 0)
     return MD_ERR_BAD_ARG;
   if (workspace_bytes < md_marching_tets_workspace_bytes(n_meshes, n_edges, n_tets)) return MD_ERR_BAD_ARG;
   if (n_meshes > 65535) return MD_ERR_UNSUPPORTED;             // gridDim.y
-  if (((uintptr_t)tets & 15) || ((uintptr_t)edges & 7)) return MD_ERR_BAD_ARG;   // read as int4 / int2 rows
+  if (md_any_misaligned<16>(tets) || md_any_misaligned<8>(edges)) return MD_ERR_BAD_ARG;   // read as int4 / int2 rows
   MtArgs g;
   g.pos = pos; g.sdf = sdf; g.tets = tets; g.edges = edges; g.tet_edges = tet_edges;
   g.n_verts = n_verts; g.n_edges = n_edges; g.n_tets = n_tets; g.ce = mt_chunks(n_edges); g.ct = mt_chunks(n_tets);
@@ -288,14 +288,14 @@ __global__ void md_normalize_normals_kernel(float* __restrict__ v_nrm, int64_t V
 
 extern "C" int md_vertex_normals(const float* verts, const int64_t* faces, int64_t n_verts, int64_t n_faces, float* v_nrm,
                                  float* f_nrm, void* stream) {
-  if (!verts || !faces || !v_nrm || n_verts <= 0 || n_faces < 0) return MD_ERR_BAD_ARG;
+  if (md_any_bad<1>(verts, faces, v_nrm) || n_verts <= 0 || n_faces < 0) return MD_ERR_BAD_ARG;
   hipError_t e = hipMemsetAsync(v_nrm, 0, (size_t)n_verts * 3 * sizeof(float), (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
   MD_HIP_CLEAR_ERROR();
   if (n_faces > 0)
-    hipLaunchKernelGGL(md_face_normals_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, verts,
+    hipLaunchKernelGGL(md_face_normals_kernel, dim3(md_blocks(n_faces, 256)), dim3(256), 0, (hipStream_t)stream, verts,
                        faces, n_faces, v_nrm, f_nrm);
-  hipLaunchKernelGGL(md_normalize_normals_kernel, dim3((unsigned)((n_verts + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(md_normalize_normals_kernel, dim3(md_blocks(n_verts, 256)), dim3(256), 0, (hipStream_t)stream,
                      v_nrm, n_verts);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;

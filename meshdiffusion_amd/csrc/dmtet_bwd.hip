@@ -11,7 +11,7 @@
 //   dpos[a] += g * (-sb / den)        dpos[b] += g * (sa / den)
 //   d = dot(g, pos[a] - pos[b]) / den^2
 //   dsdf[a] += d * sb                 dsdf[b] -= d * sa
-#include "md_common.h"
+#include "md_args.h"
 
 #pragma clang fp contract(off)
 
@@ -62,14 +62,14 @@ extern "C" int md_marching_tets_bwd(const float* pos, const float* sdf, const in
                                     const int32_t* counts, const float* grad_verts, const int32_t* inc_ptr,
                                     const int32_t* inc, int32_t n_meshes, int32_t n_verts, int32_t n_edges, float* dpos,
                                     float* dsdf, void* stream) {
-  if (!pos || !sdf || !edges || !vid || !counts || !grad_verts || !inc_ptr || !inc || !dpos || !dsdf || n_meshes <= 0 ||
-      n_verts <= 0 || n_edges <= 0)
+  if (md_any_bad<1>(pos, sdf, edges, vid, counts, grad_verts, inc_ptr, inc, dpos,
+      dsdf) || n_meshes <= 0 || n_verts <= 0 || n_edges <= 0)
     return MD_ERR_BAD_ARG;
   if (n_meshes > 65535) return MD_ERR_UNSUPPORTED;             // gridDim.y
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_mt_bwd_kernel, dim3((unsigned)((n_verts + MTB_THREADS - 1) / MTB_THREADS), (unsigned)n_meshes),
-                     dim3(MTB_THREADS), 0, (hipStream_t)stream, pos, sdf, edges, vid, counts, grad_verts, inc_ptr, inc,
-                     (int)n_verts, (int)n_edges, dpos, dsdf);
+  hipLaunchKernelGGL(md_mt_bwd_kernel, dim3(md_blocks(n_verts, MTB_THREADS), (unsigned)n_meshes), dim3(MTB_THREADS), 0,
+                     (hipStream_t)stream, pos, sdf, edges, vid, counts, grad_verts, inc_ptr, inc, (int)n_verts,
+                     (int)n_edges, dpos, dsdf);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }
@@ -174,8 +174,8 @@ __global__ __launch_bounds__(MTB_THREADS) void md_sdf_reg_bwd_kernel(const float
 
 extern "C" int md_sdf_reg_loss(const float* sdf, const int32_t* edges, int32_t n_verts, int32_t n_edges, void* workspace,
                                float* loss, int32_t* count, void* stream) {
-  if (!sdf || !edges || !workspace || !loss || !count || n_verts <= 0 || n_edges <= 0) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)edges & 7) || ((uintptr_t)workspace & 7)) return MD_ERR_BAD_ARG;      // int2 rows, fp64 slabs
+  if (md_any_bad<1>(sdf, loss, count) || md_any_bad<8>(edges, workspace)) return MD_ERR_BAD_ARG;  // int2 rows, fp64 slabs
+  if (n_verts <= 0 || n_edges <= 0) return MD_ERR_BAD_ARG;
   double* sums = (double*)workspace;
   int64_t* cnts = (int64_t*)(sums + 2 * MD_SDF_REG_SLABS);
   MD_HIP_CLEAR_ERROR();
@@ -190,11 +190,8 @@ extern "C" int md_sdf_reg_loss(const float* sdf, const int32_t* edges, int32_t n
 extern "C" int md_sdf_reg_loss_bwd(const float* sdf, const int32_t* edges, const int32_t* inc_ptr, const int32_t* inc,
                                    const int32_t* count, const float* grad_out, int32_t n_verts, int32_t n_edges,
                                    float* dsdf, void* stream) {
-  if (!sdf || !edges || !inc_ptr || !inc || !count || !grad_out || !dsdf || n_verts <= 0 || n_edges <= 0)
+  if (md_any_bad<1>(sdf, edges, inc_ptr, inc, count, grad_out, dsdf) || n_verts <= 0 || n_edges <= 0)
     return MD_ERR_BAD_ARG;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_sdf_reg_bwd_kernel, dim3((unsigned)((n_verts + MTB_THREADS - 1) / MTB_THREADS)), dim3(MTB_THREADS), 0,
-                     (hipStream_t)stream, sdf, edges, inc_ptr, inc, count, grad_out, (int)n_verts, dsdf);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  MD_LAUNCH_1D(md_sdf_reg_bwd_kernel, n_verts, MTB_THREADS, sdf, edges, inc_ptr, inc, count, grad_out, (int)n_verts,
+               dsdf);
 }

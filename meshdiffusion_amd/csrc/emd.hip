@@ -35,7 +35,7 @@
 // starts nx * nx workgroups, of which those below the diagonal return at once.
 // Before it bids, every pair scans all p x p distances once, for eps0 (the largest cost) and for the 2^21 check: 4 M square roots
 // at p = 2048, the work of 2048 single-bidder scans against the 130 - 250 k bids such a pair takes -- one or two percent.
-#include "md_common.h"
+#include "md_args.h"
 
 static constexpr int EMD_THREADS = 512;
 static constexpr int EMD_WAVES = EMD_THREADS / 64;
@@ -330,13 +330,13 @@ __global__ __launch_bounds__(EMD_THREADS) void md_emd_matrix_kernel(const float*
 extern "C" int md_emd_matrix(const float* x, const float* y, int32_t nx, int32_t ny, int32_t p, float quantum, int32_t max_rounds,
                              int32_t triangular, float* out, int32_t* status, int64_t* total, int32_t* rounds, int32_t* perm,
                              void* stream) {
-  if (!x || !y || !out || !status || nx < 1 || ny < 1 || p < 1 || max_rounds < 1) return MD_ERR_BAD_ARG;
+  if (md_any_bad<1>(x, y, out, status) || nx < 1 || ny < 1 || p < 1 || max_rounds < 1) return MD_ERR_BAD_ARG;
   int e = 0;
   if (!(quantum > 0.f) || !(quantum < __builtin_inff()) || frexpf(quantum, &e) != 0.5f) return MD_ERR_BAD_ARG;      // NaN fails the first
   if (triangular && (x != y || nx != ny)) return MD_ERR_BAD_ARG;
   if (p > EMD_MAX_P) return MD_ERR_UNSUPPORTED;
   if (e - 1 < -126 || e - 1 > 126) return MD_ERR_UNSUPPORTED;              // 1 / quantum must be a normal fp32 number
-  if ((int64_t)nx * ny > 0x7fffffffLL) return MD_ERR_UNSUPPORTED;          // one workgroup per pair along gridDim.x
+  if (!md_fits_i32((int64_t)nx * ny)) return MD_ERR_UNSUPPORTED;           // one workgroup per pair along gridDim.x
   if (max_rounds > (1 << 30)) max_rounds = 1 << 30;                         // the round counter is an int that runs to max_rounds
   const size_t lds = ((size_t)EMD_LDS_PER_POINT * p + 15) & ~(size_t)15;
   MD_HIP_CLEAR_ERROR();

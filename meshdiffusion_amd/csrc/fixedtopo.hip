@@ -36,7 +36,7 @@
 // one thread per row, 256-thread workgroups, coalesced ptr reads, no LDS, no floating-point atomics, plain stores: two runs
 // agree bit for bit.  Every row computes a term per code, so the row loops stay here; the compensated step is md_kahan_add of
 // csrc/md_gather.h.
-#include "md_common.h"
+#include "md_args.h"
 #include "md_gather.h"
 
 #pragma clang fp contract(off)
@@ -186,59 +186,42 @@ __global__ __launch_bounds__(FT_THREADS) void md_ft_laplace_bwd_kernel(const flo
 }
 
 // ---- exports -------------------------------------------------------------------------------------------------------------------
-static inline unsigned ft_blocks(int64_t n) { return (unsigned)((n + FT_THREADS - 1) / FT_THREADS); }
-
 static int ft_plan_sizes(int64_t n_verts, int64_t n_mesh_verts) {
   if (n_verts <= 0 || n_mesh_verts <= 0) return MD_ERR_BAD_ARG;
-  if (n_verts > 0x7fffffffLL || 2 * n_mesh_verts > 0x7fffffffLL) return MD_ERR_UNSUPPORTED;      // int32 indices and codes
+  if (!md_fits_i32(n_verts, 2 * n_mesh_verts)) return MD_ERR_UNSUPPORTED;                         // int32 indices and codes
   return MD_OK;
 }
 
 static int ft_mesh_sizes(int64_t n_verts, int64_t n_faces) {
   if (n_verts <= 0 || n_faces <= 0) return MD_ERR_BAD_ARG;
-  if (n_verts > 0x7fffffffLL || n_faces >= (1LL << 24)) return MD_ERR_UNSUPPORTED;               // 3 F corner codes fit int32
+  if (!md_fits_i32(n_verts) || n_faces >= (1LL << 24)) return MD_ERR_UNSUPPORTED;                // 3 F corner codes fit int32
   return MD_OK;
 }
 
 extern "C" int md_fixedtopo_verts(const float* pos, const float* sdf, const int32_t* edge, int64_t n_verts, int64_t n_mesh_verts,
                                   float* verts, void* stream) {
-  if (!pos || !sdf || !edge || !verts) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)pos & 3) || ((uintptr_t)sdf & 3) || ((uintptr_t)edge & 7) || ((uintptr_t)verts & 3)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(pos, sdf, verts) || md_any_bad<8>(edge)) return MD_ERR_BAD_ARG;
   const int rc = ft_plan_sizes(n_verts, n_mesh_verts);
   if (rc != MD_OK) return rc;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_ft_verts_kernel, dim3(ft_blocks(n_mesh_verts)), dim3(FT_THREADS), 0, (hipStream_t)stream, pos, sdf, edge,
-                     (int)n_verts, (int)n_mesh_verts, verts);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  MD_LAUNCH_1D(md_ft_verts_kernel, n_mesh_verts, FT_THREADS, pos, sdf, edge, (int)n_verts, (int)n_mesh_verts, verts);
 }
 
 extern "C" int md_fixedtopo_verts_bwd(const float* grad_verts, const float* sdf, const int32_t* edge, const int32_t* ptr,
                                       const int32_t* inc, int64_t n_verts, int64_t n_mesh_verts, float* dpos, void* stream) {
-  if (!grad_verts || !sdf || !edge || !ptr || !inc || !dpos) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)grad_verts & 3) || ((uintptr_t)sdf & 3) || ((uintptr_t)edge & 7) || ((uintptr_t)ptr & 3) || ((uintptr_t)inc & 3) ||
-      ((uintptr_t)dpos & 3))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(grad_verts, sdf, ptr, inc, dpos) || md_any_bad<8>(edge)) return MD_ERR_BAD_ARG;
   const int rc = ft_plan_sizes(n_verts, n_mesh_verts);
   if (rc != MD_OK) return rc;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_ft_verts_bwd_kernel, dim3(ft_blocks(n_verts)), dim3(FT_THREADS), 0, (hipStream_t)stream, grad_verts, sdf,
-                     edge, ptr, inc, (int)n_verts, (int)n_mesh_verts, dpos);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  MD_LAUNCH_1D(md_ft_verts_bwd_kernel, n_verts, FT_THREADS, grad_verts, sdf, edge, ptr, inc, (int)n_verts, (int)n_mesh_verts, dpos);
 }
 
 extern "C" int md_laplace_umbrella(const float* x, const float* base, const int64_t* faces, const int32_t* ptr, const int32_t* order,
                                    int64_t n_verts, int64_t n_faces, float* term, void* workspace, float* loss, void* stream) {
-  if (!x || !faces || !ptr || !order || !term || !workspace || !loss) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)x & 3) || ((uintptr_t)base & 3) || ((uintptr_t)faces & 7) || ((uintptr_t)ptr & 3) || ((uintptr_t)order & 3) ||
-      ((uintptr_t)term & 3) || ((uintptr_t)workspace & 7) || ((uintptr_t)loss & 3))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(x, ptr, order, term, loss) || md_any_bad<8>(faces, workspace) || md_any_misaligned<4>(base)) return MD_ERR_BAD_ARG;
   const int rc = ft_mesh_sizes(n_verts, n_faces);
   if (rc != MD_OK) return rc;
   const hipStream_t st = (hipStream_t)stream;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_ft_laplace_term_kernel, dim3(ft_blocks(n_verts)), dim3(FT_THREADS), 0, st, x, base, faces, ptr, order,
+  hipLaunchKernelGGL(md_ft_laplace_term_kernel, dim3(md_blocks(n_verts, FT_THREADS)), dim3(FT_THREADS), 0, st, x, base, faces, ptr, order,
                      (int)n_verts, (int)n_faces, term);
   hipLaunchKernelGGL(md_ft_sq_partial_kernel, dim3(MD_LAPLACE_SLABS), dim3(FT_THREADS), 0, st, (const float*)term, 3 * n_verts,
                      (double*)workspace);
@@ -249,18 +232,15 @@ extern "C" int md_laplace_umbrella(const float* x, const float* base, const int6
 
 extern "C" int md_laplace_umbrella_bwd(const float* term, const int64_t* faces, const int32_t* ptr, const int32_t* order,
                                        const float* grad_out, int64_t n_verts, int64_t n_faces, float* q, float* dx, void* stream) {
-  if (!term || !faces || !ptr || !order || !grad_out || !q || !dx) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)term & 3) || ((uintptr_t)faces & 7) || ((uintptr_t)ptr & 3) || ((uintptr_t)order & 3) || ((uintptr_t)grad_out & 3) ||
-      ((uintptr_t)q & 3) || ((uintptr_t)dx & 3))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(term, ptr, order, grad_out, q, dx) || md_any_bad<8>(faces)) return MD_ERR_BAD_ARG;
   const int rc = ft_mesh_sizes(n_verts, n_faces);
   if (rc != MD_OK) return rc;
   const hipStream_t st = (hipStream_t)stream;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_ft_laplace_q_kernel, dim3(ft_blocks(n_verts)), dim3(FT_THREADS), 0, st, term, ptr, grad_out, (int)n_verts,
-                     (int)n_faces, q);
-  hipLaunchKernelGGL(md_ft_laplace_bwd_kernel, dim3(ft_blocks(n_verts)), dim3(FT_THREADS), 0, st, (const float*)q, faces, ptr, order,
-                     (int)n_verts, (int)n_faces, dx);
+  hipLaunchKernelGGL(md_ft_laplace_q_kernel, dim3(md_blocks(n_verts, FT_THREADS)), dim3(FT_THREADS), 0, st, term, ptr, grad_out,
+                     (int)n_verts, (int)n_faces, q);
+  hipLaunchKernelGGL(md_ft_laplace_bwd_kernel, dim3(md_blocks(n_verts, FT_THREADS)), dim3(FT_THREADS), 0, st, (const float*)q, faces, ptr,
+                     order, (int)n_verts, (int)n_faces, dx);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }

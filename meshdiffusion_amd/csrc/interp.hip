@@ -35,7 +35,7 @@
 // one thread per covered entry (or face) writes its per-corner gradients, one thread per destination row then sums them,
 // compensated (md_kahan_add), in that order: md_csr_gather_kernel<W, true, .>.  No floating-point atomics anywhere: two runs
 // agree bit for bit.  md_interpolate: one thread per pixel, one 16-byte rast load, C unrolled at compile time.
-#include "md_common.h"
+#include "md_args.h"
 #include "md_gather.h"
 #include "md_raster_snap.h"
 
@@ -264,13 +264,12 @@ static int ip_attr_args(int32_t batch, int32_t attr_batch, int32_t n_rows, int32
 
 extern "C" int md_interpolate(const float* rast, const float* attr, const int64_t* tri, int32_t batch, int32_t attr_batch,
                               int32_t n_rows, int32_t C, int32_t n_faces, int32_t H, int32_t W, float* out, void* stream) {
-  if (!rast || !attr || !tri || !out) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)rast & 15) || ((uintptr_t)tri & 7) || ((uintptr_t)attr & 3) || ((uintptr_t)out & 3)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<16>(rast) || md_any_bad<8>(tri) || md_any_bad<4>(attr, out)) return MD_ERR_BAD_ARG;
   const int rc = ip_attr_args(batch, attr_batch, n_rows, C, n_faces, H, W);
   if (rc != MD_OK) return rc;
   const int64_t bstride = attr_batch == 1 ? 0 : (int64_t)n_rows * C;
   MD_HIP_CLEAR_ERROR();
-  IP_DISPATCH_C(C, hipLaunchKernelGGL(md_interpolate_kernel<K>, dim3((unsigned)((H * W + 255) / 256), (unsigned)batch), dim3(256), 0,
+  IP_DISPATCH_C(C, hipLaunchKernelGGL(md_interpolate_kernel<K>, dim3(md_blocks(H * W, 256), (unsigned)batch), dim3(256), 0,
                                       (hipStream_t)stream, rast, attr, tri, bstride, (int)n_faces, (int)(H * W), out));
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
@@ -283,13 +282,11 @@ extern "C" int md_interpolate_bwd(const int32_t* cov, int32_t n_cov, const float
   if (n_cov < 0 || (!dattr && !drast)) return MD_ERR_BAD_ARG;
   if (dattr && !ptr) return MD_ERR_BAD_ARG;
   if (n_cov > 0 && (!cov || !rast || !grad_out || !attr || !tri || (dattr && (!order || !corner_grad)))) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)rast & 15) || ((uintptr_t)drast & 15) || ((uintptr_t)tri & 7) || ((uintptr_t)cov & 3) || ((uintptr_t)ptr & 3) ||
-      ((uintptr_t)order & 3))
-    return MD_ERR_BAD_ARG;
+  if (md_any_misaligned<16>(rast, drast) || md_any_misaligned<8>(tri) || md_any_misaligned<4>(cov, ptr, order)) return MD_ERR_BAD_ARG;
   const int rc = ip_attr_args(batch, attr_batch, n_rows, C, n_faces, H, W);
   if (rc != MD_OK) return rc;
   const int64_t rows = (int64_t)attr_batch * n_rows, n_pix = (int64_t)batch * H * W;
-  if ((int64_t)n_cov * 3 > 0x7fffffffLL || rows >= 0x7fffffffLL) return MD_ERR_UNSUPPORTED;
+  if (!md_fits_i32((int64_t)n_cov * 3, rows + 1)) return MD_ERR_UNSUPPORTED;
   const int64_t bstride = attr_batch == 1 ? 0 : (int64_t)n_rows * C;
   if (drast) {
     hipError_t e = hipMemsetAsync(drast, 0, (size_t)n_pix * 4 * sizeof(float), (hipStream_t)stream);
@@ -297,7 +294,7 @@ extern "C" int md_interpolate_bwd(const int32_t* cov, int32_t n_cov, const float
   }
   MD_HIP_CLEAR_ERROR();
   if (n_cov > 0)
-    IP_DISPATCH_C(C, hipLaunchKernelGGL(md_interpolate_bwd_pix_kernel<K>, dim3((unsigned)((n_cov + 255) / 256)), dim3(256), 0,
+    IP_DISPATCH_C(C, hipLaunchKernelGGL(md_interpolate_bwd_pix_kernel<K>, dim3(md_blocks(n_cov, 256)), dim3(256), 0,
                                         (hipStream_t)stream, cov, (int)n_cov, rast, grad_out, attr, tri, bstride, (int)n_faces,
                                         (int)(H * W), n_pix, dattr ? corner_grad : (float*)nullptr, drast));
   if (dattr)
@@ -309,16 +306,16 @@ extern "C" int md_interpolate_bwd(const int32_t* cov, int32_t n_cov, const float
 extern "C" int md_raster_bary_bwd(const int32_t* cov, int32_t n_cov, const float* rast, const float* drast, const float* pos_clip,
                                   const int64_t* faces, const int32_t* ptr, const int32_t* order, int32_t batch, int32_t n_verts,
                                   int32_t n_faces, int32_t H, int32_t W, float* corner_grad, float* dpos_clip, void* stream) {
-  if (!dpos_clip || !ptr || batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0 || n_cov < 0) return MD_ERR_BAD_ARG;
-  if (n_cov > 0 && (!cov || !rast || !drast || !pos_clip || !faces || !order || !corner_grad)) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)rast & 15) || ((uintptr_t)drast & 15) || ((uintptr_t)pos_clip & 15) || ((uintptr_t)dpos_clip & 15) ||
-      ((uintptr_t)faces & 7) || ((uintptr_t)cov & 3) || ((uintptr_t)ptr & 3) || ((uintptr_t)order & 3))
+  if (md_any_bad<16>(dpos_clip) || md_any_bad<4>(ptr)) return MD_ERR_BAD_ARG;
+  if (batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0 || n_cov < 0) return MD_ERR_BAD_ARG;
+  if (n_cov > 0 && md_any_bad<1>(cov, rast, drast, pos_clip, faces, order, corner_grad)) return MD_ERR_BAD_ARG;
+  if (md_any_misaligned<16>(rast, drast, pos_clip) || md_any_misaligned<8>(faces) || md_any_misaligned<4>(cov, order))
     return MD_ERR_BAD_ARG;
   const int64_t BV = (int64_t)batch * n_verts;
-  if (!rs_limits_ok(batch, n_faces, H, W) || (int64_t)n_cov * 3 > 0x7fffffffLL || BV >= 0x7fffffffLL) return MD_ERR_UNSUPPORTED;
+  if (!rs_limits_ok(batch, n_faces, H, W) || !md_fits_i32((int64_t)n_cov * 3, BV + 1)) return MD_ERR_UNSUPPORTED;
   MD_HIP_CLEAR_ERROR();
   if (n_cov > 0)
-    hipLaunchKernelGGL(md_raster_bary_bwd_pix_kernel, dim3((unsigned)((n_cov + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cov,
+    hipLaunchKernelGGL(md_raster_bary_bwd_pix_kernel, dim3(md_blocks(n_cov, 256)), dim3(256), 0, (hipStream_t)stream, cov,
                        (int)n_cov, rast, drast, pos_clip, faces, (int)n_verts, (int)n_faces, (int)H, (int)W,
                        (int64_t)batch * H * W, corner_grad);
   md_csr_gather<3, true, true>(corner_grad, ptr, order, BV, (int64_t)n_cov * 3, dpos_clip, (hipStream_t)stream);
@@ -328,13 +325,13 @@ extern "C" int md_raster_bary_bwd(const int32_t* cov, int32_t n_cov, const float
 
 extern "C" int md_vertex_normals_det(const float* verts, const int64_t* faces, const int32_t* ptr, const int32_t* order,
                                      int32_t n_verts, int32_t n_faces, float* v_nrm, float* f_nrm, float* v_len, void* stream) {
-  if (!verts || !faces || !ptr || !order || !v_nrm || !f_nrm || !v_len || n_verts <= 0 || n_faces <= 0) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)faces & 7) || ((uintptr_t)ptr & 3) || ((uintptr_t)order & 3)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<1>(verts, v_nrm, f_nrm, v_len) || md_any_bad<8>(faces) || md_any_bad<4>(ptr, order)) return MD_ERR_BAD_ARG;
+  if (n_verts <= 0 || n_faces <= 0) return MD_ERR_BAD_ARG;
   if (n_faces >= RS_MAX_FACES) return MD_ERR_UNSUPPORTED;                 // 3 F corner codes fit int32
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_face_normals_det_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, verts,
+  hipLaunchKernelGGL(md_face_normals_det_kernel, dim3(md_blocks(n_faces, 256)), dim3(256), 0, (hipStream_t)stream, verts,
                      faces, (int)n_faces, f_nrm);
-  hipLaunchKernelGGL(md_vertex_normals_gather_kernel, dim3((unsigned)((n_verts + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(md_vertex_normals_gather_kernel, dim3(md_blocks(n_verts, 256)), dim3(256), 0, (hipStream_t)stream,
                      f_nrm, ptr, order, (int)n_verts, (int64_t)n_faces * 3, v_nrm, v_len);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
@@ -343,13 +340,12 @@ extern "C" int md_vertex_normals_det(const float* verts, const int64_t* faces, c
 extern "C" int md_vertex_normals_bwd(const float* verts, const int64_t* faces, const int32_t* ptr, const int32_t* order,
                                      const float* v_nrm, const float* v_len, const float* grad_v_nrm, int32_t n_verts,
                                      int32_t n_faces, float* face_grad, float* dverts, void* stream) {
-  if (!verts || !faces || !ptr || !order || !v_nrm || !v_len || !grad_v_nrm || !face_grad || !dverts || n_verts <= 0 ||
-      n_faces <= 0)
+  if (md_any_bad<1>(verts, v_nrm, v_len, grad_v_nrm, face_grad, dverts) || md_any_bad<8>(faces) || md_any_bad<4>(ptr, order))
     return MD_ERR_BAD_ARG;
-  if (((uintptr_t)faces & 7) || ((uintptr_t)ptr & 3) || ((uintptr_t)order & 3)) return MD_ERR_BAD_ARG;
+  if (n_verts <= 0 || n_faces <= 0) return MD_ERR_BAD_ARG;
   if (n_faces >= RS_MAX_FACES) return MD_ERR_UNSUPPORTED;                 // 3 F corner codes fit int32
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_vertex_normals_bwd_face_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(md_vertex_normals_bwd_face_kernel, dim3(md_blocks(n_faces, 256)), dim3(256), 0, (hipStream_t)stream,
                      verts, faces, v_nrm, v_len, grad_v_nrm, (int)n_faces, face_grad);
   md_csr_gather<3, true, false>(face_grad, ptr, order, n_verts, (int64_t)n_faces * 3, dverts, (hipStream_t)stream);
   MD_HIP_CHECK_LAUNCH();

@@ -50,13 +50,12 @@
 //
 // Kernels.  Latency- and HBM-bound gathers over short rows (valence ~6 on a marching-tets mesh) and one pass over the pixels: one
 // thread per row, face or pixel, 256-thread workgroups, no LDS, plain stores.
-#include "md_common.h"
+#include "md_args.h"
 #include "md_gather.h"
 
 #pragma clang fp contract(off)
 
 static constexpr int MP_THREADS = 256;
-static inline unsigned mp_blocks(int64_t n) { return (unsigned)((n + MP_THREADS - 1) / MP_THREADS); }
 
 // ---- smoothing -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MP_THREADS) void md_mp_smooth_kernel(const float* __restrict__ src, const int32_t* __restrict__ ptr,
@@ -209,12 +208,10 @@ __global__ __launch_bounds__(MP_THREADS) void md_mp_shade_kernel(const float* __
 // ---- exports -------------------------------------------------------------------------------------------------------------------
 extern "C" int md_mesh_smooth(const float* verts, const int32_t* ptr, const int32_t* adj, int64_t n_verts, int64_t n_codes,
                               int32_t steps, float lam, float mu, float* out, float* scratch, void* stream) {
-  if (!verts || !ptr || !adj || !out || (steps >= 2 && !scratch)) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)verts & 3) || ((uintptr_t)ptr & 3) || ((uintptr_t)adj & 3) || ((uintptr_t)out & 3) || ((uintptr_t)scratch & 3))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(verts, ptr, adj, out) || md_any_misaligned<4>(scratch) || (steps >= 2 && !scratch)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_codes <= 0 || steps < 0) return MD_ERR_BAD_ARG;
   if (!(fabsf(lam) <= 3.402823466e+38f) || !(mu != mu || fabsf(mu) <= 3.402823466e+38f)) return MD_ERR_BAD_ARG;
-  if (2 * n_verts > 0x7fffffffLL || n_codes > 0x7fffffffLL) return MD_ERR_UNSUPPORTED;          // the codes 2 * neighbour + 1 fit int32
+  if (!md_fits_i32(2 * n_verts, n_codes)) return MD_ERR_UNSUPPORTED;          // the codes 2 * neighbour + 1 fit int32
   if (out == verts || scratch == verts || (steps >= 2 && out == scratch)) return MD_ERR_BAD_ARG;  // the input is never written
   const hipStream_t st = (hipStream_t)stream;
   MD_HIP_CLEAR_ERROR();
@@ -226,7 +223,7 @@ extern "C" int md_mesh_smooth(const float* verts, const int32_t* ptr, const int3
   for (int i = 0; i < steps; ++i) {
     float* dst = ((steps - 1 - i) & 1) ? scratch : out;                                          // the last step lands in `out`
     const float w = ((i & 1) == 0 || mu != mu) ? lam : mu;
-    hipLaunchKernelGGL(md_mp_smooth_kernel, dim3(mp_blocks(n_verts)), dim3(MP_THREADS), 0, st, src, ptr, adj, (int)n_verts,
+    hipLaunchKernelGGL(md_mp_smooth_kernel, dim3(md_blocks(n_verts, MP_THREADS)), dim3(MP_THREADS), 0, st, src, ptr, adj, (int)n_verts,
                        (int)n_codes, w, dst);
     src = dst;
   }
@@ -237,22 +234,21 @@ extern "C" int md_mesh_smooth(const float* verts, const int32_t* ptr, const int3
 extern "C" int md_mesh_components(const int64_t* faces, int64_t n_verts, int64_t n_faces, int32_t* label, int32_t* comp_faces,
                                   void* workspace, int32_t* rounds, void* stream) {
   if (rounds) *rounds = 0;
-  if (!faces || !label || !comp_faces || !workspace) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)faces & 7) || ((uintptr_t)label & 3) || ((uintptr_t)comp_faces & 3) || ((uintptr_t)workspace & 3)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<8>(faces) || md_any_bad<4>(label, comp_faces, workspace)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_faces <= 0) return MD_ERR_BAD_ARG;
-  if (n_verts > 0x7fffffffLL || 3 * n_faces > 0x7fffffffLL) return MD_ERR_UNSUPPORTED;
+  if (!md_fits_i32(n_verts, 3 * n_faces)) return MD_ERR_UNSUPPORTED;
   const hipStream_t st = (hipStream_t)stream;
   const int V = (int)n_verts, F = (int)n_faces;
   int32_t* flag = (int32_t*)workspace;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_mp_init_kernel, dim3(mp_blocks(V)), dim3(MP_THREADS), 0, st, V, label, comp_faces);
+  hipLaunchKernelGGL(md_mp_init_kernel, dim3(md_blocks(V, MP_THREADS)), dim3(MP_THREADS), 0, st, V, label, comp_faces);
   MD_HIP_CHECK_LAUNCH();
   bool settled = false;
   for (int round = 1; round <= MD_MESHPOST_MAX_ROUNDS && !settled; ++round) {
     hipError_t e = hipMemsetAsync(flag, 0, sizeof(int32_t), st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(md_mp_hook_kernel, dim3(mp_blocks(F)), dim3(MP_THREADS), 0, st, faces, V, F, label, flag);
-    hipLaunchKernelGGL(md_mp_compress_kernel, dim3(mp_blocks(V)), dim3(MP_THREADS), 0, st, V, label);
+    hipLaunchKernelGGL(md_mp_hook_kernel, dim3(md_blocks(F, MP_THREADS)), dim3(MP_THREADS), 0, st, faces, V, F, label, flag);
+    hipLaunchKernelGGL(md_mp_compress_kernel, dim3(md_blocks(V, MP_THREADS)), dim3(MP_THREADS), 0, st, V, label);
     MD_HIP_CHECK_LAUNCH();
     int32_t host_flag = 1;
     e = hipMemcpyAsync(&host_flag, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st);            // the one 4-byte copy of a round
@@ -262,7 +258,8 @@ extern "C" int md_mesh_components(const int64_t* faces, int64_t n_verts, int64_t
     settled = host_flag == 0;
   }
   if (!settled) return MD_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(md_mp_count_kernel, dim3(mp_blocks(F)), dim3(MP_THREADS), 0, st, faces, (const int32_t*)label, V, F, comp_faces);
+  hipLaunchKernelGGL(md_mp_count_kernel, dim3(md_blocks(F, MP_THREADS)), dim3(MP_THREADS), 0, st, faces, (const int32_t*)label, V, F,
+                     comp_faces);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }
@@ -270,15 +267,12 @@ extern "C" int md_mesh_components(const int64_t* faces, int64_t n_verts, int64_t
 extern "C" int md_shade_diffuse(const float* rast, const float* verts, const int64_t* faces, const float* campos, const float* sh,
                                 const float* kd, int32_t batch, int64_t n_verts, int64_t n_faces, int32_t H, int32_t W, float* out,
                                 void* stream) {
-  if (!rast || !verts || !faces || !campos || !sh || !kd || !out) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)rast & 15) || ((uintptr_t)out & 15) || ((uintptr_t)faces & 7) || ((uintptr_t)verts & 3) || ((uintptr_t)campos & 3) ||
-      ((uintptr_t)sh & 3) || ((uintptr_t)kd & 3))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<16>(rast, out) || md_any_bad<8>(faces) || md_any_bad<4>(verts, campos, sh, kd)) return MD_ERR_BAD_ARG;
   if (batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0) return MD_ERR_BAD_ARG;
-  if (batch > 64 || H > 2048 || W > 2048 || n_verts > 0x7fffffffLL || n_faces >= (1LL << 24)) return MD_ERR_UNSUPPORTED;
+  if (batch > 64 || H > 2048 || W > 2048 || !md_fits_i32(n_verts) || n_faces >= (1LL << 24)) return MD_ERR_UNSUPPORTED;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_mp_shade_kernel, dim3(mp_blocks((int64_t)H * W), (unsigned)batch), dim3(MP_THREADS), 0, (hipStream_t)stream,
-                     rast, verts, faces, campos, sh, kd, (int)n_verts, (int)n_faces, (int)(H * W), out);
+  hipLaunchKernelGGL(md_mp_shade_kernel, dim3(md_blocks((int64_t)H * W, MP_THREADS), (unsigned)batch), dim3(MP_THREADS), 0,
+                     (hipStream_t)stream, rast, verts, faces, campos, sh, kd, (int)n_verts, (int)n_faces, (int)(H * W), out);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }

@@ -17,7 +17,7 @@
 // on either side, or inf - inf) wins over every number and the first one keeps the index.  The fast loop's `d < best`
 // would drop a NaN, so a tile takes the CAREFUL loop whenever it, or a query of the workgroup, holds a non-finite
 // coordinate -- and whenever skip_same_index applies to it (the tile overlaps the workgroup's own index range).
-#include "md_common.h"
+#include "md_args.h"
 
 typedef float nn_f2 __attribute__((ext_vector_type(2)));
 
@@ -175,17 +175,16 @@ extern "C" int64_t md_nn_sided_workspace_bytes(int32_t batch, int32_t n, int32_t
 
 extern "C" int md_nn_sided(const float* p, const float* q, int32_t batch, int32_t n, int32_t m, int32_t skip_same_index,
                            float* dist, int64_t* idx, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!p || !q || !dist || !idx || !workspace || batch <= 0 || n <= 0 || m <= 0) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)workspace & 7) || ((uintptr_t)idx & 7)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<1>(p, q, dist) || md_any_bad<8>(idx, workspace) || batch <= 0 || n <= 0 || m <= 0) return MD_ERR_BAD_ARG;
   if (batch > 65535) return MD_ERR_UNSUPPORTED;              // gridDim.z / gridDim.y
   int64_t nc, tpc;
   nn_chunks(batch, n, m, &nc, &tpc);
   if (workspace_bytes < (int64_t)batch * nc * n * 8) return MD_ERR_BAD_ARG;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_nn_partial_kernel, dim3((unsigned)((n + NN_QUERIES - 1) / NN_QUERIES), (unsigned)nc, (unsigned)batch),
+  hipLaunchKernelGGL(md_nn_partial_kernel, dim3(md_blocks(n, NN_QUERIES), (unsigned)nc, (unsigned)batch),
                      dim3(NN_THREADS), 0, (hipStream_t)stream, p, q, (int)n, (int)m, (int)tpc, (int)(skip_same_index != 0),
                      (uint64_t*)workspace);
-  hipLaunchKernelGGL(md_nn_final_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(md_nn_final_kernel, dim3(md_blocks(n, 256), (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
                      (const uint64_t*)workspace, (int)n, (int)nc, dist, idx);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
@@ -233,16 +232,15 @@ extern "C" int md_chamfer_bwd(const float* p, const float* q, const int64_t* idx
                               const int32_t* ptr_p, const int32_t* order_p, const int32_t* ptr_q, const int32_t* order_q,
                               int32_t batch, int32_t n, int32_t m, float w1, float w2, const float* grad_out, float* dp,
                               float* dq, void* stream) {
-  if (!p || !q || !idx_pq || !idx_qp || !ptr_p || !order_p || !grad_out || !dp || batch <= 0 || n <= 0 || m <= 0)
+  if (md_any_bad<1>(p, q, ptr_p, order_p, grad_out, dp) || md_any_bad<8>(idx_pq, idx_qp) || batch <= 0 || n <= 0 || m <= 0)
     return MD_ERR_BAD_ARG;
   if (dq && (!ptr_q || !order_q)) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)idx_pq & 7) || ((uintptr_t)idx_qp & 7)) return MD_ERR_BAD_ARG;
   if (batch > 65535) return MD_ERR_UNSUPPORTED;              // gridDim.y
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_chamfer_bwd_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0,
+  hipLaunchKernelGGL(md_chamfer_bwd_kernel, dim3(md_blocks(n, 256), (unsigned)batch), dim3(256), 0,
                      (hipStream_t)stream, p, q, idx_pq, ptr_p, order_p, (int)n, (int)m, w1, w2, grad_out, dp);
   if (dq)
-    hipLaunchKernelGGL(md_chamfer_bwd_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)batch), dim3(256), 0,
+    hipLaunchKernelGGL(md_chamfer_bwd_kernel, dim3(md_blocks(m, 256), (unsigned)batch), dim3(256), 0,
                        (hipStream_t)stream, q, p, idx_qp, ptr_q, order_q, (int)m, (int)n, w2, w1, grad_out, dq);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
@@ -328,10 +326,10 @@ __global__ __launch_bounds__(256) void md_sample_points_bwd_kernel(const float* 
 
 extern "C" int md_face_areas(const float* verts, const int64_t* faces, int32_t batch, int32_t n_verts, int32_t n_faces,
                              float* areas, void* stream) {
-  if (!verts || !faces || !areas || batch <= 0 || n_verts <= 0 || n_faces <= 0 || ((uintptr_t)faces & 7)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<1>(verts, areas) || md_any_bad<8>(faces) || batch <= 0 || n_verts <= 0 || n_faces <= 0) return MD_ERR_BAD_ARG;
   if (batch > 65535) return MD_ERR_UNSUPPORTED;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_face_areas_kernel, dim3((unsigned)((n_faces + 255) / 256), (unsigned)batch), dim3(256), 0,
+  hipLaunchKernelGGL(md_face_areas_kernel, dim3(md_blocks(n_faces, 256), (unsigned)batch), dim3(256), 0,
                      (hipStream_t)stream, verts, faces, (int)n_verts, (int)n_faces, areas);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
@@ -341,14 +339,13 @@ extern "C" int md_sample_points(const float* verts, const int64_t* faces, const 
                                 const float* r_u, const float* r_v, const int64_t* face_choices_in, int32_t batch,
                                 int32_t n_verts, int32_t n_faces, int32_t n_samples, float* points, int64_t* face_choices,
                                 float* weights, void* stream) {
-  if (!verts || !faces || !r_u || !r_v || !points || !face_choices || batch <= 0 || n_verts <= 0 || n_faces <= 0 ||
-      n_samples <= 0)
+  if (md_any_bad<1>(verts, r_u, r_v, points) || md_any_bad<8>(faces, face_choices) || md_any_misaligned<8>(face_choices_in))
     return MD_ERR_BAD_ARG;
+  if (batch <= 0 || n_verts <= 0 || n_faces <= 0 || n_samples <= 0) return MD_ERR_BAD_ARG;
   if (!face_choices_in && (!cdf || !r_face)) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)faces & 7) || ((uintptr_t)face_choices & 7) || ((uintptr_t)face_choices_in & 7)) return MD_ERR_BAD_ARG;
   if (batch > 65535) return MD_ERR_UNSUPPORTED;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_sample_points_kernel, dim3((unsigned)((n_samples + 255) / 256), (unsigned)batch), dim3(256), 0,
+  hipLaunchKernelGGL(md_sample_points_kernel, dim3(md_blocks(n_samples, 256), (unsigned)batch), dim3(256), 0,
                      (hipStream_t)stream, verts, faces, cdf, r_face, r_u, r_v, face_choices_in, (int)n_verts, (int)n_faces,
                      (int)n_samples, points, face_choices, weights);
   MD_HIP_CHECK_LAUNCH();
@@ -357,11 +354,11 @@ extern "C" int md_sample_points(const float* verts, const int64_t* faces, const 
 
 extern "C" int md_sample_points_bwd(const float* grad_points, const float* weights, const int32_t* ptr, const int32_t* order,
                                     int32_t batch, int32_t n_verts, int32_t n_samples, float* dverts, void* stream) {
-  if (!grad_points || !weights || !ptr || !order || !dverts || batch <= 0 || n_verts <= 0 || n_samples <= 0)
+  if (md_any_bad<1>(grad_points, weights, ptr, order, dverts) || batch <= 0 || n_verts <= 0 || n_samples <= 0)
     return MD_ERR_BAD_ARG;
-  if (batch > 65535 || (int64_t)n_samples * 3 > 0x7fffffffLL) return MD_ERR_UNSUPPORTED;    // gridDim.y; int32 corner codes
+  if (batch > 65535 || !md_fits_i32((int64_t)n_samples * 3)) return MD_ERR_UNSUPPORTED;    // gridDim.y; int32 corner codes
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_sample_points_bwd_kernel, dim3((unsigned)((n_verts + 255) / 256), (unsigned)batch), dim3(256), 0,
+  hipLaunchKernelGGL(md_sample_points_bwd_kernel, dim3(md_blocks(n_verts, 256), (unsigned)batch), dim3(256), 0,
                      (hipStream_t)stream, grad_points, weights, ptr, order, (int)n_verts, (int)n_samples, dverts);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;

@@ -39,7 +39,7 @@
 // Backward: one thread per covered (pixel, layer) writes its three per-corner position gradients; one thread per vertex then
 // GATHERS them, a plain fp32 sum, over a CSR of (covered entry, corner) codes sorted stably by vertex id (csrc/md_gather.h,
 // md_csr_gather_kernel<3, false, false>): no floating-point atomics, two runs agree bit for bit.
-#include "md_common.h"
+#include "md_args.h"
 #include "md_gather.h"
 #include "md_raster_snap.h"
 
@@ -248,11 +248,11 @@ static bool rs_shape_ok(int32_t batch, int32_t n_verts, int32_t n_faces, int32_t
 
 extern "C" int md_raster_bin_count(const float* pos_clip, const int64_t* faces, int32_t batch, int32_t n_verts, int32_t n_faces,
                                    int32_t H, int32_t W, int32_t* counts, void* stream) {
-  if (!pos_clip || !faces || !counts || batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)pos_clip & 15) || ((uintptr_t)faces & 7)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<16>(pos_clip) || md_any_bad<8>(faces) || md_any_bad<1>(counts)) return MD_ERR_BAD_ARG;
+  if (batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0) return MD_ERR_BAD_ARG;
   if (!rs_shape_ok(batch, n_verts, n_faces, H, W)) return MD_ERR_UNSUPPORTED;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_raster_bin_count_kernel, dim3((unsigned)((n_faces + 255) / 256), (unsigned)batch), dim3(256), 0,
+  hipLaunchKernelGGL(md_raster_bin_count_kernel, dim3(md_blocks(n_faces, 256), (unsigned)batch), dim3(256), 0,
                      (hipStream_t)stream, pos_clip, faces, (int)n_verts, (int)n_faces, (int)H, (int)W, counts);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
@@ -261,13 +261,11 @@ extern "C" int md_raster_bin_count(const float* pos_clip, const int64_t* faces, 
 extern "C" int md_raster_bin_emit(const float* pos_clip, const int64_t* faces, const int64_t* offsets, int32_t batch,
                                   int32_t n_verts, int32_t n_faces, int32_t H, int32_t W, int64_t total, int32_t* pair_tile,
                                   int32_t* pair_face, void* stream) {
-  if (!pos_clip || !faces || !offsets || !pair_tile || !pair_face || batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 ||
-      W <= 0 || total <= 0)
-    return MD_ERR_BAD_ARG;
-  if (((uintptr_t)pos_clip & 15) || ((uintptr_t)faces & 7) || ((uintptr_t)offsets & 7)) return MD_ERR_BAD_ARG;
-  if (!rs_shape_ok(batch, n_verts, n_faces, H, W) || total > 0x7fffffffLL) return MD_ERR_UNSUPPORTED;
+  if (md_any_bad<16>(pos_clip) || md_any_bad<8>(faces, offsets) || md_any_bad<1>(pair_tile, pair_face)) return MD_ERR_BAD_ARG;
+  if (batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0 || total <= 0) return MD_ERR_BAD_ARG;
+  if (!rs_shape_ok(batch, n_verts, n_faces, H, W) || !md_fits_i32(total)) return MD_ERR_UNSUPPORTED;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_raster_bin_emit_kernel, dim3((unsigned)((n_faces + 255) / 256), (unsigned)batch), dim3(256), 0,
+  hipLaunchKernelGGL(md_raster_bin_emit_kernel, dim3(md_blocks(n_faces, 256), (unsigned)batch), dim3(256), 0,
                      (hipStream_t)stream, pos_clip, faces, offsets, (int)n_verts, (int)n_faces, (int)H, (int)W, total, pair_tile,
                      pair_face);
   MD_HIP_CHECK_LAUNCH();
@@ -277,11 +275,8 @@ extern "C" int md_raster_bin_emit(const float* pos_clip, const int64_t* faces, c
 extern "C" int md_raster_tiles(const float* pos_clip, const int64_t* faces, const int32_t* tile_ptr, const int32_t* tile_faces,
                                int32_t batch, int32_t n_verts, int32_t n_faces, int32_t H, int32_t W, float* rast1, float* rast2,
                                void* stream) {
-  if (!pos_clip || !faces || !tile_ptr || !tile_faces || !rast1 || !rast2 || batch <= 0 || n_verts <= 0 || n_faces <= 0 ||
-      H <= 0 || W <= 0)
-    return MD_ERR_BAD_ARG;
-  if (((uintptr_t)pos_clip & 15) || ((uintptr_t)faces & 7) || ((uintptr_t)rast1 & 15) || ((uintptr_t)rast2 & 15))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<16>(pos_clip, rast1, rast2) || md_any_bad<8>(faces) || md_any_bad<1>(tile_ptr, tile_faces)) return MD_ERR_BAD_ARG;
+  if (batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0) return MD_ERR_BAD_ARG;
   if (!rs_shape_ok(batch, n_verts, n_faces, H, W)) return MD_ERR_UNSUPPORTED;
   const int ntiles = ((W + RS_TILE - 1) / RS_TILE) * ((H + RS_TILE - 1) / RS_TILE);
   MD_HIP_CLEAR_ERROR();
@@ -327,13 +322,12 @@ __global__ __launch_bounds__(256) void md_raster_depth_kernel(const float* __res
 extern "C" int md_raster_depth(const float* rast1, const float* rast2, const float* verts, const int64_t* faces,
                                const float* campos, int32_t batch, int32_t n_verts, int32_t n_faces, int32_t H, int32_t W,
                                float* depth1, float* depth2, float* mask1, float* mask2, void* stream) {
-  if (!rast1 || !rast2 || !verts || !faces || !campos || !depth1 || !depth2 || !mask1 || !mask2 || batch <= 0 || n_verts <= 0 ||
-      n_faces <= 0 || H <= 0 || W <= 0)
+  if (md_any_bad<16>(rast1, rast2) || md_any_bad<8>(faces) || md_any_bad<1>(verts, campos, depth1, depth2, mask1, mask2))
     return MD_ERR_BAD_ARG;
-  if (((uintptr_t)rast1 & 15) || ((uintptr_t)rast2 & 15) || ((uintptr_t)faces & 7)) return MD_ERR_BAD_ARG;
+  if (batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0) return MD_ERR_BAD_ARG;
   if (!rs_shape_ok(batch, n_verts, n_faces, H, W)) return MD_ERR_UNSUPPORTED;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_raster_depth_kernel, dim3((unsigned)((H * W + 255) / 256), (unsigned)batch, 2u), dim3(256), 0,
+  hipLaunchKernelGGL(md_raster_depth_kernel, dim3(md_blocks(H * W, 256), (unsigned)batch, 2u), dim3(256), 0,
                      (hipStream_t)stream, rast1, rast2, verts, faces, campos, (int)(H * W), depth1, depth2, mask1, mask2);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
@@ -416,16 +410,14 @@ extern "C" int md_raster_depth_bwd(const int32_t* cov, int32_t n_cov, const floa
                                    const float* mvp, const float* campos, const int32_t* ptr, const int32_t* order, int32_t batch,
                                    int32_t n_verts, int32_t n_faces, int32_t H, int32_t W, float* corner_grad, float* dverts,
                                    void* stream) {
-  if (!dverts || batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0 || n_cov < 0 || !ptr) return MD_ERR_BAD_ARG;
-  if (n_cov > 0 && (!cov || !rast1 || !rast2 || !gd1 || !gd2 || !pos_clip || !verts || !faces || !mvp || !campos || !order ||
-                    !corner_grad))
+  if (md_any_bad<1>(dverts, ptr) || batch <= 0 || n_verts <= 0 || n_faces <= 0 || H <= 0 || W <= 0 || n_cov < 0) return MD_ERR_BAD_ARG;
+  if (n_cov > 0 && md_any_bad<1>(cov, rast1, rast2, gd1, gd2, pos_clip, verts, faces, mvp, campos, order, corner_grad))
     return MD_ERR_BAD_ARG;
-  if (((uintptr_t)pos_clip & 15) || ((uintptr_t)faces & 7) || ((uintptr_t)rast1 & 15) || ((uintptr_t)rast2 & 15))
-    return MD_ERR_BAD_ARG;
-  if (!rs_shape_ok(batch, n_verts, n_faces, H, W) || (int64_t)n_cov * 3 > 0x7fffffffLL) return MD_ERR_UNSUPPORTED;
+  if (md_any_misaligned<16>(pos_clip, rast1, rast2) || md_any_misaligned<8>(faces)) return MD_ERR_BAD_ARG;
+  if (!rs_shape_ok(batch, n_verts, n_faces, H, W) || !md_fits_i32((int64_t)n_cov * 3)) return MD_ERR_UNSUPPORTED;
   MD_HIP_CLEAR_ERROR();
   if (n_cov > 0)
-    hipLaunchKernelGGL(md_raster_depth_bwd_pix_kernel, dim3((unsigned)((n_cov + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(md_raster_depth_bwd_pix_kernel, dim3(md_blocks(n_cov, 256)), dim3(256), 0, (hipStream_t)stream,
                        cov, (int)n_cov, rast1, rast2, gd1, gd2, pos_clip, verts, faces, mvp, campos, (int)n_verts, (int)H, (int)W,
                        corner_grad);
   md_csr_gather<3, false, false>(corner_grad, ptr, order, n_verts, (int64_t)n_cov * 3, dverts, (hipStream_t)stream);

@@ -75,13 +75,12 @@
 //               target <= 0 are refused by the host (ValueError).  An index outside its table is absent and never read.
 //
 // Kernels.  Latency-bound gathers over short rows (valence ~6): one thread per edge, face or vertex, 256-thread workgroups, no LDS.
-#include "md_common.h"
+#include "md_args.h"
 #include "md_gather.h"
 
 #pragma clang fp contract(off)
 
 static constexpr int RM_THREADS = 256;
-static inline unsigned rm_blocks(int64_t n) { return (unsigned)((n + RM_THREADS - 1) / RM_THREADS); }
 
 struct rm_v3 { float x, y, z; };
 __device__ __forceinline__ rm_v3 rm_load(const float* verts, int64_t v) { return {verts[v * 3], verts[v * 3 + 1], verts[v * 3 + 2]}; }
@@ -502,43 +501,31 @@ __global__ __launch_bounds__(RM_THREADS) void md_rm_relax_kernel(const float* __
 }
 
 // ---- exports -------------------------------------------------------------------------------------------------------------------
-static inline bool rm_bad(const void* p, uintptr_t align) { return !p || ((uintptr_t)p & (align - 1)); }
-static inline bool rm_big(int64_t V, int64_t E, int64_t F) { return V > 0x7fffffffLL || 2 * E > 0x7fffffffLL || 3 * F > 0x7fffffffLL; }
-#define RM_LAUNCH(kernel, n, ...)                                                                                        \
-  do {                                                                                                                   \
-    MD_HIP_CLEAR_ERROR();                                                                                                \
-    hipLaunchKernelGGL(kernel, dim3(rm_blocks(n)), dim3(RM_THREADS), 0, (hipStream_t)stream, __VA_ARGS__);               \
-    MD_HIP_CHECK_LAUNCH();                                                                                               \
-    return MD_OK;                                                                                                        \
-  } while (0)
-
 extern "C" int md_remesh_split_mark(const float* verts, const int64_t* lo, const int64_t* hi, const int32_t* vert_mesh, const float* hi2,
                                     int64_t n_verts, int64_t n_edges, int64_t n_meshes, int32_t* mark, float* mid, void* stream) {
-  if (rm_bad(verts, 4) || rm_bad(lo, 8) || rm_bad(hi, 8) || rm_bad(vert_mesh, 4) || rm_bad(hi2, 4) || rm_bad(mark, 4) || rm_bad(mid, 4))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(verts, vert_mesh, hi2, mark, mid) || md_any_bad<8>(lo, hi)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_edges <= 0 || n_meshes <= 0) return MD_ERR_BAD_ARG;
-  if (rm_big(n_verts, n_edges, 0) || n_meshes > 0x7fffffffLL) return MD_ERR_UNSUPPORTED;
-  RM_LAUNCH(md_rm_split_mark_kernel, n_edges, verts, lo, hi, vert_mesh, hi2, (int)n_verts, (int)n_edges, (int)n_meshes, mark, mid);
+  if (!md_fits_i32(n_verts, 2 * n_edges, n_meshes)) return MD_ERR_UNSUPPORTED;
+  MD_LAUNCH_1D(md_rm_split_mark_kernel, n_edges, RM_THREADS, verts, lo, hi, vert_mesh, hi2, (int)n_verts, (int)n_edges, (int)n_meshes, mark,
+               mid);
 }
 
 extern "C" int md_remesh_split_count(const int64_t* faces, const int64_t* lo, const int64_t* hi, const int32_t* mark, int64_t n_verts,
                                      int64_t n_edges, int64_t n_faces, int32_t* count, void* stream) {
-  if (rm_bad(faces, 8) || rm_bad(lo, 8) || rm_bad(hi, 8) || rm_bad(mark, 4) || rm_bad(count, 4)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<8>(faces, lo, hi) || md_any_bad<4>(mark, count)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_edges <= 0 || n_faces <= 0) return MD_ERR_BAD_ARG;
-  if (rm_big(n_verts, n_edges, n_faces)) return MD_ERR_UNSUPPORTED;
-  RM_LAUNCH(md_rm_split_count_kernel, n_faces, faces, lo, hi, mark, (int)n_verts, (int)n_edges, (int)n_faces, count);
+  if (!md_fits_i32(n_verts, 2 * n_edges, 3 * n_faces)) return MD_ERR_UNSUPPORTED;
+  MD_LAUNCH_1D(md_rm_split_count_kernel, n_faces, RM_THREADS, faces, lo, hi, mark, (int)n_verts, (int)n_edges, (int)n_faces, count);
 }
 
 extern "C" int md_remesh_split_emit(const float* verts, const int64_t* faces, const int64_t* lo, const int64_t* hi, const int32_t* mark,
                                     const int32_t* rank, const int32_t* offset, int64_t n_verts, int64_t n_edges, int64_t n_faces,
                                     int64_t n_faces_out, int64_t* out_faces, void* stream) {
-  if (rm_bad(verts, 4) || rm_bad(faces, 8) || rm_bad(lo, 8) || rm_bad(hi, 8) || rm_bad(mark, 4) || rm_bad(rank, 4) || rm_bad(offset, 4) ||
-      rm_bad(out_faces, 8))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(verts, mark, rank, offset) || md_any_bad<8>(faces, lo, hi, out_faces)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_edges <= 0 || n_faces <= 0 || n_faces_out < n_faces || out_faces == faces) return MD_ERR_BAD_ARG;
-  if (rm_big(n_verts + n_edges, n_edges, n_faces_out)) return MD_ERR_UNSUPPORTED;      // the new ids V + rank fit int32 too
-  RM_LAUNCH(md_rm_split_emit_kernel, n_faces, verts, faces, lo, hi, mark, rank, offset, (int)n_verts, (int)n_edges, (int)n_faces,
-            n_faces_out, out_faces);
+  if (!md_fits_i32(n_verts + n_edges, 2 * n_edges, 3 * n_faces_out)) return MD_ERR_UNSUPPORTED;      // the new ids V + rank fit int32 too
+  MD_LAUNCH_1D(md_rm_split_emit_kernel, n_faces, RM_THREADS, verts, faces, lo, hi, mark, rank, offset, (int)n_verts, (int)n_edges,
+               (int)n_faces, n_faces_out, out_faces);
 }
 
 extern "C" int md_remesh_collapse_candidates(const float* verts, const int64_t* faces, const int64_t* lo, const int64_t* hi,
@@ -546,79 +533,69 @@ extern "C" int md_remesh_collapse_candidates(const float* verts, const int64_t* 
                                              const int32_t* corner, const int32_t* vflag, const int32_t* vert_mesh, const float* lo2,
                                              const float* hi2, int64_t n_verts, int64_t n_edges, int64_t n_faces, int64_t n_meshes,
                                              int32_t* cand, uint64_t* prio, void* stream) {
-  if (rm_bad(verts, 4) || rm_bad(faces, 8) || rm_bad(lo, 8) || rm_bad(hi, 8) || rm_bad(mult, 8) || rm_bad(ptr, 4) || rm_bad(adj, 4) ||
-      rm_bad(cptr, 4) || rm_bad(corner, 4) || rm_bad(vflag, 4) || rm_bad(vert_mesh, 4) || rm_bad(lo2, 4) || rm_bad(hi2, 4) ||
-      rm_bad(cand, 4) || rm_bad(prio, 8))
+  if (md_any_bad<4>(verts, ptr, adj, cptr, corner, vflag, vert_mesh, lo2, hi2, cand) || md_any_bad<8>(faces, lo, hi, mult, prio))
     return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_edges <= 0 || n_faces <= 0 || n_meshes <= 0) return MD_ERR_BAD_ARG;
-  if (rm_big(n_verts, n_edges, n_faces) || n_meshes > 0x7fffffffLL) return MD_ERR_UNSUPPORTED;
-  RM_LAUNCH(md_rm_collapse_cand_kernel, n_edges, verts, faces, lo, hi, mult, ptr, adj, cptr, corner, vflag, vert_mesh, lo2, hi2,
-            (int)n_verts, (int)n_edges, (int)n_faces, (int)n_meshes, cand, (unsigned long long*)prio);
+  if (!md_fits_i32(n_verts, 2 * n_edges, 3 * n_faces, n_meshes)) return MD_ERR_UNSUPPORTED;
+  MD_LAUNCH_1D(md_rm_collapse_cand_kernel, n_edges, RM_THREADS, verts, faces, lo, hi, mult, ptr, adj, cptr, corner, vflag, vert_mesh, lo2,
+               hi2, (int)n_verts, (int)n_edges, (int)n_faces, (int)n_meshes, cand, (unsigned long long*)prio);
 }
 
 extern "C" int md_remesh_collapse_claim(const int64_t* lo, const int64_t* hi, const int32_t* ptr, const int32_t* adj, const int32_t* cand,
                                         const uint64_t* prio, int64_t n_verts, int64_t n_edges, uint64_t* word, void* stream) {
-  if (rm_bad(lo, 8) || rm_bad(hi, 8) || rm_bad(ptr, 4) || rm_bad(adj, 4) || rm_bad(cand, 4) || rm_bad(prio, 8) || rm_bad(word, 8))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<8>(lo, hi, prio, word) || md_any_bad<4>(ptr, adj, cand)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_edges <= 0) return MD_ERR_BAD_ARG;
-  if (rm_big(n_verts, n_edges, 0)) return MD_ERR_UNSUPPORTED;
-  RM_LAUNCH(md_rm_collapse_claim_kernel, n_edges, lo, hi, ptr, adj, cand, (const unsigned long long*)prio, (int)n_verts, (int)n_edges,
-            (unsigned long long*)word);
+  if (!md_fits_i32(n_verts, 2 * n_edges)) return MD_ERR_UNSUPPORTED;
+  MD_LAUNCH_1D(md_rm_collapse_claim_kernel, n_edges, RM_THREADS, lo, hi, ptr, adj, cand, (const unsigned long long*)prio, (int)n_verts,
+               (int)n_edges, (unsigned long long*)word);
 }
 
 extern "C" int md_remesh_collapse_apply(const int64_t* lo, const int64_t* hi, const int32_t* ptr, const int32_t* adj, const int32_t* cand,
                                         const uint64_t* prio, uint64_t* word, int64_t n_verts, int64_t n_edges, float* verts,
                                         int32_t* remap, int32_t* counter, void* stream) {
-  if (rm_bad(lo, 8) || rm_bad(hi, 8) || rm_bad(ptr, 4) || rm_bad(adj, 4) || rm_bad(cand, 4) || rm_bad(prio, 8) || rm_bad(word, 8) ||
-      rm_bad(verts, 4) || rm_bad(remap, 4) || rm_bad(counter, 4))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<8>(lo, hi, prio, word) || md_any_bad<4>(ptr, adj, cand, verts, remap, counter)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_edges <= 0) return MD_ERR_BAD_ARG;
-  if (rm_big(n_verts, n_edges, 0)) return MD_ERR_UNSUPPORTED;
-  RM_LAUNCH(md_rm_collapse_apply_kernel, n_edges, lo, hi, ptr, adj, cand, (const unsigned long long*)prio, (unsigned long long*)word,
-            (int)n_verts, (int)n_edges, verts, remap, counter);
+  if (!md_fits_i32(n_verts, 2 * n_edges)) return MD_ERR_UNSUPPORTED;
+  MD_LAUNCH_1D(md_rm_collapse_apply_kernel, n_edges, RM_THREADS, lo, hi, ptr, adj, cand, (const unsigned long long*)prio,
+               (unsigned long long*)word, (int)n_verts, (int)n_edges, verts, remap, counter);
 }
 
 extern "C" int md_remesh_flip_candidates(const float* verts, const int64_t* faces, const int64_t* lo, const int64_t* hi,
                                          const int64_t* mult, const int32_t* ptr, const int32_t* cptr, const int32_t* corner,
                                          const int32_t* vflag, float cos2, int64_t n_verts, int64_t n_edges, int64_t n_faces, int32_t* cand,
                                          uint64_t* prio, int32_t* info, void* stream) {
-  if (rm_bad(verts, 4) || rm_bad(faces, 8) || rm_bad(lo, 8) || rm_bad(hi, 8) || rm_bad(mult, 8) || rm_bad(ptr, 4) || rm_bad(cptr, 4) ||
-      rm_bad(corner, 4) || rm_bad(vflag, 4) || rm_bad(cand, 4) || rm_bad(prio, 8) || rm_bad(info, 4))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(verts, ptr, cptr, corner, vflag, cand, info) || md_any_bad<8>(faces, lo, hi, mult, prio)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_edges <= 0 || n_faces <= 0 || !(cos2 >= 0.f && cos2 <= 1.f)) return MD_ERR_BAD_ARG;
-  if (rm_big(n_verts, n_edges, n_faces)) return MD_ERR_UNSUPPORTED;
-  RM_LAUNCH(md_rm_flip_cand_kernel, n_edges, verts, faces, lo, hi, mult, ptr, cptr, corner, vflag, cos2, (int)n_verts, (int)n_edges,
-            (int)n_faces, cand, (unsigned long long*)prio, info);
+  if (!md_fits_i32(n_verts, 2 * n_edges, 3 * n_faces)) return MD_ERR_UNSUPPORTED;
+  MD_LAUNCH_1D(md_rm_flip_cand_kernel, n_edges, RM_THREADS, verts, faces, lo, hi, mult, ptr, cptr, corner, vflag, cos2, (int)n_verts,
+               (int)n_edges, (int)n_faces, cand, (unsigned long long*)prio, info);
 }
 
 extern "C" int md_remesh_flip_claim(const int64_t* lo, const int64_t* hi, const int32_t* cand, const uint64_t* prio, const int32_t* info,
                                     int64_t n_verts, int64_t n_edges, uint64_t* word, void* stream) {
-  if (rm_bad(lo, 8) || rm_bad(hi, 8) || rm_bad(cand, 4) || rm_bad(prio, 8) || rm_bad(info, 4) || rm_bad(word, 8)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<8>(lo, hi, prio, word) || md_any_bad<4>(cand, info)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_edges <= 0) return MD_ERR_BAD_ARG;
-  if (rm_big(n_verts, n_edges, 0)) return MD_ERR_UNSUPPORTED;
-  RM_LAUNCH(md_rm_flip_claim_kernel, n_edges, lo, hi, cand, (const unsigned long long*)prio, info, (int)n_verts, (int)n_edges,
-            (unsigned long long*)word);
+  if (!md_fits_i32(n_verts, 2 * n_edges)) return MD_ERR_UNSUPPORTED;
+  MD_LAUNCH_1D(md_rm_flip_claim_kernel, n_edges, RM_THREADS, lo, hi, cand, (const unsigned long long*)prio, info, (int)n_verts,
+               (int)n_edges, (unsigned long long*)word);
 }
 
 extern "C" int md_remesh_flip_apply(const int64_t* lo, const int64_t* hi, const int32_t* cand, const uint64_t* prio, const int32_t* info,
                                     const uint64_t* word, int64_t n_verts, int64_t n_edges, int64_t n_faces, int64_t* faces,
                                     int32_t* counter, void* stream) {
-  if (rm_bad(lo, 8) || rm_bad(hi, 8) || rm_bad(cand, 4) || rm_bad(prio, 8) || rm_bad(info, 4) || rm_bad(word, 8) || rm_bad(faces, 8) ||
-      rm_bad(counter, 4))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<8>(lo, hi, prio, word, faces) || md_any_bad<4>(cand, info, counter)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_edges <= 0 || n_faces <= 0) return MD_ERR_BAD_ARG;
-  if (rm_big(n_verts, n_edges, n_faces)) return MD_ERR_UNSUPPORTED;
-  RM_LAUNCH(md_rm_flip_apply_kernel, n_edges, lo, hi, cand, (const unsigned long long*)prio, info, (const unsigned long long*)word,
-            (int)n_verts, (int)n_edges, (int)n_faces, faces, counter);
+  if (!md_fits_i32(n_verts, 2 * n_edges, 3 * n_faces)) return MD_ERR_UNSUPPORTED;
+  MD_LAUNCH_1D(md_rm_flip_apply_kernel, n_edges, RM_THREADS, lo, hi, cand, (const unsigned long long*)prio, info,
+               (const unsigned long long*)word, (int)n_verts, (int)n_edges, (int)n_faces, faces, counter);
 }
 
 extern "C" int md_remesh_relax(const float* verts, const int64_t* faces, const int32_t* ptr, const int32_t* adj, const int32_t* cptr,
                                const int32_t* corner, const int32_t* vflag, int64_t n_verts, int64_t n_edges, int64_t n_faces, float lam,
                                float* out, void* stream) {
-  if (rm_bad(verts, 4) || rm_bad(faces, 8) || rm_bad(ptr, 4) || rm_bad(adj, 4) || rm_bad(cptr, 4) || rm_bad(corner, 4) ||
-      rm_bad(vflag, 4) || rm_bad(out, 4))
-    return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(verts, ptr, adj, cptr, corner, vflag, out) || md_any_bad<8>(faces)) return MD_ERR_BAD_ARG;
   if (n_verts <= 0 || n_edges <= 0 || n_faces <= 0 || out == verts || !(fabsf(lam) <= 3.402823466e+38f)) return MD_ERR_BAD_ARG;
-  if (rm_big(n_verts, n_edges, n_faces)) return MD_ERR_UNSUPPORTED;
-  RM_LAUNCH(md_rm_relax_kernel, n_verts, verts, faces, ptr, adj, cptr, corner, vflag, (int)n_verts, (int)n_edges, (int)n_faces, lam, out);
+  if (!md_fits_i32(n_verts, 2 * n_edges, 3 * n_faces)) return MD_ERR_UNSUPPORTED;
+  MD_LAUNCH_1D(md_rm_relax_kernel, n_verts, RM_THREADS, verts, faces, ptr, adj, cptr, corner, vflag, (int)n_verts, (int)n_edges,
+               (int)n_faces, lam, out);
 }

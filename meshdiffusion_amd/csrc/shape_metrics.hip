@@ -24,7 +24,7 @@
 // resident block, or an EARLIER tile of the same y cloud holds a non-finite coordinate: once a tile of a (y cloud, x block)
 // pass has been careful, the rest of that pass is, and a NaN minimum survives the tiles after it.  On finite data the careful
 // loop gives the fast loop's bits.
-#include "md_common.h"
+#include "md_args.h"
 
 typedef float sm_f2 __attribute__((ext_vector_type(2)));
 
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(SM_THREADS) void md_sided_mean_matrix_kernel(const 
 
 extern "C" int md_sided_mean_matrix(const float* x, const float* y, int32_t nx, int32_t ny, int32_t p, int32_t q, float* out,
                                     void* stream) {
-  if (!x || !y || !out || nx < 1 || ny < 1 || p < 1 || q < 1) return MD_ERR_BAD_ARG;
+  if (md_any_bad<1>(x, y, out) || nx < 1 || ny < 1 || p < 1 || q < 1) return MD_ERR_BAD_ARG;
   // gridDim.y = runs <= SM_TARGET_WGS; gridDim.x = nx, and a launch's threads along x must stay below 2^32
   static_assert(SM_TARGET_WGS <= 65535, "runs per x cloud must fit gridDim.y");
   if ((int64_t)nx * SM_THREADS > 0xffffffffLL) return MD_ERR_UNSUPPORTED;

@@ -35,7 +35,7 @@
 // consecutive floats per row (no bank conflict) and the stores are 128-byte rows.  md_tet_visibility: one lane per (view, tet):
 // twelve multiply-adds, three divides, one gather from Dmin.  md_rast_mark_tets: one lane per pixel.  md_tets_mark_verts: one
 // lane per tet, up to eight stores.  All three are latency-bound gathers and scatters with nothing to reuse: no LDS.
-#include "md_common.h"
+#include "md_args.h"
 
 #pragma clang fp contract(off)
 
@@ -151,8 +151,6 @@ __global__ __launch_bounds__(VS_THREADS) void md_vs_tets_mark_verts_kernel(const
 }
 
 // ---- exports -------------------------------------------------------------------------------------------------------------------
-static inline unsigned vs_blocks(int64_t n) { return (unsigned)((n + VS_THREADS - 1) / VS_THREADS); }
-
 static int vs_image_sizes(int32_t batch, int32_t H, int32_t W) {
   if (batch <= 0 || H <= 0 || W <= 0) return MD_ERR_BAD_ARG;
   if (batch > VS_MAX_VIEWS || H > VS_MAX_RES || W > VS_MAX_RES) return MD_ERR_UNSUPPORTED;
@@ -162,11 +160,11 @@ static int vs_image_sizes(int32_t batch, int32_t H, int32_t W) {
 // counts of tets, faces and vertices: positive, and small enough that a launch of one lane each fits the grid
 static int vs_count(int64_t n) {
   if (n <= 0) return MD_ERR_BAD_ARG;
-  return n > 0x7fffffffLL ? MD_ERR_UNSUPPORTED : MD_OK;
+  return md_fits_i32(n) ? MD_OK : MD_ERR_UNSUPPORTED;
 }
 
 extern "C" int md_window_min(const float* rast, int32_t batch, int32_t H, int32_t W, int32_t radius, float* dmin, void* stream) {
-  if (!rast || !dmin || ((uintptr_t)rast & 15) || ((uintptr_t)dmin & 3)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<16>(rast) || md_any_bad<4>(dmin)) return MD_ERR_BAD_ARG;
   if (radius < 0) return MD_ERR_BAD_ARG;
   const int rc = vs_image_sizes(batch, H, W);
   if (rc != MD_OK) return rc;
@@ -180,45 +178,36 @@ extern "C" int md_window_min(const float* rast, int32_t batch, int32_t H, int32_
 
 extern "C" int md_tet_visibility(const float* dmin, const float* centres, const float* mvp, int32_t batch, int64_t n_tets, int32_t H,
                                  int32_t W, uint8_t* visible, void* stream) {
-  if (!dmin || !centres || !mvp || !visible) return MD_ERR_BAD_ARG;
-  if (((uintptr_t)dmin & 3) || ((uintptr_t)centres & 3) || ((uintptr_t)mvp & 3)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(dmin, centres, mvp) || md_any_bad<1>(visible)) return MD_ERR_BAD_ARG;
   int rc = vs_image_sizes(batch, H, W);
   if (rc == MD_OK) rc = vs_count(n_tets);
   if (rc != MD_OK) return rc;
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_vs_tet_visibility_kernel, dim3(vs_blocks(n_tets), batch), dim3(VS_THREADS), 0, (hipStream_t)stream, dmin,
-                     centres, mvp, n_tets, (int)H, (int)W, visible);
+  hipLaunchKernelGGL(md_vs_tet_visibility_kernel, dim3(md_blocks(n_tets, VS_THREADS), batch), dim3(VS_THREADS), 0, (hipStream_t)stream,
+                     dmin, centres, mvp, n_tets, (int)H, (int)W, visible);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }
 
 extern "C" int md_rast_mark_tets(const float* rast, const int64_t* face_tet, int32_t batch, int32_t H, int32_t W, int64_t n_faces,
                                  int64_t n_tets, uint8_t* rast_tet, void* stream) {
-  if (!rast || !face_tet || !rast_tet || ((uintptr_t)rast & 15) || ((uintptr_t)face_tet & 7)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<16>(rast) || md_any_bad<8>(face_tet) || md_any_bad<1>(rast_tet)) return MD_ERR_BAD_ARG;
   int rc = vs_image_sizes(batch, H, W);
   if (rc == MD_OK) rc = vs_count(n_faces);
   if (rc == MD_OK) rc = vs_count(n_tets);
   if (rc != MD_OK) return rc;
   if (n_faces >= (1LL << 24)) return MD_ERR_UNSUPPORTED;      // a float32 id holds face + 1 exactly below 2^24 only
   const int64_t n_pixels = (int64_t)batch * H * W;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_vs_rast_mark_tets_kernel, dim3(vs_blocks(n_pixels)), dim3(VS_THREADS), 0, (hipStream_t)stream, rast, face_tet,
-                     n_pixels, n_faces, n_tets, rast_tet);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  MD_LAUNCH_1D(md_vs_rast_mark_tets_kernel, n_pixels, VS_THREADS, rast, face_tet, n_pixels, n_faces, n_tets, rast_tet);
 }
 
 extern "C" int md_tets_mark_verts(const uint8_t* visible, const uint8_t* rast_tet, const int64_t* indices, int32_t batch,
                                   int64_t n_tets, int64_t n_verts, float* vis, uint8_t* vis_rast, void* stream) {
-  if (!visible || !indices || !vis || !vis_rast || ((uintptr_t)indices & 7) || ((uintptr_t)vis & 3)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<1>(visible, vis_rast) || md_any_bad<8>(indices) || md_any_bad<4>(vis)) return MD_ERR_BAD_ARG;
   if (batch <= 0) return MD_ERR_BAD_ARG;
   if (batch > VS_MAX_VIEWS) return MD_ERR_UNSUPPORTED;
   int rc = vs_count(n_tets);
   if (rc == MD_OK) rc = vs_count(n_verts);
   if (rc != MD_OK) return rc;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_vs_tets_mark_verts_kernel, dim3(vs_blocks(n_tets)), dim3(VS_THREADS), 0, (hipStream_t)stream, visible, rast_tet,
-                     indices, (int)batch, n_tets, n_verts, vis, vis_rast);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  MD_LAUNCH_1D(md_vs_tets_mark_verts_kernel, n_tets, VS_THREADS, visible, rast_tet, indices, (int)batch, n_tets, n_verts, vis, vis_rast);
 }

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from ._csr import csr_by_row
-from .hip_ops import _ptr, _stream
+from .hip_ops import _ptr, _stream, call
 
 BASE_TET_EDGES = (0, 1, 0, 2, 0, 3, 1, 2, 1, 3, 2, 3)
 
@@ -191,16 +191,13 @@ class _MarchingTetsFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_verts, _gf, _gc):
-        lib = _lib.load()
         pos, sdf, ws, counts = ctx.saved_tensors
         tb = ctx.tables
         M, N = sdf.shape
         inc_ptr, inc = tb.incidence(N)
         g = grad_verts.to(torch.float32).contiguous()
         dpos, dsdf = torch.empty_like(pos), torch.empty_like(sdf)
-        _lib.check(lib.md_marching_tets_bwd(_ptr(pos), _ptr(sdf), _ptr(tb.edges), _ptr(ws), _ptr(counts), _ptr(g),
-                                            _ptr(inc_ptr), _ptr(inc), M, N, tb.n_edges, _ptr(dpos), _ptr(dsdf), _stream()),
-                   "md_marching_tets_bwd")
+        call("md_marching_tets_bwd", pos, sdf, tb.edges, ws, counts, g, inc_ptr, inc, M, N, tb.n_edges, dpos, dsdf)
         return (dpos if ctx.needs_input_grad[0] else None), (dsdf if ctx.needs_input_grad[1] else None), None
 
 
@@ -345,13 +342,11 @@ def _edge_tables_for(all_edges):
 class _SdfRegLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sdf, tables):
-        lib = _lib.load()
         dev = sdf.device
         ws = torch.empty(_lib.SDF_REG_WORKSPACE_BYTES // 8, dtype=torch.float64, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         count = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.md_sdf_reg_loss(_ptr(sdf), _ptr(tables.edges), sdf.shape[0], tables.n_edges, _ptr(ws), _ptr(loss),
-                                       _ptr(count), _stream()), "md_sdf_reg_loss")
+        call("md_sdf_reg_loss", sdf, tables.edges, sdf.shape[0], tables.n_edges, ws, loss, count)
         ctx.tables = tables
         ctx.save_for_backward(sdf, count)
         return loss.reshape(())
@@ -359,14 +354,12 @@ class _SdfRegLossFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        lib = _lib.load()
         sdf, count = ctx.saved_tensors
         tb = ctx.tables
         inc_ptr, inc = tb.incidence(sdf.shape[0])
         g = grad_out.to(torch.float32).reshape(1).contiguous()
         dsdf = torch.empty_like(sdf)
-        _lib.check(lib.md_sdf_reg_loss_bwd(_ptr(sdf), _ptr(tb.edges), _ptr(inc_ptr), _ptr(inc), _ptr(count), _ptr(g),
-                                           sdf.shape[0], tb.n_edges, _ptr(dsdf), _stream()), "md_sdf_reg_loss_bwd")
+        call("md_sdf_reg_loss_bwd", sdf, tb.edges, inc_ptr, inc, count, g, sdf.shape[0], tb.n_edges, dsdf)
         return dsdf, None
 
 
@@ -471,10 +464,8 @@ class _FixedTopoVertsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pos, sdf, plan):
-        lib = _lib.load()
         verts = torch.empty((plan.n_mesh_verts, 3), dtype=torch.float32, device=pos.device)
-        _lib.check(lib.md_fixedtopo_verts(_ptr(pos), _ptr(sdf), _ptr(plan.edge), pos.shape[0], plan.n_mesh_verts, _ptr(verts),
-                                          _stream()), "md_fixedtopo_verts")
+        call("md_fixedtopo_verts", pos, sdf, plan.edge, pos.shape[0], plan.n_mesh_verts, verts)
         ctx.plan = plan
         ctx.save_for_backward(sdf)
         return verts
@@ -482,13 +473,11 @@ class _FixedTopoVertsFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
         sdf, = ctx.saved_tensors
         plan = ctx.plan
         g = g.to(torch.float32).contiguous()
         dpos = torch.empty((sdf.shape[0], 3), dtype=torch.float32, device=g.device)
-        _lib.check(lib.md_fixedtopo_verts_bwd(_ptr(g), _ptr(sdf), _ptr(plan.edge), _ptr(plan.inc_ptr), _ptr(plan.inc), sdf.shape[0],
-                                              plan.n_mesh_verts, _ptr(dpos), _stream()), "md_fixedtopo_verts_bwd")
+        call("md_fixedtopo_verts_bwd", g, sdf, plan.edge, plan.inc_ptr, plan.inc, sdf.shape[0], plan.n_mesh_verts, dpos)
         return dpos, None, None
 
 
@@ -632,42 +621,36 @@ class DMTetGeometryFixedTopo(torch.nn.Module):
 def auto_normals(verts, faces):
     """Smooth vertex normals of a mesh (nvdiffrec/lib/render/mesh.py:200-229, the call at nvdiffrec/eval.py:422 on the
     marching-tets output): returns (v_nrm float32 [V,3], f_nrm float32 [F,3] unnormalised) -- md_vertex_normals."""
-    lib = _lib.load()
     if not verts.is_cuda:
         raise _lib.MeshDiffusionHipError("auto_normals runs on the GPU only")
     v = verts.to(torch.float32).contiguous()
     f = faces.to(torch.int64).contiguous()
     v_nrm = torch.empty_like(v)
     f_nrm = torch.empty((f.shape[0], 3), dtype=torch.float32, device=v.device)
-    _lib.check(lib.md_vertex_normals(_ptr(v), _ptr(f), v.shape[0], f.shape[0], _ptr(v_nrm), _ptr(f_nrm), _stream()),
-               "md_vertex_normals")
+    call("md_vertex_normals", v, f, v.shape[0], f.shape[0], v_nrm, f_nrm)
     return v_nrm, f_nrm
 
 
 class _VertexNormalsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, verts, faces, ptr, order):
-        lib = _lib.load()
         V, F = verts.shape[0], faces.shape[0]
         v_nrm = torch.empty_like(verts)
         f_nrm = torch.empty((F, 3), dtype=torch.float32, device=verts.device)
         v_len = torch.empty(V, dtype=torch.float32, device=verts.device)
-        _lib.check(lib.md_vertex_normals_det(_ptr(verts), _ptr(faces), _ptr(ptr), _ptr(order), V, F, _ptr(v_nrm), _ptr(f_nrm),
-                                             _ptr(v_len), _stream()), "md_vertex_normals_det")
+        call("md_vertex_normals_det", verts, faces, ptr, order, V, F, v_nrm, f_nrm, v_len)
         ctx.save_for_backward(verts, faces, ptr, order, v_nrm, v_len)
         return v_nrm
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
         verts, faces, ptr, order, v_nrm, v_len = ctx.saved_tensors
         V, F = verts.shape[0], faces.shape[0]
         g = g.to(torch.float32).contiguous()
         face_grad = torch.empty((F, 3, 3), dtype=torch.float32, device=verts.device)
         dverts = torch.empty_like(verts)
-        _lib.check(lib.md_vertex_normals_bwd(_ptr(verts), _ptr(faces), _ptr(ptr), _ptr(order), _ptr(v_nrm), _ptr(v_len), _ptr(g),
-                                             V, F, _ptr(face_grad), _ptr(dverts), _stream()), "md_vertex_normals_bwd")
+        call("md_vertex_normals_bwd", verts, faces, ptr, order, v_nrm, v_len, g, V, F, face_grad, dverts)
         return dverts, None, None, None
 
 

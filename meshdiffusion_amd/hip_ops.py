@@ -133,6 +133,18 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def call(name, *args):
+    """Run the export `name` on the current stream: tensors go as their data pointer, None as null, everything else as it is; the
+    stream is appended as the last argument.  A non-zero status raises MeshDiffusionHipError naming the export and the code."""
+    args = [_ptr(a) if a is None or torch.is_tensor(a) else a for a in args]
+    _lib.check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+
+def _gpu_only(t, what):
+    if not t.is_cuda:
+        raise _lib.MeshDiffusionHipError(f"{what} runs on the GPU only (no CPU fallback)")
+
+
 def _require_cuda(t, name):
     if not t.is_cuda:
         raise _lib.MeshDiffusionHipError(f"{name} must live on the GPU: the HIP path has no CPU fallback")

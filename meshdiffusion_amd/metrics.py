@@ -25,7 +25,7 @@ import math
 import torch
 
 from . import _lib
-from .hip_ops import _ptr, _stream
+from .hip_ops import call
 
 
 def _clouds(t, what):
@@ -37,12 +37,10 @@ def _clouds(t, what):
 
 
 def _sided(x, y):
-    lib = _lib.load()
     if y.device != x.device:
         raise ValueError("sided_mean_matrix: both sets of clouds need the same device")
     out = torch.empty((x.shape[0], y.shape[0]), dtype=torch.float32, device=x.device)
-    _lib.check(lib.md_sided_mean_matrix(_ptr(x), _ptr(y), x.shape[0], y.shape[0], x.shape[1], y.shape[1], _ptr(out),
-                                        _stream()), "md_sided_mean_matrix")
+    call("md_sided_mean_matrix", x, y, x.shape[0], y.shape[0], x.shape[1], y.shape[1], out)
     return out
 
 
@@ -165,15 +163,13 @@ def emd_matrix(x, y=None, quantum=None, max_rounds=None, return_info=False):
     quantum = float(quantum)
     if max_rounds is None:
         max_rounds = 256 * P + 4096
-    lib = _lib.load()
     dev = xc.device
     out = torch.empty((nx, ny), dtype=torch.float32, device=dev)
     status = torch.empty((nx, ny), dtype=torch.int32, device=dev)
     total = torch.empty((nx, ny), dtype=torch.int64, device=dev) if return_info else None
     rounds = torch.empty((nx, ny), dtype=torch.int32, device=dev) if return_info else None
     perm = torch.empty((nx, ny, P), dtype=torch.int32, device=dev) if return_info and nx * ny <= EMD_PERM_PAIRS else None
-    _lib.check(lib.md_emd_matrix(_ptr(xc), _ptr(yc), nx, ny, P, quantum, int(max_rounds), 1 if tri else 0, _ptr(out), _ptr(status),
-                                 _ptr(total), _ptr(rounds), _ptr(perm), _stream()), "md_emd_matrix")
+    call("md_emd_matrix", xc, yc, nx, ny, P, quantum, int(max_rounds), 1 if tri else 0, out, status, total, rounds, perm)
     if return_info:
         return out, {"status": status, "total": total, "rounds": rounds, "perm": perm, "quantum": quantum}
     failed = torch.nonzero((status == 1) | (status == 2))

@@ -14,13 +14,8 @@ indices); the summation is the kernel, so two backward passes agree bit for bit.
 import torch
 
 from . import _lib
-from ._csr import csr_by_row
-from .hip_ops import _ptr, _stream
-
-
-def _gpu_only(t, what):
-    if not t.is_cuda:
-        raise _lib.MeshDiffusionHipError(f"{what} runs on the GPU only (no CPU fallback)")
+from ._csr import check_faces, csr_by_row
+from .hip_ops import _gpu_only, call
 
 
 def _cloud(t, what):
@@ -42,8 +37,7 @@ def _nn(p, q, skip_same_index=False):
     ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=p.device)
     dist = torch.empty((B, N), dtype=torch.float32, device=p.device)
     idx = torch.empty((B, N), dtype=torch.int64, device=p.device)
-    _lib.check(lib.md_nn_sided(_ptr(p), _ptr(q), B, N, M, int(bool(skip_same_index)), _ptr(dist), _ptr(idx), _ptr(ws),
-                               ws_bytes, _stream()), "md_nn_sided")
+    call("md_nn_sided", p, q, B, N, M, int(bool(skip_same_index)), dist, idx, ws, ws_bytes)
     return dist, idx
 
 
@@ -75,7 +69,6 @@ class _ChamferFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        lib = _lib.load()
         p, q, i12, i21 = ctx.saved_tensors
         B, N, M = p.shape[0], p.shape[1], q.shape[1]
         need_q = ctx.needs_input_grad[1]
@@ -84,10 +77,7 @@ class _ChamferFn(torch.autograd.Function):
         ptr_q, order_q = _csr(i12, M) if need_q else (None, None)
         dp = torch.empty_like(p)
         dq = torch.empty_like(q) if need_q else None
-        _lib.check(lib.md_chamfer_bwd(_ptr(p), _ptr(q), _ptr(i12), _ptr(i21), _ptr(ptr_p), _ptr(order_p),
-                                      _ptr(ptr_q) if need_q else None, _ptr(order_q) if need_q else None, B, N, M,
-                                      ctx.w[0], ctx.w[1], _ptr(g), _ptr(dp), _ptr(dq) if need_q else None, _stream()),
-                   "md_chamfer_bwd")
+        call("md_chamfer_bwd", p, q, i12, i21, ptr_p, order_p, ptr_q, order_q, B, N, M, ctx.w[0], ctx.w[1], g, dp, dq)
         return (dp if ctx.needs_input_grad[0] else None), dq, None, None
 
 
@@ -113,25 +103,19 @@ def chamfer_distance(p1, p2, w1=1.0, w2=1.0, squared=True):
 # ---- surface sampling ----------------------------------------------------------------------------------------------------
 def _check_faces(faces, n_verts):
     """faces int64 [F,3] contiguous on the GPU with every index in [0, n_verts): checked once here, the kernels index unchecked."""
-    if faces.dim() != 2 or faces.shape[-1] != 3:
-        raise NotImplementedError("sample_points is only implemented for triangle meshes")
-    if faces.shape[0] < 1 or n_verts < 1:
-        raise ValueError("sample_points: the mesh has no faces or no vertices")
-    f = faces.to(torch.int64).contiguous()
-    lo, hi = torch.aminmax(f)
-    if int(lo) < 0 or int(hi) >= n_verts:
-        raise ValueError(f"faces name vertices outside [0, {n_verts})")
-    return f
+    def limits(F):
+        if F < 1 or n_verts < 1:
+            raise ValueError("sample_points: the mesh has no faces or no vertices")
+    return check_faces(faces, n_verts, "sample_points (triangle meshes only)", limits, NotImplementedError)
 
 
 def face_areas(vertices, faces):
     """Triangle areas float32 [B,F] of vertices [B,V,3], faces [F,3]: md_face_areas."""
-    lib = _lib.load()
     _gpu_only(vertices, "face_areas")
     v = vertices.detach().to(torch.float32).contiguous()
     f = _check_faces(faces, v.shape[1])
     areas = torch.empty((v.shape[0], f.shape[0]), dtype=torch.float32, device=v.device)
-    _lib.check(lib.md_face_areas(_ptr(v), _ptr(f), v.shape[0], v.shape[1], f.shape[0], _ptr(areas), _stream()), "md_face_areas")
+    call("md_face_areas", v, f, v.shape[0], v.shape[1], f.shape[0], areas)
     return areas
 
 
@@ -144,17 +128,13 @@ def area_cdf(areas):
 class _SamplePointsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vertices, faces, cdf, r_face, r_u, r_v, choices_in):
-        lib = _lib.load()
         B, V, _ = vertices.shape
         F, S = faces.shape[0], r_u.shape[1]
         dev = vertices.device
         points = torch.empty((B, S, 3), dtype=torch.float32, device=dev)
         choices = torch.empty((B, S), dtype=torch.int64, device=dev)
         weights = torch.empty((B, S, 3), dtype=torch.float32, device=dev)
-        opt = lambda t: _ptr(t) if t is not None else None      # noqa: E731
-        _lib.check(lib.md_sample_points(_ptr(vertices), _ptr(faces), opt(cdf), opt(r_face), _ptr(r_u), _ptr(r_v),
-                                        opt(choices_in), B, V, F, S, _ptr(points), _ptr(choices), _ptr(weights), _stream()),
-                   "md_sample_points")
+        call("md_sample_points", vertices, faces, cdf, r_face, r_u, r_v, choices_in, B, V, F, S, points, choices, weights)
         ctx.save_for_backward(faces, choices, weights)
         ctx.n_verts = V
         ctx.mark_non_differentiable(choices, weights)
@@ -163,7 +143,6 @@ class _SamplePointsFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_points, _gc, _gw):
-        lib = _lib.load()
         faces, choices, weights = ctx.saved_tensors
         B, S = choices.shape
         V = ctx.n_verts
@@ -172,8 +151,7 @@ class _SamplePointsFn(torch.autograd.Function):
         g = grad_points.to(torch.float32).contiguous()
         ptr, order = _csr(faces[choices].reshape(B, S * 3), V)     # entry 3 * sample + corner names vertex faces[choice][corner]
         dverts = torch.empty((B, V, 3), dtype=torch.float32, device=g.device)
-        _lib.check(lib.md_sample_points_bwd(_ptr(g), _ptr(weights), _ptr(ptr), _ptr(order), B, V, S, _ptr(dverts), _stream()),
-                   "md_sample_points_bwd")
+        call("md_sample_points_bwd", g, weights, ptr, order, B, V, S, dverts)
         return dverts, None, None, None, None, None, None
 
 

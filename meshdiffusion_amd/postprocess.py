@@ -17,30 +17,18 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._csr import INT32_MAX, csr_by_row
-from .hip_ops import _ptr, _stream
-
-
-def _gpu_only(t, what):
-    if not t.is_cuda:
-        raise _lib.MeshDiffusionHipError(f"{what} runs on the GPU only (no CPU fallback)")
+from ._csr import INT32_MAX, check_faces, csr_by_row
+from .hip_ops import _gpu_only, call
 
 
 def _check_faces(faces, n_verts, what):
     """faces [F,3] -> int64 contiguous, every index in [0, n_verts): checked once, the kernels treat anything else as absent."""
-    if faces.dim() != 2 or faces.shape[-1] != 3:
-        raise ValueError(f"{what}: expected faces [F,3], got {tuple(faces.shape)}")
-    n_verts = int(n_verts)
-    if n_verts < 0:
-        raise ValueError(f"{what}: n_verts must not be negative, got {n_verts}")
-    if n_verts > INT32_MAX or 3 * faces.shape[0] > INT32_MAX:
-        raise _lib.MeshDiffusionHipError(f"{what}: V and 3 F must fit int32 (MD_ERR_UNSUPPORTED)")
-    f = faces.to(torch.int64).contiguous()
-    if f.shape[0] > 0:
-        lo, hi = torch.aminmax(f)
-        if int(lo) < 0 or int(hi) >= n_verts:
-            raise ValueError(f"{what}: faces name vertices outside [0, {n_verts})")
-    return f
+    def limits(F):
+        if n_verts < 0:
+            raise ValueError(f"{what}: n_verts must not be negative, got {n_verts}")
+        if n_verts > INT32_MAX or 3 * F > INT32_MAX:
+            raise _lib.MeshDiffusionHipError(f"{what}: V and 3 F must fit int32 (MD_ERR_UNSUPPORTED)")
+    return check_faces(faces, n_verts, what, limits)
 
 
 def mesh_edges(faces, n_verts):
@@ -99,8 +87,7 @@ def smooth(verts, faces, steps=3, lam=0.5, mu=None, edges=None):
         out.copy_(x)
         return out
     scratch = torch.empty_like(x) if steps >= 2 else None
-    _lib.check(_lib.load().md_mesh_smooth(_ptr(x), _ptr(ptr), _ptr(adj), V, adj.numel(), steps, lam, mu, _ptr(out), _ptr(scratch),
-                                          _stream()), "md_mesh_smooth")
+    call("md_mesh_smooth", x, ptr, adj, V, adj.numel(), steps, lam, mu, out, scratch)
     return out
 
 
@@ -118,8 +105,7 @@ def components(faces, n_verts):
     comp_faces = torch.empty(V, dtype=torch.int32, device=dev)
     ws = torch.empty(_lib.MESH_COMPONENTS_WORKSPACE_BYTES // 4, dtype=torch.int32, device=dev)
     rounds = ctypes.c_int32(0)
-    _lib.check(_lib.load().md_mesh_components(_ptr(f), V, f.shape[0], _ptr(label), _ptr(comp_faces), _ptr(ws), ctypes.byref(rounds),
-                                              _stream()), "md_mesh_components")
+    call("md_mesh_components", f, V, f.shape[0], label, comp_faces, ws, ctypes.byref(rounds))
     return label, comp_faces, int(rounds.value)
 
 
@@ -222,9 +208,8 @@ def remesh_default_target(verts, faces, vert_mesh, n_meshes):
     return np.where(n > 0, s / np.maximum(n, 1), 1.0).astype(np.float32)
 
 
-def remesh_split(x, f, vm, hi2, lib=None):
+def remesh_split(x, f, vm, hi2):
     """One split pass of the remeshing contract on checked device tensors: (verts', faces', vert_mesh', marked edges)."""
-    lib = lib or _lib.load()
     V, F, M, dev = x.shape[0], f.shape[0], hi2.shape[0], x.device
     lo, hi, mult, ptr, adj, cptr, corner, vflag = _remesh_tables(f, V)
     E = lo.shape[0]
@@ -232,8 +217,7 @@ def remesh_split(x, f, vm, hi2, lib=None):
         return x, f, vm, 0
     mark = torch.empty(E, dtype=torch.int32, device=dev)
     mid = torch.empty(E, 3, dtype=torch.float32, device=dev)
-    _lib.check(lib.md_remesh_split_mark(_ptr(x), _ptr(lo), _ptr(hi), _ptr(vm), _ptr(hi2), V, E, M, _ptr(mark), _ptr(mid), _stream()),
-               "md_remesh_split_mark")
+    call("md_remesh_split_mark", x, lo, hi, vm, hi2, V, E, M, mark, mid)
     n = int(mark.sum())
     if n == 0:
         return x, f, vm, 0
@@ -241,15 +225,14 @@ def remesh_split(x, f, vm, hi2, lib=None):
         raise _lib.MeshDiffusionHipError("remesh: V must fit int32 after the split (MD_ERR_UNSUPPORTED)")
     rank = (torch.cumsum(mark, 0) - mark).to(torch.int32)
     count = torch.empty(F, dtype=torch.int32, device=dev)
-    _lib.check(lib.md_remesh_split_count(_ptr(f), _ptr(lo), _ptr(hi), _ptr(mark), V, E, F, _ptr(count), _stream()), "md_remesh_split_count")
+    call("md_remesh_split_count", f, lo, hi, mark, V, E, F, count)
     total = torch.cumsum(count.to(torch.int64), 0)
     F_out = int(total[-1])
     if 3 * F_out > INT32_MAX:
         raise _lib.MeshDiffusionHipError("remesh: 3 F must fit int32 after the split (MD_ERR_UNSUPPORTED)")
     offset = (total - count).to(torch.int32)
     out = torch.empty(F_out, 3, dtype=torch.int64, device=dev)
-    _lib.check(lib.md_remesh_split_emit(_ptr(x), _ptr(f), _ptr(lo), _ptr(hi), _ptr(mark), _ptr(rank), _ptr(offset), V, E, F, F_out,
-                                        _ptr(out), _stream()), "md_remesh_split_emit")
+    call("md_remesh_split_emit", x, f, lo, hi, mark, rank, offset, V, E, F, F_out, out)
     sel = mark.bool()
     x2, vm2 = torch.cat([x, mid[sel]]), torch.cat([vm, vm[lo[sel]]])
     if M > 1:                                                                    # vertices stay grouped by mesh
@@ -260,9 +243,8 @@ def remesh_split(x, f, vm, hi2, lib=None):
     return x2.contiguous(), out.contiguous(), vm2.contiguous(), n
 
 
-def remesh_collapse_round(x, f, vm, lo2, hi2, lib=None):
+def remesh_collapse_round(x, f, vm, lo2, hi2):
     """One collapse round of the remeshing contract: (verts', faces', vert_mesh', winners).  `x` is not written."""
-    lib = lib or _lib.load()
     V, F, M, dev = x.shape[0], f.shape[0], hi2.shape[0], x.device
     lo, hi, mult, ptr, adj, cptr, corner, vflag = _remesh_tables(f, V)
     E = lo.shape[0]
@@ -274,14 +256,9 @@ def remesh_collapse_round(x, f, vm, lo2, hi2, lib=None):
     remap = torch.arange(V, dtype=torch.int32, device=dev)
     counter = torch.zeros(1, dtype=torch.int32, device=dev)
     new = x.clone()
-    st = _stream()
-    _lib.check(lib.md_remesh_collapse_candidates(_ptr(x), _ptr(f), _ptr(lo), _ptr(hi), _ptr(mult), _ptr(ptr), _ptr(adj), _ptr(cptr),
-                                                 _ptr(corner), _ptr(vflag), _ptr(vm), _ptr(lo2), _ptr(hi2), V, E, F, M, _ptr(cand),
-                                                 _ptr(prio), st), "md_remesh_collapse_candidates")
-    _lib.check(lib.md_remesh_collapse_claim(_ptr(lo), _ptr(hi), _ptr(ptr), _ptr(adj), _ptr(cand), _ptr(prio), V, E, _ptr(word), st),
-               "md_remesh_collapse_claim")
-    _lib.check(lib.md_remesh_collapse_apply(_ptr(lo), _ptr(hi), _ptr(ptr), _ptr(adj), _ptr(cand), _ptr(prio), _ptr(word), V, E, _ptr(new),
-                                            _ptr(remap), _ptr(counter), st), "md_remesh_collapse_apply")
+    call("md_remesh_collapse_candidates", x, f, lo, hi, mult, ptr, adj, cptr, corner, vflag, vm, lo2, hi2, V, E, F, M, cand, prio)
+    call("md_remesh_collapse_claim", lo, hi, ptr, adj, cand, prio, V, E, word)
+    call("md_remesh_collapse_apply", lo, hi, ptr, adj, cand, prio, word, V, E, new, remap, counter)
     n = int(counter)                                                            # the one 4-byte copy of a round
     if n == 0:
         return x, f, vm, 0
@@ -293,9 +270,8 @@ def remesh_collapse_round(x, f, vm, lo2, hi2, lib=None):
     return new[keep].contiguous(), newid[f2].contiguous(), vm[keep].contiguous(), n
 
 
-def remesh_flip_round(x, f, cos2, lib=None):
+def remesh_flip_round(x, f, cos2):
     """One flip round of the remeshing contract: (faces', winners).  `f` is not written."""
-    lib = lib or _lib.load()
     V, F, dev = x.shape[0], f.shape[0], x.device
     lo, hi, mult, ptr, adj, cptr, corner, vflag = _remesh_tables(f, V)
     E = lo.shape[0]
@@ -307,28 +283,22 @@ def remesh_flip_round(x, f, cos2, lib=None):
     word = torch.full((V,), -1, dtype=torch.int64, device=dev)
     counter = torch.zeros(1, dtype=torch.int32, device=dev)
     out = f.clone()
-    st = _stream()
-    _lib.check(lib.md_remesh_flip_candidates(_ptr(x), _ptr(f), _ptr(lo), _ptr(hi), _ptr(mult), _ptr(ptr), _ptr(cptr), _ptr(corner),
-                                             _ptr(vflag), float(cos2), V, E, F, _ptr(cand), _ptr(prio), _ptr(info), st),
-               "md_remesh_flip_candidates")
-    _lib.check(lib.md_remesh_flip_claim(_ptr(lo), _ptr(hi), _ptr(cand), _ptr(prio), _ptr(info), V, E, _ptr(word), st), "md_remesh_flip_claim")
-    _lib.check(lib.md_remesh_flip_apply(_ptr(lo), _ptr(hi), _ptr(cand), _ptr(prio), _ptr(info), _ptr(word), V, E, F, _ptr(out),
-                                        _ptr(counter), st), "md_remesh_flip_apply")
+    call("md_remesh_flip_candidates", x, f, lo, hi, mult, ptr, cptr, corner, vflag, float(cos2), V, E, F, cand, prio, info)
+    call("md_remesh_flip_claim", lo, hi, cand, prio, info, V, E, word)
+    call("md_remesh_flip_apply", lo, hi, cand, prio, info, word, V, E, F, out, counter)
     n = int(counter)
     return (out if n else f), n
 
 
-def remesh_relax(x, f, lam=0.5, lib=None):
+def remesh_relax(x, f, lam=0.5):
     """The relax pass of the remeshing contract: a new tensor."""
-    lib = lib or _lib.load()
     V, F = x.shape[0], f.shape[0]
     lo, hi, mult, ptr, adj, cptr, corner, vflag = _remesh_tables(f, V)
     E = lo.shape[0]
     if E == 0:
         return x.clone()
     out = torch.empty_like(x)
-    _lib.check(lib.md_remesh_relax(_ptr(x), _ptr(f), _ptr(ptr), _ptr(adj), _ptr(cptr), _ptr(corner), _ptr(vflag), V, E, F, float(lam),
-                                   _ptr(out), _stream()), "md_remesh_relax")
+    call("md_remesh_relax", x, f, ptr, adj, cptr, corner, vflag, V, E, F, float(lam), out)
     return out
 
 
@@ -377,25 +347,24 @@ def remesh(verts, faces, *, iters=3, target_len=None, target_scale=1.0, relax=0.
         raise ValueError("remesh: every target length must be finite and > 0")
     lo2, hi2 = (torch.as_tensor(a, device=dev) for a in remesh_bands(target))
     cos2 = float(np.float32(math.cos(math.radians(flip_angle)) ** 2))
-    lib = _lib.load()
     info = []
     for _ in range(iters if V > 0 and f.shape[0] > 0 else 0):
         rec = dict(splits=0, collapses=0, flips=0, collapse_rounds=0, flip_rounds=0)
-        x, f, vm, rec["splits"] = remesh_split(x, f, vm, hi2, lib)
+        x, f, vm, rec["splits"] = remesh_split(x, f, vm, hi2)
         for _r in range(_lib.REMESH_COLLAPSE_ROUNDS):
-            x, f, vm, n = remesh_collapse_round(x, f, vm, lo2, hi2, lib)
+            x, f, vm, n = remesh_collapse_round(x, f, vm, lo2, hi2)
             rec["collapse_rounds"] += 1
             rec["collapses"] += n
             if n == 0:
                 break
         for _r in range(_lib.REMESH_FLIP_ROUNDS):
-            f, n = remesh_flip_round(x, f, cos2, lib)
+            f, n = remesh_flip_round(x, f, cos2)
             rec["flip_rounds"] += 1
             rec["flips"] += n
             if n == 0:
                 break
         if relax != 0.0:
-            x = remesh_relax(x, f, relax, lib)
+            x = remesh_relax(x, f, relax)
         info.append(rec)
     return x, f, vm, dict(target=target, iterations=info)
 

@@ -29,8 +29,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._csr import csr_by_row
-from .hip_ops import _ptr, _stream
+from ._csr import check_faces, csr_by_row
+from .hip_ops import _gpu_only, call
 
 TILE = 16                                # RS_TILE of csrc/raster.hip
 MAX_RES, MAX_VIEWS, MAX_FACES = 2048, 64, 2 ** 24 - 1
@@ -91,11 +91,6 @@ def xfm_points(points, matrix):
 
 
 # ---- rasterisation -----------------------------------------------------------------------------------------------------------------
-def _gpu_only(t, what):
-    if not t.is_cuda:
-        raise _lib.MeshDiffusionHipError(f"{what} runs on the GPU only (no CPU fallback)")
-
-
 def _resolution(resolution):
     H, W = (int(resolution), int(resolution)) if np.isscalar(resolution) else (int(resolution[0]), int(resolution[1]))
     if H < 1 or W < 1:
@@ -107,16 +102,10 @@ def _resolution(resolution):
 
 def _check_faces(faces, n_verts):
     """faces int64 [F,3] contiguous on the device, F >= 0, every index in [0, n_verts): checked once, the kernels index unchecked."""
-    if faces.dim() != 2 or faces.shape[-1] != 3:
-        raise ValueError(f"expected faces [F,3], got {tuple(faces.shape)}")
-    if faces.shape[0] > MAX_FACES:
-        raise _lib.MeshDiffusionHipError("the rasteriser takes fewer than 2^24 faces (MD_ERR_UNSUPPORTED)")
-    f = faces.to(torch.int64).contiguous()
-    if f.shape[0] > 0:
-        lo, hi = torch.aminmax(f)
-        if int(lo) < 0 or int(hi) >= n_verts:
-            raise ValueError(f"faces name vertices outside [0, {n_verts})")
-    return f
+    def limits(F):
+        if F > MAX_FACES:
+            raise _lib.MeshDiffusionHipError("the rasteriser takes fewer than 2^24 faces (MD_ERR_UNSUPPORTED)")
+    return check_faces(faces, n_verts, "rasterize", limits)
 
 
 def _check_clip(pos_clip):
@@ -129,12 +118,11 @@ def _check_clip(pos_clip):
 def _bin(pc, f, H, W):
     """The tile CSR of the triangles: (tile_ptr int32 [B * tiles + 1], tile_faces int32 [pairs]), or None when no triangle
     touches a tile.  Two kernels with a torch.cumsum between them, then a stable torch sort by tile."""
-    lib = _lib.load()
     B, V, F, dev = pc.shape[0], pc.shape[1], f.shape[0], pc.device
     if F == 0:
         return None
     counts = torch.empty(B * F, dtype=torch.int32, device=dev)
-    _lib.check(lib.md_raster_bin_count(_ptr(pc), _ptr(f), B, V, F, H, W, _ptr(counts), _stream()), "md_raster_bin_count")
+    call("md_raster_bin_count", pc, f, B, V, F, H, W, counts)
     ends = torch.cumsum(counts, 0, dtype=torch.int64)
     total = int(ends[-1])
     if total > 2 ** 31 - 1:
@@ -144,8 +132,7 @@ def _bin(pc, f, H, W):
     offsets = (ends - counts).contiguous()
     pair_tile = torch.empty(total, dtype=torch.int32, device=dev)
     pair_face = torch.empty(total, dtype=torch.int32, device=dev)
-    _lib.check(lib.md_raster_bin_emit(_ptr(pc), _ptr(f), _ptr(offsets), B, V, F, H, W, total, _ptr(pair_tile), _ptr(pair_face),
-                                      _stream()), "md_raster_bin_emit")
+    call("md_raster_bin_emit", pc, f, offsets, B, V, F, H, W, total, pair_tile, pair_face)
     n_tiles = B * ((H + TILE - 1) // TILE) * ((W + TILE - 1) // TILE)
     tile_ptr, order = csr_by_row(pair_tile, n_tiles)
     return tile_ptr, pair_face[order].contiguous()
@@ -153,15 +140,13 @@ def _bin(pc, f, H, W):
 
 def _rasterize(pc, f, H, W):
     """pc float32 [B,V,4] contiguous, f checked faces -> (rast1, rast2) float32 [B,H,W,4]."""
-    lib = _lib.load()
     B, V, F, dev = pc.shape[0], pc.shape[1], f.shape[0], pc.device
     csr = _bin(pc, f, H, W)
     if csr is None:
         return torch.zeros((B, H, W, 4), dtype=torch.float32, device=dev), torch.zeros((B, H, W, 4), dtype=torch.float32, device=dev)
     rast1 = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
     rast2 = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
-    _lib.check(lib.md_raster_tiles(_ptr(pc), _ptr(f), _ptr(csr[0]), _ptr(csr[1]), B, V, F, H, W, _ptr(rast1), _ptr(rast2),
-                                   _stream()), "md_raster_tiles")
+    call("md_raster_tiles", pc, f, csr[0], csr[1], B, V, F, H, W, rast1, rast2)
     return rast1, rast2
 
 
@@ -211,7 +196,6 @@ class _RasterizeFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g1, g2):
-        lib = _lib.load()
         pos_clip, faces, rast1, rast2 = ctx.saved_tensors
         B, V, F = pos_clip.shape[0], pos_clip.shape[1], faces.shape[0]
         total = None
@@ -227,9 +211,7 @@ class _RasterizeFn(torch.autograd.Function):
             g = g.to(torch.float32).contiguous()
             corner_grad = torch.empty((N, 3, 3), dtype=torch.float32, device=g.device)
             dpos = torch.empty((B, V, 4), dtype=torch.float32, device=g.device)
-            _lib.check(lib.md_raster_bary_bwd(_ptr(cov), N, _ptr(rast), _ptr(g), _ptr(pos_clip), _ptr(faces), _ptr(ptr),
-                                              _ptr(order), B, V, F, H, W, _ptr(corner_grad), _ptr(dpos), _stream()),
-                       "md_raster_bary_bwd")
+            call("md_raster_bary_bwd", cov, N, rast, g, pos_clip, faces, ptr, order, B, V, F, H, W, corner_grad, dpos)
             total = dpos if total is None else total + dpos
         return (torch.zeros_like(pos_clip) if total is None else total), None, None
 
@@ -262,7 +244,6 @@ def rasterize(pos_clip, faces, resolution, num_layers=2, grad=False):
 class _InterpolateFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, attr, rast, tri, plan, rast_grad):
-        lib = _lib.load()
         B, H, W, _ = rast.shape
         Ba, N, C = attr.shape
         F = tri.shape[0]
@@ -270,8 +251,7 @@ class _InterpolateFn(torch.autograd.Function):
             out = torch.zeros((B, H, W, C), dtype=torch.float32, device=rast.device)
         else:
             out = torch.empty((B, H, W, C), dtype=torch.float32, device=rast.device)
-            _lib.check(lib.md_interpolate(_ptr(rast), _ptr(attr), _ptr(tri), B, Ba, N, C, F, H, W, _ptr(out), _stream()),
-                       "md_interpolate")
+            call("md_interpolate", rast, attr, tri, B, Ba, N, C, F, H, W, out)
         ctx.plan, ctx.rast_grad = plan, rast_grad
         ctx.save_for_backward(attr, tri, rast)
         return out
@@ -279,7 +259,6 @@ class _InterpolateFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
         attr, tri, rast = ctx.saved_tensors
         plan = ctx.plan                                                        # the covered list and the CSRs of rast's layer
         B, H, W, _ = rast.shape
@@ -297,9 +276,7 @@ class _InterpolateFn(torch.autograd.Function):
         if need_attr:
             ptr, order = plan.csr(tri, N, Ba != 1)
             corner_grad = torch.empty((n_cov, 3, C), dtype=torch.float32, device=g.device)
-        _lib.check(lib.md_interpolate_bwd(_ptr(cov), n_cov, _ptr(rast), _ptr(g), _ptr(attr), _ptr(tri), _ptr(ptr), _ptr(order),
-                                          B, Ba, N, C, F, H, W, _ptr(corner_grad), _ptr(dattr), _ptr(drast), _stream()),
-                   "md_interpolate_bwd")
+        call("md_interpolate_bwd", cov, n_cov, rast, g, attr, tri, ptr, order, B, Ba, N, C, F, H, W, corner_grad, dattr, drast)
         return dattr, drast, None, None, None
 
 
@@ -347,7 +324,6 @@ def interpolate(attr, rast, tri, rast_grad=False, _plan=None):
 class _RenderDepthFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, verts, pos_clip, faces, mvp, campos, H, W, layers=None):
-        lib = _lib.load()
         B, V, F, dev = pos_clip.shape[0], verts.shape[0], faces.shape[0], verts.device
         rast1, rast2 = _rasterize(pos_clip, faces, H, W) if layers is None else layers     # layers: these, rasterised already
         depth1 = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev)
@@ -355,8 +331,7 @@ class _RenderDepthFn(torch.autograd.Function):
         if F == 0:
             depth1.fill_(20.0), depth2.fill_(-1.0), mask1.zero_(), mask2.zero_()
         else:
-            _lib.check(lib.md_raster_depth(_ptr(rast1), _ptr(rast2), _ptr(verts), _ptr(faces), _ptr(campos), B, V, F, H, W,
-                                           _ptr(depth1), _ptr(depth2), _ptr(mask1), _ptr(mask2), _stream()), "md_raster_depth")
+            call("md_raster_depth", rast1, rast2, verts, faces, campos, B, V, F, H, W, depth1, depth2, mask1, mask2)
         ctx.save_for_backward(verts, pos_clip, faces, mvp, campos, rast1, rast2)
         ctx.res = (H, W)
         ctx.mark_non_differentiable(mask1, mask2, rast1, rast2)
@@ -365,7 +340,6 @@ class _RenderDepthFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g1, g2, *_unused):
-        lib = _lib.load()
         verts, pos_clip, faces, mvp, campos, rast1, rast2 = ctx.saved_tensors
         H, W = ctx.res
         B, V, F, dev = pos_clip.shape[0], verts.shape[0], faces.shape[0], verts.device
@@ -380,9 +354,8 @@ class _RenderDepthFn(torch.autograd.Function):
         ptr, order = csr_by_row(faces[ids[cov].to(torch.int64) - 1].reshape(-1), V)     # entry 3 n + corner names this vertex
         cov = cov.to(torch.int32).contiguous()
         corner_grad = torch.empty((N, 3, 3), dtype=torch.float32, device=dev)
-        _lib.check(lib.md_raster_depth_bwd(_ptr(cov), N, _ptr(rast1), _ptr(rast2), _ptr(g1), _ptr(g2), _ptr(pos_clip), _ptr(verts),
-                                           _ptr(faces), _ptr(mvp), _ptr(campos), _ptr(ptr), _ptr(order), B, V, F, H, W,
-                                           _ptr(corner_grad), _ptr(dverts), _stream()), "md_raster_depth_bwd")
+        call("md_raster_depth_bwd", cov, N, rast1, rast2, g1, g2, pos_clip, verts, faces, mvp, campos, ptr, order, B, V, F, H, W,
+             corner_grad, dverts)
         return dverts, None, None, None, None, None, None, None
 
 
@@ -403,15 +376,13 @@ def edge_neighbours(faces, n_verts):
     a, b = f[:, [1, 2, 0]], f[:, [2, 0, 1]]
     keys = (torch.minimum(a, b) * n_verts + torch.maximum(a, b)).reshape(-1)
     keys, order = torch.sort(keys, stable=True)
-    _lib.check(_lib.load().md_mesh_edge_neighbours(_ptr(keys), _ptr(order), _ptr(f), F, _ptr(nbr), _stream()),
-               "md_mesh_edge_neighbours")
+    call("md_mesh_edge_neighbours", keys, order, f, F, nbr)
     return nbr
 
 
 class _AntialiasFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, color, pos_clip, rast, faces, nbr):
-        lib = _lib.load()
         B, H, W, C = color.shape
         V, F = pos_clip.shape[1], faces.shape[0]
         pairs = torch.empty((B, H, W, 2, 4), dtype=torch.int32, device=color.device)
@@ -421,9 +392,8 @@ class _AntialiasFn(torch.autograd.Function):
             out = color.clone()
         else:
             out = torch.empty_like(color)
-            _lib.check(lib.md_antialias_pairs(_ptr(rast), _ptr(pos_clip), _ptr(faces), _ptr(nbr), B, V, F, H, W, _ptr(pairs),
-                                              _stream()), "md_antialias_pairs")
-            _lib.check(lib.md_antialias_blend(_ptr(color), _ptr(pairs), B, H, W, C, _ptr(out), _stream()), "md_antialias_blend")
+            call("md_antialias_pairs", rast, pos_clip, faces, nbr, B, V, F, H, W, pairs)
+            call("md_antialias_blend", color, pairs, B, H, W, C, out)
         ctx.save_for_backward(color, pos_clip, pairs)
         ctx.mark_non_differentiable(pairs)
         return out, pairs
@@ -431,7 +401,6 @@ class _AntialiasFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g, _unused):
-        lib = _lib.load()
         color, pos_clip, pairs = ctx.saved_tensors
         B, H, W, C = color.shape
         V, dev = pos_clip.shape[1], color.device
@@ -439,7 +408,7 @@ class _AntialiasFn(torch.autograd.Function):
         dcolor = dpos = None
         if ctx.needs_input_grad[0]:
             dcolor = torch.empty_like(color)
-            _lib.check(lib.md_antialias_bwd_color(_ptr(g), _ptr(pairs), B, H, W, C, _ptr(dcolor), _stream()), "md_antialias_bwd_color")
+            call("md_antialias_bwd_color", g, pairs, B, H, W, C, dcolor)
         if ctx.needs_input_grad[1]:
             rec = pairs.view(-1, 4)
             act = torch.nonzero(rec[:, 0] >= 0)[:, 0]                          # the flat index of a pair is its code
@@ -452,9 +421,7 @@ class _AntialiasFn(torch.autograd.Function):
                 end_vert = (view[:, None] * V + rec[act, :2].to(torch.int64)).reshape(-1)     # entry 2 n + end names this vertex
                 ptr, order = csr_by_row(end_vert, B * V)
                 vert_grad = torch.empty((N, 2, 3), dtype=torch.float32, device=dev)
-                _lib.check(lib.md_antialias_bwd_pos(_ptr(act), N, _ptr(color), _ptr(g), _ptr(pairs), _ptr(pos_clip), _ptr(ptr),
-                                                    _ptr(order), B, V, H, W, C, _ptr(vert_grad), _ptr(dpos), _stream()),
-                           "md_antialias_bwd_pos")
+                call("md_antialias_bwd_pos", act, N, color, g, pairs, pos_clip, ptr, order, B, V, H, W, C, vert_grad, dpos)
         return dcolor, dpos, None, None, None
 
 
@@ -821,26 +788,22 @@ def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, view
 class _LaplaceUmbrellaFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, base, faces, ptr, order):
-        lib = _lib.load()
         V, F, dev = x.shape[0], faces.shape[0], x.device
         term = torch.empty((V, 3), dtype=torch.float32, device=dev)
         ws = torch.empty(_lib.LAPLACE_WORKSPACE_BYTES // 8, dtype=torch.float64, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        _lib.check(lib.md_laplace_umbrella(_ptr(x), _ptr(base), _ptr(faces), _ptr(ptr), _ptr(order), V, F, _ptr(term), _ptr(ws),
-                                           _ptr(loss), _stream()), "md_laplace_umbrella")
+        call("md_laplace_umbrella", x, base, faces, ptr, order, V, F, term, ws, loss)
         ctx.save_for_backward(term, faces, ptr, order)
         return loss.reshape(())
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
         term, faces, ptr, order = ctx.saved_tensors
         V, F = term.shape[0], faces.shape[0]
         g = g.to(torch.float32).reshape(1).contiguous()
         q, dx = torch.empty_like(term), torch.empty_like(term)
-        _lib.check(lib.md_laplace_umbrella_bwd(_ptr(term), _ptr(faces), _ptr(ptr), _ptr(order), _ptr(g), V, F, _ptr(q), _ptr(dx),
-                                               _stream()), "md_laplace_umbrella_bwd")
+        call("md_laplace_umbrella_bwd", term, faces, ptr, order, g, V, F, q, dx)
         return dx, None, None, None, None
 
 
@@ -1082,8 +1045,7 @@ def _shade_diffuse(r, v, f, cam, s, k):
     if f.shape[0] == 0 or v.shape[0] == 0:                                      # every id is above F
         return torch.zeros((B, H, W, 4), dtype=torch.float32, device=r.device)
     out = torch.empty((B, H, W, 4), dtype=torch.float32, device=r.device)
-    _lib.check(_lib.load().md_shade_diffuse(_ptr(r), _ptr(v), _ptr(f), _ptr(cam), _ptr(s), _ptr(k), B, v.shape[0], f.shape[0], H, W,
-                                            _ptr(out), _stream()), "md_shade_diffuse")
+    call("md_shade_diffuse", r, v, f, cam, s, k, B, v.shape[0], f.shape[0], H, W, out)
     return out
 
 

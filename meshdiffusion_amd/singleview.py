@@ -17,7 +17,7 @@ tools/fit_singleview.py is the command line around them.
 import torch
 
 from . import _lib
-from .hip_ops import _ptr, _stream
+from .hip_ops import call
 from .render import MAX_RES, MAX_VIEWS, _gpu_only, image_loss, rasterize, render_buffers, render_depth, xfm_points
 
 MAX_RADIUS = 15                          # VS_MAX_RADIUS of csrc/visibility.hip
@@ -47,7 +47,7 @@ def _check_radius(radius, what):
 
 def _window_min(rast, B, H, W, r):
     dmin = torch.empty((B, H, W), dtype=torch.float32, device=rast.device)
-    _lib.check(_lib.load().md_window_min(_ptr(rast), B, H, W, r, _ptr(dmin), _stream()), "md_window_min")
+    call("md_window_min", rast, B, H, W, r, dmin)
     return dmin
 
 
@@ -77,7 +77,7 @@ def visible_tets(rast, centres, mvp, radius=7):
     m = mvp.detach().to(device=dev, dtype=torch.float32).contiguous()
     dmin = _window_min(rast, B, H, W, r)
     visible = torch.empty((B, T), dtype=torch.uint8, device=dev)
-    _lib.check(_lib.load().md_tet_visibility(_ptr(dmin), _ptr(c), _ptr(m), B, T, H, W, _ptr(visible), _stream()), "md_tet_visibility")
+    call("md_tet_visibility", dmin, c, m, B, T, H, W, visible)
     return visible.view(torch.bool)
 
 
@@ -115,16 +115,14 @@ def label_vertices(visible, rast, face_tet, indices, n_verts):
     F = ft.shape[0]
     if F >= 2 ** 24:
         raise _lib.MeshDiffusionHipError(f"{what}: the rasteriser takes fewer than 2^24 faces (MD_ERR_UNSUPPORTED)")
-    lib = _lib.load()
     vis_u8 = visible.to(torch.uint8).contiguous() if visible.dtype != torch.bool else visible.contiguous().view(torch.uint8)
     rast_tet = None
     if F > 0:
         rast_tet = torch.zeros(T, dtype=torch.uint8, device=dev)
-        _lib.check(lib.md_rast_mark_tets(_ptr(rast), _ptr(ft), B, H, W, F, T, _ptr(rast_tet), _stream()), "md_rast_mark_tets")
+        call("md_rast_mark_tets", rast, ft, B, H, W, F, T, rast_tet)
     vis = torch.zeros(N, dtype=torch.float32, device=dev)
     vis_rast = torch.zeros(N, dtype=torch.uint8, device=dev)
-    _lib.check(lib.md_tets_mark_verts(_ptr(vis_u8), None if rast_tet is None else _ptr(rast_tet), _ptr(idx), B, T, N, _ptr(vis),
-                                      _ptr(vis_rast), _stream()), "md_tets_mark_verts")
+    call("md_tets_mark_verts", vis_u8, rast_tet, idx, B, T, N, vis, vis_rast)
     return vis, vis_rast.view(torch.bool)
 
 

@@ -131,6 +131,22 @@ def test_smoothing_exact_parts(hip_lib, name):
     assert torch.equal(one_three, postprocess.smooth(v, f, 3))
 
 
+def test_call_helper_passes_tensors_none_and_the_status(hip_lib):
+    """hip_ops.call, the one way the mesh-side modules reach an export: a tensor goes as its address, None as null (`scratch`, unused
+    with one step), the stream last; a refusal (n_verts = 0, before any launch) raises with the export's name and its code."""
+    from meshdiffusion_amd import _lib, postprocess
+    from meshdiffusion_amd.hip_ops import call
+    v, f = _gpu_mesh("quad")
+    ptr, adj = postprocess.mesh_edges(f, v.shape[0])[3:]
+    out = torch.full_like(v, float("nan"))
+    call("md_mesh_smooth", v, ptr, adj, v.shape[0], adj.numel(), 1, 0.5, float("nan"), out, None)
+    assert torch.equal(out, postprocess.smooth(v, f, 1))
+    with pytest.raises(_lib.MeshDiffusionHipError) as err:
+        call("md_mesh_smooth", v, ptr, adj, 0, adj.numel(), 1, 0.5, float("nan"), out, None)
+    print(f"\ncall: {err.value}")
+    assert "md_mesh_smooth" in str(err.value) and "-1" in str(err.value)
+
+
 def test_the_batched_form_equals_its_halves(hip_lib):
     from meshdiffusion_amd import postprocess
     pv, pf = _gpu_mesh("pair")

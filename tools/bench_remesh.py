@@ -78,23 +78,22 @@ def main():
     target = postprocess.remesh_default_target(verts, faces, vert_mesh, M)
     lo2, hi2 = (torch.as_tensor(t).cuda() for t in postprocess.remesh_bands(target))
     cos2 = float(rm.cos2_of(30.0))
-    lib = _lib.load()
     sx, sf, svm = verts.clone(), faces.clone(), vert_mesh.clone()
     for _ in range(a.iters):
         clock.key = "split"
-        sx, sf, svm, _n = clock.run("split", postprocess.remesh_split, sx, sf, svm, hi2, lib)
+        sx, sf, svm, _n = clock.run("split", postprocess.remesh_split, sx, sf, svm, hi2)
         clock.key = "collapse"
         for _r in range(_lib.REMESH_COLLAPSE_ROUNDS):
-            sx, sf, svm, n = clock.run("collapse", postprocess.remesh_collapse_round, sx, sf, svm, lo2, hi2, lib)
+            sx, sf, svm, n = clock.run("collapse", postprocess.remesh_collapse_round, sx, sf, svm, lo2, hi2)
             if n == 0:
                 break
         clock.key = "flip"
         for _r in range(_lib.REMESH_FLIP_ROUNDS):
-            sf, n = clock.run("flip", postprocess.remesh_flip_round, sx, sf, cos2, lib)
+            sf, n = clock.run("flip", postprocess.remesh_flip_round, sx, sf, cos2)
             if n == 0:
                 break
         clock.key = "relax"
-        sx = clock.run("relax", postprocess.remesh_relax, sx, sf, 0.5, lib)
+        sx = clock.run("relax", postprocess.remesh_relax, sx, sf, 0.5)
     postprocess._remesh_tables = build
     stepwise = torch.equal(sx, x) and torch.equal(sf, f)
 
