@@ -1131,6 +1131,28 @@ int md_remesh_relax(const float* verts, const int64_t* faces, const int32_t* ptr
                     const int32_t* corner, const int32_t* vflag, int64_t n_verts, int64_t n_edges, int64_t n_faces, float lam,
                     float* out, void* stream);
 
+/*
+ * Distance from points to triangle meshes (csrc/meshdist.hip): closest point and generalised winding number by brute force, for the
+ * warm start of the DMTet fit (meshdiffusion_amd/meshdist.py) and the re-projection of the remesher.  Purely additive:
+ * MD_ABI_VERSION stays 16.
+ *
+ * THE MESH DISTANCE CONTRACT (the header comment of csrc/meshdist.hip has it in full; tests/meshdist_cases.py restates it)
+ * md_mesh_query: tri float32 [T][3][3] gathered corners grouped by mesh, tri_ptr int32 [M+1] and query_ptr int32 [M+1] ascending
+ *   CSRs on the device (clamped by the kernel, not read by the export), query float32 [Q][3] grouped by mesh.  Outputs, each may be
+ *   NULL, one at least is not: dist2 float32 [Q], face int32 [Q] (index into tri, -1 when no triangle was taken), closest float32
+ *   [Q][3], winding float32 [Q].  Closest point: Ericson's region classification in fp32 without contraction on (a, b - a, c - a),
+ *   tests in the order A, B, C, AB, AC, BC, interior; triangles in ascending order, a candidate replaces the best only when d2 <
+ *   best (ties keep the lowest index, NaN is never taken); no triangle taken: +inf, -1, the query.  Winding: the sum over the mesh's
+ *   triangles of 2 atan2f(det, den) in float64 in ascending order, over 4 pi, rounded once; NaN in gives NaN.  No atomics: two
+ *   runs agree bit for bit, however the launch is cut up.  In this order: null or misaligned tri_ptr / query / query_ptr,
+ *   misaligned tri or output, no output: MD_ERR_BAD_ARG; a negative count, NULL tri with T > 0: MD_ERR_BAD_ARG; T or Q beyond
+ *   int32, M > MD_MESHDIST_MAX_MESHES: MD_ERR_UNSUPPORTED; an output that is an input: MD_ERR_BAD_ARG.  Q == 0 or M == 0: MD_OK,
+ *   nothing launched.  One mesh's triangles are not split over workgroups.  Nothing is allocated, nothing synchronises.
+ */
+#define MD_MESHDIST_MAX_MESHES 65535
+int md_mesh_query(const float* tri, const int32_t* tri_ptr, const float* query, const int32_t* query_ptr, int64_t n_tris,
+                  int64_t n_queries, int64_t n_meshes, float* dist2, int32_t* face, float* closest, float* winding, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,7 +191,9 @@ SIGNATURES = {
     "md_remesh_flip_claim": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "md_remesh_flip_apply": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
     "md_remesh_relax": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _F, _P, _P]),
+    "md_mesh_query": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
 }
+MESHDIST_MAX_MESHES = 65535                         # MD_MESHDIST_MAX_MESHES
 REMESH_COLLAPSE_ROUNDS = 8                          # MD_REMESH_COLLAPSE_ROUNDS
 REMESH_FLIP_ROUNDS = 4                              # MD_REMESH_FLIP_ROUNDS
 REMESH_MAX_ITERS = 32                               # MD_REMESH_MAX_ITERS

@@ -64,9 +64,11 @@
 //               compensated sum (md_kahan_add) of the neighbours in row order / (float)n, d = m - x; g = the plain sum, in the order of
 //               the corner row, of nrm(face) over the faces whose three indices are in range; n = g / sqrt(max(dot(g, g), 1e-20));
 //               t = dot(n, d); x' = x + lam * (d - n * t) per component.  lam == 0 skips the pass on the host.
-//   Not built   re-projection onto the input surface (it needs a closest-triangle search; each collapse to a midpoint moves inward by
-//               about L^2 / 8 R), feature-edge preservation, adaptive sizing, cotangent weights, collapses or flips that touch a
-//               boundary vertex at a or b.
+//   Projection  not a kernel of this file: with remesh(project=True) the host ends every iteration, after the relax, by replacing every
+//               vertex with its closest point on the input surface of its mesh (md_mesh_query, the mesh distance contract of
+//               csrc/meshdist.hip).  Without it each collapse to a midpoint moves inward by about L^2 / 8 R.
+//   Not built   feature-edge preservation, adaptive sizing, cotangent weights, collapses or flips that touch a boundary vertex at a
+//               or b.
 //   Safety      every loop is bounded by a row length or a constant; no kernel waits on another thread; within a launch two
 //               threads write the same word only through integer atomicMin / atomicAdd; rounds stop on the host at their cap,
 //               which is not an error.  The library allocates nothing.

@@ -143,14 +143,15 @@ def load_png(path):
 def samples_to_obj(samples, tet_vertices, tet_indices, out_dir, resolution=None, batch=32, device="cuda", start_index=0,
                    with_normals=False, smooth_steps=0, lam=0.5, mu=None, min_component_faces=0, min_component_fraction=0.0,
                    keep_largest=False, preview_dir=None, angle_ind=0, preview_res=512, preview_raw=True, remesh_iters=0,
-                   remesh_target_scale=1.0):
+                   remesh_target_scale=1.0, remesh_project=False):
     """samples: array [M,4,R,R,R] (or a path to the sampler's .npy).  Writes {out_dir}/{i:06d}.obj, returns their paths.
     with_normals: also write the smooth vertex normals the reference computes right after extraction
     (eval.py:422 `mesh.auto_normals`; its own OBJ export, eval.py:436-440, drops them); with a clean-up they are those of the
     cleaned mesh.
     smooth_steps, lam, mu, min_component_faces, min_component_fraction, keep_largest: the clean-up of `postprocess.postprocess`,
     run on each batch of meshes in one set of launches before the files are written (all off by default).
-    remesh_iters, remesh_target_scale: `postprocess.remesh` before and after the smoothing, as the reference's tail does (0 = off).
+    remesh_iters, remesh_target_scale: `postprocess.remesh` before and after the smoothing, as the reference's tail does (0 = off);
+    remesh_project: every remeshing iteration ends by projecting the vertices back onto the surface that remeshing started from.
     preview_dir: also write {preview_dir}/{i:06d}.png, `render.render_preview` at `preview_camera(angle_ind, preview_res)` of the
     raw mesh, as the reference renders before its clean-up, or with preview_raw=False of the cleaned mesh."""
     if isinstance(samples, (str, os.PathLike)):
@@ -172,7 +173,7 @@ def samples_to_obj(samples, tet_vertices, tet_indices, out_dir, resolution=None,
             from .postprocess import postprocess
             cleaned = postprocess(meshes, smooth_steps=smooth_steps, lam=lam, mu=mu, min_component_faces=min_component_faces,
                                   min_component_fraction=min_component_fraction, keep_largest=keep_largest, remesh_iters=remesh_iters,
-                                  remesh_target_scale=remesh_target_scale)
+                                  remesh_target_scale=remesh_target_scale, remesh_project=remesh_project)
         for k, (verts, faces, _face_tet) in enumerate(meshes):
             if preview_dir is not None:
                 pv, pf = (verts, faces) if preview_raw or cleaned is None else cleaned[k]
@@ -230,6 +231,7 @@ def main(argv=None):
     ap.add_argument("--keep_largest", action="store_true", help="keep only the largest connected component of each mesh")
     ap.add_argument("--remesh_iters", type=int, default=0, help="isotropic remeshing iterations before and after the smoothing (0 = off)")
     ap.add_argument("--remesh_target_scale", type=float, default=1.0, help="target edge length as a multiple of each mesh's mean edge length")
+    ap.add_argument("--remesh_project", action="store_true", help="end every remeshing iteration by projecting the vertices back onto the input surface")
     ap.add_argument("--preview_dir", default=None, help="directory for a diffuse quick-look PNG of each mesh")
     ap.add_argument("--angle_ind", type=int, default=0, help="camera pose of the preview, 0..50 around the object")
     ap.add_argument("--preview_res", type=int, default=512)
@@ -240,7 +242,7 @@ def main(argv=None):
                            smooth_steps=a.num_smooth_steps, lam=a.lam, mu=a.mu, min_component_faces=a.min_component_faces,
                            min_component_fraction=a.min_component_fraction, keep_largest=a.keep_largest, preview_dir=a.preview_dir,
                            angle_ind=a.angle_ind, preview_res=a.preview_res, preview_raw=not a.preview_post, remesh_iters=a.remesh_iters,
-                           remesh_target_scale=a.remesh_target_scale)
+                           remesh_target_scale=a.remesh_target_scale, remesh_project=a.remesh_project)
     print(f"wrote {len(paths)} meshes to {a.out}" + (f" and their previews to {a.preview_dir}" if a.preview_dir else ""))
 
 

@@ -5,10 +5,10 @@ The reference cleans each sampled mesh with pymeshlab at the end of nvdiffrec/ev
 `apply_coord_laplacian_smoothing(stepsmoothnum=--num_smooth_steps)`).  This module is built in the manner of that step under the
 mesh post-processing contract in the header comment of csrc/meshpost.hip, not bit-equal to MeshLab: uniform (umbrella) weights, a
 filter for the small disconnected shells that the sign noise of a sampled SDF leaves behind, and `remesh`, the isotropic remeshing
-(split, collapse, flip, relax) of the remeshing contract in the header comment of csrc/remesh.hip -- without re-projection onto the
-input surface, feature edges, adaptive sizing or cotangent weights.  The
-kernels run on the GPU only: a CPU tensor is an error, not a fallback.  The edge table, the compaction and the split / concat of a
-batch are torch plumbing.  Nothing here has a gradient: it runs after generation, not inside a fit.
+(split, collapse, flip, relax) of the remeshing contract in the header comment of csrc/remesh.hip -- with re-projection onto the
+input surface on request (`project=True`, the closest point of csrc/meshdist.hip), without feature edges, adaptive sizing or
+cotangent weights.  The kernels run on the GPU only: a CPU tensor is an error, not a fallback.  The edge table, the compaction and
+the split / concat of a batch are torch plumbing.  Nothing here has a gradient: it runs after generation, not inside a fit.
 """
 import ctypes
 import math
@@ -16,7 +16,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, meshdist
 from ._csr import INT32_MAX, check_faces, csr_by_row
 from .hip_ops import _gpu_only, call
 
@@ -308,13 +308,17 @@ def remesh_bands(target):
     return ((0.8 * t) ** 2).astype(np.float32), ((4.0 / 3.0 * t) ** 2).astype(np.float32)
 
 
-def remesh(verts, faces, *, iters=3, target_len=None, target_scale=1.0, relax=0.5, flip_angle=30.0, vert_mesh=None):
+def remesh(verts, faces, *, iters=3, target_len=None, target_scale=1.0, relax=0.5, flip_angle=30.0, vert_mesh=None, project=False):
     """Isotropic remeshing of a (concatenated) mesh by the remeshing contract (csrc/remesh.hip): `iters` iterations of split (edges
     longer than 4/3 L), collapse (shorter than 4/5 L), flip (towards valence six) and tangential relaxation (weight `relax`, 0 = off).
     L per mesh = (target_len float or [M], default the mesh's own mean edge length) * target_scale.  vert_mesh int [V] names the mesh
     of a vertex (None: one mesh), ascending.  Returns (verts' float32 [V',3], faces' int64 [F',3], vert_mesh' int32 [V'], info) with
     info = dict(target float32 numpy [M], iterations = [dict(splits, collapses, flips, collapse_rounds, flip_rounds), ...]).  GPU
-    only; the inputs are never written; two runs agree bit for bit.  Reaching a round cap is not an error."""
+    only; the inputs are never written; two runs agree bit for bit.  Reaching a round cap is not an error.
+    project=True keeps the checked input of this call as the reference surface and ends every iteration, after the relax, by
+    replacing every vertex with the closest point on the reference surface of its own mesh (the mesh distance contract of
+    csrc/meshdist.hip; a vertex whose mesh has no face stays); each iteration's record gains max_project_dist2, the largest squared
+    distance a vertex was moved by.  Without it the result is what it was before the flag existed, bit for bit."""
     _gpu_only(verts, "remesh")
     if verts.dim() != 2 or verts.shape[-1] != 3:
         raise ValueError(f"remesh: expected verts [V,3], got {tuple(verts.shape)}")
@@ -347,6 +351,8 @@ def remesh(verts, faces, *, iters=3, target_len=None, target_scale=1.0, relax=0.
         raise ValueError("remesh: every target length must be finite and > 0")
     lo2, hi2 = (torch.as_tensor(a, device=dev) for a in remesh_bands(target))
     cos2 = float(np.float32(math.cos(math.radians(flip_angle)) ** 2))
+    if project:
+        ref_tri, ref_ptr, _, _ = meshdist.mesh_triangles(x, f, vm, "remesh")
     info = []
     for _ in range(iters if V > 0 and f.shape[0] > 0 else 0):
         rec = dict(splits=0, collapses=0, flips=0, collapse_rounds=0, flip_rounds=0)
@@ -365,15 +371,19 @@ def remesh(verts, faces, *, iters=3, target_len=None, target_scale=1.0, relax=0.
                 break
         if relax != 0.0:
             x = remesh_relax(x, f, relax)
+        if project:
+            d2, _, x, _ = meshdist.mesh_query(x, ref_tri, ref_ptr, None, M, vm, "remesh", True, False)
+            rec["max_project_dist2"] = float(d2.max()) if d2.numel() > 0 else 0.0
         info.append(rec)
     return x, f, vm, dict(target=target, iterations=info)
 
 
 def postprocess(meshes, *, smooth_steps=0, lam=0.5, mu=None, min_component_faces=0, min_component_fraction=0.0, keep_largest=False,
-                remesh_iters=0, remesh_target_scale=1.0):
+                remesh_iters=0, remesh_target_scale=1.0, remesh_project=False):
     """The clean-up of a whole batch (a list of (verts, faces, ...) or a `dmtet.MeshBatch`) in one set of launches, in the
     reference's order: the floater filter first (when min_component_faces > 0, min_component_fraction > 0 or keep_largest), then,
-    with remesh_iters > 0, `remesh`, then `smooth_steps` smoothing steps, then `remesh` again.
+    with remesh_iters > 0, `remesh`, then `smooth_steps` smoothing steps, then `remesh` again (remesh_project: each of the two
+    with project=True, onto its own input).
     Returns a list of (verts float32 [V_m,3], faces int64 [F_m,3]).  With every keyword at its default the meshes come back as they
     are."""
     verts, faces, vert_mesh = concat_meshes(meshes)
@@ -385,9 +395,11 @@ def postprocess(meshes, *, smooth_steps=0, lam=0.5, mu=None, min_component_faces
                                                   keep_largest=keep_largest, vert_mesh=vert_mesh)
         vert_mesh = vert_mesh[vert_map >= 0]
     if remesh_iters > 0 and verts.shape[0] > 0:
-        verts, faces, vert_mesh, _ = remesh(verts, faces, iters=remesh_iters, target_scale=remesh_target_scale, vert_mesh=vert_mesh)
+        verts, faces, vert_mesh, _ = remesh(verts, faces, iters=remesh_iters, target_scale=remesh_target_scale, vert_mesh=vert_mesh,
+                                            project=remesh_project)
     if smooth_steps > 0 and verts.shape[0] > 0:
         verts = smooth(verts, faces, smooth_steps, lam, mu)
     if remesh_iters > 0 and verts.shape[0] > 0:
-        verts, faces, vert_mesh, _ = remesh(verts, faces, iters=remesh_iters, target_scale=remesh_target_scale, vert_mesh=vert_mesh)
+        verts, faces, vert_mesh, _ = remesh(verts, faces, iters=remesh_iters, target_scale=remesh_target_scale, vert_mesh=vert_mesh,
+                                            project=remesh_project)
     return split_meshes(verts, faces, vert_mesh, n)

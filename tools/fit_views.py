@@ -65,6 +65,8 @@ def main(argv=None):
     ap.add_argument("--fovy", type=float, default=math.radians(45.0))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--sphere_init", type=float, default=0.0, help="start from a sphere of this radius instead of the random SDF")
+    ap.add_argument("--mesh_init", action="store_true",
+                    help="start from the signed distance of the normalised target at the grid's vertices (meshdist.init_sdf) instead of the random SDF")
     ap.add_argument("--pass2_iters", type=int, default=0,
                     help="> 0: after the fit, this many iterations of the fixed-topology second pass; the pass-1 dict goes to tets_pre/ next to --out")
     ap.add_argument("--pass2_lr", type=float, default=0.01)
@@ -72,6 +74,8 @@ def main(argv=None):
     ap.add_argument("--second_stage_deform", type=float, default=None,
                     help="deform_scale of the second pass (default: --deform_scale); deform is rescaled by deform_scale / this")
     a = ap.parse_args(argv)
+    if a.mesh_init and a.sphere_init > 0:
+        ap.error("--mesh_init and --sphere_init exclude each other")
     if not torch.cuda.is_available():
         raise SystemExit("fit_views.py needs a GPU: the HIP path has no CPU fallback")
     from meshdiffusion_amd import mesh_export, render
@@ -93,6 +97,9 @@ def main(argv=None):
     if a.sphere_init > 0:
         with torch.no_grad():
             geo.sdf.copy_((a.sphere_init - geo.verts.norm(dim=1)).clamp(-1.0, 1.0))
+    if a.mesh_init:
+        from meshdiffusion_amd import meshdist
+        meshdist.init_sdf(geo, v, f)
 
     def report(it, loss, mesh):
         if it % 100 == 0 or it == a.iters - 1:
