@@ -2,6 +2,13 @@
 every computation happens in libmeshdiffusion_hip.so.  No fallback paths.
 
 Blocked device layouts: F32B float32 [B][C/8][P][8]; S16B bf16 [B][C/8][2][P][8].
+
+Which kernels a 3x3x3 convolution runs through is decided in one place, layers.plan_conv3 (-> Conv3Plan), from the `*_ok` predicates
+of this module and the flags of the conv's F32Operand; the predicates read shapes and the module state below, never tensor data.
+The environment is read for the arithmetic (MD_PRECISION, MD_FORCE_PRECISION, MD_WINO_EQ), the A/B switches bench.py, the tests or
+the documents still use (MD_WINO, MD_WINO_PREP_V2, MD_WINO_TRAIN_FWD, MD_PREP_COMPACT_UPS, MD_FUSE_GN_APPLY, MD_FUSE_ATTN,
+MD_PACK_BATCH, MD_DGRAD_F6, MD_DGRAD_LIFT) and nothing else: the switches of experiments that were closed (DESIGN.md section 3,
+docs/HISTORY.md) are gone, their measured thresholds (WINO_MIN_WGS, WINO_MIN_WGS_TRAIN, S2_MIN_WGS) are constants.
 """
 import ctypes as C
 import math
@@ -18,9 +25,6 @@ from ._lib import (A_PACKED, A_S16B, PREC_BF16X3, PREC_FP16X2, CFG_C3_128, CFG_C
 CFG_ABL1, CFG_ABL2, CFG_ABL3, CFG_ABL4, CFG_ABL5 = 101, 102, 103, 104, 105
 CFG_F1, CFG_F3, CFG_F4, CFG_F6, CFG_F7, CFG_F8 = 111, 113, 114, 116, 117, 118   # timing-only ablations of the dedicated kernel (MD_BUILD_ABLATIONS=1)
 CFG_FAST_EC = 122   # A/B variant of the dedicated kernel (valid results): early weight commit
-# shader cycles over which the dedicated conv kernel spreads the start of each CU's first workgroup (0 = off)
-CONV_STAGGER = int(os.environ.get("MD_CONV_STAGGER", "0"))
-DEBUG_ACT_FP16 = 2 if os.environ.get("MD_DEBUG_ACT_FP16") == "1" else 0   # precision experiment only
 # Arithmetic of the 3x3x3 conv kernels:
 #   "bf16x3"  three bf16 MFMAs per product, fp32 range: ~1.7e-5 per U-Net evaluation.  Training always runs in it.
 #   "f16f8"   bf16x3 everywhere except the INFERENCE Winograd convs behind a GroupNorm (md_wino_prep_f8 + md_conv3_wino_f8): a product
@@ -31,7 +35,7 @@ DEBUG_ACT_FP16 = 2 if os.environ.get("MD_DEBUG_ACT_FP16") == "1" else 0   # prec
 #   "fp16x2"  weights split fp16, activations one fp16 in the direct kernels (~1e-3 per evaluation): opt-in experiment.
 # f16f8 / f16f6 apply only where the operand comes out of GroupNorm (+ SiLU): there the static equaliser (md_wino_equaliser, WINO_EQ)
 # flattens the per-channel magnitudes the 4-bit-significand images are sensitive to.  Convs on the raw residual stream (Upsample)
-# keep bf16x3: nothing is known about their operand before the data arrives (F8_RAW=1: the round-4 behaviour, A/B only).
+# keep bf16x3: nothing is known about their operand before the data arrives (until a calibration measured it: CALIBRATE).
 #
 # The arithmetic is a property of the MODEL CALL, not of the process: DDPMUNet3D.forward / forward_train / backward enter
 # `precision_scope(config.model.hip_precision)` and leave it again, so a model never inherits what another one ran in.  Outside any
@@ -40,7 +44,6 @@ _MODES = ("bf16x3", "fp16x2", "f16f8", "f16f6")
 DEFAULT_PRECISION = os.environ.get("MD_PRECISION", "bf16x3")
 FORCE_PRECISION = os.environ.get("MD_FORCE_PRECISION")      # A/B runs of the test suite / CLI: wins over config.model.hip_precision in INFERENCE scopes
 WINO_EQ = os.environ.get("MD_WINO_EQ", "1") == "1"          # A/B: 0 = f16f8 / f16f6 without the static equaliser
-F8_RAW = os.environ.get("MD_F8_RAW", "0") == "1"            # A/B: 1 = f16f8 / f16f6 also on un-normalised operands (round 4)
 
 
 def _decode(mode):
@@ -107,20 +110,8 @@ def bump_param_epoch():
     PARAM_EPOCH += 1
 
 
-# A/B (MD_NIN_SIDE_STREAM=1): ResnetBlock shortcut GEMM on a second HIP stream next to Conv_0.  Measured neutral on
-# MI355X (62.3 vs 62.8 sample-steps/s): a 125 KB-LDS conv workgroup and the GEMM never share a CU, so the two
-# kernels only trade CUs.  Off by default.
-NIN_SIDE_STREAM = os.environ.get("MD_NIN_SIDE_STREAM", "0") == "1"
-_SIDE = {}
-
-
-def side_stream():
-    dev = torch.cuda.current_device()
-    if dev not in _SIDE:
-        _SIDE[dev] = torch.cuda.Stream(device=dev)
-    return _SIDE[dev]
-
-
+# (A ResnetBlock's shortcut GEMM on a second HIP stream next to Conv_0 was measured neutral on MI355X, 62.3 vs 62.8
+# sample-steps/s: a 125 KB-LDS conv workgroup and the GEMM never share a CU, so the two kernels only trade CUs.  That path is gone.)
 PROFILE = None   # set to a list by bench.py to collect (cfg, flops, start_event, end_event) per GEMM/conv launch
 AUDIT = None     # set to a list by tools/audit_precision.py: every f16f8 / f16f6 conv launch is repeated in bf16x3 and the difference recorded
 
@@ -220,7 +211,6 @@ class PackedWeight:
 
 _PACK_QUEUE = []      # (owner, job) pairs waiting for flush_packs()
 PACK_BATCH = os.environ.get("MD_PACK_BATCH", "1") == "1"   # A/B switch: 0 = one md_pack_weights / md_wino_pack_weights launch per weight
-PACK_TILED = os.environ.get("MD_PACK_TILED", "1") == "1"   # A/B switch: 0 = the batch packs every weight one item per thread
 
 
 def flush_packs():
@@ -247,13 +237,13 @@ def _flush(queue):
         outs.append(torch.empty(j["nbytes"] // 2, dtype=torch.bfloat16, device=j["w"].device))
     if PACK_BATCH and len(queue) > 1 and len({j["w"].device for _, j in queue}) == 1:
         def tiled(j):      # block-cooperative form (md_pack_tiled_kernel): the 3x3x3 weights -- most of the parameters
-            return (PACK_TILED and j["kind"] == _lib.PACK_WPK and j["taps"] > 1 and abs(j["s_tap"]) == 1
+            return (j["kind"] == _lib.PACK_WPK and j["taps"] > 1 and abs(j["s_tap"]) == 1
                     and 16 * j["kc"] * j["taps"] <= 13824 and j["nt"] % 16 == 0)
 
         def mode(j):       # md_pack_batch `tiled` argument for this job
             if j["kind"] == _lib.PACK_WINO_F6:
                 return 0
-            if PACK_TILED and j["kind"] == _lib.PACK_WINO:
+            if j["kind"] == _lib.PACK_WINO:
                 return 3
             if not tiled(j):
                 return 0
@@ -356,30 +346,57 @@ def pack_s16b_from_matrix(w_kp, device):
 # ---------------------------------------------------------------------------------------------
 # GEMM / conv
 # ---------------------------------------------------------------------------------------------
+class F32Operand:
+    """The B operand of a conv / GEMM as fp32 F32B tensors instead of an S16B split (`b_f32` of gemm_conv, layers.run_conv3,
+    layers.run_gemm).  A field that does not exist raises (a misspelt flag must not silently pick another route).
+    Inputs, set by the caller:
+      parts      [(F32B tensor, C), ...] (1 or 2): stands for their concatenation along the channels
+      ac         folded GroupNorm affine [B][K][2] (gn_params(want_ac=True)) applied while loading, or None
+      silu       SiLU after the affine
+      drop       (p, seed): training dropout after SiLU (Winograd operand pass only)
+      keep       training, layers with wgrad_wino_ok: the Winograd operand T gets a tensor of its own and comes back as `t_kept`
+      wino_only  training: describes the operand of the Winograd path only; the direct kernel keeps reading the S16B activation
+      nin        (PackedWeight, bias) of a ResnetBlock's shortcut NIN on the same parts: a shortcut is wanted
+    Outputs, reset to None by layers.run_conv3 on entry and filled where the route produces them:
+      t_kept     the kept operand T (`keep`, Winograd path)
+      shortcut   NIN(parts) (`nin`), where the conv's operand pass wrote it too (block_pass_ok); None: the caller computes it"""
+    __slots__ = ("parts", "ac", "silu", "drop", "keep", "wino_only", "nin", "t_kept", "shortcut")
+
+    def __init__(self, parts, ac=None, silu=False, drop=None, keep=False, wino_only=False, nin=None):
+        self.parts, self.ac, self.silu, self.drop, self.nin = parts, ac, bool(silu), drop, nin
+        self.keep, self.wino_only = bool(keep), bool(wino_only)
+        self.t_kept = self.shortcut = None
+
+    @classmethod
+    def of(cls, b_f32):
+        """None, an F32Operand, or (callers older than this class) a dict of its INPUT fields turned into one: an unknown key raises."""
+        return cls(**b_f32) if isinstance(b_f32, dict) else b_f32
+
+
 def gemm_conv(*, cfg, a, b, out, batch, rows, rows_alloc, kdim, dims, bias=None, bias_bstride=0,
               residual=None, res_bstride=0, alpha=1.0, ups=0, a_src=A_PACKED, a_rows=0, a_bstride=0,
-              b_bstride=None, out_mode=OUT_F32B, ksplit=1, prec=PREC_BF16X3, stats=None, stagger=None,
+              b_bstride=None, out_mode=OUT_F32B, ksplit=1, prec=PREC_BF16X3, stats=None, stagger=0,
               b_f32=None):
     """stats: optional zeroed float64 [batch][rows_alloc][2] receiving per-(sample, channel) sum / sum of squares of
     the output (F32B output: CFG_C3_128_FAST's epilogue, or with ksplit > 1 any configuration's split-K finish kernel).
-    b_f32: dict(parts=[(F32B tensor, C), ...] (1 or 2), ac=[B][K][2] or None, silu=bool): the B operand is read as fp32
+    b_f32: F32Operand(parts, ac, silu): the B operand is read as fp32
     and GroupNorm affine + SiLU + the bf16 split happen in the kernel's halo loader (MD_B_F32B_GN; `b` is ignored):
     CFG_C3_128_FAST (also with `ups`), CFG_C3_LOW, and split-only (ac = None) the 1x1x1 configurations CFG_G1_128 / _N128."""
     lib = _lib.load()
+    b_f32 = F32Operand.of(b_f32)
     D, H, W = dims
     args = MdGemmConvArgs()
     args.a, args.out = a.data_ptr(), out.data_ptr()
     if b_f32 is not None:
-        parts = b_f32["parts"]
+        parts = b_f32.parts
         assert 1 <= len(parts) <= 2 and sum(c for _, c in parts) == kdim and all(c % 8 == 0 for _, c in parts)
         pin = D * H * W // (8 if ups else 1)
         args.b, args.b_split = parts[0][0].data_ptr(), parts[0][1]
         b_bstride = parts[0][1] * pin                       # floats between batches of part 1
         if len(parts) == 2:
             args.b2, args.b2_bstride = parts[1][0].data_ptr(), parts[1][1] * pin
-        ac = b_f32.get("ac")
-        args.b_ac = ac.data_ptr() if ac is not None else None
-        args.b_silu = 1 if b_f32.get("silu") else 0
+        args.b_ac = b_f32.ac.data_ptr() if b_f32.ac is not None else None
+        args.b_silu = 1 if b_f32.silu else 0
         args.b_mode = _lib.B_F32B_GN
     else:
         args.b = b.data_ptr()
@@ -400,7 +417,7 @@ def gemm_conv(*, cfg, a, b, out, batch, rows, rows_alloc, kdim, dims, bias=None,
     args.b_bstride = b_bstride
     args.prec = prec
     args.stats = stats.data_ptr() if stats is not None else None
-    args.stagger = CONV_STAGGER if stagger is None else int(stagger)
+    args.stagger = int(stagger)    # shader cycles over which the dedicated kernel spreads the start of each CU's first workgroup (tools/bench_conv.py)
     part = None
     if ksplit > 1:
         if out_mode != OUT_F32B:
@@ -600,8 +617,8 @@ def wino_operand_ms(parts, ac, silu, B, P):
 # workgroups beats the direct bf16x3 kernel with split-K: res64 B = 1 15.00 -> 14.50 ms per step at 128 (the 32^3 level), 14.59 at 64, 15.38 at
 # 32 (profiles/r05_b1_wino_floor.txt); sampling at batches >= 2 of the registered configs is unaffected (every level already has >= 256).
 # Training steps (precision_scope(training=True)) keep 256: their kernels are the ones the gradient goldens and the B = 8 bench pinned.
-WINO_MIN_WGS = int(os.environ.get("MD_WINO_MIN_WGS", "128"))
-WINO_MIN_WGS_TRAIN = int(os.environ.get("MD_WINO_MIN_WGS_TRAIN", "256"))
+WINO_MIN_WGS = 128
+WINO_MIN_WGS_TRAIN = 256
 
 
 def wino_ok(rows, kdim, S, B):
@@ -610,11 +627,9 @@ def wino_ok(rows, kdim, S, B):
             and B * (S ** 3 // 256) * (rows // 128) >= (max(WINO_MIN_WGS, WINO_MIN_WGS_TRAIN) if TRAINING_SCOPE else WINO_MIN_WGS))
 
 
-WGRAD_NIN = os.environ.get("MD_WGRAD_NIN", "1") == "1"   # NIN weight gradients straight from S16B tensors (md_wgrad_nin)
-
-
 def wgrad_nin_ok(co, ci, P):
-    return WGRAD_NIN and co % 128 == 0 and ci % 128 == 0 and P % 16 == 0
+    """NIN weight gradients straight from S16B tensors (md_wgrad_nin)."""
+    return co % 128 == 0 and ci % 128 == 0 and P % 16 == 0
 
 
 def wgrad_nin(dy_s16, x_s16, B, co, ci, P, dw):
@@ -659,7 +674,7 @@ def wino_f8_ok(S, drop=None, keep=False, parts=None, normalised=True):
     two-phase operand pass takes, whose operand comes out of a GroupNorm (`normalised`: the static equaliser applies; the raw
     residual stream in front of an Upsample conv stays in bf16x3).  Returns False or the cross-term format ("f8" / "f6"; f6 needs
     whole 16-channel blocks per part and falls back to f8 otherwise)."""
-    if not (WINO_F8 and PRECISION == "bf16x3" and not drop and not keep and 256 % S == 0 and (normalised or F8_RAW)):
+    if not (WINO_F8 and PRECISION == "bf16x3" and not drop and not keep and 256 % S == 0 and normalised):
         return False
     if WINO_F8 == "f6" and parts is not None and any(c % 16 for _, c in parts):
         return "f8"
@@ -742,12 +757,9 @@ def wino_prep(parts, ac, silu, ups, B, S, drop=None, keep=False, dual=False, sum
 
 # Winograd weight gradient (csrc/wgrad_wino.hip): the training backward of the layers on the Winograd path contracts the
 # forward's operand T (kept on the tape) with the transformed output gradient -- no S16B activations, no PB16 re-layout
-WGRAD_WINO = os.environ.get("MD_WGRAD_WINO", "1") == "1"
-
-
 def wgrad_wino_ok(co, ci, S, B):
     """Layers whose weight gradient md_wgrad_wino takes: on the Winograd forward path, whole 128-channel tiles, rows of 16 / 32 pairs."""
-    return WGRAD_WINO and WINO_TRAIN_FWD and S in (32, 64) and co % 128 == 0 and ci % 128 == 0 and wino_ok(co, ci, S, B)
+    return WINO_TRAIN_FWD and S in (32, 64) and co % 128 == 0 and ci % 128 == 0 and wino_ok(co, ci, S, B)
 
 
 def wgrad_wino(u_dy, t_act, B, co, ci, S, dw):
@@ -763,9 +775,6 @@ def wgrad_wino(u_dy, t_act, B, co, ci, S, dw):
     check(lib.md_wgrad_wino(_ptr(u_dy), _ptr(t_act), _ptr(dw), _ptr(ws), nbytes, B, co, ci, S, S, S, ksplit, ci * 27, 27, 1,
                             _stream()), "md_wgrad_wino")
     _prof_end(ev, "wgrad_wino", 2.0 * B * co * ci * 27 * S ** 3, 16.0 * B * (co + ci) * S ** 3 / 2, f"{ci}->{co}@{S}x{S}x{S}")
-
-
-WINO_VARIANT = int(os.environ.get("MD_WINO_VARIANT", "0"))
 
 
 def conv3_wino(ww, t, B, S, *, bias=None, bias_bstride=0, residual=None, res_bstride=0, stats=None, out=None, variant=None, out_scale=1.0,
@@ -798,7 +807,7 @@ def conv3_wino(ww, t, B, S, *, bias=None, bias_bstride=0, residual=None, res_bst
                  _ptr(stats), B, ww.kdim, ww.rows, D, H, W, _stream()), "md_conv3_wino_" + ww.fmt)
     else:
         check(lib.md_conv3_wino(_ptr(t), _ptr(ww.data), _ptr(out), _ptr(bias), bias_bstride, _ptr(residual), res_bstride,
-                                _ptr(stats), B, ww.kdim, ww.rows, D, H, W, WINO_VARIANT if variant is None else variant, _stream()),
+                                _ptr(stats), B, ww.kdim, ww.rows, D, H, W, 0 if variant is None else variant, _stream()),
               "md_conv3_wino")
     _prof_end(ev, "wino", 2.0 * B * ww.rows * ww.kdim * 27 * P,
               4.0 * (2 * B * ww.kdim * P + ww.rows * ww.kdim * 36 + B * ww.rows * P * (2 if residual is not None else 1)),
@@ -808,17 +817,15 @@ def conv3_wino(ww, t, B, S, *, bias=None, bias_bstride=0, residual=None, res_bst
 
 
 # Stride-2 3x3x3 convolution of Downsample on the raw fp32 tensor (csrc/conv3_s2.hip): no split pass, slab-wise K loop
-CONV3_S2 = os.environ.get("MD_CONV3_S2", "1") == "1"   # A/B switch: 0 = md_gn_apply (split) + md_gemm_conv(CFG_C3_S2)
+# (instead of md_gn_apply (split) + md_gemm_conv(CFG_C3_S2))
 CFG_S2_PACK = CFG_C3_128_K16                           # tile geometry of its packed weights: nt = 128, kc = 16, 27 taps
-
-
-S2_MIN_WGS = int(os.environ.get("MD_S2_MIN_WGS", "100"))   # no split-K in md_conv3_s2: below this the generic tile (split-K) is faster
+S2_MIN_WGS = 100                                       # no split-K in md_conv3_s2: below this the generic tile (split-K) is faster
 
 
 def conv3_s2_ok(rows, kdim, S_out, B=None):
     """Shapes md_conv3_s2 takes; with `B`: and is launched with enough workgroups for (measured, B = 8: 16^3 outputs 0.16 ms
     against 0.20 + the split pass; 8^3 outputs = 32 workgroups 0.25 against 0.10)."""
-    ok = CONV3_S2 and PRECISION == "bf16x3" and kdim % 32 == 0 and rows % 8 == 0 and S_out % 8 == 0
+    ok = PRECISION == "bf16x3" and kdim % 32 == 0 and rows % 8 == 0 and S_out % 8 == 0
     return ok and (B is None or B * (S_out ** 3 // 256) * ((rows + 127) // 128) >= S2_MIN_WGS)
 
 
@@ -840,11 +847,9 @@ def conv3_s2(pw, x, B, S_out, *, bias=None, bias_bstride=0, stats=None, out=None
 
 
 # The dx-folded 3x3x3 stem in its own kernel (csrc/conv3_stem.hip), with the GroupNorm sums of its output
-CONV3_STEM = os.environ.get("MD_CONV3_STEM", "1") == "1"   # A/B switch: 0 = md_gemm_conv(CFG_C3X_128_K16) + md_gn_stats
-
-
+# (instead of md_gemm_conv(CFG_C3X_128_K16) + md_gn_stats)
 def conv3_stem_ok(rows, kdim, S):
-    return CONV3_STEM and PRECISION == "bf16x3" and kdim == 16 and rows % 8 == 0 and S % 8 == 0
+    return PRECISION == "bf16x3" and kdim == 16 and rows % 8 == 0 and S % 8 == 0
 
 
 def conv3_stem(pw, x16, B, S, *, bias=None, residual=None, stats=None, dims=None):
@@ -863,12 +868,12 @@ def conv3_stem(pw, x16, B, S, *, bias=None, residual=None, stats=None, dims=None
 
 
 # GroupNorm + SiLU + dx-folded 3x3x3 head in one kernel (csrc/conv3_head.hip): no md_gn_apply pass, no generic tile
-CONV3_HEAD = os.environ.get("MD_CONV3_HEAD", "1") == "1"   # A/B switch: 0 = md_gn_apply + md_gemm_conv(CFG_C3X_32)
+# (instead of md_gn_apply + md_gemm_conv(CFG_C3X_32))
 CFG_HEAD_PACK = CFG_C5X_32_K16                             # tile geometry of its packed weights: nt = 32, kc = 16
 
 
 def conv3_head_ok(rows, cin, S):
-    return CONV3_HEAD and FUSE_GN_APPLY and PRECISION == "bf16x3" and rows <= 32 and cin % 32 == 0 and S % 8 == 0
+    return FUSE_GN_APPLY and PRECISION == "bf16x3" and rows <= 32 and cin % 32 == 0 and S % 8 == 0
 
 
 def conv3_head(pw, x, ac, B, S, rows_alloc, dims=None):
@@ -905,23 +910,19 @@ def _prof_end(e0, cfg, flops, abytes, tag):
 # GroupNorm (+SiLU) + split, with concatenated sources
 # ---------------------------------------------------------------------------------------------
 FUSE_GN_APPLY = os.environ.get("MD_FUSE_GN_APPLY", "1") == "1"   # GroupNorm affine + SiLU + split inside the conv's halo loader (inference)
-FUSE_GN_STATS = True     # take GroupNorm sums from the producing conv's epilogue when it recorded them (A/B switch)
-SPLITK_STATS = os.environ.get("MD_SPLITK_STATS", "1") == "1"   # ... and from the split-K finish kernel (8^3 / 4^3 levels)
+FUSE_GN_STATS = True     # take GroupNorm sums from the producing conv's epilogue, or from the split-K finish kernel (8^3 / 4^3 levels), when it recorded them (A/B switch)
 
 
 # GroupNorm sum buffers ([B][C][2] float64, zero before the producing conv's epilogue / md_gn_stats adds into them) come
 # out of one arena per device that the U-Net zeroes ONCE at the start of a forward (stats_arena_reset): ~90 fill launches
 # per sampling step otherwise (torch.zeros per conv, md_zero per GroupNorm).  Without a reset nothing is ever handed out
 # twice: an exhausted arena is replaced by a fresh zeroed one.
-STATS_ARENA = os.environ.get("MD_STATS_ARENA", "1") == "1"
 _STATS_ARENAS = {}
 _STATS_ARENA_DOUBLES = 1 << 20
 
 
 def stats_arena_reset(device):
     """Start of a forward: everything handed out before is dead (consumed by the GroupNorms of the previous forward)."""
-    if not STATS_ARENA:
-        return
     a = _STATS_ARENAS.get(device)
     if a is None:
         return
@@ -933,7 +934,7 @@ def stats_arena_reset(device):
 def stats_zeros(B, rows, device):
     """Zeroed float64 [B][rows][2]."""
     n = B * rows * 2
-    if not STATS_ARENA or n > _STATS_ARENA_DOUBLES // 4:
+    if n > _STATS_ARENA_DOUBLES // 4:
         return torch.zeros((B, rows, 2), dtype=torch.float64, device=device)
     device = torch.device(device)
     if device.index is None:
@@ -999,7 +1000,7 @@ def gn_apply(parts, params, B, P, norm=True, silu=True, out=None, fp16=False, wa
     off = 0
     for t, c in parts:
         check(lib.md_gn_apply(_ptr(t), _ptr(params) if norm else None, _ptr(out), _ptr(raw), B, c, P, ctot, off,
-                              1 if norm else 0, (1 if silu else 0) | DEBUG_ACT_FP16 | (4 if fp16 else 0), dp, dseed,
+                              1 if norm else 0, (1 if silu else 0) | (4 if fp16 else 0), dp, dseed,
                               _stream()),
               "md_gn_apply")
         off += c
@@ -1088,12 +1089,10 @@ def s16b_to_ncdhw(x, spatial):
     return out
 
 
-NIN_STREAM = os.environ.get("MD_NIN_STREAM", "1") == "1"   # persistent streaming kernel for the HBM-bound shortcut NINs
-
-
 def nin_stream_ok(parts, rows, P):
+    """Shapes of md_nin_f32: the persistent streaming kernel for the HBM-bound shortcut NINs."""
     k = sum(c for _, c in parts)
-    return (NIN_STREAM and rows == 128 and k in (128, 256) and len(parts) <= 2 and all(c % 16 == 0 for _, c in parts)
+    return (rows == 128 and k in (128, 256) and len(parts) <= 2 and all(c % 16 == 0 for _, c in parts)
             and P % 256 == 0 and P >= 32768)
 
 
@@ -1109,14 +1108,11 @@ def nin_f32(parts, pw, bias, B, P, out=None):
 
 
 # A ResnetBlock with a NIN shortcut reads its input once: Conv_0's f16f6 operand and the shortcut from one kernel
-# (md_wino_prep_f6_nin; A/B switch, 0 = md_wino_prep_f6 + md_nin_f32, same bits either way)
-BLOCK_PASS = os.environ.get("MD_BLOCK_PASS", "1") == "1"
-
-
+# (md_wino_prep_f6_nin; the same bits as md_wino_prep_f6 + md_nin_f32)
 def block_pass_ok(parts, rows, B, D, H, W):
     """Shapes md_wino_prep_f6_nin takes: those of the f16f6 operand pass and of md_nin_f32 (nin_stream_ok)."""
     P = D * H * W
-    return bool(BLOCK_PASS and WINO_PREP_V2 and nin_stream_ok(parts, rows, P) and 256 % W == 0 and W % 2 == 0 and P <= 1 << 25
+    return bool(WINO_PREP_V2 and nin_stream_ok(parts, rows, P) and 256 % W == 0 and W % 2 == 0 and P <= 1 << 25
                 and B * (P // 256) < 1 << 31)
 
 
@@ -1284,12 +1280,10 @@ def conv_cfg_for(spatial, stride=1):
     return CFG_C3_128_FAST if spatial % 8 == 0 else CFG_C3_LOW
 
 
-NIN_N128 = os.environ.get("MD_NIN_N128", "1") == "1"   # A/B: 128-column GEMM tile (3 workgroups / CU) for the HBM-bound shortcut NINs
-
-
 def gemm_cfg_for(ncols, nrows, hbm_bound=False):
-    """hbm_bound: a 1x1x1 layer over a big grid with few channels (ResnetBlock shortcut): prefer the 128-column tile."""
-    if hbm_bound and NIN_N128 and ncols % 128 == 0 and ncols >= 32768:
+    """hbm_bound: a 1x1x1 layer over a big grid with few channels (ResnetBlock shortcut): prefer the 128-column tile
+    (3 workgroups / CU)."""
+    if hbm_bound and ncols % 128 == 0 and ncols >= 32768:
         return CFG_G1_128_N128
     if ncols % 256 == 0:
         return CFG_G1_128

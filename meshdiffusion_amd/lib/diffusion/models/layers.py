@@ -13,6 +13,7 @@ Each layer has two entry points:
                                   torch.cat(parts, dim=1) without materialising the concat.
 """
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -159,90 +160,82 @@ def fused_operand_ok(pw, ups=0):
     return ops.FUSE_GN_APPLY and pw.cfg in cfgs and pw.prec == ops.PREC_BF16X3
 
 
+class Conv3Plan(NamedTuple):
+    """Which kernels one 3x3x3 convolution runs through (plan_conv3); run_conv3 consults nothing else."""
+    path: str                  # "wino": md_wino_prep* + md_conv3_wino*; "direct": md_gemm_conv
+    fmt: object                # wino: False (bf16x3) | "f8" | "f6", the cross-term format of operand and weights
+    compact: bool              # wino: the upsampled operand once per source row (md_wino_prep_upsdh + md_conv3_wino_upsdh)
+    shortcut_in_pass: bool     # wino: the operand pass also writes the block's NIN shortcut (md_wino_prep_f6_nin)
+    keep: bool                 # wino: T in a tensor of its own, handed back for the Winograd weight gradient
+    stats: bool                # this launch accumulates the GroupNorm sums of its output
+    ksplit: int                # direct: split-K factor
+    fused_loader: bool         # direct: the kernel reads the fp32 parts itself (GroupNorm affine + SiLU + split in its halo loader)
+
+
+def plan_conv3(pw, operand, B, S_out, *, ups, out_mode, rows_alloc, want_stats, wino):
+    """The route of run_conv3(pw, ..., b_f32=operand, wino=wino): from shapes, channel counts, the operand's flags, the layer's
+    calibration state (wino.measured(), owner.md_bf16x3_sites) and the hip_ops module state.  Reads no tensor data, launches nothing."""
+    P = S_out ** 3
+    plain = out_mode == ops.OUT_F32B and rows_alloc == pw.rows      # what the Winograd kernels and every statistics epilogue write
+    sums = bool(want_stats and ops.FUSE_GN_STATS and plain)         # asked for, switched on, a layout an epilogue can sum
+    if (operand is not None and wino is not None and plain and pw.prec == ops.PREC_BF16X3
+            and ops.wino_ok(pw.rows, pw.kdim, S_out, B)):
+        # reduced precision, the compact operand and the block pass are inference layouts: no dropout, T not kept for a backward
+        infer = not (operand.wino_only or operand.drop or operand.keep)
+        # f16f8 / f16f6: inference operands that come out of a GroupNorm (the layer's static equaliser flattens their channels), or
+        # any operand whose layer holds a measured equaliser (DDPMUNet3D.calibrate); an uncalibrated raw residual stream (Upsample:
+        # ac None) stays in bf16x3
+        fmt = infer and ops.wino_f8_ok(
+            S_out, parts=operand.parts, normalised=operand.ac is not None
+            or (ops.WINO_EQ and hasattr(wino, "measured") and wino.measured() is not None))     # measured: only with its equaliser
+        owner = getattr(wino, "owner", None)
+        if fmt and owner is not None and wino.site in getattr(owner, "md_bf16x3_sites", ()):
+            fmt = False                  # this conv was taken off the reduced-precision path (layer.md_bf16x3_sites: tools/audit_precision.py)
+        # inference: an upsampled operand is written once per source row (the training forward keeps the full layout: md_wgrad_wino reads it)
+        compact = infer and ops.prep_compact_ok(ups, S_out, S_out, S_out)
+        # a block with a NIN shortcut: the shortcut comes out of the operand pass, which holds the block input anyway
+        shortcut = bool(operand.nin is not None and fmt == "f6" and not compact and not ups
+                        and ops.block_pass_ok(operand.parts, operand.nin[0].rows, B, S_out, S_out, S_out))
+        return Conv3Plan("wino", fmt, compact, shortcut, operand.keep, sums, 1, False)
+    ksplit = ops.ksplit_for(pw.cfg, B, pw.rows, pw.kdim, S_out) if out_mode == ops.OUT_F32B else 1
+    # statistics of the output: the dedicated kernel's epilogue, or (8^3 / 4^3 levels) the split-K finish kernel
+    # (one block per (sample, 8-channel group) there: only where that fills the chip -- at B = 1 the 32^3 level would run on 16 blocks)
+    sums = sums and ((pw.cfg == ops.CFG_C3_128_FAST and ksplit == 1) or (ksplit > 1 and P <= 512 and B * rows_alloc >= 2048))
+    # training (`wino_only`): the direct kernel takes the taped S16B activation, not the fp32 parts
+    return Conv3Plan("direct", False, False, False, False, sums, ksplit, operand is not None and not operand.wino_only)
+
+
 def run_conv3(pw, act_s16, B, S_out, *, bias=None, bias_bstride=0, residual=None, res_bstride=None, ups=0,
               out=None, out_mode=ops.OUT_F32B, rows_alloc=None, want_stats=False, b_f32=None, wino=None):
     """3x3x3 conv of an S16B activation tensor with packed weights `pw` on an S_out^3 output grid.
-    want_stats: the output feeds a GroupNorm -- when the launch allows it (dedicated kernel, no split-K) its
-    epilogue also accumulates the per-(sample, channel) sums, attached to the result as `_md_sums`.
-    b_f32 (see hip_ops.gemm_conv): fp32 parts + folded GroupNorm affine instead of `act_s16` (fused_operand_ok); with
-    `wino_only` (training: `drop` = (p, seed) allowed) it only describes the operand of the Winograd path and the direct
-    kernel keeps reading `act_s16`.
+    want_stats: the output feeds a GroupNorm -- when the launch allows it (Winograd or dedicated kernel, split-K finish) it
+    also accumulates the per-(sample, channel) sums, attached to the result as `_md_sums`.
+    b_f32 (hip_ops.F32Operand, which documents its flags and the two products handed back through it): fp32 parts + folded
+    GroupNorm affine instead of `act_s16` (fused_operand_ok); `act_s16` may be None where nothing reads it (inference; training
+    layers with b_f32.keep).
     wino (with b_f32): builder of the layer's WinoWeight (conv3_wino_packed); where hip_ops.wino_ok says so the conv runs as
     md_wino_prep + md_conv3_wino (Winograd F(2,3) along w: 2/3 of the matrix-core work) instead of the direct kernel.
-    b_f32["nin"] = (pwn, bias) (inference, a ResnetBlock's shortcut NIN on the same parts): where the conv's operand pass can also
-    write the shortcut (hip_ops.block_pass_ok, f16f6) it does, handed back as b_f32["res_out"]; otherwise the key is left unset.
-    b_f32["keep"] (training, layers with hip_ops.wgrad_wino_ok): the operand T is allocated on its own and handed back as
-    b_f32["t_out"]; `act_s16` may then be None (nothing else reads the S16B activation of such a layer)."""
+    The route is plan_conv3's; what follows only carries it out."""
     P = S_out ** 3
-    dev = act_s16.device if act_s16 is not None else b_f32["parts"][0][0].device
+    b_f32 = ops.F32Operand.of(b_f32)
+    dev = act_s16.device if act_s16 is not None else b_f32.parts[0][0].device
     rows_alloc = rows_alloc if rows_alloc is not None else ((pw.rows + 7) // 8) * 8
     if out is None:
         out = ops.f32b_empty(B, rows_alloc, P, dev)
     if residual is not None and res_bstride is None:
         res_bstride = rows_alloc * P
-    if (b_f32 is not None and wino is not None and out_mode == ops.OUT_F32B and rows_alloc == pw.rows
-            and pw.prec == ops.PREC_BF16X3 and ops.wino_ok(pw.rows, pw.kdim, S_out, B)):
-        stats = ops.stats_zeros(B, rows_alloc, dev) if want_stats and ops.FUSE_GN_STATS else None
-        # f16f8 / f16f6: inference operands that come out of a GroupNorm (the layer's static equaliser flattens their channels), or
-        # any operand whose layer holds a measured equaliser (DDPMUNet3D.calibrate); an uncalibrated raw residual stream (Upsample:
-        # ac None) stays in bf16x3
-        owner = getattr(wino, "owner", None)
-        if ops.CALIBRATE is not None and owner is not None and not b_f32.get("wino_only"):
-            # calibration evaluation: what this conv's operand really looks like, per input channel (nearest-x2 upsampling does not
-            # change a channel's mean square: measured on the coarse tensor)
-            ms = ops.wino_operand_ms(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), B, b_f32["parts"][0][0].shape[2])
-            rec = ops.CALIBRATE.setdefault((id(owner), wino.site), [owner, wino.site, torch.zeros_like(ms), 0])
-            rec[2] += ms
-            rec[3] += 1
-        f8 = (not b_f32.get("wino_only")) and ops.wino_f8_ok(
-            S_out, drop=b_f32.get("drop"), keep=bool(b_f32.get("keep")), parts=b_f32["parts"],
-            normalised=b_f32.get("ac") is not None
-            or (ops.WINO_EQ and hasattr(wino, "measured") and wino.measured() is not None))     # measured: only with its equaliser
-        if f8 and owner is not None and wino.site in getattr(owner, "md_bf16x3_sites", ()):
-            f8 = False                   # this conv was taken off the reduced-precision path (layer.md_bf16x3_sites: tools/audit_precision.py)
-        # inference: an upsampled operand is written once per source row (the training forward keeps the full layout: md_wgrad_wino reads it)
-        compact = (not b_f32.get("wino_only")) and ops.prep_compact_ok(ups, S_out, S_out, S_out, drop=b_f32.get("drop"), keep=bool(b_f32.get("keep")))
-        nin = b_f32.get("nin")
-        if (nin is not None and f8 == "f6" and not compact and not ups and not b_f32.get("drop") and not b_f32.get("keep")
-                and not b_f32.get("wino_only") and ops.block_pass_ok(b_f32["parts"], nin[0].rows, B, S_out, S_out, S_out)):
-            # a block with a NIN shortcut: the shortcut comes out of the operand pass, which holds the block input anyway
-            t, b_f32["res_out"] = ops.wino_prep_nin(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), B, S_out,
-                                                    wino.eq() if hasattr(wino, "eq") else None, nin[0], nin[1])
-        else:
-            t = ops.wino_prep(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), ups, B, S_out, drop=b_f32.get("drop"),
-                              keep=bool(b_f32.get("keep")), f8=f8, eq=wino.eq() if f8 and hasattr(wino, "eq") else None, compact=compact)
-        if b_f32.get("keep"):
-            b_f32["t_out"] = t           # training: the Winograd weight gradient reads the operand again (tape)
-        ops.conv3_wino(wino(f8) if f8 else wino(), t, B, S_out, bias=bias, bias_bstride=bias_bstride, residual=residual,
-                       res_bstride=res_bstride or 0, stats=stats, out=out)
-        if f8 and ops.AUDIT is not None:
-            # diagnostic mode (tools/audit_precision.py): the same launch once more in bf16x3; the pair's relative difference is the
-            # error the reduced-precision format adds on THIS layer with THESE weights and activations
-            t3 = ops.wino_prep(b_f32["parts"], b_f32.get("ac"), b_f32.get("silu"), ups, B, S_out, compact=compact)      # the audited launch's layout
-            ref = ops.conv3_wino(wino(), t3, B, S_out, bias=bias, bias_bstride=bias_bstride, residual=residual, res_bstride=res_bstride or 0)
-            ops.AUDIT.append(dict(owner=getattr(wino, "owner", None), site=getattr(wino, "site", None), fmt=f8, cin=pw.kdim, cout=pw.rows,
-                                  S=S_out, rel_l2=float((torch.linalg.vector_norm(out - ref, dtype=torch.float64)
-                                                         / torch.linalg.vector_norm(ref, dtype=torch.float64).clamp_min(1e-300)).item())))
-            del t3, ref
-        if stats is not None:
-            out._md_sums = stats
-        elif hasattr(out, "_md_sums"):
-            del out._md_sums
-        return out
-    if b_f32 is not None and b_f32.get("wino_only"):
-        b_f32 = None                     # training: the direct kernel takes the taped S16B activation (`act_s16`)
-    ksplit = ops.ksplit_for(pw.cfg, B, pw.rows, pw.kdim, S_out) if out_mode == ops.OUT_F32B else 1
-    stats = None
-    # statistics of the output: the dedicated kernel's epilogue, or (8^3 / 4^3 levels) the split-K finish kernel
-    # (one block per (sample, 8-channel group) there: only where that fills the chip -- at B = 1 the 32^3 level would run on 16 blocks)
-    if (want_stats and ops.FUSE_GN_STATS and ((pw.cfg == ops.CFG_C3_128_FAST and ksplit == 1)
-                                              or (ksplit > 1 and ops.SPLITK_STATS and P <= 512 and B * rows_alloc >= 2048))
-            and out_mode == ops.OUT_F32B and rows_alloc == pw.rows):
-        stats = ops.stats_zeros(B, rows_alloc, dev)
-    ops.gemm_conv(cfg=pw.cfg, a=pw.data, b=act_s16, out=out, batch=B, rows=pw.rows,
-                  rows_alloc=rows_alloc, kdim=pw.kdim, dims=(S_out, S_out, S_out), bias=bias,
-                  bias_bstride=bias_bstride, residual=residual, res_bstride=res_bstride or 0, ups=ups,
-                  out_mode=out_mode, ksplit=ksplit, prec=pw.prec, stats=stats, b_f32=b_f32)
+    if b_f32 is not None:
+        b_f32.t_kept = b_f32.shortcut = None
+    plan = plan_conv3(pw, b_f32, B, S_out, ups=ups, out_mode=out_mode, rows_alloc=rows_alloc, want_stats=want_stats, wino=wino)
+    stats = ops.stats_zeros(B, rows_alloc, dev) if plan.stats else None
+    if plan.path == "wino":
+        _conv3_wino(plan, pw, b_f32, wino, B, S_out, ups, out, stats, bias=bias, bias_bstride=bias_bstride, residual=residual,
+                    res_bstride=res_bstride or 0)
+    else:
+        ops.gemm_conv(cfg=pw.cfg, a=pw.data, b=act_s16, out=out, batch=B, rows=pw.rows,
+                      rows_alloc=rows_alloc, kdim=pw.kdim, dims=(S_out, S_out, S_out), bias=bias,
+                      bias_bstride=bias_bstride, residual=residual, res_bstride=res_bstride or 0, ups=ups,
+                      out_mode=out_mode, ksplit=plan.ksplit, prec=pw.prec, stats=stats, b_f32=b_f32 if plan.fused_loader else None)
     if stats is not None:
         out._md_sums = stats
     elif hasattr(out, "_md_sums"):
@@ -250,12 +243,41 @@ def run_conv3(pw, act_s16, B, S_out, *, bias=None, bias_bstride=0, residual=None
     return out
 
 
+def _conv3_wino(plan, pw, op, wino, B, S_out, ups, out, stats, **epilogue):
+    """The Winograd route of run_conv3: operand pass (+ shortcut), conv; calibration record before, audit re-run after."""
+    owner = getattr(wino, "owner", None)
+    if ops.CALIBRATE is not None and owner is not None and not op.wino_only:
+        # calibration evaluation: what this conv's operand really looks like, per input channel (nearest-x2 upsampling does not
+        # change a channel's mean square: measured on the coarse tensor)
+        ms = ops.wino_operand_ms(op.parts, op.ac, op.silu, B, op.parts[0][0].shape[2])
+        rec = ops.CALIBRATE.setdefault((id(owner), wino.site), [owner, wino.site, torch.zeros_like(ms), 0])
+        rec[2] += ms
+        rec[3] += 1
+    eq = wino.eq() if plan.fmt and hasattr(wino, "eq") else None
+    if plan.shortcut_in_pass:
+        t, op.shortcut = ops.wino_prep_nin(op.parts, op.ac, op.silu, B, S_out, eq, op.nin[0], op.nin[1])
+    else:
+        t = ops.wino_prep(op.parts, op.ac, op.silu, ups, B, S_out, drop=op.drop, keep=plan.keep, f8=plan.fmt, eq=eq, compact=plan.compact)
+    if plan.keep:
+        op.t_kept = t                    # training: the Winograd weight gradient reads the operand again (tape)
+    ops.conv3_wino(wino(plan.fmt) if plan.fmt else wino(), t, B, S_out, stats=stats, out=out, **epilogue)
+    if plan.fmt and ops.AUDIT is not None:
+        # diagnostic mode (tools/audit_precision.py): the same launch once more in bf16x3; the pair's relative difference is the
+        # error the reduced-precision format adds on THIS layer with THESE weights and activations
+        t3 = ops.wino_prep(op.parts, op.ac, op.silu, ups, B, S_out, compact=plan.compact)      # the audited launch's layout
+        ref = ops.conv3_wino(wino(), t3, B, S_out, **epilogue)
+        ops.AUDIT.append(dict(owner=owner, site=getattr(wino, "site", None), fmt=plan.fmt, cin=pw.kdim, cout=pw.rows,
+                              S=S_out, rel_l2=float((torch.linalg.vector_norm(out - ref, dtype=torch.float64)
+                                                     / torch.linalg.vector_norm(ref, dtype=torch.float64).clamp_min(1e-300)).item())))
+
+
 def run_gemm(pw, act_s16, B, P, *, bias=None, bias_bstride=0, residual=None, out=None, out_mode=ops.OUT_F32B,
              alpha=1.0, b_bstride=None, b_f32=None):
     """1x1x1 conv / GEMM with packed weights: out[rows][P].  b_f32: fp32 F32B parts split by the kernel's loader
     (CFG_G1_128 only; hip_ops.gemm_conv) instead of the S16B operand `act_s16`."""
     rows_alloc = ((pw.rows + 7) // 8) * 8
-    dev = act_s16.device if act_s16 is not None else b_f32["parts"][0][0].device
+    b_f32 = ops.F32Operand.of(b_f32)
+    dev = act_s16.device if act_s16 is not None else b_f32.parts[0][0].device
     if out is None:
         out = (ops.f32b_empty if out_mode == ops.OUT_F32B else ops.s16b_empty)(B, rows_alloc, P, dev)
     return ops.gemm_conv(cfg=pw.cfg, a=pw.data, b=act_s16, out=out, batch=B, rows=pw.rows,
@@ -377,7 +399,7 @@ class Upsample(HipLayer):
         pw = conv3_packed(self, "w", self.Conv_0, ops.conv_cfg_for(s_out))
         if tape is None and fused_operand_ok(pw, ups=1) and pw.kdim == Cc:   # the conv splits the raw fp32 input while loading it
             return run_conv3(pw, None, B, s_out, bias=self.Conv_0.bias, ups=1, want_stats=True,
-                             b_f32=dict(parts=[(x, Cc)], ac=None, silu=False), wino=conv3_wino_packed(self, "w", self.Conv_0))
+                             b_f32=ops.F32Operand([(x, Cc)]), wino=conv3_wino_packed(self, "w", self.Conv_0))
         fw = None
         ww = (tape is not None and pw.prec == ops.PREC_BF16X3 and pw.kdim == Cc
               and ops.wgrad_wino_ok(pw.rows, pw.kdim, s_out, B))      # Winograd weight gradient: T instead of the S16B operand
@@ -385,11 +407,11 @@ class Upsample(HipLayer):
         if tape is not None:
             assert pw.prec == ops.PREC_BF16X3
             if ops.WINO_TRAIN_FWD:
-                fw = dict(parts=[(x, Cc)], ac=None, silu=False, wino_only=True, keep=ww)
+                fw = ops.F32Operand([(x, Cc)], wino_only=True, keep=ww)
         out = run_conv3(pw, act, B, s_out, bias=self.Conv_0.bias, ups=1, want_stats=True, b_f32=fw,
                         wino=conv3_wino_packed(self, "w", self.Conv_0) if fw is not None else None)
         if tape is not None:
-            tape.append(dict(layer=self, act=act, t=fw.get("t_out") if fw else None, B=B, S_out=s_out))
+            tape.append(dict(layer=self, act=act, t=fw.t_kept if fw else None, B=B, S_out=s_out))
         return out
 
     def backward_blocked(self, sv, dy):
@@ -466,6 +488,15 @@ class ResnetBlockDDPM(HipLayer):
                                 lambda: (self.Conv_0.bias.detach() + self.Dense_0.bias.detach()).contiguous())
         return self.Conv_0.bias
 
+    def _film_bias(self, temb, bias0, bias0_stride):
+        """(bias, batch stride) of Conv_0's additive per-(sample, channel) constant: the caller's precomputed rows, or
+        Conv_0.b + Dense_0(SiLU(temb)) computed here, or the plain bias."""
+        if bias0 is not None:
+            return bias0, bias0_stride
+        if temb is not None:
+            return ops.linear(temb, self.Dense_0.weight, self._bias0(), silu_in=True), self.out_ch
+        return self.Conv_0.bias, 0
+
     def forward_blocked(self, parts, B, P, temb=None, bias0=None, bias0_stride=None, tape=None):
         """bias0 (optional): precomputed Conv_0.bias + Dense_0(SiLU(temb)) rows [B, out_ch] with row stride
         `bias0_stride` floats (the U-Net computes all blocks' FiLM biases in one launch).
@@ -480,28 +511,23 @@ class ResnetBlockDDPM(HipLayer):
         f16 = pw0.prec == ops.PREC_FP16X2   # operand format follows the kernel that consumes the tensor
         need_nin = self.in_ch != self.out_ch
         if (tape is None and drop is None and fused_operand_ok(pw0) and fused_operand_ok(pw1) and pw0.kdim == cin
-                and pw1.kdim == self.out_ch and not ops.NIN_SIDE_STREAM):
+                and pw1.kdim == self.out_ch):
             # inference: no GroupNorm-apply pass at all -- both convs read the fp32 tensors and normalise / activate /
             # split them in their halo loaders; the statistics come from the producing convs' epilogues
             _, ac0 = ops.gn_params(parts, g0.weight, g0.bias, B, P, eps=g0.eps, groups=g0.num_groups, want_ac=True)
-            if bias0 is None:
-                if temb is not None:
-                    bias0, bias0_stride = ops.linear(temb, self.Dense_0.weight, self._bias0(), silu_in=True), self.out_ch
-                else:
-                    bias0, bias0_stride = self.Conv_0.bias, 0
-            f0 = dict(parts=parts, ac=ac0, silu=True)
+            bias0, bias0_stride = self._film_bias(temb, bias0, bias0_stride)
             pwn = self.NIN_0.packed(P, hbm_bound=True) if need_nin else None
-            if need_nin and ops.BLOCK_PASS and pwn.kdim == cin and ops.nin_stream_ok(parts, self.out_ch, P):
-                f0["nin"] = (pwn, self.NIN_0.b)                     # Conv_0's operand pass may write the shortcut too
+            # a shortcut is wanted: Conv_0's operand pass writes it too where plan_conv3 finds that it can
+            f0 = ops.F32Operand(parts, ac0, silu=True, nin=(pwn, self.NIN_0.b) if need_nin else None)
             h = run_conv3(pw0, None, B, S, bias=bias0, bias_bstride=bias0_stride, want_stats=True,
                           b_f32=f0, wino=conv3_wino_packed(self, "w0", self.Conv_0, gn=g0))
             if need_nin:
-                if f0.get("res_out") is not None:                   # one pass over the block input wrote operand and shortcut
-                    res = f0["res_out"]
+                if f0.shortcut is not None:                         # one pass over the block input wrote operand and shortcut
+                    res = f0.shortcut
                 elif pwn.kdim == cin and ops.nin_stream_ok(parts, self.out_ch, P):   # weights resident in LDS, input streamed once
                     res = ops.nin_f32(parts, pwn, self.NIN_0.b, B, P)
                 elif pwn.cfg in (ops.CFG_G1_128, ops.CFG_G1_128_N128) and pwn.kdim == cin:   # the shortcut GEMM splits the raw fp32 parts itself
-                    res = run_gemm(pwn, None, B, P, bias=self.NIN_0.b, b_f32=dict(parts=parts, ac=None, silu=False))
+                    res = run_gemm(pwn, None, B, P, bias=self.NIN_0.b, b_f32=ops.F32Operand(parts))
                 else:                                               # small grids: one raw split pass of the block input
                     xs = ops.gn_apply(parts, None, B, P, norm=False, silu=False)
                     res = self.NIN_0.forward_s16(xs, B, P)
@@ -509,7 +535,7 @@ class ResnetBlockDDPM(HipLayer):
                 res = parts[0][0]
             _, ac1 = ops.gn_params([(h, self.out_ch)], g1.weight, g1.bias, B, P, eps=g1.eps, groups=g1.num_groups, want_ac=True)
             return run_conv3(pw1, None, B, S, bias=self.Conv_1.bias, residual=res, want_stats=True,
-                             b_f32=dict(parts=[(h, self.out_ch)], ac=ac1, silu=True), wino=conv3_wino_packed(self, "w1", self.Conv_1, gn=g1))
+                             b_f32=ops.F32Operand([(h, self.out_ch)], ac1, silu=True), wino=conv3_wino_packed(self, "w1", self.Conv_1, gn=g1))
         # training (tape): the convs go through the Winograd path where it applies (its operand pass repeats GroupNorm + SiLU
         # + dropout from the fp32 tensors); the S16B activations are still written: the weight gradients read them
         wino_fwd = tape is not None and not f16 and ops.WINO_TRAIN_FWD
@@ -518,10 +544,9 @@ class ResnetBlockDDPM(HipLayer):
         ww0 = wino_fwd and pw0.kdim == cin and ops.wgrad_wino_ok(self.out_ch, cin, S, B)
         ww1 = wino_fwd and pw1.kdim == self.out_ch and ops.wgrad_wino_ok(self.out_ch, self.out_ch, S, B)
         prm, ac0 = ops.gn_params(parts, g0.weight, g0.bias, B, P, eps=g0.eps, groups=g0.num_groups, want_ac=True)
-        f0 = dict(parts=parts, ac=ac0, silu=True, wino_only=True, keep=ww0) if wino_fwd else None
+        f0 = ops.F32Operand(parts, ac0, silu=True, wino_only=True, keep=ww0) if wino_fwd else None
         w0 = conv3_wino_packed(self, "w0", self.Conv_0) if f0 is not None else None
         xs = None
-        res = None
         if ww0:
             a0 = None
             if need_nin:                 # the shortcut NIN (forward GEMM and its weight gradient) still takes the raw bf16 split
@@ -530,31 +555,14 @@ class ResnetBlockDDPM(HipLayer):
             a0 = ops.gn_apply(parts, prm, B, P, norm=True, silu=True, fp16=f16, want_raw=need_nin)
             if need_nin:
                 a0, xs = a0
-        if need_nin and ops.NIN_SIDE_STREAM:
-            # The shortcut GEMM is HBM-bound and independent of Conv_0 (MFMA-bound): launch it on a second HIP
-            # stream so that it shares the GPU with the convolution instead of preceding Conv_1 serially.
-            main, side = torch.cuda.current_stream(), ops.side_stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                res = self.NIN_0.forward_s16(xs, B, P)
-            res.record_stream(main)
-            xs.record_stream(side)
-        if bias0 is not None:
-            h = run_conv3(pw0, a0, B, S, bias=bias0, bias_bstride=bias0_stride, want_stats=True, b_f32=f0, wino=w0)
-        elif temb is not None:   # per-(sample, channel) additive bias = Conv_0.b + Dense_0(SiLU(temb))
-            bias0 = ops.linear(temb, self.Dense_0.weight, self._bias0(), silu_in=True)
-            h = run_conv3(pw0, a0, B, S, bias=bias0, bias_bstride=self.out_ch, want_stats=True, b_f32=f0, wino=w0)
-        else:
-            h = run_conv3(pw0, a0, B, S, bias=self.Conv_0.bias, want_stats=True, b_f32=f0, wino=w0)
+        bias0, bias0_stride = self._film_bias(temb, bias0, bias0_stride)
+        h = run_conv3(pw0, a0, B, S, bias=bias0, bias_bstride=bias0_stride, want_stats=True, b_f32=f0, wino=w0)
         prm1, ac1 = ops.gn_params([(h, self.out_ch)], g1.weight, g1.bias, B, P, eps=g1.eps, groups=g1.num_groups, want_ac=True)
         a1 = None if ww1 else ops.gn_apply([(h, self.out_ch)], prm1, B, P, norm=True, silu=True, fp16=f16, drop=drop)
-        f1 = dict(parts=[(h, self.out_ch)], ac=ac1, silu=True, drop=drop, wino_only=True, keep=ww1) if wino_fwd else None
+        f1 = ops.F32Operand([(h, self.out_ch)], ac1, silu=True, drop=drop, wino_only=True, keep=ww1) if wino_fwd else None
         w1 = conv3_wino_packed(self, "w1", self.Conv_1) if f1 is not None else None
         if need_nin:
-            if res is None:
-                res = self.NIN_0.forward_s16(xs, B, P)
-            else:
-                torch.cuda.current_stream().wait_stream(ops.side_stream())
+            res = self.NIN_0.forward_s16(xs, B, P)
         else:
             assert len(parts) == 1
             res = parts[0][0]
@@ -562,7 +570,7 @@ class ResnetBlockDDPM(HipLayer):
         if tape is not None:
             assert not f16, "the backward pass uses the bf16x3 operand format"
             tape.append(dict(layer=self, parts=parts, prm0=prm, a0=a0, h=h, prm1=prm1, a1=a1, xs=xs, B=B, P=P, S=S,
-                             temb=temb, drop=drop, t0=f0.get("t_out") if f0 else None, t1=f1.get("t_out") if f1 else None))
+                             temb=temb, drop=drop, t0=f0.t_kept if f0 else None, t1=f1.t_kept if f1 else None))
         return out
 
     def backward_blocked(self, sv, dy):

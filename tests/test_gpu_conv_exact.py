@@ -140,7 +140,7 @@ def test_gemm_conv_exact(ops, case_id):
             pw, rows, rows_alloc = ops.PackedWeight(w.cuda(), "conv", cfg, "cuda", prec), cout, ((cout + 7) // 8) * 8
         # ---- operand
         if spec.get("b_f32"):
-            kw.update(b=None, b_f32=dict(parts=_parts(ops, case), ac=case["ac"].cuda() if case["ac"] is not None else None, silu=False))
+            kw.update(b=None, b_f32=ops.F32Operand(_parts(ops, case), case["ac"].cuda() if case["ac"] is not None else None, silu=False))
         elif spec["cfg"] in XFOLD_CFGS:
             kw.update(b=ops.ncdhw_to_s16b_xfold(x, k, pw.kdim))
         elif prec == ops.PREC_FP16X2:
@@ -312,7 +312,7 @@ def test_silu_loaders_through_a_transparent_conv(ops, name):
             cfg = ops.CFG_C3_128_FAST if kind == "fast" else ops.CFG_C3_LOW
             pw = ops.PackedWeight(w.cuda(), "conv", cfg, "cuda")
             out = ops.gemm_conv(cfg=cfg, a=pw.data, b=None, out=_nan_f32b(ops, B, cout, P), batch=B, rows=cout, rows_alloc=cout, kdim=cin, dims=dims,
-                                b_f32=dict(parts=parts, ac=ac, silu=True))
+                                b_f32=ops.F32Operand(parts, ac, silu=True))
             y = ops.f32b_to_ncdhw(out, dims)
         elif kind == "wino":
             bound = cc.wino_transparent_bound(dict(case, w=w, w_eff=w))

@@ -418,7 +418,7 @@ def test_conv3_fused_groupnorm_silu_operand(ops, case):
     out = ops.f32b_empty(B, cout, S ** 3, "cuda")
     ops.gemm_conv(cfg=ops.CFG_C3_128_FAST, a=pw.data, b=None, out=out, batch=B, rows=cout, rows_alloc=cout, kdim=cin,
                   dims=(S, S, S), bias=bias.cuda(), bias_bstride=cout, ups=1 if ups else 0,
-                  b_f32=dict(parts=parts, ac=ac, silu=silu))
+                  b_f32=ops.F32Operand(parts, ac, silu=silu))
     y = ops.f32b_to_ncdhw(out, (S, S, S)).cpu()
     ref = F.conv3d(ref_in, w, padding=1) + bias[:, :, None, None, None]
     e = rel_l2(y, ref)
@@ -453,7 +453,7 @@ def test_generic_conv_fused_groupnorm_silu_operand(ops, case):
     pw = ops.PackedWeight(w.cuda(), "conv", cfg, "cuda")
     rows_alloc = ((rows + 7) // 8) * 8
     kw = dict(cfg=cfg, a=pw.data, batch=B, rows=rows, rows_alloc=rows_alloc, kdim=cin, dims=(S, S, S), bias=bias.cuda(), ksplit=ks)
-    out = ops.gemm_conv(b=None, out=ops.f32b_empty(B, rows_alloc, P, "cuda"), b_f32=dict(parts=parts, ac=ac, silu=silu), **kw)
+    out = ops.gemm_conv(b=None, out=ops.f32b_empty(B, rows_alloc, P, "cuda"), b_f32=ops.F32Operand(parts, ac, silu=silu), **kw)
     y = ops.f32b_to_ncdhw(out, (S, S, S)).cpu()[:, :rows]
     ref_in = F.group_norm(x, 32, gamma, beta, eps=1e-6)
     ref_in = F.silu(ref_in) if silu else ref_in
@@ -577,7 +577,7 @@ def test_nin_gemm_fp32_parts_operand(ops, cfg_name):
     pw = ops.PackedWeight(W.cuda(), "nin", cfg, "cuda")
     out = ops.f32b_empty(B, cout, P, "cuda")
     ops.gemm_conv(cfg=cfg, a=pw.data, b=None, out=out, batch=B, rows=cout, rows_alloc=cout, kdim=cin,
-                  dims=(1, 1, P), bias=bias.cuda(), b_f32=dict(parts=parts, ac=None, silu=False))
+                  dims=(1, 1, P), bias=bias.cuda(), b_f32=ops.F32Operand(parts, None, silu=False))
     a16 = ops.gn_apply(parts, None, B, P, norm=False, silu=False)
     out2 = ops.f32b_empty(B, cout, P, "cuda")
     ops.gemm_conv(cfg=cfg, a=pw.data, b=a16, out=out2, batch=B, rows=cout, rows_alloc=cout, kdim=cin,

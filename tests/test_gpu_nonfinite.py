@@ -99,7 +99,7 @@ def test_wino_conv_gn_silu_operand_nonfinite_voxel(ops, mode, val, place, monkey
         ops.PROFILE = []
         try:
             with ops.precision_scope(mode):
-                out = layers.run_conv3(pw, None, B, S, bias=bias.cuda(), bias_bstride=cout, b_f32=dict(parts=ps, ac=ac, silu=True),
+                out = layers.run_conv3(pw, None, B, S, bias=bias.cuda(), bias_bstride=cout, b_f32=ops.F32Operand(ps, ac, silu=True),
                                        wino=layers.conv3_wino_packed(pair, "w", pair.conv, gn=pair.gn))
             tags = [r[5] for r in ops.PROFILE if r[0] == "wino"]
         finally:
@@ -221,7 +221,7 @@ def test_groupnorm_operand_dominant_voxel(ops, mode, monkeypatch):
     _, ac = ops.gn_params(parts, pair.gn.weight, pair.gn.bias, B, S ** 3, want_ac=True)
     pw = layers.conv3_packed(pair, "w", pair.conv, ops.conv_cfg_for(S))
     with ops.precision_scope(mode):
-        out = layers.run_conv3(pw, None, B, S, b_f32=dict(parts=parts, ac=ac, silu=True),
+        out = layers.run_conv3(pw, None, B, S, b_f32=ops.F32Operand(parts, ac, silu=True),
                                wino=layers.conv3_wino_packed(pair, "w", pair.conv, gn=pair.gn))
     y = ops.f32b_to_ncdhw(out, (S, S, S)).cpu()
     ref = F.conv3d(F.silu(F.group_norm(x.double(), 32, gamma.double(), beta.double(), eps=1e-6)), w.double(), padding=1)

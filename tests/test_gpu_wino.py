@@ -121,7 +121,7 @@ def test_conv3_wino_full_tiles_bitwise_repeatable_and_vs_direct(ops):
     pw = ops.PackedWeight(w.cuda(), "conv", ops.CFG_C3_128_FAST, "cuda")
     direct = ops.f32b_empty(B, cout, S ** 3, "cuda")
     ops.gemm_conv(cfg=ops.CFG_C3_128_FAST, a=pw.data, b=None, out=direct, batch=B, rows=cout, rows_alloc=cout, kdim=cin,
-                  dims=(S, S, S), bias=bias.cuda(), bias_bstride=cout, b_f32=dict(parts=parts, ac=ac, silu=True))
+                  dims=(S, S, S), bias=bias.cuda(), bias_bstride=cout, b_f32=ops.F32Operand(parts, ac, silu=True))
     e = rel_l2(outs[0].cpu(), direct.cpu())
     print(f"wino vs direct fused kernel: {e:.2e}")
     assert e < 2e-5
@@ -734,7 +734,7 @@ def test_conv3_wino_f8_adversarial_operands(ops, case, fmt, monkeypatch):
         try:
             with ops.precision_scope(mode):
                 out = layers.run_conv3(pw, None, B, S, bias=bias.cuda(), bias_bstride=cout,
-                                       b_f32=dict(parts=parts, ac=ac, silu=True), wino=layers.conv3_wino_packed(pair, "w", pair.conv, gn=gn))
+                                       b_f32=ops.F32Operand(parts, ac, silu=True), wino=layers.conv3_wino_packed(pair, "w", pair.conv, gn=gn))
             tags = [r[5] for r in ops.PROFILE if r[0] == "wino"]
         finally:
             ops.PROFILE = None
@@ -801,7 +801,7 @@ def test_conv3_wino_f8_inside_group_spread_static_vs_measured_equaliser(ops, cin
         ops.PROFILE = []
         try:
             with ops.precision_scope(mode):
-                out = layers.run_conv3(pw, None, B, S, bias=bias.cuda(), bias_bstride=cout, b_f32=dict(parts=parts, ac=ac, silu=True),
+                out = layers.run_conv3(pw, None, B, S, bias=bias.cuda(), bias_bstride=cout, b_f32=ops.F32Operand(parts, ac, silu=True),
                                        wino=layers.conv3_wino_packed(pair, "w", pair.conv, gn=pair.gn))
             tags = [r[5] for r in ops.PROFILE if r[0] == "wino"]
         finally:
@@ -926,7 +926,7 @@ def test_precision_audit_record_and_per_layer_override(ops, monkeypatch):
         ops.PROFILE = []
         try:
             with ops.precision_scope("f16f6"):
-                out = layers.run_conv3(pw, None, B, S, bias=pair.conv.bias, b_f32=dict(parts=[(x, cin)], ac=ac, silu=True),
+                out = layers.run_conv3(pw, None, B, S, bias=pair.conv.bias, b_f32=ops.F32Operand([(x, cin)], ac, silu=True),
                                        wino=layers.conv3_wino_packed(pair, "w", pair.conv, gn=pair.gn))
             return out.clone(), [r[5] for r in ops.PROFILE if r[0] == "wino"]
         finally:
