@@ -565,6 +565,12 @@ int md_inpaint_renoise(float* x, float* x_mean, const float* z, const float* pma
  *   md_adam_ema_step: clip by min(1, max_norm/(sqrt(*grad_sqnorm)+1e-6)) (skipped when grad_sqnorm NULL or
  *                     max_norm < 0), torch.optim.Adam update with bias correction for `step` (1-based),
  *                     then ema -= (1-ema_decay)*(ema - p) (ema may be NULL).  One pass over 5 flat arrays.
+ *   md_adam_ema_step_d: the same with every hyper-parameter as a double, so that the fp32 scalars are formed as the reference
+ *                     forms them: fl(1.0 - beta1), fl(1.0 - beta2), bias corrections from the double betas, EMA rate
+ *                     fl(1.0 - ema_decay) (torch.optim.Adam; models/ema.py `update`).  A value that went through a float first
+ *                     gives 1 - x up to 2^-24/(1-x) relative off (1.3e-5 for beta2 = 0.999, 1.66e-4 for a decay of 0.9999);
+ *                     md_adam_ema_step widens its floats and is exact only for hyper-parameters that are floats.
+ *                     Purely additive: MD_ABI_VERSION stays 16, no existing entry point changes.
  */
 int md_ddpm_perturb(const float* x0, const float* noise, const float* mask, const float* coef, float* out,
                     int32_t batch, int32_t C, int64_t P, void* stream);
@@ -574,6 +580,9 @@ int md_grad_sqnorm(const float* g, int64_t n, double* out, void* stream);
 int md_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1,
                      float beta2, float eps, float weight_decay, int32_t step, float ema_decay,
                      const double* grad_sqnorm, float max_norm, void* stream);
+int md_adam_ema_step_d(float* p, const float* g, float* m, float* v, float* ema, int64_t n, double lr, double beta1,
+                       double beta2, double eps, double weight_decay, int32_t step, double ema_decay,
+                       const double* grad_sqnorm, float max_norm, void* stream);
 
 /*
  * Backward-pass support (csrc/backward.hip).  Contractions of the backward re-use md_gemm_conv:

@@ -58,7 +58,7 @@ class MdPackJob(C.Structure):
 PACK_WPK, PACK_WINO, PACK_WINO_F6 = 0, 1, 2
 WINO_FMT = {False: 0, "f8": 1, "f6": 2}                  # MD_WINO_FMT_*
 ABI_VERSION = 16     # MD_ABI_VERSION of include/meshdiffusion_hip.h this host code was written against
-_P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
+_P, _I32, _I64, _F, _U64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes); exactly the entry points of include/meshdiffusion_hip.h
 SIGNATURES = {
@@ -127,6 +127,7 @@ SIGNATURES = {
     "md_masked_sq_err": (C.c_int, [_P, _P, _P, _P, _P, _F, _I32, _I32, _I64, _P]),
     "md_grad_sqnorm": (C.c_int, [_P, _I64, _P, _P]),
     "md_adam_ema_step": (C.c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I32, _F, _P, _F, _P]),
+    "md_adam_ema_step_d": (C.c_int, [_P, _P, _P, _P, _P, _I64, _D, _D, _D, _D, _D, _I32, _D, _P, _F, _P]),
     "md_pb16_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     "md_to_pb16": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "md_wgrad_finish": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I64, _I64, _P]),

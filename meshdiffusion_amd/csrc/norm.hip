@@ -159,7 +159,7 @@ extern "C" int md_gn_stats(const float* x, double* sums, int32_t batch, int32_t 
 extern "C" int md_gn_finalize(const double* sums, const float* gamma, const float* beta,
                               float* params, int32_t batch, int32_t c_total, int32_t groups,
                               int64_t P, float eps, float* ac, void* stream) {
-  if (!sums || !gamma || !beta || !params || batch <= 0 || groups <= 0 || (c_total % groups))
+  if (!sums || !gamma || !beta || !params || batch <= 0 || groups <= 0 || c_total <= 0 || (c_total % groups) || P <= 0)
     return MD_ERR_BAD_ARG;
   MD_HIP_CLEAR_ERROR();
   hipLaunchKernelGGL(md_gn_finalize_kernel, dim3((unsigned)(batch * groups)), dim3(64), 0,
@@ -172,7 +172,7 @@ extern "C" int md_gn_apply(const float* x, const float* params, void* out, void*
                            int32_t C, int64_t P, int32_t c_total, int32_t c_off, int32_t norm, int32_t silu,
                            float drop_p, uint64_t drop_seed, void* stream) {
   if (!(drop_p >= 0.f && drop_p < 1.f)) return MD_ERR_BAD_ARG;
-  if (!x || !out || (norm && !params) || batch <= 0 || C <= 0 || (C % 8) || (c_off % 8) ||
+  if (!x || !out || (norm && !params) || batch <= 0 || C <= 0 || (C % 8) || c_off < 0 || (c_off % 8) ||
       (c_total % 8) || c_off + C > c_total || P <= 0)
     return MD_ERR_BAD_ARG;
   dim3 grid((unsigned)((P + GN_CHUNK - 1) / GN_CHUNK), (unsigned)(C / 8), (unsigned)batch);
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void md_dropout_scale_kernel(float* __restrict
 
 extern "C" int md_dropout_scale(float* out, int32_t batch, int32_t C, int64_t P, int32_t c_total, int32_t c_off,
                                 float drop_p, uint64_t drop_seed, void* stream) {
-  if (!out || batch <= 0 || C <= 0 || (C % 8) || (c_off % 8) || c_off + C > c_total || P <= 0 || !(drop_p >= 0.f && drop_p < 1.f))
+  if (!out || batch <= 0 || C <= 0 || (C % 8) || c_off < 0 || (c_off % 8) || c_off + C > c_total || P <= 0 || !(drop_p >= 0.f && drop_p < 1.f))
     return MD_ERR_BAD_ARG;
   dim3 grid((unsigned)((P * 2 + 255) / 256), (unsigned)(C / 8), (unsigned)batch);
   MD_HIP_CLEAR_ERROR();

@@ -84,8 +84,8 @@ __global__ __launch_bounds__(256) void md_grad_sqnorm_kernel(const float* __rest
 // `clip_from_sqnorm` (device double, may be NULL): clip = min(1, max_norm / (sqrt(*sq) + 1e-6)).
 __global__ __launch_bounds__(256) void md_adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v,
-                                                          float* __restrict__ ema, int64_t n, float b1, float b2,
-                                                          float eps, float wd, float step_size, float bc2_sqrt,
+                                                          float* __restrict__ ema, int64_t n, float one_minus_b1, float b2,
+                                                          float one_minus_b2, float eps, float wd, float step_size, float bc2_sqrt,
                                                           float one_minus_decay, const double* __restrict__ sqnorm,
                                                           float max_norm) {
   float clip = 1.f;
@@ -99,8 +99,8 @@ __global__ __launch_bounds__(256) void md_adam_ema_kernel(float* __restrict__ p,
     float pi = p[i];
     if (wd != 0.f) gi = gi + wd * pi;
     float mi = m[i], vi = v[i];
-    mi = mi + (gi - mi) * (1.f - b1);
-    vi = vi * b2 + (1.f - b2) * gi * gi;
+    mi = mi + (gi - mi) * one_minus_b1;
+    vi = vi * b2 + one_minus_b2 * gi * gi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     pi = pi - step_size * (mi / denom);
     p[i] = pi; m[i] = mi; v[i] = vi;
@@ -187,17 +187,30 @@ extern "C" int md_grad_sqnorm(const float* g, int64_t n, double* out, void* stre
   return MD_OK;
 }
 
-extern "C" int md_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
-                                float beta1, float beta2, float eps, float weight_decay, int32_t step,
-                                float ema_decay, const double* grad_sqnorm, float max_norm, void* stream) {
+// Every hyper-parameter travels as a double, because the reference forms its fp32 scalars from doubles: the lerp weight is
+// fl(1.0 - beta1), the second-moment weight fl(1.0 - beta2), the bias corrections come from the double betas, the EMA rate is
+// fl(1.0 - d) (torch.optim.Adam; models/ema.py `update`).  Formed from betas or a decay that went through a float first they are
+// off by up to 2^-24 / (1 - x) relative: 1.3e-5 for 1 - beta2 at 0.999, 1.66e-4 for the EMA rate at d = 0.9999.
+extern "C" int md_adam_ema_step_d(float* p, const float* g, float* m, float* v, float* ema, int64_t n, double lr,
+                                  double beta1, double beta2, double eps, double weight_decay, int32_t step,
+                                  double ema_decay, const double* grad_sqnorm, float max_norm, void* stream) {
   if (!p || !g || !m || !v || n <= 0 || step <= 0) return MD_ERR_BAD_ARG;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  const float step_size = (float)(lr / bc1);
   const float bc2_sqrt = (float)sqrt(bc2);
   MD_HIP_CLEAR_ERROR();
   hipLaunchKernelGGL(md_adam_ema_kernel, dim3((unsigned)grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     ema, n, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, 1.f - ema_decay, grad_sqnorm, max_norm);
+                     ema, n, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, step_size,
+                     bc2_sqrt, (float)(1.0 - ema_decay), grad_sqnorm, max_norm);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
+}
+
+// The entry point of ABI 16, kept for callers that hold their hyper-parameters as floats: exact for those values, and only those.
+extern "C" int md_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
+                                float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                                float ema_decay, const double* grad_sqnorm, float max_norm, void* stream) {
+  return md_adam_ema_step_d(p, g, m, v, ema, n, (double)lr, (double)beta1, (double)beta2, (double)eps, (double)weight_decay, step,
+                            (double)ema_decay, grad_sqnorm, max_norm, stream);
 }

@@ -48,7 +48,7 @@ FUSED_OPT = __import__("os").environ.get("MD_FUSED_OPT", "1") == "1"
 
 class _FlatOptState:
     """torch.optim.Adam + clip_grad_norm_ + ExponentialMovingAverage.update as the two launches of md_grad_sqnorm /
-    md_adam_ema_step over flat buffers -- WITHOUT changing what the caller holds: parameters, Adam's `exp_avg` /
+    md_adam_ema_step_d over flat buffers -- WITHOUT changing what the caller holds: parameters, Adam's `exp_avg` /
     `exp_avg_sq` and the EMA's `shadow_params` become views of flat buffers laid out like parallel.FlatGrads, so
     `optimizer.state_dict()`, `ema.state_dict()` and therefore the reference checkpoint format keep working, and a
     `load_state_dict` (new tensors) is detected and re-imported on the next step."""
@@ -102,7 +102,7 @@ class _FlatOptState:
 
     def params_alias_flat(self):
         """The first and the last parameter still are views of the flat buffer (model.to() / float() / a manual
-        `p.data = ...` / load_state_dict(assign=True) replace the storage: md_adam_ema_step would then update an orphan)."""
+        `p.data = ...` / load_state_dict(assign=True) replace the storage: md_adam_ema_step_d would then update an orphan)."""
         for p in (self.fg.params[0], self.fg.params[-1]):
             _, o, n = self.fg.slices[id(p)]
             if p.data_ptr() != self.p.data_ptr() + 4 * o or p.numel() != n:
@@ -133,10 +133,10 @@ class _FlatOptState:
             _lib.check(lib.md_grad_sqnorm(ops._ptr(self.fg.flat), self.fg.n, ops._ptr(self.sq), ops._stream()), "md_grad_sqnorm")
             sq = self.sq
         b1, b2 = g["betas"]
-        _lib.check(lib.md_adam_ema_step(ops._ptr(self.p), ops._ptr(self.fg.flat), ops._ptr(self.m), ops._ptr(self.v),
-                                        ops._ptr(self.e), self.fg.n, lr, float(b1), float(b2), float(g["eps"]),
-                                        float(g["weight_decay"]), self.opt_steps, float(d), ops._ptr(sq), float(grad_clip),
-                                        ops._stream()), "md_adam_ema_step")
+        _lib.check(lib.md_adam_ema_step_d(ops._ptr(self.p), ops._ptr(self.fg.flat), ops._ptr(self.m), ops._ptr(self.v),
+                                          ops._ptr(self.e), self.fg.n, lr, float(b1), float(b2), float(g["eps"]),
+                                          float(g["weight_decay"]), self.opt_steps, float(d), ops._ptr(sq), float(grad_clip),
+                                          ops._stream()), "md_adam_ema_step_d")
         ops.bump_param_epoch()   # raw-pointer update: packed-weight caches are keyed on data_ptr/_version
 
 
@@ -306,7 +306,7 @@ def get_step_fn(sde, train, optimize_fn=None, mask=None, loss_type="l2"):
 
 class FusedAdamEMA:
     """clip_grad_norm_ + torch.optim.Adam + ExponentialMovingAverage.update as TWO kernel launches over flat
-    buffers (md_grad_sqnorm, md_adam_ema_step) instead of ~12 passes over 1.46 GB of state.
+    buffers (md_grad_sqnorm, md_adam_ema_step_d) instead of ~12 passes over 1.46 GB of state.
 
     Parameters are re-pointed at views of one flat fp32 buffer (so are their .grad), m / v / ema are flat too.
     `lr` warm-up follows optimization_manager: lr * min(step / warmup, 1).
@@ -352,10 +352,10 @@ class FusedAdamEMA:
             self._sq.zero_()
             _lib.check(lib.md_grad_sqnorm(ops._ptr(self.grad), self.n, ops._ptr(self._sq), ops._stream()), "md_grad_sqnorm")
             sq = self._sq
-        _lib.check(lib.md_adam_ema_step(ops._ptr(self.flat), ops._ptr(self.grad), ops._ptr(self.m), ops._ptr(self.v),
-                                        ops._ptr(self.ema), self.n, lr, self.b1, self.b2, self.eps, self.wd,
-                                        self.opt_steps, d, ops._ptr(sq), float(self.grad_clip), ops._stream()),
-                   "md_adam_ema_step")
+        _lib.check(lib.md_adam_ema_step_d(ops._ptr(self.flat), ops._ptr(self.grad), ops._ptr(self.m), ops._ptr(self.v),
+                                          ops._ptr(self.ema), self.n, lr, self.b1, self.b2, self.eps, self.wd,
+                                          self.opt_steps, d, ops._ptr(sq), float(self.grad_clip), ops._stream()),
+                   "md_adam_ema_step_d")
         ops.bump_param_epoch()   # packed-weight caches must be rebuilt: raw-pointer updates do not bump _version
 
     def _views(self, flat):

@@ -30,29 +30,70 @@ def test_perturb_bit_exact_and_masked_loss(hip_lib):
 
 
 def test_fused_clip_adam_ema_matches_torch(hip_lib):
+    """FusedAdamEMA against torch's clip_grad_norm_ + Adam + EMA, four steps from one state, twice: through the EMA's warm-up
+    (d = 2/11, 3/12, ...) and late in training (d = 0.9999).  Parameters are 1e-3 randn with lr = 1e-3 and the shadow starts at an
+    independent 1e-5 randn, so that one step moves both by amounts fp32 resolves: besides the parameters and the shadow themselves,
+    the INCREMENTS of every step are compared -- with float64 under the rounding-count bounds of tests/stream_cases.py, and with
+    torch's own increments under the sum of both sides' bounds (each side's float64 step taken from its own fp32 state, and from
+    the norm it clipped with)."""
+    import stream_cases as sc
     from meshdiffusion_amd.lib.diffusion.losses import FusedAdamEMA
     from meshdiffusion_amd.lib.diffusion.models.ema import ExponentialMovingAverage
     shapes = [(64, 32, 3, 3, 3), (64,), (257, 5), (1000,)]
-    ref_p = [torch.nn.Parameter(_rand(s, 10 + i).cuda()) for i, s in enumerate(shapes)]
-    my_p = [torch.nn.Parameter(p.detach().clone()) for p in ref_p]
-    opt = torch.optim.Adam(ref_p, lr=2e-5, betas=(0.9, 0.999), eps=1e-8)
-    ema = ExponentialMovingAverage(ref_p, decay=0.9999)
-    fused = FusedAdamEMA(my_p, lr=2e-5, grad_clip=1.0, warmup=5)
-    for step in range(1, 5):
-        grads = [_rand(s, 100 * step + i).cuda() * (3.0 if step == 2 else 0.01) for i, s in enumerate(shapes)]
-        for p, q, g in zip(ref_p, my_p, grads):
-            p.grad = g.clone()
-            q.grad.copy_(g)
-        for gr in opt.param_groups:
-            gr["lr"] = 2e-5 * np.minimum(step / 5, 1.0)
-        torch.nn.utils.clip_grad_norm_(ref_p, max_norm=1.0)
-        opt.step()
-        ema.update(ref_p)
-        fused.step(step)
-        for p, q, s in zip(ref_p, my_p, ema.shadow_params):
-            assert rel_l2(q.detach().cpu(), p.detach().cpu()) < 1e-6
-        for mine, s in zip(fused.ema_shadow_params(), ema.shadow_params):
-            assert rel_l2(mine.cpu(), s.cpu()) < 1e-6
+    lr0 = 1e-3
+    flat = lambda ts: torch.cat([t.detach().reshape(-1) for t in ts]).cpu()
+    for updates0 in (0, 10 ** 6):
+        ref_p = [torch.nn.Parameter(1e-3 * _rand(s, 10 + i).cuda()) for i, s in enumerate(shapes)]
+        my_p = [torch.nn.Parameter(p.detach().clone()) for p in ref_p]
+        opt = torch.optim.Adam(ref_p, lr=lr0, betas=(0.9, 0.999), eps=1e-8)
+        ema = ExponentialMovingAverage(ref_p, decay=0.9999)
+        fused = FusedAdamEMA(my_p, lr=lr0, grad_clip=1.0, warmup=5)
+        for i, (s, mine) in enumerate(zip(ema.shadow_params, fused.ema_shadow_params())):
+            s.copy_(1e-5 * _rand(shapes[i], 50 + i).cuda())
+            mine.copy_(s)
+        ema.num_updates = fused.ema_updates = updates0
+        for step in range(1, 5):
+            grads = [_rand(s, 100 * step + i).cuda() * (3.0 if step == 2 else 0.01) for i, s in enumerate(shapes)]
+            for p, q, g in zip(ref_p, my_p, grads):
+                p.grad = g.clone()
+                q.grad.copy_(g)
+            lr = float(lr0 * np.minimum(step / 5, 1.0))
+            for gr in opt.param_groups:
+                gr["lr"] = lr
+            zeros = [torch.zeros_like(p) for p in ref_p]
+            before_t = dict(p=flat(ref_p), m=flat([opt.state[p]["exp_avg"] for p in ref_p] if step > 1 else zeros),
+                            v=flat([opt.state[p]["exp_avg_sq"] for p in ref_p] if step > 1 else zeros), ema=flat(ema.shadow_params))
+            before_f = dict(p=fused.flat.cpu(), m=fused.m.cpu(), v=fused.v.cpu(), ema=fused.ema.cpu())
+            g_flat = flat(grads)
+            total_norm = torch.nn.utils.clip_grad_norm_(ref_p, max_norm=1.0)
+            opt.step()
+            ema.update(ref_p)
+            fused.step(step)
+            for p, q, s in zip(ref_p, my_p, ema.shadow_params):
+                assert rel_l2(q.detach().cpu(), p.detach().cpu()) < 1e-6
+            for mine, s in zip(fused.ema_shadow_params(), ema.shadow_params):
+                assert rel_l2(mine.cpu(), s.cpu()) < 1e-6
+            assert rel_l2(fused.m.cpu(), flat([opt.state[p]["exp_avg"] for p in ref_p])) < 1e-6
+            assert rel_l2(fused.v.cpu(), flat([opt.state[p]["exp_avg_sq"] for p in ref_p])) < 1e-6
+            # the increments of this step
+            common = dict(n=g_flat.numel(), step=step, wd=0.0, g=g_flat, lr=lr, b1=0.9, b2=0.999, eps=1e-8, max_norm=1.0,
+                          d=sc.ema_decay(0.9999, updates0 + step), clip="norm")
+            assert ema.num_updates == fused.ema_updates == updates0 + step
+            ref_f = sc.adam_reference(dict(common, sq=float((g_flat.double() ** 2).sum()), **before_f), sq_rel_err=2 * sc.U)
+            ref_t = sc.adam_reference(dict(common, sq=float(total_norm.double()) ** 2, **before_t))
+            got_f = (fused.flat.cpu(), fused.m.cpu(), fused.v.cpu(), fused.ema.cpu())
+            w = sc.adam_worst(got_f, dict(common, **before_f), ref_f)
+            print(f"fused adam updates0={updates0} step {step} (d = {common['d']:.6f}): worst err/bound vs float64 "
+                  + ", ".join(f"{k} {x:.3f}" for k, x in w.items()))
+            assert max(w.values()) <= 1.0, w
+            for key, new_f, new_t, e in (("p", fused.flat.cpu(), flat(ref_p), "e_dp"), ("ema", fused.ema.cpu(), flat(ema.shadow_params), "e_dema")):
+                inc_f = new_f.double() - before_f[key].double()
+                inc_t = new_t.double() - before_t[key].double()
+                r = "dp" if key == "p" else "dema"
+                allowed = ref_f[e] + ref_t[e] + (ref_f[r] - ref_t[r]).abs()
+                worst = float(((inc_f - inc_t).abs() / allowed).max())
+                print(f"    increment of {key} vs torch: worst difference/allowed {worst:.3f}")
+                assert worst <= 1.0
 
 
 def test_eval_step_fn_matches_oracle_loss(hip_lib):
