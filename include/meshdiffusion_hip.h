@@ -15,6 +15,17 @@
  *     re-entrant and stateless.
  *   - return value: 0 = ok, negative = MD_ERR_*, positive = hipError_t.
  *
+ * This file is also what the Python host reads its ctypes binding from (meshdiffusion_amd/_lib.py parse_header), so outside
+ * comments and preprocessor lines it keeps to a subset of C, and anything else is an error at import:
+ *   - `#define MD_X <integer expression>`: decimal literals, earlier MD_ names, + - * and parentheses, on one line;
+ *   - `enum { MD_X = <integer expression>, ... };` (an enumerator without a value is the previous one plus 1);
+ *   - `typedef struct Name { members } Name;`, a member being `[const] type[*] name[, name...];` (one name after a `*`);
+ *   - prototypes `type md_<name> (parameters);`, a parameter being `[const] type[*] [name]`, `(void)` for none;
+ *   - types: int, int32_t, int64_t, uint32_t, uint64_t, float, double by value (void as a return type); one level of pointer
+ *     to those, to void, to int8_t / uint8_t or to a struct declared above.  No arrays, no function pointers.
+ *   A pointer parameter is an address to ctypes (c_void_p), except a pointer to a struct, which is that struct in HOST memory
+ *   (POINTER(struct)) unless the parameter's name ends in `_dev`: an array of the struct in device memory, an address again.
+ *
  * Device tensor layouts (see DESIGN.md "Data layout in HBM")
  *   NCDHW : float32 [B][C][P]                      (the reference's layout, P = D*H*W)
  *   F32B  : float32 [B][C/8][P][8]                 (8-channel blocked fp32)

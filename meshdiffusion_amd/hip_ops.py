@@ -159,9 +159,10 @@ class PackedWeight:
 
     def __init__(self, w, kind, cfg, device, prec=PREC_BF16X3):
         self.prec = prec
-        nt, kc = CFG_NT_KC[cfg]
         w = w.detach().to(device=device, dtype=torch.float32).contiguous()
         _require_cuda(w, "weight")
+        _lib.load()                           # fills CFG_NT_KC from the library
+        nt, kc = CFG_NT_KC[cfg]
         base_off = 0
         if kind == "conv":  # [Co][Ci][k][k][k]
             rows, kdim, taps = w.shape[0], w.shape[1], w.shape[2] * w.shape[3] * w.shape[4]
