@@ -425,6 +425,21 @@ int md_conv3_head(const float* x, const float* ac, const void* wpk, float* y, in
                   int32_t D, int32_t H, int32_t W, void* stream);
 
 /*
+ * md_conv3_stem_dgrad: data gradient of the 3x3x3 stem conv (csrc/conv3_head.hip, the head kernel's second instantiation;
+ * ddpm_res64.py:72 applied :150), dx-folded like the head; md_fold_dx (kx = 3, bias NULL) finishes it:
+ *   dx[b][ci][p] = sum_co sum_tap W[co][ci][tap] g0[b][co][p - (tap - 1)],  ci < 4 (rows (ci, kw): 12 of rows_alloc = 16)
+ *   g0  : F32B [B][cout/8][P][8], the gradient of the stem's output, read as raw fp32 (no affine, no SiLU; bf16x3 split inside)
+ *   wpk : md_pack_weights(W2, rows = ci * 3, kdim = cout, taps = 9, nt = 32, kc = 16),
+ *         W2[(ci, kw)][co][kd][kh] = W[co][ci][2 - kd][2 - kh][2 - kw] (the flipped, transposed stem weight)
+ *   y   : F32B [B][rows_alloc/8][P][8], rows (ci, kw)
+ * Null or 16-byte-misaligned pointers, batch <= 0: MD_ERR_BAD_ARG.
+ * Supported: cout % 32 == 0, rows_alloc in {8, 16, 24, 32}, D % 4 == 0, H % 8 == 0, W % 8 == 0, D*H*W < 2^30;
+ * else MD_ERR_UNSUPPORTED.  Purely additive: MD_ABI_VERSION stays 16, no existing entry point changes.
+ */
+int md_conv3_stem_dgrad(const float* g0, const void* wpk, float* y, int32_t batch, int32_t cout, int32_t rows_alloc,
+                        int32_t D, int32_t H, int32_t W, void* stream);
+
+/*
  * md_pack_batch: several md_pack_weights / md_wino_pack_weights jobs in one launch (csrc/pack_batch.hip; a training step
  * re-packs every weight once: ~260 launches otherwise).  Bit-identical to the single-weight entry points.
  *   jobs_dev     : DEVICE array of n_jobs MdPackJob, sorted by block0; job j owns the blocks from block0 on
@@ -548,6 +563,19 @@ int md_langevin_step(const float* x, const float* eps, const float* z, const flo
                      int32_t batch, int32_t C, int64_t P, void* stream);
 int md_sde_step(const float* x, const float* eps, const float* z, const float* mask, const float* coef, int32_t kind,
                 float* x_out, float* x_mean_out, int32_t batch, int32_t C, int64_t P, void* stream);
+/*
+ * Right-hand side of the probability-flow ODE of the VP SDE (likelihood.py:63-78 drift_fn / div_fn; one launch):
+ *   drift = (c_x*x + c_e*eps_hat) * mask              formed in double, rounded to float once
+ *   coef[b][2] = {c_x = -0.5*beta(t), c_e = 0.5*beta(t)/sigma(t)} as doubles (score = -eps_hat/sigma, built by the host)
+ * With g (the vector-Jacobian product J^T probe of eps_hat) and probe, both [B][C][P]:
+ *   slabs[b][s] = sum over workgroup s's share of sample b of probe*(c_x*probe + c_e*g)*mask    (written, not added to)
+ * slabs is double[batch][MD_LANGEVIN_SLABS]; the sum of a sample's slabs is the Hutchinson estimate of the drift's
+ * divergence.  Deterministic: fixed grid, fixed order, fp64 partial sums, no atomics.  g and probe are both NULL (drift
+ * only: the ODE sampler) or both given, then with slabs; mask [P] binary or NULL.  P % 4 == 0; pointers 16-byte aligned (coef,
+ * slabs: 8); anything else MD_ERR_BAD_ARG.  Purely additive: MD_ABI_VERSION stays 16.
+ */
+int md_pf_ode_rhs(const float* x, const float* eps_hat, const float* g, const float* probe, const float* mask,
+                  const double* coef, float* drift, double* slabs, int32_t batch, int32_t C, int64_t P, void* stream);
 /*
  * Inpainting blend of one channel (sampling.py:443-467):
  *   v = (x*(1-m) + src*m) * gm     applied in place to channel `ch` of x [B][C][P];

@@ -5,6 +5,8 @@
 
 `--config` may be a reference-style python config file (get_config()) or one of the built-in
 names `res64` / `res128`.  `--mode=train` runs one rank per GPU under torchrun.
+`--mode=likelihood` writes {eval_dir}/likelihood.npz: bits/dim of the grids of `--config.data.meta_path` through the
+probability-flow ODE (`--config.eval.ode_rtol=1e-5 --config.eval.ode_atol=1e-5 --config.eval.num_batches=N` optional).
 """
 import sys
 
@@ -30,8 +32,8 @@ def parse(argv):
         i += 1
     if cfg_path is None or mode is None:
         raise SystemExit("flags --config and --mode are required")
-    if mode not in ("train", "uncond_gen", "cond_gen"):
-        raise SystemExit(f"--mode must be one of train|uncond_gen|cond_gen, got {mode}")
+    if mode not in ("train", "uncond_gen", "cond_gen", "likelihood"):
+        raise SystemExit(f"--mode must be one of train|uncond_gen|cond_gen|likelihood, got {mode}")
     if cfg_path in ("res64", "res128"):
         config = getattr(mdconfig, f"get_config_{cfg_path}")()
     else:
@@ -49,6 +51,8 @@ def main(argv=None):
         evaler.uncond_gen(config)
     elif mode == "cond_gen":
         evaler.cond_gen(config)
+    elif mode == "likelihood":
+        evaler.likelihood(config)
     else:
         from meshdiffusion_amd.lib.diffusion import trainer
         trainer.train(config)

@@ -13,11 +13,11 @@
 //   * weights of a chunk: 9 tap tiles x 2 KB (WPK, nt = 32, kc = 16) through LDS;
 //   * per tap a wave issues 3 dependent MFMAs (bf16x3, one accumulator) on 2 + 2 fragment reads: a wave is latency-bound by
 //     itself, and the transform is as much VALU time (16 quarter-rate exp / rcp per item) as the chunk's MFMAs.  So the halo
-//     and the weights are SINGLE-buffered (48 KB of LDS, < 128 registers): TWO workgroups per CU, four waves per SIMD -- one
-//     workgroup's transform phase runs under the other's MFMA phase.  Per chunk: request chunk c + 1 | 9 taps | barrier |
+//     and the weights are SINGLE-buffered (48 KB of LDS, 80 registers): THREE workgroups per CU, six waves per SIMD -- one
+//     workgroup's transform phase runs under the others' MFMA phases.  Per chunk: request chunk c + 1 | 9 taps | barrier |
 //     transform + commit | barrier.  (First form: double-buffered, one workgroup per CU, 0.77-0.81 ms at 64^3, B = 8; staggering
 //     the transform between the two waves of a SIMD changed nothing -- each wave's serial chain is the bound.)
-#include "md_common.h"
+#include "md_args.h"
 
 namespace {
 constexpr int HD_KC = 16, HD_TZ = 4, HD_TY = 8, HD_TX = 8;
@@ -38,6 +38,8 @@ struct HdArgs {
 };
 
 // (512 threads, 6 waves per SIMD: 80 registers and 48 KB of LDS put three workgroups on a CU)
+// RAW: the operand is read as it is -- no affine, no SiLU -- and only split (md_conv3_stem_dgrad below).
+template <bool RAW>
 __global__ __launch_bounds__(HD_THREADS, 6) void md_conv3_head_kernel(const HdArgs A) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[HD_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(HD_THREADS, 6) void md_conv3_head_kernel(const HdAr
   const float* acb = A.ac + (int64_t)b * A.cin * 2;
   const uint4* wbase = A.wpk + tid;
 
-  struct Stage { uint4 h[4]; uint4 w[3]; f32x4 ac[4]; };
+  struct Stage { uint4 h[4]; uint4 w[3]; f32x4 ac[RAW ? 1 : 4]; };     // RAW: no affine to carry
   Stage S;
   auto issue = [&](int cc) {                              // fp32 halo items, weights and affine of chunk cc -> registers
     const int g8 = cc * 2 + kg;
@@ -84,9 +86,11 @@ __global__ __launch_bounds__(HD_THREADS, 6) void md_conv3_head_kernel(const HdAr
     const uint4* wp = wbase + (int64_t)cc * (9 * HD_WTAP);
     S.w[0] = wp[0]; S.w[1] = wp[HD_THREADS];
     S.w[2] = wp[tid < 9 * HD_WTAP - 2 * HD_THREADS ? 2 * HD_THREADS : 0];
-    const f32x4* ap = (const f32x4*)(acb + g8 * 16);
+    if constexpr (!RAW) {
+      const f32x4* ap = (const f32x4*)(acb + g8 * 16);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) S.ac[q] = ap[q];
+      for (int q = 0; q < 4; ++q) S.ac[q] = ap[q];
+    }
   };
   auto commit = [&]() {                                   // affine + SiLU + zero pad + split -> halo buffer; weights -> stage
     unsigned char* hb = lds + HD_WSTAGE;
@@ -99,8 +103,11 @@ __global__ __launch_bounds__(HD_THREADS, 6) void md_conv3_head_kernel(const HdAr
       float yv[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        float y = v[e] * S.ac[e >> 1][(e & 1) * 2] + S.ac[e >> 1][(e & 1) * 2 + 1];
-        y = y * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y * -1.4426950408889634f));
+        float y = v[e];
+        if constexpr (!RAW) {
+          y = y * S.ac[e >> 1][(e & 1) * 2] + S.ac[e >> 1][(e & 1) * 2 + 1];
+          y = y * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y * -1.4426950408889634f));
+        }
         yv[e] = lv ? y : 0.f;
       }
       uint32_t hi[4], lo[4];
@@ -169,9 +176,9 @@ __global__ __launch_bounds__(HD_THREADS, 6) void md_conv3_head_kernel(const HdAr
   }
 }
 
-extern "C" int md_conv3_head(const float* x, const float* ac, const void* wpk, float* y, int32_t batch, int32_t cin,
-                             int32_t rows_alloc, int32_t D, int32_t H, int32_t W, void* stream) {
-  if (!x || !ac || !wpk || !y || batch <= 0) return MD_ERR_BAD_ARG;
+template <bool RAW>
+static int hd_launch(const float* x, const float* ac, const void* wpk, float* y, int32_t batch, int32_t cin, int32_t rows_alloc,
+                     int32_t D, int32_t H, int32_t W, void* stream) {
   if (cin <= 0 || (cin % (2 * HD_KC)) || rows_alloc <= 0 || rows_alloc > 32 || (rows_alloc & 7)) return MD_ERR_UNSUPPORTED;
   if (D <= 0 || H <= 0 || W <= 0 || (D % HD_TZ) || (H % HD_TY) || (W % HD_TX)) return MD_ERR_UNSUPPORTED;
   if ((int64_t)D * H * W * 2 >= (int64_t)1 << 31) return MD_ERR_UNSUPPORTED;
@@ -180,7 +187,26 @@ extern "C" int md_conv3_head(const float* x, const float* ac, const void* wpk, f
   a.batch = batch; a.cin = cin; a.rows_alloc = rows_alloc; a.D = D; a.H = H; a.W = W;
   const int tiles = (D / HD_TZ) * (H / HD_TY) * (W / HD_TX);
   MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_conv3_head_kernel, dim3((unsigned)(tiles * batch)), dim3(HD_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(md_conv3_head_kernel<RAW>, dim3((unsigned)(tiles * batch)), dim3(HD_THREADS), 0, (hipStream_t)stream, a);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
+}
+
+extern "C" int md_conv3_head(const float* x, const float* ac, const void* wpk, float* y, int32_t batch, int32_t cin,
+                             int32_t rows_alloc, int32_t D, int32_t H, int32_t W, void* stream) {
+  if (!x || !ac || !wpk || !y || batch <= 0) return MD_ERR_BAD_ARG;
+  return hd_launch<false>(x, ac, wpk, y, batch, cin, rows_alloc, D, H, W, stream);
+}
+
+// md_conv3_stem_dgrad: the data gradient of the 3x3x3 stem (lib/diffusion/models/ddpm_res64.py:72 applied :150) -- the head's shape
+// the other way round: g0, the F32B gradient of h0 (cout = nf channels, the largest gradient tensor of the net), to the 4 input
+// channels.  Same tile, same single-buffered schedule and the same dx fold as the head (rows = (ci, kw), 12 of 32; md_fold_dx adds
+// the three x-shifted columns); the loader reads raw fp32 and only splits it, so a chunk's transform phase is a fraction of the
+// head's (no exp / rcp) and the workgroup is bound by its three dependent MFMAs per tap alone.
+//   dx[b][ci][p] = sum_co sum_tap W[co][ci][tap] g0[b][co][p - (tap - 1)]:  wpk = md_pack_weights of W2[(ci, kw)][co][kd][kh] =
+//   W[co][ci][2 - kd][2 - kh][2 - kw], the flipped and transposed stem weight.
+extern "C" int md_conv3_stem_dgrad(const float* g0, const void* wpk, float* y, int32_t batch, int32_t cout, int32_t rows_alloc,
+                                   int32_t D, int32_t H, int32_t W, void* stream) {
+  if (md_any_bad<16>(g0, y) || md_any_bad<16>((const char*)wpk) || batch <= 0) return MD_ERR_BAD_ARG;
+  return hd_launch<true>(g0, nullptr, wpk, y, batch, cout, rows_alloc, D, H, W, stream);
 }

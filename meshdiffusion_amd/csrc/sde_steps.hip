@@ -3,7 +3,7 @@
 // per-sample coefficients come from the host, built once per sampler with the reference's float32 torch expressions.
 // Same operation order as the reference, no FMA contraction: with identical eps / z the updates are bit-identical to the
 // PyTorch elementwise chains.
-#include "md_common.h"
+#include "md_args.h"
 
 #pragma clang fp contract(off)
 
@@ -157,6 +157,49 @@ __global__ __launch_bounds__(256) void md_sde_step_kernel(const float* __restric
   }
 }
 
+// ---- probability-flow ODE right-hand side (reference lib/diffusion/likelihood.py:63-78 drift_fn / div_fn, one launch) ----
+// coef[b] = {c_x = -0.5*beta(t), c_e = 0.5*beta(t)/sigma(t)} as doubles (VPSDE.sde with score = -eps_hat/sigma under
+// probability flow): drift = (c_x*x + c_e*eps_hat)*mask, formed in double and rounded once.  With the vector-Jacobian product
+// g = J^T probe: slabs[b][s] = sum over workgroup s's share of probe*(c_x*probe + c_e*g)*mask -- the Hutchinson estimate of the
+// drift's divergence, in the manner of md_langevin_norms: fixed grid, fixed per-thread order, fp64 partial sums, no atomics.
+template <bool DIV>
+__global__ __launch_bounds__(256) void md_pf_ode_rhs_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                            const float* __restrict__ g, const float* __restrict__ probe,
+                                                            const float* __restrict__ mask, const double* __restrict__ coef,
+                                                            float* __restrict__ drift, double* __restrict__ slabs, int64_t CP,
+                                                            int64_t P) {
+  const int b = blockIdx.y;
+  const double cx = coef[b * 2 + 0], ce = coef[b * 2 + 1];
+  const int64_t base = (int64_t)b * CP;
+  double acc = 0.0;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
+    const f32x4 xv = *(const f32x4*)(x + base + i);
+    const f32x4 ev = *(const f32x4*)(eps + base + i);
+    f32x4 mv = {1.f, 1.f, 1.f, 1.f};
+    if (mask) mv = *(const f32x4*)(mask + (i % P));
+    f32x4 dv;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dv[e] = (float)((cx * (double)xv[e] + ce * (double)ev[e]) * (double)mv[e]);
+    *(f32x4*)(drift + base + i) = dv;
+    if constexpr (DIV) {
+      const f32x4 gv = *(const f32x4*)(g + base + i);
+      const f32x4 pv = *(const f32x4*)(probe + base + i);
+      double t[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) t[e] = ((double)pv[e] * (cx * (double)pv[e] + ce * (double)gv[e])) * (double)mv[e];
+      acc += (t[0] + t[1]) + (t[2] + t[3]);
+    }
+  }
+  if constexpr (DIV) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) slabs[(int64_t)b * MD_LANGEVIN_SLABS + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  }
+}
+
 // one workgroup per 1024 values, at most 1024 workgroups in all (B*S <= 1024 keeps the slab prologue's L2 reads small)
 static int stream_blocks(int64_t CP, int batch) {
   int64_t blocks = (CP / 4 + 255) / 256;
@@ -198,6 +241,25 @@ extern "C" int md_sde_step(const float* x, const float* eps, const float* z, con
   MD_HIP_CLEAR_ERROR();
   hipLaunchKernelGGL(md_sde_step_kernel, dim3((unsigned)stream_blocks(CP, batch), (unsigned)batch), dim3(256), 0,
                      (hipStream_t)stream, x, eps, z, mask, coef, (int)kind, x_out, x_mean_out, CP, P);
+  MD_HIP_CHECK_LAUNCH();
+  return MD_OK;
+}
+
+extern "C" int md_pf_ode_rhs(const float* x, const float* eps_hat, const float* g, const float* probe, const float* mask,
+                             const double* coef, float* drift, double* slabs, int32_t batch, int32_t C, int64_t P, void* stream) {
+  if (md_any_bad<16>(x, eps_hat, drift) || md_any_bad<8>(coef) || md_any_misaligned<16>(g, probe, mask) ||
+      md_any_misaligned<8>(slabs))
+    return MD_ERR_BAD_ARG;
+  if (batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
+  if ((g == nullptr) != (probe == nullptr) || (g && !slabs)) return MD_ERR_BAD_ARG;     // the divergence needs both, and its slabs
+  const int64_t CP = (int64_t)C * P;
+  MD_HIP_CLEAR_ERROR();
+  if (g)
+    hipLaunchKernelGGL(md_pf_ode_rhs_kernel<true>, dim3(MD_LANGEVIN_SLABS, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, x,
+                       eps_hat, g, probe, mask, coef, drift, slabs, CP, P);
+  else
+    hipLaunchKernelGGL(md_pf_ode_rhs_kernel<false>, dim3((unsigned)stream_blocks(CP, batch), (unsigned)batch), dim3(256), 0,
+                       (hipStream_t)stream, x, eps_hat, g, probe, mask, coef, drift, slabs, CP, P);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }

@@ -891,6 +891,25 @@ def conv3_head(pw, x, ac, B, S, rows_alloc, dims=None):
     return y
 
 
+def conv3_stem_dgrad_ok(cout, D, H, W):
+    """The shapes md_conv3_stem_dgrad takes (its header comment); the caller's other route is the generic dx-folded tile."""
+    return cout % 32 == 0 and D % 4 == 0 and H % 8 == 0 and W % 8 == 0 and D * H * W < (1 << 30)
+
+
+def conv3_stem_dgrad(pw, g0, B, S, rows_alloc, dims=None):
+    """y F32B [B][rows_alloc][S^3] (rows = (ci, kw)) of the dx-folded data gradient of the 3x3x3 stem on the raw F32B gradient g0
+    of its output -- md_conv3_stem_dgrad; fold_dx finishes it.  dims: the grid (D, H, W) where it is not the cube S^3."""
+    lib = _lib.load()
+    D, H, W = dims if dims is not None else (S, S, S)
+    P = D * H * W
+    y = f32b_empty(B, rows_alloc, P, g0.device)
+    ev = _prof_begin()
+    check(lib.md_conv3_stem_dgrad(_ptr(g0), _ptr(pw.data), _ptr(y), B, pw.kdim, rows_alloc, D, H, W, _stream()), "md_conv3_stem_dgrad")
+    _prof_end(ev, "stem_dgrad", 2.0 * B * pw.rows * pw.kdim * 9 * P, 4.0 * (B * pw.kdim * P + pw.rows * pw.kdim * 9 + B * rows_alloc * P),
+              f"{pw.kdim}->{pw.rows}@{D}x{H}x{W}")
+    return y
+
+
 def _prof_begin():
     if PROFILE is None:
         return None
@@ -1223,6 +1242,34 @@ def sde_step(x, eps, z, mask, coef, kind):
     check(lib.md_sde_step(_ptr(x), _ptr(eps), _ptr(z), _ptr(mask), _ptr(coef), k, _ptr(x_out), _ptr(xm_out), B, Cc, P,
                           _stream()), "md_sde_step")
     return x_out, xm_out
+
+
+def pf_ode_rhs(x, eps_hat, mask, coef, g=None, probe=None):
+    """Right-hand side of the probability-flow ODE in one launch (md_pf_ode_rhs).  x, eps_hat: [B,C,D,H,W] fp32; mask [P] or
+    None; coef [B,2] float64 = (-0.5*beta(t), 0.5*beta(t)/sigma(t)).  Returns (drift fp32 like x, div): with g = J^T probe and
+    probe given, div [B] float64 = sum probe*(c_x*probe + c_e*g)*mask, the Hutchinson estimate of the drift's divergence (64
+    slab sums per sample, added in a fixed order); without them div is None (the ODE sampler)."""
+    lib = _lib.load()
+    ts = [("x", x), ("eps_hat", eps_hat), ("coef", coef)] + ([("g", g), ("probe", probe)] if g is not None else [])
+    for name, t in ts:
+        _require_cuda(t, name)
+    assert (g is None) == (probe is None)
+    x, eps_hat, coef = x.contiguous(), eps_hat.contiguous(), coef.contiguous()
+    B, Cc = x.shape[0], x.shape[1]
+    P = x[0, 0].numel()
+    assert x.dtype == eps_hat.dtype == torch.float32 and coef.dtype == torch.float64 and coef.shape == (B, 2), (coef.dtype, coef.shape)
+    if mask is not None:
+        _require_cuda(mask, "mask")
+        assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == P, (mask.dtype, tuple(mask.shape), P)
+    drift = torch.empty_like(x)
+    slabs = None
+    if g is not None:
+        g, probe = g.contiguous(), probe.contiguous()
+        assert g.dtype == probe.dtype == torch.float32 and g.shape == probe.shape == x.shape
+        slabs = torch.empty((B, _lib.LANGEVIN_SLABS), dtype=torch.float64, device=x.device)
+    check(lib.md_pf_ode_rhs(_ptr(x), _ptr(eps_hat), _ptr(g), _ptr(probe), _ptr(mask), _ptr(coef), _ptr(drift), _ptr(slabs), B, Cc, P,
+                            _stream()), "md_pf_ode_rhs")
+    return drift, (slabs.sum(dim=1) if slabs is not None else None)
 
 
 def ddim_step(x64, eps, mask, coef, partial=None, pmask=None, ch=0):

@@ -25,25 +25,37 @@ from .models.ema import ExponentialMovingAverage
 from .utils import restore_checkpoint
 
 
-def _setup(config, mask_shape, local_batch=None):
-    eval_dir, ckpt_path = config.eval.eval_dir, config.eval.ckpt_path
-    os.makedirs(eval_dir, exist_ok=True)
+def _load_model(config):
+    """The score model of `config.eval.ckpt_path` with its EMA weights, and the SDE."""
+    ckpt_path = config.eval.ckpt_path
+    os.makedirs(config.eval.eval_dir, exist_ok=True)
     score_model = mutils.create_model(config)
     optimizer = losses.get_optimizer(config, score_model.parameters())
     ema = ExponentialMovingAverage(score_model.parameters(), decay=config.model.ema_rate)
     state = dict(optimizer=optimizer, model=score_model, ema=ema, step=0)
     sde = sde_lib.VPSDE(beta_min=config.model.beta_min, beta_max=config.model.beta_max,
                         N=config.model.num_scales, device=config.device)
-    R = config.data.image_size
-    mask_path = getattr(config.eval, "grid_mask_path", None) or f"./data/grid_mask_{R}.pt"
-    grid_mask = torch.load(mask_path, map_location=config.device).view(*mask_shape(R)).to(config.device)
-    shape = (config.eval.batch_size if local_batch is None else local_batch, config.data.num_channels, R, R, R)
-    sampling_fn = sampling.get_sampling_fn(config, sde, shape, lambda x: x, 1e-3, grid_mask=grid_mask)
     assert os.path.exists(ckpt_path), ckpt_path
     print("ckpt path:", ckpt_path)
     state = restore_checkpoint(ckpt_path, state, device=config.device)
     ema.copy_to(score_model.parameters())
     print(f"loaded model is trained till iter {state['step'] // config.training.iter_size}")
+    return score_model, sde
+
+
+def _grid_mask(config, shape):
+    R = config.data.image_size
+    mask_path = getattr(config.eval, "grid_mask_path", None) or f"./data/grid_mask_{R}.pt"
+    return torch.load(mask_path, map_location=config.device).view(*shape).to(config.device)
+
+
+def _setup(config, mask_shape, local_batch=None):
+    eval_dir = config.eval.eval_dir
+    score_model, sde = _load_model(config)
+    R = config.data.image_size
+    grid_mask = _grid_mask(config, mask_shape(R))
+    shape = (config.eval.batch_size if local_batch is None else local_batch, config.data.num_channels, R, R, R)
+    sampling_fn = sampling.get_sampling_fn(config, sde, shape, lambda x: x, 1e-3, grid_mask=grid_mask)
     # the checkpoint's weights meet the reduced-precision conv formats here for the first time: measure every conv's operand on a
     # few noise batches, rebuild the equalisers from the measurement, audit each conv against its bf16x3 form and demote the ones
     # above the bar (models/utils.calibrate_model; config.eval.calibrate = False skips it)
@@ -121,3 +133,46 @@ def cond_gen(config, save_fname="0"):
                            freeze_iters=config.eval.freeze_iters)[0]
 
     return _generate(config, lambda R: (1, 1, R, R, R), save_fname, run)
+
+
+def likelihood(config):
+    """Held-out log-likelihood of the grids of `config.data.meta_path` through the probability-flow ODE
+    (likelihood.get_likelihood_fn on the grid mask; the reference ships the function, lib/diffusion/likelihood.py, but no driver
+    that reaches it).  Restores the checkpoint, applies the EMA, no calibration: every evaluation is the bf16x3 taped forward and
+    the data-gradient-only backward.  `config.eval.batch_size` grids per batch, read as the trainer reads them but without
+    augmentation; optional config.eval fields: ode_rtol / ode_atol (1e-5), ode_eps (1e-5), num_batches (all), hutchinson
+    ('Rademacher').  Writes {eval_dir}/likelihood.npz: bpd, logp, delta_logp (nats), nfe per batch, the dataset indices.
+    Single process."""
+    from ..dataset.shapenet_dmtet_dataset import ShapeNetDMTetDataset
+    from . import likelihood as lk
+    ev = config.eval
+    R = config.data.image_size
+    score_model, sde = _load_model(config)
+    score_model.eval()
+    mask = _grid_mask(config, (1, 1, R, R, R))
+    dataset = ShapeNetDMTetDataset(config.data.meta_path, deform_scale=config.model.deform_scale, aug=False, grid_mask=mask,
+                                   filter_meta_path=config.data.filter_meta_path, normalize_sdf=config.data.normalize_sdf,
+                                   extension=config.data.extension)
+    gen = torch.Generator(device=config.device).manual_seed(int(getattr(config, "seed", 0)))
+    fn = lk.get_likelihood_fn(sde, lambda x: x, hutchinson_type=getattr(ev, "hutchinson", "Rademacher"),
+                              rtol=float(getattr(ev, "ode_rtol", 1e-5)), atol=float(getattr(ev, "ode_atol", 1e-5)),
+                              eps=float(getattr(ev, "ode_eps", 1e-5)), grid_mask=mask, generator=gen)
+    B, n = int(ev.batch_size), len(dataset)
+    starts = list(range(0, n, B))
+    if getattr(ev, "num_batches", None):
+        starts = starts[:int(ev.num_batches)]
+    out = dict(bpd=[], logp=[], delta_logp=[], nfe=[], index=[])
+    for s in starts:
+        idx = list(range(s, min(s + B, n)))
+        batch = (torch.stack([dataset[i] for i in idx]).float().to(config.device) * mask).contiguous()
+        bpd, _, nfe, delta_logp, prior_logp = fn(score_model, batch, return_parts=True)
+        out["bpd"].append(bpd.cpu().numpy())
+        out["logp"].append((prior_logp + delta_logp).cpu().numpy())
+        out["delta_logp"].append(delta_logp.cpu().numpy())
+        out["nfe"].append(nfe)
+        out["index"].append(np.array(idx, dtype=np.int64))
+        print(f"grids {idx[0]}..{idx[-1]}: bits/dim {out['bpd'][-1]}, nfe {nfe}")
+    res = {k: (np.array(v, dtype=np.int64) if k == "nfe" else np.concatenate(v)) for k, v in out.items()}
+    np.savez(os.path.join(ev.eval_dir, "likelihood.npz"), **res)
+    ops_release()
+    return res

@@ -114,14 +114,16 @@ def resample(t, B, C, Sc, mode, accumulate_into=None):
 # ---------------------------------------------------------------------------------------------------------
 # GroupNorm (+SiLU) backward over concatenated parts
 # ---------------------------------------------------------------------------------------------------------
-def gn_backward(parts, dy, params, gn, B, P, silu, d_into=None, drop=None, residual=None, sums_out=None, want_amax=False):
+def gn_backward(parts, dy, params, gn, B, P, silu, d_into=None, drop=None, residual=None, sums_out=None, want_amax=False,
+                param_grads=True):
     """parts: forward inputs [(F32B, C)]; dy: F32B [B][Ctot][P]; returns one F32B [B][Ctot][P] gradient
     (written into / accumulated onto `d_into` when given) and accumulates gn.weight/.bias grads.
     drop=(p, seed): the forward applied dropout after the activation (same mask regenerated here).
     Single-part extras: residual (F32B): result = residual + gradient (identity shortcut, no separate copy);
     sums_out (zeroed float [B, Ctot]): += per-(sample, channel) sums of the gradient (bias / FiLM gradients);
     want_amax: the result carries `_md_amax`, the device word with its max |.| (hip_ops.absmax_word's, without the extra pass) -- for
-    a consumer that is the f16f6 data-gradient conv and reads the tensor unmodified."""
+    a consumer that is the f16f6 data-gradient conv and reads the tensor unmodified.
+    param_grads=False: the data gradient alone; gn.weight/.bias get no gradient and no `.grad` is created."""
     lib = _lib.load()
     dp, dseed = (float(drop[0]), int(drop[1])) if drop else (0.0, 0)
     dev = dy.device
@@ -133,8 +135,9 @@ def gn_backward(parts, dy, params, gn, B, P, silu, d_into=None, drop=None, resid
                                   dp, dseed, _stream()), "md_gn_bwd_stats")
         off += c
     coef = torch.empty((B, ctot, 4), dtype=torch.float32, device=dev)
-    check(lib.md_gn_bwd_finalize(_ptr(sums), _ptr(params), _ptr(gn.weight), _ptr(coef), _ptr(_grad_of(gn.weight)),
-                                 _ptr(_grad_of(gn.bias)), B, ctot, gn.num_groups, P, _stream()), "md_gn_bwd_finalize")
+    dgamma, dbeta = (_grad_of(gn.weight), _grad_of(gn.bias)) if param_grads else (None, None)   # the kernel skips a null sum
+    check(lib.md_gn_bwd_finalize(_ptr(sums), _ptr(params), _ptr(gn.weight), _ptr(coef), _ptr(dgamma),
+                                 _ptr(dbeta), B, ctot, gn.num_groups, P, _stream()), "md_gn_bwd_finalize")
     acc = d_into is not None
     assert (residual is None and sums_out is None) or (len(parts) == 1 and not acc)
     outs = []
@@ -184,7 +187,7 @@ def dgrad_wino_weight_f6(layer, name, conv):
 
 
 def conv3_backward(layer, name, conv, dy, act_s16, B, S_out, ups=0, stride=1, need_dx=True, act_channels=None,
-                   bias_sums=None, shared=None, t_act=None, bias_sums_out=False):
+                   bias_sums=None, shared=None, t_act=None, bias_sums_out=False, param_grads=True):
     """Backward of y = conv k^3 (act) (+bias), k = 3 (any layer) or 5 (stem / head of ddpm_res128, stride 1).
     dy: F32B [B][co][S_out^3]; act_s16: S16B input operand of the forward (coarse grid when ups, fine grid 2*S_out
     when stride 2).  Returns dx (F32B) or None.
@@ -193,8 +196,13 @@ def conv3_backward(layer, name, conv, dy, act_s16, B, S_out, ups=0, stride=1, ne
     t_act: the forward conv's Winograd operand T (layers on the Winograd path, hip_ops.wgrad_wino_ok) in place of `act_s16`:
     ONE pass over dy (md_wino_prep_dual) feeds the Winograd data-gradient conv and the Winograd weight gradient (md_wgrad_wino);
     no S16B / PB16 tensors at all.  bias_sums_out (with t_act): `bias_sums` is a ZEROED [B, co] float tensor that this call
-    fills (the operand pass over dy adds up its channels) for the caller's other consumers of the same sums."""
+    fills (the operand pass over dy adds up its channels) for the caller's other consumers of the same sums.
+    param_grads=False: the data gradient alone -- no bias sums, no PB16 operands, no weight-gradient launch, no `.grad`; a layer
+    on the Winograd path takes the single operand pass + md_conv3_wino below instead of the dual pass (`t_act` is not read)."""
     from . import layers
+    if not param_grads:
+        assert need_dx and not bias_sums_out
+        t_act, bias_sums = None, False
     co, ci, ksz = conv.weight.shape[0], conv.weight.shape[1], conv.weight.shape[-1]
     taps, pad = ksz ** 3, ksz // 2
     assert ksz == 3 or (ksz == 5 and stride == 1 and not ups)
@@ -243,18 +251,19 @@ def conv3_backward(layer, name, conv, dy, act_s16, B, S_out, ups=0, stride=1, ne
         return dx
     # weight gradient
     S_fine = S_out * stride
-    if stride == 2:
-        dy_pb = to_pb16(dy, B, co_t, S_fine, 0, stuff=1, zhalo=False)
-    elif shared is not None and pad == 1:
-        dy_pb = shared.get("dy_pb")
-        if dy_pb is None:
-            dy_pb = shared["dy_pb"] = to_pb16(dy, B, co_t, S_out, 0, pad=pad, zhalo=False)
-    else:
-        dy_pb = to_pb16(dy, B, co_t, S_out, 0, pad=pad, zhalo=False)
-    c_src = act_channels if act_channels is not None else ci      # channels of the S16B operand tensor
-    act_pb = to_pb16(act_s16, B, c_src, S_fine, 1, up=ups, pad=pad)
-    wgrad(dy_pb, act_pb, B, co, ci, S_fine, taps, _grad_of(conv.weight), ci * taps, taps, 1, a_ch=co_t, b_ch=c_src)
-    del dy_pb, act_pb
+    if param_grads:
+        if stride == 2:
+            dy_pb = to_pb16(dy, B, co_t, S_fine, 0, stuff=1, zhalo=False)
+        elif shared is not None and pad == 1:
+            dy_pb = shared.get("dy_pb")
+            if dy_pb is None:
+                dy_pb = shared["dy_pb"] = to_pb16(dy, B, co_t, S_out, 0, pad=pad, zhalo=False)
+        else:
+            dy_pb = to_pb16(dy, B, co_t, S_out, 0, pad=pad, zhalo=False)
+        c_src = act_channels if act_channels is not None else ci      # channels of the S16B operand tensor
+        act_pb = to_pb16(act_s16, B, c_src, S_fine, 1, up=ups, pad=pad)
+        wgrad(dy_pb, act_pb, B, co, ci, S_fine, taps, _grad_of(conv.weight), ci * taps, taps, 1, a_ch=co_t, b_ch=c_src)
+        del dy_pb, act_pb
     if not need_dx:
         return None
     # data gradient: same conv kernels, flipped/transposed weights
@@ -329,20 +338,24 @@ def wgrad_nin(dy_pb, xs_s16, B, co, ci, S, dw):
     wgrad(dy_pb, x_pb, B, co, ci, S, 1, dw, 1, co, 0)
 
 
-def nin_backward(nin, dy, xs_s16, B, P, S, need_dx=True, with_bias=True, bias_sums=None, shared=None, accumulate_into=None):
+def nin_backward(nin, dy, xs_s16, B, P, S, need_dx=True, with_bias=True, bias_sums=None, shared=None, accumulate_into=None,
+                 param_grads=True):
     """Backward of y[co] = sum_ci x[ci] W[ci][co] + b.  xs_s16: S16B of the forward input.
     bias_sums / shared: per-(sample, channel) sums and dy-derived operands already computed for another consumer of `dy`.
     accumulate_into: [(F32B tensor, channels), ...] covering the input channels in order -- the data gradient is ADDED to those
     tensors by one GEMM per part (rows of W sliced, the tensor as residual and output) instead of being returned: no
     concatenated gradient tensor and no separate add passes (the ResnetBlock shortcut: the parts already hold the GroupNorm_0
-    path's gradient)."""
+    path's gradient).
+    param_grads=False: the data gradient alone (`xs_s16` is not read; no bias sums, no weight-gradient launch, no `.grad`)."""
     from . import layers
     ci, co = nin.W.shape
-    if with_bias:
+    if with_bias and param_grads:
         bs = bias_sums if bias_sums is not None else channel_sums(dy, B, co, P)
         _grad_of(nin.b).add_(bs.sum(0)[:co])
     dy16 = shared.get("dy_s16") if shared is not None else None
-    if ops.wgrad_nin_ok(co, ci, P):
+    if not param_grads:
+        assert need_dx
+    elif ops.wgrad_nin_ok(co, ci, P):
         # both operands as they are (S16B): no PB16 re-layout; the same split of dy feeds the data-gradient GEMM below
         if dy16 is None:
             dy16 = split_f32b(dy, B, co, P)
@@ -378,15 +391,17 @@ def nin_backward(nin, dy, xs_s16, B, P, S, need_dx=True, with_bias=True, bias_su
     return layers.run_gemm(pw, dy16, B, P)
 
 
-def attn_backward(blk, sv, dy):
-    """Backward of AttnBlock.forward_blocked (single head, keys blocked by 8; see layers.AttnBlock)."""
+def attn_backward(blk, sv, dy, param_grads=True):
+    """Backward of AttnBlock.forward_blocked (single head, keys blocked by 8; see layers.AttnBlock).
+    param_grads=False: the data gradient alone (the same GEMMs without the bias sums and the four NIN weight gradients)."""
     from . import layers
     B, P, S, Cc = sv["B"], sv["P"], sv["S"], blk.channels
     x, prm, hN, qk, vT, pr, o = sv["x"], sv["prm"], sv["hN"], sv["qk"], sv["vT"], sv["pr"], sv["o"]
     alpha = ops.attn_scale(Cc)
     # y = NIN_3(o) + x
-    d_o = nin_backward(blk.NIN_3, dy, o, B, P, S)                               # F32B [C][P]
-    _grad_of(blk.NIN_2.b).add_(channel_sums(d_o, B, Cc, P).sum(0))              # o = V P + b_v
+    d_o = nin_backward(blk.NIN_3, dy, o, B, P, S, param_grads=param_grads)      # F32B [C][P]
+    if param_grads:
+        _grad_of(blk.NIN_2.b).add_(channel_sums(d_o, B, Cc, P).sum(0))          # o = V P + b_v
     d_o16 = split_f32b(d_o, B, Cc, P)                                           # [C/8][2][q][8c]
     v_cb = s16b_transpose(vT, B, P, Cc)                                         # [C/8][2][key][8c]
     dP = bgemm(v_cb, P, d_o16, P, Cc, B)                                        # [key/8][q][8]
@@ -407,22 +422,24 @@ def attn_backward(blk, sv, dy):
     dqk = torch.cat([dq, dk], dim=1).contiguous()                               # F32B [2C][P]
     # q|k = NIN_0|NIN_1 (h)
     wqk = torch.cat([blk.NIN_0.W.detach(), blk.NIN_1.W.detach()], dim=1).contiguous()   # [C][2C]
-    bsum = channel_sums(dqk, B, 2 * Cc, P).sum(0)
-    _grad_of(blk.NIN_0.b).add_(bsum[:Cc]); _grad_of(blk.NIN_1.b).add_(bsum[Cc:])
-    dw = torch.zeros_like(wqk)
-    dqk_pb = to_pb16(dqk, B, 2 * Cc, S, 0, zhalo=False)
-    wgrad_nin(dqk_pb, hN, B, 2 * Cc, Cc, S, dw)
-    _grad_of(blk.NIN_0.W).add_(dw[:, :Cc]); _grad_of(blk.NIN_1.W).add_(dw[:, Cc:])
-    del dqk_pb
+    if param_grads:
+        bsum = channel_sums(dqk, B, 2 * Cc, P).sum(0)
+        _grad_of(blk.NIN_0.b).add_(bsum[:Cc]); _grad_of(blk.NIN_1.b).add_(bsum[Cc:])
+        dw = torch.zeros_like(wqk)
+        dqk_pb = to_pb16(dqk, B, 2 * Cc, S, 0, zhalo=False)
+        wgrad_nin(dqk_pb, hN, B, 2 * Cc, Cc, S, dw)
+        _grad_of(blk.NIN_0.W).add_(dw[:, :Cc]); _grad_of(blk.NIN_1.W).add_(dw[:, Cc:])
+        del dqk_pb
     cfg = ops.gemm_cfg_for(P, Cc)
     pw = ops.PackedWeight(wqk, "rows", cfg, wqk.device)
     d_h = layers.run_gemm(pw, split_f32b(dqk, B, 2 * Cc, P), B, P)
     # v = NIN_2(h) (bias handled above)
-    dv_pb = to_pb16(dV, B, Cc, S, 0, zhalo=False)
-    wgrad_nin(dv_pb, hN, B, Cc, Cc, S, _grad_of(blk.NIN_2.W))
-    del dv_pb
+    if param_grads:
+        dv_pb = to_pb16(dV, B, Cc, S, 0, zhalo=False)
+        wgrad_nin(dv_pb, hN, B, Cc, Cc, S, _grad_of(blk.NIN_2.W))
+        del dv_pb
     pw2 = blk.NIN_2._cached(f"dgrad{cfg}", [blk.NIN_2.W], lambda: ops.PackedWeight(blk.NIN_2.W, "rows", cfg, blk.NIN_2.W.device))
     d_h.add_(layers.run_gemm(pw2, split_f32b(dV, B, Cc, P), B, P))
     dx = dy.clone()
-    gn_backward([(x, Cc)], d_h, prm, blk.GroupNorm_0, B, P, silu=False, d_into=dx)
+    gn_backward([(x, Cc)], d_h, prm, blk.GroupNorm_0, B, P, silu=False, d_into=dx, param_grads=param_grads)
     return dx

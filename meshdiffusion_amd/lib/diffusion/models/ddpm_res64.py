@@ -14,6 +14,7 @@ is computed once per weight version and added in the stem conv's epilogue.
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import layers, utils
 from .... import hip_ops as ops
@@ -156,10 +157,14 @@ class DDPMUNet3D(layers.HipLayer):
         with ops.precision_scope(None, training=True):
             return self._forward_train(x, labels)
 
-    def backward(self, ctx, d_eps):
-        """Accumulate d(loss)/d(parameter) into `.grad` for every trainable parameter, given d(loss)/d(eps_hat)."""
+    def backward(self, ctx, d_eps, input_grad=False, param_grads=True):
+        """Accumulate d(loss)/d(parameter) into `.grad` for every trainable parameter, given d(loss)/d(eps_hat).
+        input_grad: also return d(loss)/dx as NCDHW fp32 [B, C, R, R, R] (with the factor 2 of xin = 2x - 1 when the data
+        is not centered; the mask and coords slots of the stem operand get none).
+        param_grads=False: the vector-Jacobian product with respect to x alone -- no weight-gradient, bias-sum or
+        GroupNorm-parameter launch, no `.grad` created or touched, no gradient-ready hook, no parameter-epoch bump."""
         with ops.precision_scope(None, training=True):
-            return self._backward(ctx, d_eps)
+            return self._backward(ctx, d_eps, input_grad, param_grads)
 
     def _forward_train(self, x, labels):
         if self.scale_by_sigma:
@@ -256,7 +261,7 @@ class DDPMUNet3D(layers.HipLayer):
                    a_final=a, foffs=foffs, ftot=ftot, fw=fw)
         return out, ctx
 
-    def _backward(self, ctx, d_eps):
+    def _backward(self, ctx, d_eps, input_grad=False, param_grads=True):
         from . import backward as bw
         from torch.nn import functional as F
         mods = self.all_modules
@@ -276,11 +281,11 @@ class DDPMUNet3D(layers.HipLayer):
         dy = ops.ncdhw_to_f32b(d8)
         gn, head = mods[-2], mods[-1]
         hl, c, p = acts[ctx["last"]]
-        d_a = bw.conv3_backward(self, "head", head, dy, ctx["a_final"], B, R)
-        acc(ctx["last"], bw.gn_backward([(hl, c)], d_a, ctx["gn_prm"], gn, B, p, silu=True)[0])
+        d_a = bw.conv3_backward(self, "head", head, dy, ctx["a_final"], B, R, param_grads=param_grads)
+        acc(ctx["last"], bw.gn_backward([(hl, c)], d_a, ctx["gn_prm"], gn, B, p, silu=True, param_grads=param_grads)[0])
         del d_a
-        d_film = torch.zeros((B, ctx["ftot"]), dtype=torch.float32, device=dev)
-        hook = self.__dict__.get("_grad_ready_hook")     # parallel.GradReducer.ready during multi-GPU training
+        d_film = torch.zeros((B, ctx["ftot"]), dtype=torch.float32, device=dev) if param_grads else None
+        hook = self.__dict__.get("_grad_ready_hook") if param_grads else None     # parallel.GradReducer.ready during multi-GPU training
 
         def announce(layer):
             # gradients that are final once this layer's backward ran (Dense_0 / Conv_0.bias of a ResnetBlock
@@ -295,19 +300,22 @@ class DDPMUNet3D(layers.HipLayer):
         for kind, layer, sv, ins, out in reversed(tape):
             g = grads.pop(out)
             if kind == "res":
-                dparts, dbias0 = layer.backward_blocked(sv, g)
-                o = ctx["foffs"][id(layer)]
-                d_film[:, o:o + layer.out_ch] = dbias0
+                dparts, dbias0 = layer.backward_blocked(sv, g, param_grads=param_grads)
+                if param_grads:
+                    o = ctx["foffs"][id(layer)]
+                    d_film[:, o:o + layer.out_ch] = dbias0
                 for vid, dp in zip(ins, dparts):
                     acc(vid, dp)
             else:
-                acc(ins[0], layer.backward_blocked(sv, g))
+                acc(ins[0], layer.backward_blocked(sv, g, param_grads=param_grads))
             del g
             sv.clear()          # the layer's saved tensors (Winograd operands T, S16B activations) are dead: free them now
             announce(layer)
         # stem: h0 = conv(x) + pos_layer(coords) + mask_layer(mask) (+ biases)
         g0 = grads.pop(ctx["v0"])
         stem = mods[2]
+        if not param_grads:
+            return self._stem_dgrad(stem, g0, B, R) if input_grad else None
         bsum = bw.channel_sums(g0, B, self.nf, P).sum(0)     # all three biases receive the same sum of g0
         convs = [(stem, 0, stem.weight.shape[1]), (self.mask_layer, stem.weight.shape[1], 1)]
         if self.USE_COORDS:
@@ -322,6 +330,7 @@ class DDPMUNet3D(layers.HipLayer):
         for conv, c0, c in convs:
             bw._grad_of(conv.weight).add_(dw[:, c0:c0 + c].reshape(conv.weight.shape))
             bw._grad_of(conv.bias).add_(bsum[:self.nf])
+        dx = self._stem_dgrad(stem, g0, B, R) if input_grad else None
         del g0
         # FiLM table + timestep MLP (tiny [B,512] algebra: torch ops on the device)
         temb, t1, emb = ctx["temb"], ctx["t1"], ctx["emb"]
@@ -344,6 +353,7 @@ class DDPMUNet3D(layers.HipLayer):
         bw._grad_of(mods[0].weight).add_(d_t1.t() @ emb)
         bw._grad_of(mods[0].bias).add_(d_t1.sum(0))
         ops.bump_param_epoch()   # nothing cached depends on grads, but keep caches honest if an optimizer steps next
+        return dx
 
     def grad_completion_order(self):
         """Trainable parameters in the order `backward` finishes (and announces) their gradients: final GroupNorm + head,
@@ -396,6 +406,30 @@ class DDPMUNet3D(layers.HipLayer):
             return out
         return layers.run_conv3(pw, xf, B, R, bias=stem.bias, residual=self._stem_const(), res_bstride=0)
 
+    def _stem_dgrad(self, stem, g0, B, R):
+        """d(loss)/dx NCDHW [B, C, R, R, R] from g0, the F32B gradient of h0: the stem's data gradient
+        dx[ci][p] = sum_co sum_tap W[co][ci][tap] g0[co][p - (tap - 1)], the head's shape (nf -> C) and dx-folded like it: rows are
+        the (ci, kx) pairs of the flipped, transposed stem weight, `md_fold_dx` adds the k x-shifted columns.  k = 3 on a grid
+        md_conv3_stem_dgrad takes: that kernel reads g0 as raw fp32; otherwise (the 5x5x5 stem of ddpm_res128, odd grids) one
+        bf16 split of g0 and the generic dx-folded tile.  The factor 2 of xin = 2x - 1 rides in the packed weights (exact)."""
+        from . import backward as bw
+        k, ci = self.KSIZE, stem.weight.shape[1]
+        scale = 1.0 if self.centered else 2.0
+        fused = k == 3 and ops.PRECISION == "bf16x3" and ops.conv3_stem_dgrad_ok(self.nf, R, R, R)
+        cfg = ops.CFG_HEAD_PACK if fused else (ops.CFG_C3X_32 if k == 3 else ops.CFG_C5X_32_K16)
+
+        def build():
+            w = stem.weight.detach().flip(2, 3, 4).transpose(0, 1) * scale           # W'[ci][co][kz][ky][kx]
+            w2 = w.permute(0, 4, 1, 2, 3).reshape(ci * k, w.shape[1], k, k, 1).contiguous()
+            return ops.PackedWeight(w2, "conv", cfg, w.device)
+        pw = self._cached(f"stem_dgrad{cfg}x{scale}", [stem.weight], build, mark=False)
+        rows_alloc = ((ci * k + 7) // 8) * 8
+        if fused:
+            y = ops.conv3_stem_dgrad(pw, g0, B, R, rows_alloc)
+        else:
+            y = layers.run_conv3(pw, bw.split_f32b(g0, B, self.nf, R ** 3), B, R, rows_alloc=rows_alloc)
+        return ops.fold_dx(y, None, B, ci, k, rows_alloc, R)
+
     def _head_forward_fused(self, head, h, ac, B, R):
         """_head_forward on the un-normalised tensor `h` (F32B) with the folded GroupNorm affine `ac`: md_conv3_head."""
         k, co = self.KSIZE, self.out_channels
@@ -429,9 +463,10 @@ class DDPMUNet3D(layers.HipLayer):
     def forward(self, x, labels):
         if not x.is_cuda:
             raise RuntimeError(f"{type(self).__name__} (meshdiffusion_amd) runs on the GPU only: no CPU fallback")
-        if torch.is_grad_enabled() and self.training:
+        if torch.is_grad_enabled() and (self.training or x.requires_grad):
             # training: the HIP forward records a tape and the HIP backward accumulates parameter .grad; torch
-            # autograd only sees one opaque node (so `loss.backward()` of the reference's step_fn works)
+            # autograd only sees one opaque node (so `loss.backward()` of the reference's step_fn works).
+            # x.requires_grad: the same node hands back d/dx; in eval mode that is all it computes (no dropout, no `.grad`)
             return _UNetTrainFn.apply(x, labels, self, self._autograd_anchor())
         with ops.precision_scope(self.hip_precision):
             return self._forward_eval(x, labels)
@@ -560,19 +595,24 @@ class DDPMRes64(DDPMUNet3D):
 
 class _UNetTrainFn(torch.autograd.Function):
     """One opaque autograd node around the HIP forward/backward.  Parameter gradients are accumulated straight
-    into `.grad` by `DDPMUNet3D.backward`; the `anchor` input only makes autograd schedule this node.
-    The gradient w.r.t. the input `x` is NOT produced (the DDPM loss never needs it): `x.grad` stays None."""
+    into `.grad` by `DDPMUNet3D.backward` in training mode only; the `anchor` input only makes autograd schedule this node.
+    The gradient w.r.t. the input `x` is produced when autograd asks for it (`x.requires_grad`); the tape is freed as the
+    backward runs, so the node is differentiable once."""
 
     @staticmethod
     def forward(ctx, x, labels, model, anchor):
         with torch.no_grad():
             out, tape_ctx = model.forward_train(x, labels)
-        ctx.model, ctx.tape_ctx = model, tape_ctx
+        ctx.model, ctx.tape_ctx, ctx.param_grads = model, tape_ctx, model.training
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, d_eps):
-        with torch.no_grad():
-            ctx.model.backward(ctx.tape_ctx, d_eps.contiguous())
+        if ctx.tape_ctx is None:
+            raise RuntimeError("the U-Net's tape was freed by its first backward: run the forward again")
+        dx = None
+        if ctx.param_grads or ctx.needs_input_grad[0]:
+            dx = ctx.model.backward(ctx.tape_ctx, d_eps.contiguous(), input_grad=ctx.needs_input_grad[0], param_grads=ctx.param_grads)
         ctx.tape_ctx = None
-        return None, None, None, None
+        return dx, None, None, None

@@ -377,9 +377,9 @@ class AttnBlock(HipLayer):
             tape.append(dict(layer=self, x=x, prm=params, hN=h, qk=qk, vT=vT, pr=pr, o=o, B=B, P=P, S=_spatial_edge(P)))
         return self.NIN_3.forward_s16(o, B, P, residual=x)
 
-    def backward_blocked(self, sv, dy):
+    def backward_blocked(self, sv, dy, param_grads=True):
         from . import backward as bw
-        return bw.attn_backward(self, sv, dy)
+        return bw.attn_backward(self, sv, dy, param_grads=param_grads)
 
     def forward(self, x):
         parts, B, P, spatial = _parts_of(x)
@@ -414,9 +414,10 @@ class Upsample(HipLayer):
             tape.append(dict(layer=self, act=act, t=fw.t_kept if fw else None, B=B, S_out=s_out))
         return out
 
-    def backward_blocked(self, sv, dy):
+    def backward_blocked(self, sv, dy, param_grads=True):
         from . import backward as bw
-        return bw.conv3_backward(self, "w", self.Conv_0, dy, sv["act"], sv["B"], sv["S_out"], ups=1, t_act=sv.get("t"))
+        return bw.conv3_backward(self, "w", self.Conv_0, dy, sv["act"], sv["B"], sv["S_out"], ups=1, t_act=sv.get("t"),
+                                 param_grads=param_grads)
 
     def forward(self, x):
         parts, B, P, spatial = _parts_of(x)
@@ -450,9 +451,9 @@ class Downsample(HipLayer):
             tape.append(dict(layer=self, act=act, B=B, S_out=s_out))
         return run_conv3(pw, act, B, s_out, bias=self.Conv_0.bias)
 
-    def backward_blocked(self, sv, dy):
+    def backward_blocked(self, sv, dy, param_grads=True):
         from . import backward as bw
-        return bw.conv3_backward(self, "w", self.Conv_0, dy, sv["act"], sv["B"], sv["S_out"], stride=2)
+        return bw.conv3_backward(self, "w", self.Conv_0, dy, sv["act"], sv["B"], sv["S_out"], stride=2, param_grads=param_grads)
 
     def forward(self, x):
         parts, B, P, spatial = _parts_of(x)
@@ -573,11 +574,27 @@ class ResnetBlockDDPM(HipLayer):
                              temb=temb, drop=drop, t0=f0.t_kept if f0 else None, t1=f1.t_kept if f1 else None))
         return out
 
-    def backward_blocked(self, sv, dy):
+    def backward_blocked(self, sv, dy, param_grads=True):
         """dy: F32B [B][out_ch][P].  Returns ([grad per input part], dbias0 [B, out_ch]); accumulates .grad of
-        Conv_0/Conv_1/GroupNorm_0/GroupNorm_1/NIN_0 (Dense_0 is handled by the caller from dbias0)."""
+        Conv_0/Conv_1/GroupNorm_0/GroupNorm_1/NIN_0 (Dense_0 is handled by the caller from dbias0).
+        param_grads=False: the data gradients alone -- no `.grad` is touched and dbias0 is None."""
         from . import backward as bw
         B, P, S, parts = sv["B"], sv["P"], sv["S"], sv["parts"]
+        if not param_grads:
+            pg = dict(param_grads=False)
+            shared = {} if self.in_ch != self.out_ch else None      # Conv_1 and NIN_0 share the one bf16 split of dy
+            d_a1 = bw.conv3_backward(self, "w1", self.Conv_1, dy, None, B, S, shared=shared, **pg)
+            d_h = bw.gn_backward([(sv["h"], self.out_ch)], d_a1, sv["prm1"], self.GroupNorm_1, B, P, silu=True, drop=sv.get("drop"), **pg)[0]
+            del d_a1
+            d_a0 = bw.conv3_backward(self, "w0", self.Conv_0, d_h, None, B, S, **pg)
+            del d_h
+            if self.in_ch != self.out_ch:
+                dparts = bw.gn_backward(parts, d_a0, sv["prm0"], self.GroupNorm_0, B, P, silu=True, **pg)
+                bw.nin_backward(self.NIN_0, dy, None, B, P, S, shared=shared,
+                                accumulate_into=[(g, c) for g, (_, c) in zip(dparts, parts)], **pg)
+                shared.clear()
+                return dparts, None
+            return [bw.gn_backward(parts, d_a0, sv["prm0"], self.GroupNorm_0, B, P, silu=True, residual=dy, **pg)[0]], None
         # Conv_1 and the shortcut NIN_0 both start from the block's output gradient: its channel sums (both biases), its PB16
         # operand (both weight gradients) and its bf16 split (both data gradients) are computed once
         shared = {} if self.in_ch != self.out_ch else None

@@ -153,6 +153,10 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps, grid_mask=None, ret
         return get_ddim_sampler(sde=sde, shape=shape, predictor=get_predictor("ddim"), inverse_scaler=inverse_scaler,
                                 n_steps=config.sampling.n_steps_each, denoise=config.sampling.noise_removal, eps=eps,
                                 device=config.device, grid_mask=grid_mask)
+    if name == "ode":
+        return get_ode_sampler(sde=sde, shape=shape, inverse_scaler=inverse_scaler, eps=eps, device=config.device,
+                               rtol=float(getattr(config.sampling, "ode_rtol", 1e-5)),
+                               atol=float(getattr(config.sampling, "ode_atol", 1e-5)), grid_mask=grid_mask)
     if name != "pc":
         raise ValueError(f"Sampler name {config.sampling.method} unknown.")
     return get_pc_sampler(sde=sde, shape=shape,
@@ -440,3 +444,29 @@ def get_ddim_sampler(sde, shape, predictor, inverse_scaler, n_steps=1, denoise=F
             return inverse_scaler(out), sde.N * (n_steps + 1)
 
     return ddim_sampler
+
+
+def get_ode_sampler(sde, shape, inverse_scaler, rtol=1e-5, atol=1e-5, eps=1e-3, device="cuda", grid_mask=None):
+    """Probability-flow ODE sampler (the reference's likelihood.py ODE run backwards, T -> eps; `config.sampling.method = 'ode'`):
+    the ODE of likelihood.get_likelihood_fn without the log-density entries, so no divergence and no backward -- the model's
+    inference path, one md_pf_ode_rhs launch per evaluation, likelihood.rk45 as the integrator (float64 state on the device).
+    ode_sampler(model, x0=None) -> (samples, nfe); x0: the latent to start from (likelihood_fn's z decodes back to its data)
+    instead of a prior draw.  get_sampling_fn reads rtol / atol from config.sampling.ode_rtol / ode_atol (default 1e-5)."""
+    from . import likelihood
+    shape = tuple(shape)
+    dev = torch.device(device)
+
+    def ode_sampler(model, x0=None, partial=None, **unknown):
+        if partial is not None or unknown:
+            raise NotImplementedError(f"the ODE sampler takes no conditioning or other options ({['partial'] * (partial is not None) + sorted(unknown)})")
+        with torch.no_grad():
+            x = (x0 if x0 is not None else sde.prior_sampling(shape)).to(dev)
+            if x.dtype not in (torch.float32, torch.float64):
+                x = x.float()
+            if grid_mask is not None:
+                x = x * grid_mask.to(dev).reshape((1, 1) + shape[2:]).to(x.dtype)
+            fun = likelihood.get_ode_rhs(sde, model, shape, x, grid_mask=grid_mask)
+            y, nfe, _ = likelihood.rk45(fun, (sde.T, eps), x.double().reshape(-1), rtol=rtol, atol=atol)
+            return inverse_scaler(y.view(shape).to(x.dtype)), nfe
+
+    return ode_sampler
