@@ -577,6 +577,34 @@ int md_sde_step(const float* x, const float* eps, const float* z, const float* m
 int md_pf_ode_rhs(const float* x, const float* eps_hat, const float* g, const float* probe, const float* mask,
                   const double* coef, float* drift, double* slabs, int32_t batch, int32_t C, int64_t P, void* stream);
 /*
+ * Reconstruction guidance of the conditional samplers (diffusion posterior sampling, Chung et al. 2023): each step also descends
+ * the gradient of the measurement error ||r|| of the predicted clean grid on the visible voxels of channel `ch`.  With
+ * alpha = sqrt(abar_t), sigma = sqrt(1-abar_t) of the level the step starts from, y the partial grid (src, batch stride
+ * src_bstride = 0 or P), pm its visibility mask [P], gm the grid mask [P] or NULL, all NCDHW [B][C][P]:
+ *   md_guide_residual : coef[b][2] = {alpha, sigma} as doubles.  x0_hat = (x - sigma*eps_hat)/alpha ;
+ *                       cot[ch] = r = (pm*gm)*(x0_hat[ch] - y), formed in double and rounded to float once; every other channel
+ *                       of cot is written as +0 (x and eps_hat are read in channel ch only).  slabs[b][s] = sum over workgroup
+ *                       s's share of sample b of the squares of the ROUNDED r (written, not added to): the norm belongs to the
+ *                       cotangent that the U-Net's backward sees.  slabs is double[batch][MD_LANGEVIN_SLABS].
+ *   the caller then forms g = J^T cot, the vector-Jacobian product of eps_hat with respect to x.
+ *   md_guide_apply_f32: in place.  coef[b][3] = {alpha, sigma, zeta} as doubles.  n_b = sqrt(slabs[b][0] + slabs[b][1] + ...),
+ *                       added in ascending order in double ; k_b = zeta/(alpha*n_b), exactly 0 when n_b == 0 (nothing visible),
+ *                       NaN when n_b is NaN.  d = (k_b*(cot - sigma*g))*gm = zeta * d||r||/dx, formed in double and rounded to
+ *                       float once ; x = fl(x - d) ; x_mean (may be NULL) likewise from the same d.
+ *   md_guide_apply_f64: the same update of the DDIM sampler's float64 state with d kept in double: x64 -= d ;
+ *                       x_f32 = float(x64), the next U-Net input.
+ * Deterministic: fixed grid, fixed order, fp64 partial sums, no atomics.  P % 4 == 0; pointers 16-byte aligned (coef, slabs: 8);
+ * 0 <= ch < C; no output may share memory with an input or with the other output; anything else MD_ERR_BAD_ARG, before any
+ * launch.  Purely additive: MD_ABI_VERSION stays 16.
+ */
+int md_guide_residual(const float* x, const float* eps_hat, const float* src, int64_t src_bstride, const float* pmask,
+                      const float* gmask, const double* coef, int32_t ch, float* cot, double* slabs, int32_t batch, int32_t C,
+                      int64_t P, void* stream);
+int md_guide_apply_f32(float* x, float* x_mean, const float* cot, const float* g, const float* gmask, const double* coef,
+                       const double* slabs, int32_t batch, int32_t C, int64_t P, void* stream);
+int md_guide_apply_f64(double* x64, float* x_f32, const float* cot, const float* g, const float* gmask, const double* coef,
+                       const double* slabs, int32_t batch, int32_t C, int64_t P, void* stream);
+/*
  * Inpainting blend of one channel (sampling.py:443-467):
  *   v = (x*(1-m) + src*m) * gm     applied in place to channel `ch` of x [B][C][P];
  *   src has batch stride src_bstride (0 = shared partial grid).

@@ -7,6 +7,8 @@
 names `res64` / `res128`.  `--mode=train` runs one rank per GPU under torchrun.
 `--mode=likelihood` writes {eval_dir}/likelihood.npz: bits/dim of the grids of `--config.data.meta_path` through the
 probability-flow ODE (`--config.eval.ode_rtol=1e-5 --config.eval.ode_atol=1e-5 --config.eval.num_batches=N` optional).
+`--mode=cond_gen --config.eval.guidance_scale=1.0 [--config.eval.guidance_replace=False]` adds reconstruction guidance to the
+conditional samplers (`--config.sampling.method=ddim` is the form to run: 99 guided evaluations instead of 1000).
 """
 import sys
 

@@ -200,6 +200,108 @@ __global__ __launch_bounds__(256) void md_pf_ode_rhs_kernel(const float* __restr
   }
 }
 
+// ---- reconstruction guidance (diffusion posterior sampling, Chung et al. 2023) on one channel of the predicted clean grid ----
+// launch 1: coef[b] = {alpha, sigma} as doubles.  x0_hat = (x - sigma*eps_hat)/alpha ; r = (pm*gm)*(x0_hat[ch] - y), formed in
+// double and rounded once, is channel `ch` of the cotangent; every other channel is +0.  slabs[b][s] = sum over workgroup s's
+// share of the squares of the ROUNDED r, so the norm is that of the cotangent the backward sees.  Grid and order as
+// md_langevin_norms: two runs give the same bits.
+__global__ __launch_bounds__(256) void md_guide_residual_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                                const float* __restrict__ src, int64_t src_bstride,
+                                                                const float* __restrict__ pmask, const float* __restrict__ gmask,
+                                                                const double* __restrict__ coef, int ch, float* __restrict__ cot,
+                                                                double* __restrict__ slabs, int64_t CP, int64_t P) {
+  const int b = blockIdx.y;
+  const double alpha = coef[b * 2 + 0], sigma = coef[b * 2 + 1];
+  const int64_t base = (int64_t)b * CP, lo = (int64_t)ch * P, hi = lo + P;
+  double acc = 0.0;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
+    f32x4 rv = {0.f, 0.f, 0.f, 0.f};
+    if (i >= lo && i < hi) {                    // P % 4 == 0: four values never straddle two channels
+      const int64_t p = i - lo;
+      const f32x4 xv = *(const f32x4*)(x + base + i);
+      const f32x4 ev = *(const f32x4*)(eps + base + i);
+      const f32x4 yv = *(const f32x4*)(src + (int64_t)b * src_bstride + p);
+      const f32x4 pv = *(const f32x4*)(pmask + p);
+      f32x4 mv = {1.f, 1.f, 1.f, 1.f};
+      if (gmask) mv = *(const f32x4*)(gmask + p);
+      double t[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double x0 = ((double)xv[e] - sigma * (double)ev[e]) / alpha;
+        rv[e] = (float)(((double)pv[e] * (double)mv[e]) * (x0 - (double)yv[e]));
+        t[e] = (double)rv[e] * (double)rv[e];
+      }
+      acc += (t[0] + t[1]) + (t[2] + t[3]);
+    }
+    *(f32x4*)(cot + base + i) = rv;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) slabs[(int64_t)b * MD_LANGEVIN_SLABS + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// launch 2, in place: coef[b] = {alpha, sigma, zeta} as doubles.  Prologue: n_b = sqrt(slabs[b][0] + slabs[b][1] + ...) in
+// ascending order, k_b = zeta/(alpha*n_b), exactly 0 where n_b == 0 (nothing visible: no step), NaN where n_b is NaN.
+//   d = (k_b*(cot - sigma*g))*gm = zeta * d||r||/dx, formed in double
+// F64 false: d rounded to float once, x = fl(x - d), x_mean (may be NULL) likewise from the same d.
+// F64 true (the DDIM sampler's float64 state): x64 -= d with d kept in double, aux = float(x64), the next U-Net input.
+template <bool F64>
+__global__ __launch_bounds__(256) void md_guide_apply_kernel(void* __restrict__ state, float* __restrict__ aux,
+                                                             const float* __restrict__ cot, const float* __restrict__ g,
+                                                             const float* __restrict__ gmask, const double* __restrict__ coef,
+                                                             const double* __restrict__ slabs, int64_t CP, int64_t P) {
+  const int b = blockIdx.y;
+  __shared__ double s_slab[MD_LANGEVIN_SLABS];
+  __shared__ double s_k;
+  if (threadIdx.x < MD_LANGEVIN_SLABS) s_slab[threadIdx.x] = slabs[(int64_t)b * MD_LANGEVIN_SLABS + threadIdx.x];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double sum = 0.0;
+    for (int s = 0; s < MD_LANGEVIN_SLABS; ++s) sum += s_slab[s];
+    const double n = sqrt(sum);
+    s_k = (n == 0.0) ? 0.0 : coef[b * 3 + 2] / (coef[b * 3 + 0] * n);
+  }
+  __syncthreads();
+  const double k = s_k, sigma = coef[b * 3 + 1];
+  const int64_t base = (int64_t)b * CP;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
+    const f32x4 cv = *(const f32x4*)(cot + base + i);
+    const f32x4 gv = *(const f32x4*)(g + base + i);
+    f32x4 mv = {1.f, 1.f, 1.f, 1.f};
+    if (gmask) mv = *(const f32x4*)(gmask + (i % P));
+    double d[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) d[e] = (k * ((double)cv[e] - sigma * (double)gv[e])) * (double)mv[e];
+    if constexpr (F64) {
+      double* x64 = (double*)state + base + i;
+      f64x2 a = *(const f64x2*)x64, c = *(const f64x2*)(x64 + 2);
+      a[0] -= d[0];
+      a[1] -= d[1];
+      c[0] -= d[2];
+      c[1] -= d[3];
+      *(f64x2*)x64 = a;
+      *(f64x2*)(x64 + 2) = c;
+      const f32x4 xo = {(float)a[0], (float)a[1], (float)c[0], (float)c[1]};
+      *(f32x4*)(aux + base + i) = xo;
+    } else {
+      float* x32 = (float*)state + base + i;
+      f32x4 xv = *(const f32x4*)x32;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xv[e] -= (float)d[e];
+      *(f32x4*)x32 = xv;
+      if (aux) {
+        f32x4 xm = *(const f32x4*)(aux + base + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xm[e] -= (float)d[e];
+        *(f32x4*)(aux + base + i) = xm;
+      }
+    }
+  }
+}
+
 // one workgroup per 1024 values, at most 1024 workgroups in all (B*S <= 1024 keeps the slab prologue's L2 reads small)
 static int stream_blocks(int64_t CP, int batch) {
   int64_t blocks = (CP / 4 + 255) / 256;
@@ -262,4 +364,64 @@ extern "C" int md_pf_ode_rhs(const float* x, const float* eps_hat, const float* 
                        (hipStream_t)stream, x, eps_hat, g, probe, mask, coef, drift, slabs, CP, P);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
+}
+
+// an output of `na` bytes at `a` shares memory with an input (null: absent) of `nb` bytes at `b`
+static bool md_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return b && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+}
+
+extern "C" int md_guide_residual(const float* x, const float* eps_hat, const float* src, int64_t src_bstride, const float* pmask,
+                                 const float* gmask, const double* coef, int32_t ch, float* cot, double* slabs, int32_t batch,
+                                 int32_t C, int64_t P, void* stream) {
+  if (md_any_bad<16>(x, eps_hat, src, pmask, cot) || md_any_bad<8>(coef, slabs) || md_any_misaligned<16>(gmask))
+    return MD_ERR_BAD_ARG;
+  if (batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
+  if (ch < 0 || ch >= C || (src_bstride != 0 && src_bstride != P)) return MD_ERR_BAD_ARG;
+  const int64_t CP = (int64_t)C * P, n = 4 * CP * batch, np = 4 * P, ns = src_bstride ? np * batch : np;
+  const int64_t nc = 16LL * batch, nl = 8LL * MD_LANGEVIN_SLABS * batch;
+  if (md_overlap(cot, n, x, n) || md_overlap(cot, n, eps_hat, n) || md_overlap(cot, n, src, ns) || md_overlap(cot, n, pmask, np) ||
+      md_overlap(cot, n, gmask, np) || md_overlap(cot, n, coef, nc) || md_overlap(cot, n, slabs, nl))
+    return MD_ERR_BAD_ARG;
+  if (md_overlap(slabs, nl, x, n) || md_overlap(slabs, nl, eps_hat, n) || md_overlap(slabs, nl, src, ns) ||
+      md_overlap(slabs, nl, pmask, np) || md_overlap(slabs, nl, gmask, np) || md_overlap(slabs, nl, coef, nc))
+    return MD_ERR_BAD_ARG;
+  MD_HIP_CLEAR_ERROR();
+  hipLaunchKernelGGL(md_guide_residual_kernel, dim3(MD_LANGEVIN_SLABS, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
+                     src, src_bstride, pmask, gmask, coef, (int)ch, cot, slabs, CP, P);
+  MD_HIP_CHECK_LAUNCH();
+  return MD_OK;
+}
+
+// the checks and the launch of both md_guide_apply exports: the state is float with x_mean as `aux`, or double with x_f32
+template <bool F64>
+static int md_guide_apply(void* state, float* aux, const float* cot, const float* g, const float* gmask, const double* coef,
+                          const double* slabs, int32_t batch, int32_t C, int64_t P, void* stream) {
+  if (md_any_bad<16>(state, cot, g) || md_any_bad<8>(coef, slabs) || md_any_misaligned<16>(aux, gmask)) return MD_ERR_BAD_ARG;
+  if (F64 && !aux) return MD_ERR_BAD_ARG;
+  if (batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
+  const int64_t CP = (int64_t)C * P, n = 4 * CP * batch, nx = (F64 ? 8 : 4) * CP * batch, np = 4 * P;
+  const int64_t nc = 24LL * batch, nl = 8LL * MD_LANGEVIN_SLABS * batch;
+  if (md_overlap(state, nx, cot, n) || md_overlap(state, nx, g, n) || md_overlap(state, nx, gmask, np) ||
+      md_overlap(state, nx, coef, nc) || md_overlap(state, nx, slabs, nl) || md_overlap(state, nx, aux, n))
+    return MD_ERR_BAD_ARG;
+  if (aux && (md_overlap(aux, n, cot, n) || md_overlap(aux, n, g, n) || md_overlap(aux, n, gmask, np) ||
+              md_overlap(aux, n, coef, nc) || md_overlap(aux, n, slabs, nl)))
+    return MD_ERR_BAD_ARG;
+  MD_HIP_CLEAR_ERROR();
+  hipLaunchKernelGGL(md_guide_apply_kernel<F64>, dim3((unsigned)stream_blocks(CP, batch), (unsigned)batch), dim3(256), 0,
+                     (hipStream_t)stream, state, aux, cot, g, gmask, coef, slabs, CP, P);
+  MD_HIP_CHECK_LAUNCH();
+  return MD_OK;
+}
+
+extern "C" int md_guide_apply_f32(float* x, float* x_mean, const float* cot, const float* g, const float* gmask, const double* coef,
+                                  const double* slabs, int32_t batch, int32_t C, int64_t P, void* stream) {
+  return md_guide_apply<false>(x, x_mean, cot, g, gmask, coef, slabs, batch, C, P, stream);
+}
+
+extern "C" int md_guide_apply_f64(double* x64, float* x_f32, const float* cot, const float* g, const float* gmask,
+                                  const double* coef, const double* slabs, int32_t batch, int32_t C, int64_t P, void* stream) {
+  return md_guide_apply<true>(x64, x_f32, cot, g, gmask, coef, slabs, batch, C, P, stream);
 }

@@ -1272,6 +1272,71 @@ def pf_ode_rhs(x, eps_hat, mask, coef, g=None, probe=None):
     return drift, (slabs.sum(dim=1) if slabs is not None else None)
 
 
+def _guide_operand(t, name, dtype, shape=None, numel=None):
+    """A tensor of the guidance exports: on the GPU, contiguous, of the stated dtype and shape (or element count)."""
+    _require_cuda(t, name)
+    assert t.dtype == dtype and t.is_contiguous(), (name, t.dtype, t.is_contiguous())
+    assert shape is None or tuple(t.shape) == tuple(shape), (name, tuple(t.shape), tuple(shape))
+    assert numel is None or t.numel() == numel, (name, tuple(t.shape), numel)
+
+
+def guide_residual(x, eps_hat, src, pmask, gmask, coef, ch, src_bstride=0):
+    """Cotangent and squared norm of reconstruction guidance in one launch (md_guide_residual).  x, eps_hat: [B,C,D,H,W] fp32;
+    src: the partial grid, P values shared by the batch (src_bstride 0) or B*P (src_bstride P); pmask [P]; gmask [P] or None;
+    coef [B,2] float64 = (alpha, sigma).
+    Returns (cot fp32 like x: r = pmask*gmask*(x0_hat[ch] - src) in channel `ch`, +0 elsewhere; slabs [B, 64] float64, whose
+    sum over a sample is ||r||^2 of the rounded r)."""
+    lib = _lib.load()
+    B, Cc = x.shape[0], x.shape[1]
+    P = x[0, 0].numel()
+    f32 = torch.float32
+    _guide_operand(x, "x", f32)
+    _guide_operand(eps_hat, "eps_hat", f32, shape=x.shape)
+    _guide_operand(pmask, "pmask", f32, numel=P)
+    _guide_operand(coef, "coef", torch.float64, shape=(B, 2))
+    assert src_bstride in (0, P), (src_bstride, P)
+    _guide_operand(src, "src", f32, numel=B * P if src_bstride else P)
+    if gmask is not None:
+        _guide_operand(gmask, "gmask", f32, numel=P)
+    assert 0 <= int(ch) < Cc, (ch, Cc)
+    cot = torch.empty_like(x)
+    slabs = torch.empty((B, _lib.LANGEVIN_SLABS), dtype=torch.float64, device=x.device)
+    check(lib.md_guide_residual(_ptr(x), _ptr(eps_hat), _ptr(src), src_bstride, _ptr(pmask), _ptr(gmask), _ptr(coef), int(ch),
+                                _ptr(cot), _ptr(slabs), B, Cc, P, _stream()), "md_guide_residual")
+    return cot, slabs
+
+
+def _guide_apply(name, state, sdtype, aux, cot, g, gmask, coef, slabs):
+    lib = _lib.load()
+    B, Cc = state.shape[0], state.shape[1]
+    P = state[0, 0].numel()
+    _guide_operand(state, "the state", sdtype)
+    for nm, t in (("cot", cot), ("g", g)) + ((("x_mean / x_f32", aux),) if aux is not None else ()):
+        _guide_operand(t, nm, torch.float32, shape=state.shape)
+    _guide_operand(coef, "coef", torch.float64, shape=(B, 3))
+    _guide_operand(slabs, "slabs", torch.float64, shape=(B, _lib.LANGEVIN_SLABS))
+    if gmask is not None:
+        _guide_operand(gmask, "gmask", torch.float32, numel=P)
+    check(getattr(lib, name)(_ptr(state), _ptr(aux), _ptr(cot), _ptr(g), _ptr(gmask), _ptr(coef), _ptr(slabs), B, Cc, P, _stream()),
+          name)
+
+
+def guide_apply_(x, x_mean, cot, g, gmask, coef, slabs):
+    """In place (md_guide_apply_f32): x -= d, x_mean (or None) -= d with d = zeta/(alpha*||r||) * (cot - sigma*g) * gmask, zero
+    where ||r|| == 0.  x, x_mean, cot, g: [B,C,D,H,W] fp32; coef [B,3] float64 = (alpha, sigma, zeta); slabs [B,64] float64 of
+    guide_residual.  Returns x."""
+    _guide_apply("md_guide_apply_f32", x, torch.float32, x_mean, cot, g, gmask, coef, slabs)
+    return x
+
+
+def guide_apply64_(x64, x_f32, cot, g, gmask, coef, slabs):
+    """The same update in place on the DDIM sampler's float64 state (md_guide_apply_f64), d kept in double; x_f32 (fp32, same
+    shape) receives float(x64).  Returns x64."""
+    assert x_f32 is not None
+    _guide_apply("md_guide_apply_f64", x64, torch.float64, x_f32, cot, g, gmask, coef, slabs)
+    return x64
+
+
 def ddim_step(x64, eps, mask, coef, partial=None, pmask=None, ch=0):
     """x64 [B,C,D,H,W] float64 state, eps float32 U-Net output, mask [P] or None, coef [B,4] float64 = a1, a2, r1, r2;
     partial / pmask: [P] float32 each or None.  Returns (x_new f64, x0_pred f64, x_new as f32)."""

@@ -128,9 +128,19 @@ def cond_gen(config, save_fname="0"):
     vis_grid = torch.zeros((1, 1, R, R, R))
     vis_grid[0, 0, idx[:, 0], idx[:, 1], idx[:, 2]] = partial["vis"].cpu().float()
 
+    # reconstruction guidance (sampling.guidance_terms): optional config.eval fields guidance_scale (unset or 0: none, the call
+    # below is the unguided one), guidance_replace (True: the replacement of the known voxels stays), guidance_chunk (samples per
+    # taped forward).  The load-time calibration still runs; the taped forward of a guided step is bf16x3 and does not read it.
+    scale = float(getattr(config.eval, "guidance_scale", 0.0) or 0.0)
+    kw = dict(freeze_iters=config.eval.freeze_iters)
+    if scale > 0:
+        if config.sampling.method.lower() == "ddim":
+            kw = {}                                     # the DDIM sampler visits its own sub-sequence: no freeze_iters
+        kw.update(guidance_scale=scale, guidance_replace=bool(getattr(config.eval, "guidance_replace", True)),
+                  guidance_chunk=getattr(config.eval, "guidance_chunk", None))
+
     def run(model, sampling_fn):
-        return sampling_fn(model, partial=sdf_grid.to(config.device), partial_mask=vis_grid.to(config.device),
-                           freeze_iters=config.eval.freeze_iters)[0]
+        return sampling_fn(model, partial=sdf_grid.to(config.device), partial_mask=vis_grid.to(config.device), **kw)[0]
 
     return _generate(config, lambda R: (1, 1, R, R, R), save_fname, run)
 

@@ -15,6 +15,8 @@ prior, device generator per step) so that, on the same device and seed, the stre
 numbers is the reference's.  Two optional keyword extensions used by tests/bench:
     n_iters  -- run only the first n iterations of the N-step schedule
     noise_fn -- callable(x) -> z replacing torch.randn_like (to replay recorded noise)
+Reconstruction guidance of the conditional samplers (not in the reference; `guidance_terms`): pc_sampler and ddim_sampler take
+    guidance_scale, guidance_replace, guidance_chunk -- each step also descends zeta * grad_x ||pm (x0_hat[ch] - partial)||
 """
 import numpy as np
 import torch
@@ -309,6 +311,65 @@ def _check_pc_pair(sde, predictor, corrector, n_steps, probability_flow, continu
         raise NotImplementedError("return_traj is only used by the reference's unreachable uncond_gen_interp")
 
 
+def _check_guidance(guidance_scale, partial, predictor=None, corrector=None, probability_flow=False):
+    """Refuse, before any GPU work, the guided runs that are not implemented.  Returns whether the run is guided."""
+    scale = float(guidance_scale)
+    if scale == 0.0:
+        return False
+    if not scale > 0.0:
+        raise ValueError(f"guidance_scale must be >= 0, got {guidance_scale}")
+    if partial is None:
+        raise NotImplementedError("guidance_scale > 0 needs `partial`: the guidance descends the error against the partial grid")
+    if probability_flow:
+        raise NotImplementedError("guidance under probability flow is not implemented")
+    if predictor is not None and predictor is not AncestralSamplingPredictor:
+        raise NotImplementedError(f"guidance runs with the ancestral predictor (or method 'ddim'), not {predictor.__name__}")
+    if corrector is not None and corrector is not NoneCorrector:
+        raise NotImplementedError(f"guidance with a corrector ({corrector.__name__}) is not implemented")
+    return True
+
+
+def guidance_terms(model, sde_or_coef, x, labels, alpha, sigma, src, pm_flat, gm_flat, ch, chunk=None):
+    """What one step of reconstruction guidance needs, at the state `x` [B,C,D,H,W] (fp32, on the GPU) the step starts from:
+        eps_hat = model(x, labels)                       one evaluation, the one the step itself uses
+        cot     = pm*gm*(x0_hat[ch] - src) in channel ch, 0 elsewhere, x0_hat = (x - sigma*eps_hat)/alpha    (md_guide_residual)
+        g       = J^T cot                                the vector-Jacobian product of eps_hat with respect to x
+        slabs   [B, 64] float64, summing to ||cot_b||^2
+    Returns (eps_hat, cot, g, slabs), none of them attached to a graph.  A DDPMUNet3D runs its taped eval-mode forward and the
+    data-gradient-only HIP backward (no weight-gradient work, every parameter's `.grad` stays None); any other callable goes
+    through plain torch autograd.  Grad mode is switched on here: the samplers run under no_grad.
+    sde_or_coef: the [B,2] float64 rows (alpha, sigma) as md_guide_residual takes them (then `alpha` / `sigma` are not read), or
+    the SDE (or None): the rows are built from `alpha` and `sigma`, floats or [B] tensors.
+    src: the partial grid, one shared by the batch (P values) or one per sample (B*P); pm_flat / gm_flat: [P] fp32, gm_flat may
+    be None.  chunk: samples per forward and backward (default: the whole batch); exact per sample up to the forward's own
+    batch dependence."""
+    B = x.shape[0]
+    P = x[0, 0].numel()
+    if torch.is_tensor(sde_or_coef):
+        coef = sde_or_coef
+    else:
+        rows = [torch.as_tensor(v, dtype=torch.float64, device=x.device).expand(B) for v in (alpha, sigma)]
+        coef = torch.stack(rows, dim=1).contiguous()
+    eps_fn = mutils.get_model_fn(model, train=False) if isinstance(model, torch.nn.Module) else model
+    per_sample = src.numel() == B * P and B > 1
+    src = src.reshape(B, P) if per_sample else src.reshape(P)
+    step = B if not chunk else max(1, min(int(chunk), B))
+    parts = []
+    for b0 in range(0, B, step):
+        b1 = min(B, b0 + step)
+        with torch.enable_grad():
+            xr = x[b0:b1].detach().requires_grad_(True)
+            eps_hat = eps_fn(xr, labels[b0:b1])
+            e = eps_hat.detach().contiguous()
+            cot, slabs = ops.guide_residual(xr.detach(), e, src[b0:b1] if per_sample else src, pm_flat, gm_flat, coef[b0:b1], ch,
+                                            src_bstride=P if per_sample else 0)
+            g, = torch.autograd.grad(eps_hat, xr, cot)
+        parts.append((e, cot, g.contiguous(), slabs))
+    if len(parts) == 1:
+        return parts[0]
+    return tuple(torch.cat(p) for p in zip(*parts))
+
+
 def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_steps=1, probability_flow=False,
                    continuous=False, denoise=True, eps=1e-3, device="cuda", grid_mask=None, return_traj=False):
     """Each iteration runs the reference's order (sampling.py:443-481): corrector x n_steps (one U-Net evaluation and
@@ -323,7 +384,11 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
     n_corr = 0 if corrector is NoneCorrector else int(n_steps)
 
     def pc_sampler(model, partial=None, partial_mask=None, partial_channel=0, freeze_iters=None,
-                   n_iters=None, noise_fn=None):
+                   n_iters=None, noise_fn=None, guidance_scale=0.0, guidance_replace=True, guidance_chunk=None):
+        """guidance_scale > 0 (reconstruction guidance; needs `partial`, the ancestral predictor, no corrector): each iteration
+        is guidance_terms at the state it starts from, md_ancestral_step with that eps_hat, md_guide_apply_f32 on (x, x_mean),
+        then the blend and re-noise below unless guidance_replace is off.  guidance_chunk: samples per taped forward."""
+        guided = _check_guidance(guidance_scale, partial, predictor, corrector, probability_flow)
         with torch.no_grad():
             if freeze_iters is None:
                 freeze_iters = sde.N + 10
@@ -335,12 +400,21 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
             x = st.prior()
 
             cond = partial is not None
+            replace = cond and (guidance_replace or not guided)
             if cond:
                 assert st.gm is not None and partial.dim() == 5 and partial_mask is not None
                 ch = partial_channel
                 pm_flat = partial_mask[0, ch].reshape(-1).to(dev, torch.float32).contiguous()
                 src = (partial[:, ch].to(dev, torch.float32)).contiguous()
                 src_bstride = 0 if src.shape[0] == 1 else P
+            if guided:
+                # (alpha, sigma, zeta) of every iteration's level, from the float32 tables the step's own coefficients come from
+                k_all = (timesteps * (sde.N - 1) / sde.T).long()
+                a_all, s_all = sde.sqrt_alphas_cumprod.to(dev)[k_all].double(), sde.sqrt_1m_alphas_cumprod.to(dev)[k_all].double()
+                gcoef = torch.stack([a_all, s_all, torch.full_like(a_all, float(guidance_scale))], dim=1)
+                gcoef = gcoef[:, None, :].expand(sde.N, B, 3).contiguous()
+                rcoef = gcoef[:, :, :2].contiguous()
+            if replace:
                 # ---- initial conditioning (sampling.py:429-440), including its broadcasting quirk:
                 # `sampled_update` is [B,B,R,R,R] there and `[:, partial_channel]` indexes its SECOND batch
                 # axis, so every sample receives batch element `ch`'s mean and noise, scaled by its own std.
@@ -361,7 +435,13 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
                     z = draw(x)
                     x, x_mean, _ = ops.langevin_step(x, eps_hat, z, gm_flat if j == n_corr - 1 else None, ccoef[i], snr,
                                                      corrector.mode)
-                if predictor is AncestralSamplingPredictor:
+                if guided:
+                    eps_hat, cot, g, slabs = guidance_terms(model, rcoef[i], x, st.labels[i], None, None, src, pm_flat, gm_flat, ch,
+                                                            chunk=guidance_chunk)
+                    z = draw(x)
+                    x, x_mean = ops.ancestral_step(x, eps_hat, z, gm_flat, st.coef[i])
+                    ops.guide_apply_(x, x_mean, cot, g, gm_flat, gcoef[i], slabs)
+                elif predictor is AncestralSamplingPredictor:
                     x, x_mean = st.step(model_fn, x, i, draw)
                 elif predictor is not NonePredictor:
                     eps_hat = model_fn(x, st.labels[i])
@@ -369,7 +449,7 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
                     x, x_mean = ops.sde_step(x, eps_hat, z, gm_flat, pcoef[i], predictor.kind)
                 else:   # the reference's predictor returns (x, x) and masks them into two tensors
                     x_mean = x.clone() if cond else x
-                if cond and i != sde.N - 1 and i < freeze_iters:
+                if replace and i != sde.N - 1 and i < freeze_iters:
                     ops.inpaint_blend_(x, src, pm_flat, gm_flat, ch, src_bstride=src_bstride)
                     ops.inpaint_blend_(x_mean, src, pm_flat, gm_flat, ch, src_bstride=src_bstride)
                     t_i = timesteps[i]
@@ -409,7 +489,11 @@ def get_ddim_sampler(sde, shape, predictor, inverse_scaler, n_steps=1, denoise=F
     dev = torch.device(device)
 
     def ddim_sampler(model, schedule="quad", num_steps=100, x0=None, partial=None, partial_mask=None, partial_channel=0,
-                     n_iters=None):
+                     n_iters=None, guidance_scale=0.0, guidance_replace=True, guidance_chunk=None):
+        """guidance_scale > 0 (reconstruction guidance; needs `partial`): each update is guidance_terms at the float32 state the
+        U-Net sees, md_ddim_step with that eps_hat, then md_guide_apply_f64 on the float64 state and its float32 copy; x0_pred stays
+        the step's own prediction.  guidance_replace off: no replacement of the known voxels, at the start or in the steps."""
+        guided = _check_guidance(guidance_scale, partial)
         with torch.no_grad():
             gm = grid_mask.to(dev) if grid_mask is not None else None
             gm_flat = None
@@ -425,7 +509,8 @@ def get_ddim_sampler(sde, shape, predictor, inverse_scaler, n_steps=1, denoise=F
                 part = partial.to(dev, torch.float32).reshape(-1).contiguous()
                 pm = partial_mask.to(dev, torch.float32).reshape(-1).contiguous()
                 assert part.numel() == P and pm.numel() == P, "partial / partial_mask: one grid shared by the batch"
-                x[:, ch] = x[:, ch] * (1 - pm.view(shape[2:])) + part.view(shape[2:]) * pm.view(shape[2:])
+                if guidance_replace or not guided:
+                    x[:, ch] = x[:, ch] * (1 - pm.view(shape[2:])) + part.view(shape[2:]) * pm.view(shape[2:])
             timesteps = ddim_schedule(sde.N, schedule, num_steps)
             pred = predictor(sde, None)
             model_fn = mutils.get_model_fn(model, train=False)
@@ -436,8 +521,17 @@ def get_ddim_sampler(sde, shape, predictor, inverse_scaler, n_steps=1, denoise=F
             for i in order:
                 vec_t = torch.ones(B, device=dev) * timesteps[i]
                 vec_tprev = torch.ones(B, device=dev) * timesteps[i - 1]
-                eps_hat = model_fn(x32, vec_t.float() * (sde.N - 1))
-                x64, x0_pred, x32 = ops.ddim_step(x64, eps_hat, gm_flat, pred.coefficients(vec_t, vec_tprev), part, pm, ch)
+                if guided:
+                    coef = pred.coefficients(vec_t, vec_tprev)
+                    gcoef = torch.cat([coef[:, :2], torch.full_like(coef[:, :1], float(guidance_scale))], dim=1).contiguous()
+                    eps_hat, cot, g, slabs = guidance_terms(model, gcoef[:, :2].contiguous(), x32, vec_t.float() * (sde.N - 1), None,
+                                                            None, part, pm, gm_flat, ch, chunk=guidance_chunk)
+                    rep = (part, pm) if guidance_replace else (None, None)
+                    x64, x0_pred, x32 = ops.ddim_step(x64, eps_hat, gm_flat, coef, rep[0], rep[1], ch)
+                    ops.guide_apply64_(x64, x32, cot, g, gm_flat, gcoef, slabs)
+                else:
+                    eps_hat = model_fn(x32, vec_t.float() * (sde.N - 1))
+                    x64, x0_pred, x32 = ops.ddim_step(x64, eps_hat, gm_flat, pred.coefficients(vec_t, vec_tprev), part, pm, ch)
             out = x0_pred if denoise else x64
             if gm is not None:
                 out = out * gm

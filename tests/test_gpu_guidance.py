@@ -1,0 +1,341 @@
+"""Reconstruction guidance on the GPU: md_guide_residual, md_guide_apply_f32 and md_guide_apply_f64 against their numpy
+restatements; one guided evaluation (taped forward + md_guide_residual + data-gradient-only backward) against the oracle under
+autograd; the guided ancestral and DDIM loops against the float64 recursion of a closed-form model; guidance switched off is
+today's sampler bit for bit; the CLI."""
+import math
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import guidance_cases as gc
+import likelihood_cases as lc
+from conftest import ROOT, rel_l2
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 4), (3, 64), (2, 16 ** 3)]
+C = 4
+
+
+def _levels(B):
+    """(alpha, sigma) rows of the levels t = 1e-3, 0.5, 1 (one per sample)."""
+    return np.array([lc.vp_coefficients_f64(t)[2:] for t in (1e-3, 0.5, 1.0)][:B])
+
+
+# ---- md_guide_residual ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("per_sample", [False, True])
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("ch", [0, 3])
+@pytest.mark.parametrize("B,P", SHAPES)
+def test_guide_residual_kernel(hip_lib, B, P, ch, masked, per_sample):
+    from meshdiffusion_amd import hip_ops as ops
+    g = torch.Generator().manual_seed(B * 1000 + P + ch)
+    x, e = (torch.randn((B, C, P), generator=g) for _ in range(2))
+    src = torch.sign(torch.randn((B, P) if per_sample else (P,), generator=g))
+    pm = (torch.rand(P, generator=g) < 0.5).float()
+    pm[0] = 1.0
+    gm = (torch.rand(P, generator=g) < 0.6).float() if masked else None
+    if masked:
+        gm[0] = 1.0
+    coef = _levels(B)
+    args = (x.cuda(), e.cuda(), src.cuda(), pm.cuda(), gm.cuda() if masked else None, torch.from_numpy(coef).cuda(), ch)
+    kw = dict(src_bstride=P if per_sample else 0)
+    cot, slabs = ops.guide_residual(*args, **kw)
+    r_cot, r64, _ = gc.guide_residual_ref(x.numpy(), e.numpy(), src.numpy(), pm.numpy(), gm.numpy() if masked else None, coef, ch)
+    got = cot.cpu().numpy()
+    assert np.all(np.abs(got[:, ch].astype(np.float64) - r64) <= np.spacing(np.abs(r_cot[:, ch]))), "cot: more than 1 ulp from float64"
+    others = [c for c in range(C) if c != ch]
+    assert np.all(got[:, others] == 0) and not np.signbit(got[:, others]).any()          # written as +0
+    dead = (pm * (gm if masked else 1.0)).numpy() == 0
+    assert np.all(got[:, ch][:, dead] == 0)
+    sq = got[:, ch].astype(np.float64) ** 2                                              # of the ROUNDED r the kernel wrote
+    want = np.array([math.fsum(sq[b]) for b in range(B)])
+    assert slabs.shape == (B, gc.SLABS) and slabs.dtype == torch.float64
+    err = np.abs(slabs.sum(dim=1).cpu().numpy() - want) / want
+    print(f"B={B} P={P} ch={ch} masked={masked} per_sample={per_sample}: sum of slabs |err| / sum|terms| {err}")
+    assert np.all(want > 0) and np.all(err <= 1e-12)
+    cot2, slabs2 = ops.guide_residual(*args, **kw)                                       # the same bits again
+    assert torch.equal(cot, cot2) and torch.equal(slabs, slabs2)
+    none = list(args)
+    none[3] = torch.zeros_like(args[3])
+    cot0, slabs0 = ops.guide_residual(*none, **kw)                                       # nothing visible
+    assert float(slabs0.abs().max()) == 0.0 and float(cot0.abs().max()) == 0.0
+
+
+# ---- md_guide_apply_f32 / _f64 ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("B,P", SHAPES)
+def test_guide_apply_kernels(hip_lib, B, P, masked):
+    """The slabs are GIVEN (arbitrary positive doubles), so that the two kernels are pinned apart from md_guide_residual."""
+    from meshdiffusion_amd import hip_ops as ops
+    g = torch.Generator().manual_seed(B * 77 + P)
+    x, xm, cot, jt = (torch.randn((B, C, P), generator=g) for _ in range(4))
+    gm = (torch.rand(P, generator=g) < 0.6).float() if masked else None
+    if masked:
+        gm[0] = 1.0
+    gm_np, gm_cu = (gm.numpy(), gm.cuda()) if masked else (None, None)
+    slabs = torch.rand((B, gc.SLABS), generator=g, dtype=torch.float64) * 10.0 ** torch.randint(-3, 4, (B, gc.SLABS), generator=g).double()
+    coef = np.concatenate([_levels(B), np.array([[1.0], [0.3], [2.5]])[:B]], axis=1)
+    x64 = (x.double() + 1e-9 * torch.randn((B, C, P), generator=g, dtype=torch.float64))
+
+    def run32(coef, slabs, with_mean=True):
+        a, b = x.cuda().clone(), (xm.cuda().clone() if with_mean else None)
+        ops.guide_apply_(a, b, cot.cuda(), jt.cuda(), gm_cu, torch.from_numpy(coef).cuda(), slabs.cuda())
+        return a.cpu().numpy(), (b.cpu().numpy() if with_mean else None)
+
+    def run64(coef, slabs):
+        a, b = x64.cuda().clone(), torch.full((B, C, P), 7.0, device="cuda")
+        ops.guide_apply64_(a, b, cot.cuda(), jt.cuda(), gm_cu, torch.from_numpy(coef).cuda(), slabs.cuda())
+        return a.cpu().numpy(), b.cpu().numpy()
+
+    same = lambda a, b: a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))        # noqa: E731   bit-equal
+    want_x, want_m = gc.guide_apply_f32_ref(x.numpy(), xm.numpy(), cot.numpy(), jt.numpy(), gm_np, coef, slabs.numpy())
+    got_x, got_m = run32(coef, slabs)
+    assert same(got_x, want_x) and same(got_m, want_m) and not same(got_x, x.numpy())
+    got_x2, none = run32(coef, slabs, with_mean=False)                                  # x_mean = NULL
+    assert none is None and same(got_x2, want_x)
+    want64, want64f = gc.guide_apply_f64_ref(x64.numpy(), cot.numpy(), jt.numpy(), gm_np, coef, slabs.numpy())
+    got64, got64f = run64(coef, slabs)
+    assert same(got64, want64) and same(got64f, want64f) and same(got64f, got64.astype(np.float32))
+    # a sample with nothing visible (all slabs 0) keeps its bits; the others move
+    z = slabs.clone()
+    z[B - 1] = 0.0
+    gx, gmn = run32(coef, z)
+    g64, g64f = run64(coef, z)
+    assert same(gx[B - 1], x.numpy()[B - 1]) and same(gmn[B - 1], xm.numpy()[B - 1]) and same(g64[B - 1], x64.numpy()[B - 1])
+    assert same(g64f[B - 1], x64.numpy()[B - 1].astype(np.float32))
+    assert B == 1 or (same(gx[:B - 1], want_x[:B - 1]) and same(g64[:B - 1], want64[:B - 1]))
+    # zeta = 0 keeps every bit
+    c0 = coef.copy()
+    c0[:, 2] = 0.0
+    gx, gmn = run32(c0, slabs)
+    assert same(gx, x.numpy()) and same(gmn, xm.numpy()) and same(run64(c0, slabs)[0], x64.numpy())
+    # a NaN slab: NaN in that sample and only there
+    n = slabs.clone()
+    n[0, 5] = float("nan")
+    gx, gmn = run32(coef, n)
+    g64, g64f = run64(coef, n)
+    for a, w in ((gx, want_x), (gmn, want_m), (g64, want64), (g64f, want64f)):
+        assert np.isnan(a[0]).all() and (B == 1 or same(a[1:], w[1:]))
+
+
+# ---- one guided evaluation of the small network against the oracle ---------------------------------------------------------------
+@pytest.fixture(scope="module")
+def net():
+    from meshdiffusion_amd.lib.diffusion import sde_lib
+    from meshdiffusion_amd.lib.diffusion.models import utils as mutils
+    cfg, gm, x0 = lc.golden_setup("cuda:0")
+    model = mutils.create_model(cfg).eval()
+    sd = lc.golden_state_dict(cfg, model.module.state_dict(), gm)
+    model.module.load_state_dict(sd, strict=True)
+    sde = sde_lib.VPSDE(cfg.model.beta_min, cfg.model.beta_max, cfg.model.num_scales, device=cfg.device)
+    R = cfg.data.image_size
+    g = torch.Generator().manual_seed(21)
+    y = torch.sign(torch.randn((R, R, R), generator=g))
+    pm = (torch.rand((R, R, R), generator=g) < 0.3).float() * gm                       # about 30 % of the grid mask
+    assert 0.2 < float(pm.sum() / gm.sum()) < 0.4
+    noise = torch.randn(x0.shape, generator=g)
+    return dict(cfg=cfg, model=model, sd=sd, gm=gm, x0=x0, sde=sde, y=y, pm=pm, noise=noise, R=R)
+
+
+@pytest.mark.parametrize("which", ["first", "middle", "last"])
+def test_one_guided_evaluation_against_the_oracle(hip_lib, net, which):
+    """sampling.guidance_terms at x = alpha x0 + sigma noise on the level of the first, the middle and the last iteration of the
+    ancestral table, against oracle.unet_oracle under torch autograd on the CPU: eps_hat within 1e-4 rel-L2 (the forward bar),
+    ||r|| within 1e-4 relative, r - sigma J^T r = alpha ||r|| grad ||r|| within 2e-3 rel-L2 (the whole-net gradient bar)."""
+    from meshdiffusion_amd import synth
+    from meshdiffusion_amd.lib.diffusion import sampling
+    from oracle import unet_oracle as uo
+    cfg, sde, gm, y, pm, R = net["cfg"], net["sde"], net["gm"], net["y"], net["pm"], net["R"]
+    B, ch, N = 2, 0, net["sde"].N
+    i = {"first": 0, "middle": N // 2, "last": N - 1}[which]
+    t = torch.linspace(sde.T, 1e-3, N)[i]
+    label = float(t * (N - 1))
+    k = int((t * (N - 1) / sde.T).long())
+    alpha, sigma = float(sde.sqrt_alphas_cumprod[k].double()), float(sde.sqrt_1m_alphas_cumprod[k].double())
+    mask = gm.view(1, 1, R, R, R)
+    x = ((alpha * net["x0"] + sigma * net["noise"]) * mask).float()
+    # the oracle, float32 forward under autograd on the CPU
+    xr = x.clone().requires_grad_(True)
+    e = uo.unet_res64_forward(net["sd"], synth.oracle_cfg(cfg), xr, torch.full((B,), label))
+    x0_hat = (xr - sigma * e) / alpha
+    r_ref = pm * gm * (x0_hat[:, ch] - y)
+    n_ref = r_ref.flatten(1).norm(dim=1)
+    grad, = torch.autograd.grad(n_ref.sum(), xr)
+    ref_dir = (grad * (alpha * n_ref.detach()).view(B, 1, 1, 1, 1)).double()             # r - sigma J^T r
+    # the GPU
+    coef = torch.tensor([[alpha, sigma]] * B, dtype=torch.float64, device="cuda")
+    eps_hat, cot, g, slabs = sampling.guidance_terms(net["model"], coef, x.cuda(), torch.full((B,), label, device="cuda"), None, None,
+                                                     y.cuda().reshape(-1), pm.cuda().reshape(-1), gm.cuda().reshape(-1).float(), ch)
+    n_got = slabs.sum(dim=1).sqrt().cpu()
+    got_dir = (cot.double() - sigma * g.double()).cpu()
+    err_e = rel_l2(eps_hat.cpu() * mask, e.detach() * mask)
+    err_n = float(((n_got - n_ref.detach().double()).abs() / n_ref.detach().double()).max())
+    err_d = rel_l2(got_dir * mask, ref_dir * mask)
+    print(f"{which} (level {k}, alpha {alpha:.4g}, sigma {sigma:.4g}): eps_hat rel-L2 {err_e:.2e}; ||r|| {n_got.tolist()} vs "
+          f"{n_ref.tolist()}: rel {err_n:.2e}; r - sigma J^T r rel-L2 {err_d:.2e}")
+    assert err_e < 1e-4 and err_n < 1e-4 and err_d < 2e-3
+    assert not eps_hat.requires_grad and not g.requires_grad
+    assert all(p.grad is None for p in net["model"].parameters())
+    # chunked: one sample per taped forward and backward
+    e1, c1, g1, s1 = sampling.guidance_terms(net["model"], coef, x.cuda(), torch.full((B,), label, device="cuda"), None, None,
+                                             y.cuda().reshape(-1), pm.cuda().reshape(-1), gm.cuda().reshape(-1).float(), ch, chunk=1)
+    assert e1.shape == eps_hat.shape and rel_l2(e1, eps_hat) < 1e-4 and rel_l2(c1 - sigma * g1, got_dir) < 2e-3
+
+
+# ---- the loops against the closed form ---------------------------------------------------------------------------------------
+def _replay(noise):
+    it = iter([z.cuda() for z in noise])
+
+    def draw(like):
+        z = next(it)
+        assert z.shape == like.shape
+        return z
+    return draw
+
+
+def test_guided_ancestral_loop_against_the_closed_form(hip_lib):
+    """pc_sampler on eps_hat = k_t x against the float64 recursion.  Yardstick u: the unguided conditional run (today's code
+    path) against its own recursion; bar max(2u, 1e-6): guidance adds two roundings per element per step to a chain of about six.
+    Measured on an MI355X: u = 1.5e-7, guided distance 1.5e-7 (replacement on) / 1.6e-7 (off)."""
+    from meshdiffusion_amd.lib.diffusion import sampling
+    s = gc.loop_setup()
+    sde, N, ch, y, pm, gm, shape = s["sde"], s["N"], s["ch"], s["y"], s["pm"], s["gm"], s["shape"]
+    model = gc.GaussianEps(s["s"], N)
+    fn = sampling.get_pc_sampler(sde, shape, sampling.get_predictor("ancestral_sampling"), sampling.get_corrector("none"),
+                                 lambda v: v, 0.1, n_steps=1, denoise=True, device="cuda", grid_mask=gm.float())
+    partial = torch.zeros((1,) + shape[1:])
+    partial[0, ch] = y.float()
+    pmask = torch.zeros((1,) + shape[1:])
+    pmask[0, ch] = pm.float()
+    noise = gc.loop_noise(shape, 5, N)
+
+    def gpu(zeta, replace, **kw):
+        torch.manual_seed(3)
+        return fn(model, partial=partial.cuda(), partial_mask=pmask.cuda(), partial_channel=ch,
+                  noise_fn=_replay(gc.noise_for(noise, replace, N)), guidance_scale=zeta, guidance_replace=replace, **kw)[0].cpu().double()
+
+    def ref(zeta, replace):
+        torch.manual_seed(3)
+        x_init = sde.prior_sampling(shape) * gm.float()
+        return gc.ancestral_recursion(sde, s["s"], x_init, y, pm, gm, ch, zeta, replace, iter(gc.noise_for(noise, replace, N)))[1]
+
+    plain = gpu(0.0, True)
+    u = rel_l2(plain, ref(0.0, True))
+    bar = max(2 * u, 1e-6)
+    print(f"ancestral: unguided u = {u:.3e}, bar {bar:.3e}")
+    for replace in (True, False):
+        got, want = gpu(s["zeta"], replace), ref(s["zeta"], replace)
+        dist, moved = rel_l2(got, want), rel_l2(got, plain)
+        print(f"ancestral, replacement {'on' if replace else 'off'}: guided distance {dist:.3e}; guided vs unguided {moved:.3e}")
+        assert torch.isfinite(got).all() and float((got * (1 - gm)).abs().max()) == 0.0
+        assert moved >= 100 * bar
+        assert dist <= bar
+        assert torch.equal(gpu(s["zeta"], replace, guidance_chunk=1), got)          # the callable is per-sample: chunking is exact
+
+
+def test_guided_ddim_loop_against_the_closed_form(hip_lib):
+    """ddim_sampler likewise, on the 25 uniform points of guidance_cases.loop_setup (why not the default schedule: there).
+    Measured on an MI355X: u = 4.6e-8, guided distance 4.4e-8 (replacement on) / 1.1e-7 (off); on the 100-point quadratic
+    schedule u = 2.6e-8, 2.5e-8 (on) / 6.7e-6 (off), the last being the recursion's own amplification of float32 roundings."""
+    from meshdiffusion_amd.lib.diffusion import sampling
+    s = gc.loop_setup()
+    sde, N, ch, y, pm, gm, shape = s["sde"], s["N"], s["ch"], s["y"], s["pm"], s["gm"], s["shape"]
+    model = gc.GaussianEps(s["s"], N)
+    fn = sampling.get_ddim_sampler(sde, shape, sampling.get_predictor("ddim"), lambda v: v, denoise=False, device="cuda",
+                                   grid_mask=gm.float())
+    x0 = torch.randn(shape, generator=torch.Generator().manual_seed(9))
+    schedule, num_steps = s["ddim"]
+    ts = sampling.ddim_schedule(N, schedule, num_steps)
+
+    def gpu(zeta, replace, **kw):
+        return fn(model, schedule=schedule, num_steps=num_steps, x0=x0, partial=y.float(), partial_mask=pm.float(), partial_channel=ch, guidance_scale=zeta,
+                  guidance_replace=replace, **kw)[0].cpu().double()
+
+    ref = lambda zeta, replace: gc.ddim_recursion(sde, s["s"], x0, y, pm, gm, ch, zeta, replace, ts)      # noqa: E731
+    plain = gpu(0.0, True)
+    u = rel_l2(plain, ref(0.0, True))
+    bar = max(2 * u, 1e-6)
+    print(f"ddim: unguided u = {u:.3e}, bar {bar:.3e}")
+    for replace in (True, False):
+        got, want = gpu(s["zeta"], replace), ref(s["zeta"], replace)
+        dist, moved = rel_l2(got, want), rel_l2(got, plain)
+        print(f"ddim, replacement {'on' if replace else 'off'}: guided distance {dist:.3e}; guided vs unguided {moved:.3e}")
+        assert torch.isfinite(got).all() and float((got * (1 - gm)).abs().max()) == 0.0
+        assert moved >= 100 * bar
+        assert dist <= bar
+        assert torch.equal(gpu(s["zeta"], replace, guidance_chunk=1), got)
+
+
+# ---- off means off ----------------------------------------------------------------------------------------------------------
+def test_guidance_off_is_todays_sampler(hip_lib, net):
+    from meshdiffusion_amd.lib.diffusion import sampling
+    cfg, sde, gm, R = net["cfg"], net["sde"], net["gm"], net["R"]
+    shape, ch = tuple(net["x0"].shape), 0
+    mask = gm.view(1, 1, R, R, R)
+    partial = torch.zeros((1,) + shape[1:])
+    partial[0, ch] = net["y"]
+    pmask = torch.zeros((1,) + shape[1:])
+    pmask[0, ch] = net["pm"]
+    pc = sampling.get_pc_sampler(sde, shape, sampling.get_predictor("ancestral_sampling"), sampling.get_corrector("none"),
+                                 lambda v: v, 0.1, n_steps=1, denoise=True, device="cuda", grid_mask=gm)
+    ddim = sampling.get_ddim_sampler(sde, shape, sampling.get_predictor("ddim"), lambda v: v, denoise=False, device="cuda",
+                                     grid_mask=gm)
+
+    def run(fn, part, pm, **kw):
+        torch.manual_seed(17)
+        return fn(net["model"], partial=part.cuda(), partial_mask=pm.cuda(), partial_channel=ch, n_iters=3, **kw)[0].cpu()
+
+    for name, fn, part, pm in (("pc", pc, partial, pmask), ("ddim", ddim, net["y"], net["pm"])):
+        unset, zero = run(fn, part, pm), run(fn, part, pm, guidance_scale=0.0, guidance_replace=False, guidance_chunk=1)
+        assert torch.equal(unset, zero), name
+        for replace in (True, False):
+            guided = run(fn, part, pm, guidance_scale=1.0, guidance_replace=replace)
+            assert guided.shape == unset.shape and torch.isfinite(guided).all(), name
+            assert float((guided * (1 - mask)).abs().max()) == 0.0 and not torch.equal(guided, unset), name
+    assert all(p.grad is None for p in net["model"].parameters())
+
+
+# ---- the CLI ----------------------------------------------------------------------------------------------------------------
+def test_cli_cond_gen_with_guidance(hip_lib, tmp_path, monkeypatch):
+    """`main_diffusion.py --mode=cond_gen --config.sampling.method=ddim --config.eval.guidance_scale=1.0` writes a finite 0.npy;
+    without the option the run is today's: twice under one seed, byte-identical files."""
+    sys.path.insert(0, ROOT)
+    import main_diffusion
+    from meshdiffusion_amd import synth
+    from test_gpu_cli import _write_ckpt_and_mask
+    cfg = synth.small_config(); cfg.device = torch.device("cuda")
+    cfg.model.num_scales = 40
+    ck = _write_ckpt_and_mask(tmp_path, cfg, synth)
+    cdir = tmp_path / "configs"; cdir.mkdir()
+    (cdir / "small.py").write_text("from meshdiffusion_amd import synth\n\ndef get_config():\n    c = synth.small_config()\n"
+                                   "    c.model.num_scales = 40\n    return c\n")
+    monkeypatch.chdir(tmp_path)
+    R = cfg.data.image_size
+    m = synth.synthetic_grid_mask(R).numpy()
+    idx = np.argwhere(m > 0).astype(np.float32)
+    verts = (idx / (R - 1) - 0.5).astype(np.float32)
+    tet_path = tmp_path / "tets.npz"
+    np.savez(tet_path, vertices=verts, indices=np.zeros((1, 4), np.int32))
+    g = torch.Generator().manual_seed(1)
+    part = {"sdf": torch.sign(torch.randn(len(verts), generator=g)), "vis": torch.rand(len(verts), generator=g) < 0.5}
+    ppath = tmp_path / "dmtet.pt"
+    torch.save(part, ppath)
+
+    def run(out, *more):
+        torch.manual_seed(0)
+        main_diffusion.main(["--config", str(cdir / "small.py"), "--mode=cond_gen", f"--config.eval.eval_dir={out}",
+                             f"--config.eval.ckpt_path={ck}", "--config.eval.batch_size=2", f"--config.eval.partial_dmtet_path={ppath}",
+                             f"--config.eval.tet_path={tet_path}", "--config.eval.freeze_iters=30", *more])
+        return open(out / "0.npy", "rb").read(), np.load(out / "0.npy")
+
+    _, xg = run(tmp_path / "guided", "--config.sampling.method=ddim", "--config.eval.guidance_scale=1.0")
+    assert xg.shape == (2, 4, R, R, R) and np.isfinite(xg).all() and np.abs(xg * (1 - m)).max() == 0.0 and np.abs(xg).max() > 0
+    _, xf = run(tmp_path / "free", "--config.sampling.method=ddim", "--config.eval.guidance_scale=1.0",
+                "--config.eval.guidance_replace=False", "--config.eval.guidance_chunk=1", "--config.eval.calibrate=False")
+    assert xf.shape == xg.shape and np.isfinite(xf).all() and not np.array_equal(xf, xg)
+    a, xa = run(tmp_path / "plain_a")
+    b, _ = run(tmp_path / "plain_b")
+    assert a == b and xa.shape == (2, 4, R, R, R) and np.isfinite(xa).all()
