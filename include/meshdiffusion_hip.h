@@ -605,6 +605,24 @@ int md_guide_apply_f32(float* x, float* x_mean, const float* cot, const float* g
 int md_guide_apply_f64(double* x64, float* x_f32, const float* cot, const float* g, const float* gmask, const double* coef,
                        const double* slabs, int32_t batch, int32_t C, int64_t P, void* stream);
 /*
+ * One update of the multistep exponential integrator in the data prediction (DPM-Solver++, Lu et al. 2022; orders 1-3, the ODE
+ * and the SDE variant), one launch.  All tensors NCDHW [B][C][P]; state and history in float64 like md_ddim_step's state.  With
+ * coef[b][8] = {alpha_s, sigma_s, c_x, c_0, c_1, c_2, c_z, unused} as doubles (alpha_s, sigma_s: the level the step starts from;
+ * the c's formed by the host from the half-log-SNR of the two levels), everything evaluated in double:
+ *   x0    = (x - sigma_s*eps)/alpha_s                           the clean-grid prediction of this step
+ *   x_new = c_x*x + c_0*x0 + c_1*h1 + c_2*h2 + c_z*z            added left to right; a term whose pointer is NULL is skipped
+ *   x_new, x0 *= mask[P]   (mask may be NULL)
+ *   channel `ch`: v = v*(1-pmask) + partial*pmask on both when partial/pmask ([P] each) are given: the order of md_ddim_step
+ * h1, h2: the x0_out of the previous step and of the one before it (the caller keeps them); z: float32 noise (SDE variant).
+ * x_out = x_new ; x0_out = x0 ; x_f32 = (float)x_new, the next U-Net input.  Deterministic: no atomics, no LDS.
+ * P % 4 == 0; pointers 16-byte aligned (coef: 8); 0 <= ch < C; partial and pmask both given or both NULL; h2 only with h1; no
+ * output may share memory with an input or with another output; anything else MD_ERR_BAD_ARG, before any launch.  Purely
+ * additive: MD_ABI_VERSION stays 16.
+ */
+int md_multistep_step(const double* x, const float* eps, const double* h1, const double* h2, const float* z,
+                      const float* mask, const double* coef, const float* partial, const float* pmask, int32_t ch,
+                      double* x_out, double* x0_out, float* x_f32, int32_t batch, int32_t C, int64_t P, void* stream);
+/*
  * Inpainting blend of one channel (sampling.py:443-467):
  *   v = (x*(1-m) + src*m) * gm     applied in place to channel `ch` of x [B][C][P];
  *   src has batch stride src_bstride (0 = shared partial grid).

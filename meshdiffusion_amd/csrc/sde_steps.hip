@@ -302,6 +302,82 @@ __global__ __launch_bounds__(256) void md_guide_apply_kernel(void* __restrict__ 
   }
 }
 
+// ---- multistep exponential-integrator update (DPM-Solver++, Lu et al. 2022; ODE and SDE variants), one launch ----------------
+// coef[b] = {alpha_s, sigma_s, c_x, c_0, c_1, c_2, c_z, unused} as doubles, formed by the host from the half-log-SNR of the two
+// levels (sampling.dpmpp_tables).  Everything in double, in this order, no FMA contraction:
+//   x0 = (x - sigma_s*eps)/alpha_s ; x_new = c_x*x + c_0*x0 [+ c_1*h1] [+ c_2*h2] [+ c_z*z]    (added left to right)
+// then both times the grid mask, then on channel `ch` the replacement v*(1-pm) + partial*pm: the order of md_ddim_step.
+// x0 enters x_new as formed, before the mask; x0_out is the masked and replaced one, which the caller keeps as h1 / h2.
+// NH: how many earlier predictions are read; Z, MASK, REP: whether z / mask / partial+pmask are: an absent operand costs no load.
+// Four values per thread and trip, 16-byte loads and stores; the row is uniform per workgroup (scalar loads).
+template <int NH, bool Z, bool MASK, bool REP>
+__global__ __launch_bounds__(256) void md_multistep_step_kernel(const double* __restrict__ x, const float* __restrict__ eps,
+                                                                const double* __restrict__ h1, const double* __restrict__ h2,
+                                                                const float* __restrict__ z, const float* __restrict__ mask,
+                                                                const double* __restrict__ coef, const float* __restrict__ partial,
+                                                                const float* __restrict__ pmask, int ch, double* __restrict__ x_out,
+                                                                double* __restrict__ x0_out, float* __restrict__ x_f32, int64_t CP,
+                                                                int64_t P) {
+  const int b = blockIdx.y;
+  const double* row = coef + (int64_t)b * 8;
+  const double alpha = row[0], sigma = row[1], cx = row[2], c0 = row[3], c1 = row[4], c2 = row[5], cz = row[6];
+  const int64_t base = (int64_t)b * CP, lo = (int64_t)ch * P, hi = lo + P;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
+    const f64x2 xa = *(const f64x2*)(x + base + i), xb = *(const f64x2*)(x + base + i + 2);
+    const f32x4 ev = *(const f32x4*)(eps + base + i);
+    double xv[4] = {xa[0], xa[1], xb[0], xb[1]}, xn[4], x0[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      x0[e] = (xv[e] - sigma * (double)ev[e]) / alpha;
+      xn[e] = cx * xv[e] + c0 * x0[e];
+    }
+    if constexpr (NH >= 1) {
+      const f64x2 a = *(const f64x2*)(h1 + base + i), c = *(const f64x2*)(h1 + base + i + 2);
+      const double hv[4] = {a[0], a[1], c[0], c[1]};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xn[e] = xn[e] + c1 * hv[e];
+    }
+    if constexpr (NH >= 2) {
+      const f64x2 a = *(const f64x2*)(h2 + base + i), c = *(const f64x2*)(h2 + base + i + 2);
+      const double hv[4] = {a[0], a[1], c[0], c[1]};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xn[e] = xn[e] + c2 * hv[e];
+    }
+    if constexpr (Z) {
+      const f32x4 zv = *(const f32x4*)(z + base + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xn[e] = xn[e] + cz * (double)zv[e];
+    }
+    const int64_t pos = i % P;                  // P % 4 == 0: four values never straddle two channels
+    if constexpr (MASK) {
+      const f32x4 mv = *(const f32x4*)(mask + pos);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        xn[e] = xn[e] * (double)mv[e];
+        x0[e] = x0[e] * (double)mv[e];
+      }
+    }
+    if constexpr (REP) {
+      if (i >= lo && i < hi) {
+        const f32x4 pm = *(const f32x4*)(pmask + pos), pv = *(const f32x4*)(partial + pos);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const double m = (double)pm[e], v = (double)pv[e];
+          xn[e] = xn[e] * (1.0 - m) + v * m;
+          x0[e] = x0[e] * (1.0 - m) + v * m;
+        }
+      }
+    }
+    const f64x2 na = {xn[0], xn[1]}, nb = {xn[2], xn[3]}, pa = {x0[0], x0[1]}, pb = {x0[2], x0[3]};
+    *(f64x2*)(x_out + base + i) = na;
+    *(f64x2*)(x_out + base + i + 2) = nb;
+    *(f64x2*)(x0_out + base + i) = pa;
+    *(f64x2*)(x0_out + base + i + 2) = pb;
+    const f32x4 xo = {(float)xn[0], (float)xn[1], (float)xn[2], (float)xn[3]};
+    *(f32x4*)(x_f32 + base + i) = xo;
+  }
+}
+
 // one workgroup per 1024 values, at most 1024 workgroups in all (B*S <= 1024 keeps the slab prologue's L2 reads small)
 static int stream_blocks(int64_t CP, int batch) {
   int64_t blocks = (CP / 4 + 255) / 256;
@@ -424,4 +500,48 @@ extern "C" int md_guide_apply_f32(float* x, float* x_mean, const float* cot, con
 extern "C" int md_guide_apply_f64(double* x64, float* x_f32, const float* cot, const float* g, const float* gmask,
                                   const double* coef, const double* slabs, int32_t batch, int32_t C, int64_t P, void* stream) {
   return md_guide_apply<true>(x64, x_f32, cot, g, gmask, coef, slabs, batch, C, P, stream);
+}
+
+template <int NH, bool Z>
+static void md_multistep_launch(bool has_mask, bool rep, dim3 grid, hipStream_t s, const double* x, const float* eps, const double* h1,
+                                const double* h2, const float* z, const float* mask, const double* coef, const float* partial,
+                                const float* pmask, int ch, double* x_out, double* x0_out, float* x_f32, int64_t CP, int64_t P) {
+#define MD_MULTISTEP_GO(M, R)                                                                                                \
+  hipLaunchKernelGGL((md_multistep_step_kernel<NH, Z, M, R>), grid, dim3(256), 0, s, x, eps, h1, h2, z, mask, coef, partial, \
+                     pmask, ch, x_out, x0_out, x_f32, CP, P)
+  if (has_mask && rep) MD_MULTISTEP_GO(true, true);
+  else if (has_mask) MD_MULTISTEP_GO(true, false);
+  else if (rep) MD_MULTISTEP_GO(false, true);
+  else MD_MULTISTEP_GO(false, false);
+#undef MD_MULTISTEP_GO
+}
+
+extern "C" int md_multistep_step(const double* x, const float* eps, const double* h1, const double* h2, const float* z,
+                                 const float* mask, const double* coef, const float* partial, const float* pmask, int32_t ch,
+                                 double* x_out, double* x0_out, float* x_f32, int32_t batch, int32_t C, int64_t P, void* stream) {
+  if (md_any_bad<16>(x, eps, x_out, x0_out, x_f32) || md_any_bad<8>(coef) || md_any_misaligned<16>(h1, h2, z, mask, partial, pmask))
+    return MD_ERR_BAD_ARG;
+  if (batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
+  if (ch < 0 || ch >= C || (partial == nullptr) != (pmask == nullptr) || (h2 && !h1)) return MD_ERR_BAD_ARG;
+  const int64_t CP = (int64_t)C * P, n4 = 4 * CP * batch, n8 = 8 * CP * batch, np = 4 * P, nc = 64LL * batch;
+  const struct { const void* p; int64_t n; } in[] = {{x, n8}, {eps, n4}, {h1, n8}, {h2, n8}, {z, n4}, {mask, np}, {coef, nc},
+                                                     {partial, np}, {pmask, np}},
+                                             out[] = {{x_out, n8}, {x0_out, n8}, {x_f32, n4}};
+  for (int o = 0; o < 3; ++o) {
+    for (const auto& i : in)
+      if (md_overlap(out[o].p, out[o].n, i.p, i.n)) return MD_ERR_BAD_ARG;
+    for (int q = o + 1; q < 3; ++q)
+      if (md_overlap(out[o].p, out[o].n, out[q].p, out[q].n)) return MD_ERR_BAD_ARG;
+  }
+  const dim3 grid((unsigned)stream_blocks(CP, batch), (unsigned)batch);
+  const bool m = mask != nullptr, r = partial != nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  MD_HIP_CLEAR_ERROR();
+#define MD_MULTISTEP_ARGS m, r, grid, s, x, eps, h1, h2, z, mask, coef, partial, pmask, (int)ch, x_out, x0_out, x_f32, CP, P
+  if (h2) z ? md_multistep_launch<2, true>(MD_MULTISTEP_ARGS) : md_multistep_launch<2, false>(MD_MULTISTEP_ARGS);
+  else if (h1) z ? md_multistep_launch<1, true>(MD_MULTISTEP_ARGS) : md_multistep_launch<1, false>(MD_MULTISTEP_ARGS);
+  else z ? md_multistep_launch<0, true>(MD_MULTISTEP_ARGS) : md_multistep_launch<0, false>(MD_MULTISTEP_ARGS);
+#undef MD_MULTISTEP_ARGS
+  MD_HIP_CHECK_LAUNCH();
+  return MD_OK;
 }

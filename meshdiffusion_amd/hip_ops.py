@@ -1354,6 +1354,41 @@ def ddim_step(x64, eps, mask, coef, partial=None, pmask=None, ch=0):
     return x_out, x0_out, x_f32
 
 
+def multistep_step(x64, eps, hist, z, mask, coef, partial=None, pmask=None, ch=0, out=None):
+    """One DPM-Solver++ update in one launch (md_multistep_step).  x64 [B,C,D,H,W] float64 state; eps fp32 U-Net output at it;
+    hist: the earlier clean-grid predictions the step reads, newest first -- (), (h1,) or (h1, h2), float64 like x64; z: fp32
+    noise or None; mask [P] fp32 or None; coef [B,8] float64 = alpha_s, sigma_s, c_x, c_0, c_1, c_2, c_z, 0; partial / pmask:
+    [P] fp32 each or None.  out: (x_new f64, x0_pred f64, x_new as fp32) to write into -- the sampler's own buffers, none of them
+    an input -- or None: allocated here.  Returns that triple."""
+    lib = _lib.load()
+    B, Cc = x64.shape[0], x64.shape[1]
+    P = x64.numel() // (B * Cc)
+    f32, f64 = torch.float32, torch.float64
+    hist = tuple(hist or ())
+    assert len(hist) <= 2, len(hist)
+    _guide_operand(x64, "x", f64)
+    _guide_operand(eps, "eps", f32, shape=x64.shape)
+    _guide_operand(coef, "coef", f64, shape=(B, 8))
+    for t in hist:
+        _guide_operand(t, "history", f64, shape=x64.shape)
+    if z is not None:
+        _guide_operand(z, "z", f32, shape=x64.shape)
+    for nm, t in (("mask", mask), ("partial", partial), ("pmask", pmask)):
+        if t is not None:
+            _guide_operand(t, nm, f32, numel=P)
+    if out is None:
+        out = (torch.empty_like(x64), torch.empty_like(x64), torch.empty_like(eps))
+    x_out, x0_out, x_f32 = out
+    _guide_operand(x_out, "x_out", f64, shape=x64.shape)
+    _guide_operand(x0_out, "x0_out", f64, shape=x64.shape)
+    _guide_operand(x_f32, "x_f32", f32, shape=x64.shape)
+    h1, h2 = (hist + (None, None))[:2]
+    check(lib.md_multistep_step(_ptr(x64), _ptr(eps), _ptr(h1), _ptr(h2), _ptr(z), _ptr(mask), _ptr(coef), _ptr(partial),
+                                _ptr(pmask), int(ch), _ptr(x_out), _ptr(x0_out), _ptr(x_f32), B, Cc, P, _stream()),
+          "md_multistep_step")
+    return x_out, x0_out, x_f32
+
+
 def inpaint_blend_(x, src, pmask, gmask, ch, src_bstride=0):
     """In place on channel `ch` of x: (x*(1-pmask) + src*pmask) * gmask."""
     lib = _lib.load()

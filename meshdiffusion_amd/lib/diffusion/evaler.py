@@ -132,9 +132,10 @@ def cond_gen(config, save_fname="0"):
     # below is the unguided one), guidance_replace (True: the replacement of the known voxels stays), guidance_chunk (samples per
     # taped forward).  The load-time calibration still runs; the taped forward of a guided step is bf16x3 and does not read it.
     scale = float(getattr(config.eval, "guidance_scale", 0.0) or 0.0)
-    kw = dict(freeze_iters=config.eval.freeze_iters)
+    method = str(getattr(getattr(config, "sampling", None), "method", "pc")).lower()
+    kw = {} if method == "dpmpp" else dict(freeze_iters=config.eval.freeze_iters)      # DPM-Solver++ has its own time grid
     if scale > 0:
-        if config.sampling.method.lower() == "ddim":
+        if method == "ddim":
             kw = {}                                     # the DDIM sampler visits its own sub-sequence: no freeze_iters
         kw.update(guidance_scale=scale, guidance_replace=bool(getattr(config.eval, "guidance_replace", True)),
                   guidance_chunk=getattr(config.eval, "guidance_chunk", None))
