@@ -1247,6 +1247,55 @@ int md_remesh_relax(const float* verts, const int64_t* faces, const int32_t* ptr
 int md_mesh_query(const float* tri, const int32_t* tri_ptr, const float* query, const int32_t* query_ptr, int64_t n_tris,
                   int64_t n_queries, int64_t n_meshes, float* dist2, int32_t* face, float* closest, float* winding, void* stream);
 
+/*
+ * Generation metrics under a light-field distance in the manner of Chen et al. 2003 (csrc/lfd.hip): a 48-byte descriptor per
+ * silhouette and the all-pairs matrix of models, each L light fields of 10 silhouettes.  The original executable traces contours
+ * and scales differently: values are NOT comparable with its numbers.  The reference has no counterpart.  Purely additive:
+ * MD_ABI_VERSION stays 16.
+ *
+ * THE LFD CONTRACT (the header comment of csrc/lfd.hip has it in full; tests/lfd_cases.py restates it and derives the bars)
+ * md_lfd_describe: mask uint8 [n][R][R] -> desc uint8 [n][48], coef float32 [n][45] (may be NULL), status int32 [n].
+ *   A pixel is set where its byte is non-zero; pixel (row y, column x) sits at (x, y).  With `count` set pixels the centroid is
+ *   c = (sum x / count, sum y / count) (integer sums, exact), rmax = max(0.5, max_p |p - c|), and per set pixel rho = |p - c| / rmax,
+ *   theta = atan2(dy, dx).
+ *   Zernike: for n = 1..10, m = n mod 2, ..., n in steps of 2 (35 values, in that order)
+ *       z_nm = |sum_p R_nm(rho) e^{-i m theta}| / count,   R_nm(rho) = sum_s (-1)^s (n-s)! / (s! ((n+m)/2-s)! ((n-m)/2-s)!) rho^(n-2s).
+ *   Signature: 64 angular bins, b = floor(64 theta / 2 pi + 0.5) mod 64; sig[b] = the largest rho of the bin's pixels, 0 when empty.
+ *   Fourier: f_k = |sum_b sig[b] e^{-2 pi i k b / 64}| / sum_b sig[b] for k = 1..10; 0 when sum_b sig[b] = 0 (one pixel).
+ *   coef = the 45 values 512 z, 512 f rounded to fp32; desc = min(255, rint(coef)) as bytes, then three zero bytes.
+ *   An empty mask: desc and coef 0, status 1; otherwise status 0.
+ *   Evaluation scheme: the integers Nx = x count - sum x, Ny = y count - sum y, q = Nx^2 + Ny^2 and Q = max q are exact; Qe =
+ *   max(Q, count^2 / 4), inv = fp32(1 / sqrt(Qe)), inv2 = fp32(1 / Qe), both formed in float64 once per mask.  Per pixel, in fp32
+ *   without contraction: w = (fp32(Nx) inv, -(fp32(Ny) inv)) = rho e^{-i theta}, t = fp32(q) inv2 = rho^2; W_0 = 1, W_m = W_{m-1} w
+ *   (complex product, four multiplies, an add and a subtract); R_nm(rho) e^{-i m theta} = P_nm(t) W_m with P_nm the polynomial of
+ *   degree (n-m)/2 in t with the integer coefficients above, by Horner's rule from the highest power (a multiply and an add per
+ *   step); both components of P W_m are multiplied by 2^32, rounded to integers and summed as 64-bit integers, so the sums are
+ *   exact in any order.  |sum| / count, the signature (sig[b] = sqrt(max q of the bin / Qe), the maximum an exact integer), the
+ *   64-point transform and the normalisation are float64, rounded once to fp32.  The bin of a pixel is computed in fp32:
+ *   floorf(atan2f(fp32(Ny), fp32(Nx)) * fp32(64 / 2 pi) + 0.5f) mod 64.  Two runs agree bit for bit, however the launch is cut up.
+ *   Null mask, desc or status, coef not 4-byte aligned, n < 1 or R < 1: MD_ERR_BAD_ARG; R > MD_LFD_MAX_RES or n >= 2^31 / 256:
+ *   MD_ERR_UNSUPPORTED.  One workgroup per mask.
+ * md_lfd_matrix: x uint8 [nx][L][10][48], y uint8 [ny][L][10][48] on the device (4-byte aligned), perm uint8 [G][10] ON THE HOST
+ *   (read by the export before it returns) -> out int32 [nx][ny],
+ *       out[i][j] = min over la, lb < L and g < G of sum_{v<10} SAD48(x[i][la][v], y[j][lb][perm[g][v]]),
+ *   SAD48 the sum of absolute differences over all 48 bytes.  Integers throughout: exact, independent of the launch.
+ *   triangular != 0 (needs x == y and nx == ny): only the pairs i < j are computed and written to [i][j] and [j][i]; the diagonal
+ *   is 0.  In this order: null or misaligned pointers, sizes < 1: MD_ERR_BAD_ARG; L > MD_LFD_MAX_FIELDS or G >
+ *   MD_LFD_MAX_ROTATIONS: MD_ERR_UNSUPPORTED; a perm entry >= 10, triangular with x != y or nx != ny: MD_ERR_BAD_ARG; nx >= 2^24 or
+ *   ny > 65535 MD_LFD_RUN: MD_ERR_UNSUPPORTED.  A workgroup owns one x model and
+ *   MD_LFD_RUN consecutive y models.  Nothing is allocated, nothing synchronises.
+ */
+#define MD_LFD_MAX_RES 512
+#define MD_LFD_DESC_BYTES 48
+#define MD_LFD_COEFS 45
+#define MD_LFD_VIEWS 10
+#define MD_LFD_MAX_FIELDS 16
+#define MD_LFD_MAX_ROTATIONS 64
+#define MD_LFD_RUN 8
+int md_lfd_describe(const uint8_t* mask, int32_t n, int32_t R, uint8_t* desc, float* coef, int32_t* status, void* stream);
+int md_lfd_matrix(const uint8_t* x, const uint8_t* y, const uint8_t* perm, int32_t nx, int32_t ny, int32_t L, int32_t G,
+                  int32_t triangular, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
