@@ -633,11 +633,13 @@ def wgrad_nin_ok(co, ci, P):
     return co % 128 == 0 and ci % 128 == 0 and P % 16 == 0
 
 
-def wgrad_nin(dy_s16, x_s16, B, co, ci, P, dw):
-    """dw[ci][co] += sum x[ci] dy[co] over samples and positions, both operands S16B -- md_wgrad_nin (no PB16 tensors)."""
+def wgrad_nin(dy_s16, x_s16, B, co, ci, P, dw, ksplit=None):
+    """dw[ci][co] += sum x[ci] dy[co] over samples and positions, both operands S16B -- md_wgrad_nin (no PB16 tensors).
+    ksplit: the number of K ranges instead of the one chosen here."""
     lib = _lib.load()
     units = (co // 128) * (ci // 128)
-    ksplit = max(1, min(256 // units, B * P // 16 // 8))
+    if ksplit is None:
+        ksplit = max(1, min(256 // units, B * P // 16 // 8))
     nbytes = lib.md_wgrad_nin_workspace_bytes(co, ci, ksplit)
     if nbytes <= 0:
         raise _lib.MeshDiffusionHipError("md_wgrad_nin_workspace_bytes: unsupported shape")
@@ -763,19 +765,23 @@ def wgrad_wino_ok(co, ci, S, B):
     return WINO_TRAIN_FWD and S in (32, 64) and co % 128 == 0 and ci % 128 == 0 and wino_ok(co, ci, S, B)
 
 
-def wgrad_wino(u_dy, t_act, B, co, ci, S, dw):
-    """dw[co][ci][27] += weight gradient from U (md_wino_prep_dual of dY) and the forward's T -- md_wgrad_wino."""
+def wgrad_wino(u_dy, t_act, B, co, ci, S, dw, dims=None, ksplit=None):
+    """dw[co][ci][27] += weight gradient from U (md_wino_prep_dual of dY) and the forward's T -- md_wgrad_wino.
+    dims: the grid (D, H, W) where it is not the cube S^3 (`S` is ignored then); ksplit: the number of K ranges instead of the
+    one chosen here."""
     lib = _lib.load()
+    D, H, W = dims if dims is not None else (S, S, S)
     units = (co // 128) * (ci // 128) * 12
-    ksplit = max(1, min(256 // units, B * (S - 1)))
+    if ksplit is None:
+        ksplit = max(1, min(256 // units, B * (D - 1)))
     nbytes = lib.md_wgrad_wino_workspace_bytes(co, ci, ksplit)
     if nbytes <= 0:
         raise _lib.MeshDiffusionHipError("md_wgrad_wino_workspace_bytes: unsupported shape")
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=u_dy.device)
     ev = _prof_begin()
-    check(lib.md_wgrad_wino(_ptr(u_dy), _ptr(t_act), _ptr(dw), _ptr(ws), nbytes, B, co, ci, S, S, S, ksplit, ci * 27, 27, 1,
+    check(lib.md_wgrad_wino(_ptr(u_dy), _ptr(t_act), _ptr(dw), _ptr(ws), nbytes, B, co, ci, D, H, W, ksplit, ci * 27, 27, 1,
                             _stream()), "md_wgrad_wino")
-    _prof_end(ev, "wgrad_wino", 2.0 * B * co * ci * 27 * S ** 3, 16.0 * B * (co + ci) * S ** 3 / 2, f"{ci}->{co}@{S}x{S}x{S}")
+    _prof_end(ev, "wgrad_wino", 2.0 * B * co * ci * 27 * D * H * W, 16.0 * B * (co + ci) * D * H * W / 2, f"{ci}->{co}@{D}x{H}x{W}")
 
 
 def conv3_wino(ww, t, B, S, *, bias=None, bias_bstride=0, residual=None, res_bstride=0, stats=None, out=None, variant=None, out_scale=1.0,

@@ -53,15 +53,18 @@ def zsplit_for(B, S):
     return zs
 
 
-def to_pb16(src, B, C, S, mode, up=0, stuff=0, c_src=None, pad=1, zhalo=True):
+def to_pb16(src, B, C, S, mode, up=0, stuff=0, c_src=None, pad=1, zhalo=True, dims=None):
     """src: F32B (mode 0) or S16B (mode 1) on an S^3 grid (or (S/2)^3 when up/stuff) -> PB16 on the padded S^3 grid.
     c_src: channels actually present in `src` (the PB16 tensor is zero for channels c_src..C-1).
     pad: halo of the padded grid = kernel size // 2 of the conv whose wgrad consumes it (1 for NIN).
-    zhalo: True for an activation operand, False for a dY operand (see md_to_pb16: z-slab virtual samples)."""
+    zhalo: True for an activation operand, False for a dY operand (see md_to_pb16: z-slab virtual samples).
+    dims: the grid (D, S, S) where its depth is not S (`S` is ignored then; md_wgrad needs H == W)."""
     lib = _lib.load()
+    D, S = (dims[0], dims[1]) if dims is not None else (S, S)
+    assert dims is None or dims[1] == dims[2], "md_wgrad contracts grids with H == W"
     g = _guard(S, pad)
-    zs = zsplit_for(B, S)
-    VB, Dz = B * zs, S // zs
+    zs = zsplit_for(B, D)
+    VB, Dz = B * zs, D // zs
     nbytes = lib.md_pb16_bytes(VB, C, Dz, S, S, g, pad)
     if nbytes <= 0:
         raise _lib.MeshDiffusionHipError("md_pb16_bytes failed")
@@ -73,18 +76,21 @@ def to_pb16(src, B, C, S, mode, up=0, stuff=0, c_src=None, pad=1, zhalo=True):
     return out
 
 
-def wgrad(dy_pb, act_pb, B, co, ci, S, taps, dw, s_row, s_k, s_tap, a_ch=None, b_ch=None):
+def wgrad(dy_pb, act_pb, B, co, ci, S, taps, dw, s_row, s_k, s_tap, a_ch=None, b_ch=None, dims=None, ksplit=None):
     """dw[co*s_row + ci*s_k + tap*s_tap] += sum_{pos,b} dy[co][pos,b] * act[ci][pos + off(tap), b]  (taps = 125, 27 or 1)
-    -- md_wgrad (csrc/wgrad.hip).  a_ch / b_ch: channel counts of the two PB16 tensors when they exceed co / ci."""
+    -- md_wgrad (csrc/wgrad.hip).  a_ch / b_ch: channel counts of the two PB16 tensors when they exceed co / ci.
+    dims: the grid (D, S, S) of to_pb16(dims=...); ksplit: the number of K ranges instead of the one chosen here."""
     lib = _lib.load()
+    D, S = (dims[0], dims[1]) if dims is not None else (S, S)
     g = _guard(S, 2 if taps == 125 else 1)
     a_ch = co if a_ch is None else a_ch
     b_ch = ci if b_ch is None else b_ch
-    zs = zsplit_for(B, S)
-    VB, Dz = B * zs, S // zs
+    zs = zsplit_for(B, D)
+    VB, Dz = B * zs, D // zs
     stages = ((VB + 7) // 8) * Dz * S * ((S + 7) // 8)
     units = ((co + 127) // 128) * ((ci + 127) // 128) * {125: 50, 27: 9, 1: 1}[taps]
-    ksplit = max(1, min(WGRAD_BLOCKS // units, stages // 4))
+    if ksplit is None:
+        ksplit = max(1, min(WGRAD_BLOCKS // units, stages // 4))
     nbytes = lib.md_wgrad_workspace_bytes(co, ci, taps, ksplit)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dy_pb.device)
     check(lib.md_wgrad(_ptr(dy_pb), _ptr(act_pb), _ptr(dw), _ptr(ws), nbytes, VB, a_ch, b_ch, co, ci, Dz, S, S, g, taps,
