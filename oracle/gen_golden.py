@@ -19,6 +19,7 @@ outputs are stored):
   train_grads_trained.npz the same at B = 1 on the adversarial trained-like weights (--only train_trained)
   dataset.npz        reference ShapeNetDMTetDataset items (augmentation on/off) for seeded on-disk grids
   dmtet.npz          reference DMTet.__call__ on the shipped 64-grid: counts, hashes, samples
+  tetgrid.npz        reference DMTet.__call__ on the small synthetic grids of tests/tetgrid_cases.py: counts and hashes
   64_tets_cropped.npz  the tet-grid DATA asset (vertices/indices), copied verbatim
 Every reference result is also compared with the oracle restatement (assert), which is the pin
 that lets the GPU box use the oracle as the checker.
@@ -505,6 +506,42 @@ def gen_dmtet():
     np.savez_compressed(os.path.join(GOLD, "dmtet.npz"), **out)
 
 
+def gen_tetgrid():
+    """tetgrid.npz: the unmodified reference DMTet.__call__ on the small synthetic grids of tests/tetgrid_cases.py (one tet, the
+    chunk- and block-edge lattices, the star), every field of `forward_fields`: counts and SHA-256 of faces, vertices, uv_idx and
+    valid_vert_idx.  The oracle and the numpy restatements of uv_idx / valid_vert_idx are asserted equal to the reference first."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import tetgrid_cases as tc
+    mod = import_ref_dmtet()
+    names, counts, shas = [], [], []
+    with _CudaToCpu():
+        dm = mod.DMTet()
+        for cname in tc.SMALL_CASES:
+            c = tc.case(cname)
+            tets_t = torch.as_tensor(c.tets, dtype=torch.long)
+            for fname, sdf in tc.forward_fields(c).items():
+                key = f"{cname}/{fname}"
+                occ = tc.tet_sign_cases(sdf.numpy(), c.tets)
+                if not ((occ > 0) & (occ < 15)).any():
+                    print(f"[tetgrid] {key}: no surface, not recorded (the reference cannot run on an empty mesh)")
+                    continue
+                v, f, uvs, uv_idx, ftet, vvi = dm(c.pos.clone(), sdf.clone(), tets_t)
+                with np.errstate(all="ignore"):
+                    vo, fo, fto = dmtet_oracle.marching_tets(c.pos.numpy(), sdf.numpy(), c.tets)
+                assert tc.same_mesh((vo, fo, fto), (v.numpy(), f.numpy(), ftet.numpy())), key
+                n1 = int((tc.NUM_TRI[occ] == 1).sum())
+                assert np.array_equal(tc.uv_idx_of(fto, n1, c.T), uv_idx.numpy()), key
+                assert np.array_equal(tc.valid_vert_idx_of(fto, c.tets), vvi.numpy()), key
+                counts.append([v.shape[0], f.shape[0]])
+                shas.append([sha(f.numpy().astype(np.int64)), sha(v.numpy().astype(np.float32)),
+                             sha(uv_idx.numpy().astype(np.int64)), sha(vvi.numpy().astype(np.int64))])
+                names.append(key)
+            print(f"[tetgrid] {cname}: oracle == reference (faces, face_tet, vertex bits, uv_idx, valid_vert_idx) on "
+                  f"{sum(k.startswith(cname + '/') for k in names)} fields")
+    # one row per recorded field `<case>/<field>`: counts (V, F), sha (faces, verts, uv_idx, valid_vert_idx)
+    np.savez_compressed(os.path.join(GOLD, "tetgrid.npz"), fields=np.array(names), counts=np.array(counts), sha=np.array(shas))
+
+
 def train_step_inputs(B, R, seed):
     """Seeded (batch, labels, noise) of one DDPM training step; the GPU test regenerates them and feeds the same
     tensors to the HIP loss function by patching torch.randint / torch.randn_like exactly as done here."""
@@ -632,13 +669,15 @@ def gen_dataset():
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-res64", action="store_true")
-    ap.add_argument("--only", choices=["unet", "dmtet", "dataset", "train", "train_b2", "train_trained", "graded", "ddim", "trained"], default=None)
+    ap.add_argument("--only", choices=["unet", "dmtet", "tetgrid", "dataset", "train", "train_b2", "train_trained", "graded", "ddim", "trained"], default=None)
     ap.add_argument("--graded", default="config1,cond32,res128", help="which graded-size sampler fixtures to (re)generate")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(os.cpu_count())
     if a.only in (None, "dmtet"):
         gen_dmtet()
+    if a.only in (None, "tetgrid"):
+        gen_tetgrid()
     if a.only in (None, "dataset"):
         gen_dataset()
     if a.only in (None, "train"):
