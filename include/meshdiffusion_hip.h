@@ -515,6 +515,7 @@ int md_attn_fwd(const void* qk, const void* vT, void* out, const float* bias_v, 
  *   x_mean = (x - beta/sigma * eps) / sqrt(1-beta);  x = x_mean + sqrt(beta)*z
  *   x, x_mean *= mask[P]   (mask may be NULL)
  * beta/sigma/… are passed per batch element (coef[b][4] = beta, sigma, sqrt(1-beta), sqrt(beta)).
+ * P % 4 == 0; x, eps, z, mask and the outputs 16-byte aligned (coef: 4), else MD_ERR_BAD_ARG.
  */
 int md_ancestral_step(const float* x, const float* eps, const float* z, const float* mask,
                       const float* coef, float* x_out, float* x_mean_out, int32_t batch,
@@ -550,7 +551,8 @@ int md_ddim_step(const double* x, const float* eps, const float* mask, const dou
  *   MD_SDE_EULER_MARUYAMA   : x_mean = x + (c1*x - c2*score)*c3 ; x = x_mean + c4*z
  *                             c1 = -0.5*beta(t), c2 = sqrt(beta(t))^2, c3 = -1/N, c4 = sqrt(beta(t))*sqrt(1/N)
  *   x, x_mean *= mask
- * P % 4 == 0 for all three.
+ * P % 4 == 0 for all three; every state-sized tensor, the mask and the slabs 16-byte aligned (coef, step_out: 4), else
+ * MD_ERR_BAD_ARG.
  */
 #define MD_LANGEVIN_SLABS 64
 #define MD_CORRECTOR_LANGEVIN 0

@@ -1,5 +1,5 @@
-// Small streaming kernels: timestep embedding, dense layers, layout conversion,
-// the DDPM ancestral update and the inpainting blend.
+// Small streaming kernels: timestep embedding, dense layers, layout conversion, attention softmax.
+// The sampler updates (ancestral, DDIM, inpainting) are in sde_steps.hip.
 #include "md_common.h"
 
 // ---- y[b][o] = sum_i act(x[b][i]) * w[o][i] + bias[o]  (nn.Linear; one wave per output) ----
@@ -150,167 +150,6 @@ extern "C" int md_ncdhw_to_f32b(const float* x, float* out, int32_t batch, int32
 }
 extern "C" int md_s16b_to_ncdhw(const void* x, float* out, int32_t batch, int32_t C, int64_t P, void* stream) {
   return relayout(x, out, batch, C, P, 2, stream);
-}
-
-// ---- DDPM ancestral update (reference models/utils.py:191-198, sampling.py:222-230,476-478) ----
-// Same operation order as the reference, no FMA contraction, so that with identical eps/z the
-// update is bit-identical to the PyTorch elementwise chain.
-#pragma clang fp contract(off)
-__global__ void md_ancestral_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
-                                         const float* __restrict__ z, const float* __restrict__ mask,
-                                         const float* __restrict__ coef, float* __restrict__ x_out,
-                                         float* __restrict__ xm_out, int64_t CP, int64_t P) {
-  const int b = blockIdx.y;
-  const float beta = coef[b * 4 + 0], sigma = coef[b * 4 + 1], sq1mb = coef[b * 4 + 2], sqb = coef[b * 4 + 3];
-  const int64_t base = (int64_t)b * CP;
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP;
-       i += (int64_t)gridDim.x * blockDim.x * 4) {
-    const f32x4 xv = *(const f32x4*)(x + base + i);
-    const f32x4 ev = *(const f32x4*)(eps + base + i);
-    const f32x4 zv = *(const f32x4*)(z + base + i);
-    f32x4 mv = {1.f, 1.f, 1.f, 1.f};
-    if (mask) mv = *(const f32x4*)(mask + (i % P));
-    f32x4 xo, xmo;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float score = (-ev[e]) / sigma;
-      const float xm = (xv[e] + beta * score) / sq1mb;
-      const float xn = xm + sqb * zv[e];
-      xo[e] = xn * mv[e];
-      xmo[e] = xm * mv[e];
-    }
-    *(f32x4*)(x_out + base + i) = xo;
-    *(f32x4*)(xm_out + base + i) = xmo;
-  }
-}
-
-extern "C" int md_ancestral_step(const float* x, const float* eps, const float* z, const float* mask,
-                                 const float* coef, float* x_out, float* x_mean_out, int32_t batch,
-                                 int32_t C, int64_t P, void* stream) {
-  if (!x || !eps || !z || !coef || !x_out || !x_mean_out || batch <= 0 || C <= 0 || P <= 0 || (P % 4))
-    return MD_ERR_BAD_ARG;
-  const int64_t CP = (int64_t)C * P;
-  int blocks = (int)((CP / 4 + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_ancestral_step_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0,
-                     (hipStream_t)stream, x, eps, z, mask, coef, x_out, x_mean_out, CP, P);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
-}
-
-// ---- deterministic DDIM update (reference sde_lib.py:113-140 `discretize_ddim`, sampling.py:556-565) ----
-// The reference keeps the state in float64 from the first update on (x.double() arithmetic, float32 only for the U-Net
-// input); so does this kernel.  Same operation order, no FMA contraction:
-//   x0s = x - a2*eps ; sst = x - x0s ; x0_pred = x0s / a1 ; x_new = r1*x + (r2 - r1)*sst   (r1 = a1p/a1, r2 = a2p/a2)
-// then both results times the grid mask, and the optional channel-`ch` inpainting blend v*(1-pm) + partial*pm
-// (sampling.py:562-564).  coef[b] = {a1, a2, r1, r2} as doubles (a1, a2 are float32 table entries widened).
-__global__ void md_ddim_step_kernel(const double* __restrict__ x, const float* __restrict__ eps,
-                                    const float* __restrict__ mask, const double* __restrict__ coef,
-                                    const float* __restrict__ partial, const float* __restrict__ pmask, int ch,
-                                    double* __restrict__ x_out, double* __restrict__ x0_out, float* __restrict__ x_f32,
-                                    int64_t CP, int64_t P) {
-  const int b = blockIdx.y;
-  const double a1 = coef[b * 4 + 0], a2 = coef[b * 4 + 1], r1 = coef[b * 4 + 2], r2 = coef[b * 4 + 3];
-  const double r21 = (-r1) + r2;
-  const int64_t base = (int64_t)b * CP;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < CP; i += (int64_t)gridDim.x * blockDim.x) {
-    const double xv = x[base + i];
-    const double x0s = xv - a2 * (double)eps[base + i];
-    const double sst = xv - x0s;
-    double x0p = x0s / a1;
-    double xn = r1 * xv + r21 * sst;
-    const int64_t pos = i % P;
-    if (mask) { const double m = (double)mask[pos]; xn = xn * m; x0p = x0p * m; }
-    if (partial != nullptr && i / P == ch) {
-      const double pm = (double)pmask[pos], pv = (double)partial[pos];
-      xn = xn * (1.0 - pm) + pv * pm;
-      x0p = x0p * (1.0 - pm) + pv * pm;
-    }
-    x_out[base + i] = xn;
-    x0_out[base + i] = x0p;
-    x_f32[base + i] = (float)xn;
-  }
-}
-
-extern "C" int md_ddim_step(const double* x, const float* eps, const float* mask, const double* coef, const float* partial,
-                            const float* pmask, int32_t ch, double* x_out, double* x0_out, float* x_f32, int32_t batch,
-                            int32_t C, int64_t P, void* stream) {
-  if (!x || !eps || !coef || !x_out || !x0_out || !x_f32 || batch <= 0 || C <= 0 || P <= 0) return MD_ERR_BAD_ARG;
-  if ((partial != nullptr) != (pmask != nullptr) || (partial != nullptr && (ch < 0 || ch >= C))) return MD_ERR_BAD_ARG;
-  const int64_t CP = (int64_t)C * P;
-  int blocks = (int)((CP + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_ddim_step_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, eps,
-                     mask, coef, partial, pmask, ch, x_out, x0_out, x_f32, CP, P);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
-}
-
-// ---- inpainting blend of one channel (reference sampling.py:455-466) -----------------------
-__global__ void md_inpaint_blend_kernel(float* __restrict__ x, const float* __restrict__ src,
-                                        const float* __restrict__ pmask, const float* __restrict__ gmask,
-                                        int C, int ch, int64_t P, int64_t src_bstride) {
-  const int b = blockIdx.y;
-  float* xc = x + ((int64_t)b * C + ch) * P;
-  const float* sc = src + (int64_t)b * src_bstride;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x) {
-    const float m = pmask[i];
-    float v = xc[i] * (1.f - m) + sc[i] * m;
-    if (gmask) v = v * gmask[i];
-    xc[i] = v;
-  }
-}
-
-// re-noise the conditioned channel to level t (reference sampling.py:460-466):
-//   upd = mean_coef[b]*x + std[b]*z ;  x = (x*(1-m) + upd*m)*gm ;  x_mean[ch] = x[ch]
-__global__ void md_inpaint_renoise_kernel(float* __restrict__ x, float* __restrict__ x_mean,
-                                          const float* __restrict__ z, const float* __restrict__ pmask,
-                                          const float* __restrict__ gmask, const float* __restrict__ coef,
-                                          int C, int ch, int64_t P) {
-  const int b = blockIdx.y;
-  const float mc = coef[b * 2 + 0], sd = coef[b * 2 + 1];
-  float* xc = x + ((int64_t)b * C + ch) * P;
-  float* xm = x_mean ? x_mean + ((int64_t)b * C + ch) * P : nullptr;
-  const float* zc = z + (int64_t)b * P;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x) {
-    const float m = pmask[i];
-    const float xv = xc[i];
-    const float mean = mc * xv;
-    const float upd = mean + sd * zc[i];
-    float v = xv * (1.f - m) + upd * m;
-    if (gmask) v = v * gmask[i];
-    xc[i] = v;
-    if (xm) xm[i] = v;
-  }
-}
-#pragma clang fp contract(fast)
-
-extern "C" int md_inpaint_blend(float* x, const float* src, const float* pmask, const float* gmask,
-                                int32_t batch, int32_t C, int32_t ch, int64_t P, int64_t src_bstride,
-                                void* stream) {
-  if (!x || !src || !pmask || batch <= 0 || C <= 0 || ch < 0 || ch >= C || P <= 0) return MD_ERR_BAD_ARG;
-  int blocks = (int)((P + 255) / 256);
-  if (blocks > 1024) blocks = 1024;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_inpaint_blend_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0,
-                     (hipStream_t)stream, x, src, pmask, gmask, C, ch, P, src_bstride);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
-}
-
-extern "C" int md_inpaint_renoise(float* x, float* x_mean, const float* z, const float* pmask,
-                                  const float* gmask, const float* coef, int32_t batch, int32_t C,
-                                  int32_t ch, int64_t P, void* stream) {
-  if (!x || !z || !pmask || !coef || batch <= 0 || C <= 0 || ch < 0 || ch >= C || P <= 0) return MD_ERR_BAD_ARG;
-  int blocks = (int)((P + 255) / 256);
-  if (blocks > 1024) blocks = 1024;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_inpaint_renoise_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0,
-                     (hipStream_t)stream, x, x_mean, z, pmask, gmask, coef, C, ch, P);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
 }
 
 // ---- attention softmax over keys (reference layers.py:603-605) -------------------------------

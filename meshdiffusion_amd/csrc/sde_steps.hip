@@ -1,13 +1,198 @@
-// Predictor-corrector sampling updates other than the ancestral one (reference lib/diffusion/sampling.py:185-210
-// predictors, :259-321 correctors, sde_lib.py:83-111 reverse SDE, :198-232 VPSDE).  All NCDHW fp32 [B][C][P]; the
-// per-sample coefficients come from the host, built once per sampler with the reference's float32 torch expressions.
-// Same operation order as the reference, no FMA contraction: with identical eps / z the updates are bit-identical to the
-// PyTorch elementwise chains.
+// Every sampler update: the DDPM ancestral step, the DDIM step and the inpainting blend / re-noise, the predictor-corrector
+// updates (reference lib/diffusion/sampling.py:185-210 predictors, :259-321 correctors, sde_lib.py:83-111 reverse SDE, :198-232
+// VPSDE), the probability-flow right-hand side, reconstruction guidance and the DPM-Solver++ multistep update.  All NCDHW
+// [B][C][P]; the per-sample coefficients come from the host, built once per sampler with the reference's torch expressions.
+// Same operation order as the reference, no FMA contraction anywhere in this file: with identical eps / z the float32 updates
+// are bit-identical to the PyTorch elementwise chains.
+// An export refuses, in this order: null or misaligned pointers (16 bytes where the kernel moves four floats or two doubles at
+// a time, the element size elsewhere), sizes and scalars, aliasing.
 #include "md_args.h"
 
 #pragma clang fp contract(off)
 
 typedef __attribute__((ext_vector_type(2))) double f64x2;
+typedef __attribute__((ext_vector_type(4))) double f64x4;
+
+// ---- device vocabulary ----------------------------------------------------------------------------------------------
+// grid-stride loops over [0, n) of one sample (blockIdx.y picks the sample): four values or one value per thread and trip
+#define MD_STREAM4(i, CP) \
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4)
+#define MD_STREAM1(i, n) \
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+
+// four values at a 16-byte aligned address: one f32x4, or a pair of f64x2
+static __device__ __forceinline__ f32x4 md_load4(const float* p) { return *(const f32x4*)p; }
+static __device__ __forceinline__ void md_store4(float* p, f32x4 v) { *(f32x4*)p = v; }
+static __device__ __forceinline__ f64x4 md_load4(const double* p) {
+  const f64x2 a = *(const f64x2*)p, c = *(const f64x2*)(p + 2);
+  return f64x4{a[0], a[1], c[0], c[1]};
+}
+static __device__ __forceinline__ void md_store4(double* p, f64x4 v) {
+  *(f64x2*)p = f64x2{v[0], v[1]};
+  *(f64x2*)(p + 2) = f64x2{v[2], v[3]};
+}
+// the optional grid mask at `pos`: ones without one
+static __device__ __forceinline__ f32x4 md_mask4(const float* mask, int64_t pos) {
+  f32x4 mv = {1.f, 1.f, 1.f, 1.f};
+  if (mask) mv = md_load4(mask + pos);
+  return mv;
+}
+
+// wave64 xor butterfly over the offsets 32, 16, ..., 1: every lane ends with the same bits
+template <int N>
+static __device__ __forceinline__ void md_wave_sum(double (&v)[N]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += __shfl_xor(v[k], o, 64);
+  }
+}
+
+// N sums over a workgroup of 256 in a fixed order: butterfly, one LDS word per wave, (r0 + r1) + (r2 + r3).  True in
+// thread 0 only, which then holds the sums in v.  The order of these additions is what makes the slabs reproducible.
+template <int N>
+static __device__ __forceinline__ bool md_block_sum(double (&v)[N]) {
+  md_wave_sum(v);
+  __shared__ double red[N][4];
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) red[k][threadIdx.x >> 6] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return false;
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+  return true;
+}
+
+// ---- host vocabulary ------------------------------------------------------------------------------------------------
+// the sizes of a [batch][C][P] state; four_wide: the kernel moves four values at a time, which must not straddle two channels
+static bool md_bad_dims(int32_t batch, int32_t C, int64_t P, bool four_wide) {
+  return batch <= 0 || C <= 0 || P <= 0 || (four_wide && (P % 4));
+}
+
+// workgroups of 256 threads for `threads` of them, at most `cap`
+static unsigned md_grid_x(int64_t threads, int64_t cap) {
+  const int64_t blocks = (threads + 255) / 256;
+  return (unsigned)(blocks < cap ? blocks : cap);
+}
+// one workgroup per 1024 values, at most 1024 workgroups in all (B*S <= 1024 keeps the slab prologue's L2 reads small)
+static unsigned stream_blocks(int64_t CP, int batch) { return md_grid_x(CP / 4, batch >= 1024 ? 1 : 1024 / batch); }
+
+struct md_span { const void* p; int64_t n; };       // n bytes at p; null: an absent operand
+static bool md_overlap(const md_span& a, const md_span& b) {
+  const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
+  return a.p && b.p && pa < pb + (uintptr_t)b.n && pb < pa + (uintptr_t)a.n;
+}
+// an output shares memory with an input or with another output
+template <int NO, int NI>
+static bool md_any_alias(const md_span (&out)[NO], const md_span (&in)[NI]) {
+  for (int o = 0; o < NO; ++o) {
+    for (const md_span& i : in)
+      if (md_overlap(out[o], i)) return true;
+    for (int q = o + 1; q < NO; ++q)
+      if (md_overlap(out[o], out[q])) return true;
+  }
+  return false;
+}
+
+// ---- DDPM ancestral update (reference models/utils.py:191-198, sampling.py:222-230,476-478) ----
+__global__ void md_ancestral_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                         const float* __restrict__ z, const float* __restrict__ mask,
+                                         const float* __restrict__ coef, float* __restrict__ x_out,
+                                         float* __restrict__ xm_out, int64_t CP, int64_t P) {
+  const int b = blockIdx.y;
+  const float beta = coef[b * 4 + 0], sigma = coef[b * 4 + 1], sq1mb = coef[b * 4 + 2], sqb = coef[b * 4 + 3];
+  const int64_t base = (int64_t)b * CP;
+  MD_STREAM4(i, CP) {
+    const f32x4 xv = md_load4(x + base + i), ev = md_load4(eps + base + i), zv = md_load4(z + base + i);
+    const f32x4 mv = md_mask4(mask, i % P);
+    f32x4 xo, xmo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float score = (-ev[e]) / sigma;
+      const float xm = (xv[e] + beta * score) / sq1mb;
+      const float xn = xm + sqb * zv[e];
+      xo[e] = xn * mv[e];
+      xmo[e] = xm * mv[e];
+    }
+    md_store4(x_out + base + i, xo);
+    md_store4(xm_out + base + i, xmo);
+  }
+}
+
+// ---- deterministic DDIM update (reference sde_lib.py:113-140 `discretize_ddim`, sampling.py:556-565) ----
+// The reference keeps the state in float64 from the first update on (x.double() arithmetic, float32 only for the U-Net
+// input); so does this kernel.  Same operation order:
+//   x0s = x - a2*eps ; sst = x - x0s ; x0_pred = x0s / a1 ; x_new = r1*x + (r2 - r1)*sst   (r1 = a1p/a1, r2 = a2p/a2)
+// then both results times the grid mask, and the optional channel-`ch` inpainting blend v*(1-pm) + partial*pm
+// (sampling.py:562-564).  coef[b] = {a1, a2, r1, r2} as doubles (a1, a2 are float32 table entries widened).
+// One value per thread and trip: P need not be a multiple of four.
+__global__ void md_ddim_step_kernel(const double* __restrict__ x, const float* __restrict__ eps,
+                                    const float* __restrict__ mask, const double* __restrict__ coef,
+                                    const float* __restrict__ partial, const float* __restrict__ pmask, int ch,
+                                    double* __restrict__ x_out, double* __restrict__ x0_out, float* __restrict__ x_f32,
+                                    int64_t CP, int64_t P) {
+  const int b = blockIdx.y;
+  const double a1 = coef[b * 4 + 0], a2 = coef[b * 4 + 1], r1 = coef[b * 4 + 2], r2 = coef[b * 4 + 3];
+  const double r21 = (-r1) + r2;
+  const int64_t base = (int64_t)b * CP;
+  MD_STREAM1(i, CP) {
+    const double xv = x[base + i];
+    const double x0s = xv - a2 * (double)eps[base + i];
+    const double sst = xv - x0s;
+    double x0p = x0s / a1;
+    double xn = r1 * xv + r21 * sst;
+    const int64_t pos = i % P;
+    if (mask) { const double m = (double)mask[pos]; xn = xn * m; x0p = x0p * m; }
+    if (partial != nullptr && i / P == ch) {
+      const double pm = (double)pmask[pos], pv = (double)partial[pos];
+      xn = xn * (1.0 - pm) + pv * pm;
+      x0p = x0p * (1.0 - pm) + pv * pm;
+    }
+    x_out[base + i] = xn;
+    x0_out[base + i] = x0p;
+    x_f32[base + i] = (float)xn;
+  }
+}
+
+// ---- inpainting blend of one channel (reference sampling.py:455-466), scalar: any P ----------------------------------
+__global__ void md_inpaint_blend_kernel(float* __restrict__ x, const float* __restrict__ src,
+                                        const float* __restrict__ pmask, const float* __restrict__ gmask,
+                                        int C, int ch, int64_t P, int64_t src_bstride) {
+  const int b = blockIdx.y;
+  float* xc = x + ((int64_t)b * C + ch) * P;
+  const float* sc = src + (int64_t)b * src_bstride;
+  MD_STREAM1(i, P) {
+    const float m = pmask[i];
+    float v = xc[i] * (1.f - m) + sc[i] * m;
+    if (gmask) v = v * gmask[i];
+    xc[i] = v;
+  }
+}
+
+// re-noise the conditioned channel to level t (reference sampling.py:460-466):
+//   upd = mean_coef[b]*x + std[b]*z ;  x = (x*(1-m) + upd*m)*gm ;  x_mean[ch] = x[ch]
+__global__ void md_inpaint_renoise_kernel(float* __restrict__ x, float* __restrict__ x_mean,
+                                          const float* __restrict__ z, const float* __restrict__ pmask,
+                                          const float* __restrict__ gmask, const float* __restrict__ coef,
+                                          int C, int ch, int64_t P) {
+  const int b = blockIdx.y;
+  const float mc = coef[b * 2 + 0], sd = coef[b * 2 + 1];
+  float* xc = x + ((int64_t)b * C + ch) * P;
+  float* xm = x_mean ? x_mean + ((int64_t)b * C + ch) * P : nullptr;
+  const float* zc = z + (int64_t)b * P;
+  MD_STREAM1(i, P) {
+    const float m = pmask[i];
+    const float xv = xc[i];
+    const float mean = mc * xv;
+    const float upd = mean + sd * zc[i];
+    float v = xv * (1.f - m) + upd * m;
+    if (gmask) v = v * gmask[i];
+    xc[i] = v;
+    if (xm) xm[i] = v;
+  }
+}
 
 // ---- Langevin corrector, launch 1: per-workgroup partial sums of eps^2 and z^2 ---------------------------------
 // grid (MD_LANGEVIN_SLABS, B): workgroup (s, b) writes slabs[b][s] = {sum eps^2, sum z^2} over its strided share of
@@ -18,29 +203,13 @@ __global__ __launch_bounds__(256) void md_langevin_norms_kernel(const float* __r
   const int64_t base = (int64_t)b * CP;
   double ae = 0.0, az = 0.0;
 #pragma unroll 4
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    const f32x4 ev = *(const f32x4*)(eps + base + i);
-    const f32x4 zv = *(const f32x4*)(z + base + i);
+  MD_STREAM4(i, CP) {
+    const f32x4 ev = md_load4(eps + base + i), zv = md_load4(z + base + i);
     ae += (double)(ev[0] * ev[0] + ev[1] * ev[1]) + (double)(ev[2] * ev[2] + ev[3] * ev[3]);
     az += (double)(zv[0] * zv[0] + zv[1] * zv[1]) + (double)(zv[2] * zv[2] + zv[3] * zv[3]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ae += __shfl_xor(ae, o, 64);
-    az += __shfl_xor(az, o, 64);
-  }
-  __shared__ double red[2][4];
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = ae;
-    red[1][threadIdx.x >> 6] = az;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    f64x2 v;
-    v[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    v[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    *(f64x2*)(slabs + ((int64_t)b * MD_LANGEVIN_SLABS + blockIdx.x) * 2) = v;
-  }
+  double acc[2] = {ae, az};
+  if (md_block_sum(acc)) *(f64x2*)(slabs + ((int64_t)b * MD_LANGEVIN_SLABS + blockIdx.x) * 2) = f64x2{acc[0], acc[1]};
 }
 
 // ---- Langevin / ALD corrector, launch 2 ---------------------------------------------------------------------------
@@ -68,14 +237,10 @@ __global__ __launch_bounds__(256) void md_langevin_step_kernel(const float* __re
       double gsum = 0.0, nsum = 0.0;
       for (int bb = 0; bb < B; ++bb) {
         const f64x2 v = *(const f64x2*)(slabs + ((int64_t)bb * MD_LANGEVIN_SLABS + lane) * 2);
-        double se = v[0], sz = v[1];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          se += __shfl_xor(se, o, 64);
-          sz += __shfl_xor(sz, o, 64);
-        }
-        gsum += sqrt(se) / (double)coef[bb * 3 + 0];
-        nsum += sqrt(sz);
+        double s[2] = {v[0], v[1]};
+        md_wave_sum(s);
+        gsum += sqrt(s[0]) / (double)coef[bb * 3 + 0];
+        nsum += sqrt(s[1]);
       }
       const float grad_norm = (float)(gsum / (double)B), noise_norm = (float)(nsum / (double)B);
       const float r = (snr * noise_norm) / grad_norm;
@@ -93,12 +258,9 @@ __global__ __launch_bounds__(256) void md_langevin_step_kernel(const float* __re
   const float sigma = coef[b * 3 + 0];
   const float sq = sqrtf(step * 2.f);
   const int64_t base = (int64_t)b * CP;
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    const f32x4 xv = *(const f32x4*)(x + base + i);
-    const f32x4 ev = *(const f32x4*)(eps + base + i);
-    const f32x4 zv = *(const f32x4*)(z + base + i);
-    f32x4 mv = {1.f, 1.f, 1.f, 1.f};
-    if (mask) mv = *(const f32x4*)(mask + (i % P));
+  MD_STREAM4(i, CP) {
+    const f32x4 xv = md_load4(x + base + i), ev = md_load4(eps + base + i), zv = md_load4(z + base + i);
+    const f32x4 mv = md_mask4(mask, i % P);
     f32x4 xo, xmo;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -108,8 +270,8 @@ __global__ __launch_bounds__(256) void md_langevin_step_kernel(const float* __re
       xo[e] = xn * mv[e];
       xmo[e] = xm * mv[e];
     }
-    *(f32x4*)(x_out + base + i) = xo;
-    *(f32x4*)(xm_out + base + i) = xmo;
+    md_store4(x_out + base + i, xo);
+    md_store4(xm_out + base + i, xmo);
   }
 }
 
@@ -129,12 +291,9 @@ __global__ __launch_bounds__(256) void md_sde_step_kernel(const float* __restric
   const int b = blockIdx.y;
   const float sigma = coef[b * 5 + 0], c1 = coef[b * 5 + 1], c2 = coef[b * 5 + 2], c3 = coef[b * 5 + 3], c4 = coef[b * 5 + 4];
   const int64_t base = (int64_t)b * CP;
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    const f32x4 xv = *(const f32x4*)(x + base + i);
-    const f32x4 ev = *(const f32x4*)(eps + base + i);
-    const f32x4 zv = *(const f32x4*)(z + base + i);
-    f32x4 mv = {1.f, 1.f, 1.f, 1.f};
-    if (mask) mv = *(const f32x4*)(mask + (i % P));
+  MD_STREAM4(i, CP) {
+    const f32x4 xv = md_load4(x + base + i), ev = md_load4(eps + base + i), zv = md_load4(z + base + i);
+    const f32x4 mv = md_mask4(mask, i % P);
     f32x4 xo, xmo;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -152,8 +311,8 @@ __global__ __launch_bounds__(256) void md_sde_step_kernel(const float* __restric
       xo[e] = xn * mv[e];
       xmo[e] = xm * mv[e];
     }
-    *(f32x4*)(x_out + base + i) = xo;
-    *(f32x4*)(xm_out + base + i) = xmo;
+    md_store4(x_out + base + i, xo);
+    md_store4(xm_out + base + i, xmo);
   }
 }
 
@@ -171,32 +330,24 @@ __global__ __launch_bounds__(256) void md_pf_ode_rhs_kernel(const float* __restr
   const int b = blockIdx.y;
   const double cx = coef[b * 2 + 0], ce = coef[b * 2 + 1];
   const int64_t base = (int64_t)b * CP;
-  double acc = 0.0;
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    const f32x4 xv = *(const f32x4*)(x + base + i);
-    const f32x4 ev = *(const f32x4*)(eps + base + i);
-    f32x4 mv = {1.f, 1.f, 1.f, 1.f};
-    if (mask) mv = *(const f32x4*)(mask + (i % P));
+  double acc[1] = {0.0};
+  MD_STREAM4(i, CP) {
+    const f32x4 xv = md_load4(x + base + i), ev = md_load4(eps + base + i);
+    const f32x4 mv = md_mask4(mask, i % P);
     f32x4 dv;
 #pragma unroll
     for (int e = 0; e < 4; ++e) dv[e] = (float)((cx * (double)xv[e] + ce * (double)ev[e]) * (double)mv[e]);
-    *(f32x4*)(drift + base + i) = dv;
+    md_store4(drift + base + i, dv);
     if constexpr (DIV) {
-      const f32x4 gv = *(const f32x4*)(g + base + i);
-      const f32x4 pv = *(const f32x4*)(probe + base + i);
+      const f32x4 gv = md_load4(g + base + i), pv = md_load4(probe + base + i);
       double t[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) t[e] = ((double)pv[e] * (cx * (double)pv[e] + ce * (double)gv[e])) * (double)mv[e];
-      acc += (t[0] + t[1]) + (t[2] + t[3]);
+      acc[0] += (t[0] + t[1]) + (t[2] + t[3]);
     }
   }
   if constexpr (DIV) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    __shared__ double red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) slabs[(int64_t)b * MD_LANGEVIN_SLABS + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (md_block_sum(acc)) slabs[(int64_t)b * MD_LANGEVIN_SLABS + blockIdx.x] = acc[0];
   }
 }
 
@@ -213,17 +364,14 @@ __global__ __launch_bounds__(256) void md_guide_residual_kernel(const float* __r
   const int b = blockIdx.y;
   const double alpha = coef[b * 2 + 0], sigma = coef[b * 2 + 1];
   const int64_t base = (int64_t)b * CP, lo = (int64_t)ch * P, hi = lo + P;
-  double acc = 0.0;
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
+  double acc[1] = {0.0};
+  MD_STREAM4(i, CP) {
     f32x4 rv = {0.f, 0.f, 0.f, 0.f};
     if (i >= lo && i < hi) {                    // P % 4 == 0: four values never straddle two channels
       const int64_t p = i - lo;
-      const f32x4 xv = *(const f32x4*)(x + base + i);
-      const f32x4 ev = *(const f32x4*)(eps + base + i);
-      const f32x4 yv = *(const f32x4*)(src + (int64_t)b * src_bstride + p);
-      const f32x4 pv = *(const f32x4*)(pmask + p);
-      f32x4 mv = {1.f, 1.f, 1.f, 1.f};
-      if (gmask) mv = *(const f32x4*)(gmask + p);
+      const f32x4 xv = md_load4(x + base + i), ev = md_load4(eps + base + i);
+      const f32x4 yv = md_load4(src + (int64_t)b * src_bstride + p), pv = md_load4(pmask + p);
+      const f32x4 mv = md_mask4(gmask, p);
       double t[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -231,16 +379,11 @@ __global__ __launch_bounds__(256) void md_guide_residual_kernel(const float* __r
         rv[e] = (float)(((double)pv[e] * (double)mv[e]) * (x0 - (double)yv[e]));
         t[e] = (double)rv[e] * (double)rv[e];
       }
-      acc += (t[0] + t[1]) + (t[2] + t[3]);
+      acc[0] += (t[0] + t[1]) + (t[2] + t[3]);
     }
-    *(f32x4*)(cot + base + i) = rv;
+    md_store4(cot + base + i, rv);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  __shared__ double red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) slabs[(int64_t)b * MD_LANGEVIN_SLABS + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if (md_block_sum(acc)) slabs[(int64_t)b * MD_LANGEVIN_SLABS + blockIdx.x] = acc[0];
 }
 
 // launch 2, in place: coef[b] = {alpha, sigma, zeta} as doubles.  Prologue: n_b = sqrt(slabs[b][0] + slabs[b][1] + ...) in
@@ -267,36 +410,30 @@ __global__ __launch_bounds__(256) void md_guide_apply_kernel(void* __restrict__ 
   __syncthreads();
   const double k = s_k, sigma = coef[b * 3 + 1];
   const int64_t base = (int64_t)b * CP;
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    const f32x4 cv = *(const f32x4*)(cot + base + i);
-    const f32x4 gv = *(const f32x4*)(g + base + i);
-    f32x4 mv = {1.f, 1.f, 1.f, 1.f};
-    if (gmask) mv = *(const f32x4*)(gmask + (i % P));
+  MD_STREAM4(i, CP) {
+    const f32x4 cv = md_load4(cot + base + i), gv = md_load4(g + base + i);
+    const f32x4 mv = md_mask4(gmask, i % P);
     double d[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) d[e] = (k * ((double)cv[e] - sigma * (double)gv[e])) * (double)mv[e];
     if constexpr (F64) {
       double* x64 = (double*)state + base + i;
-      f64x2 a = *(const f64x2*)x64, c = *(const f64x2*)(x64 + 2);
-      a[0] -= d[0];
-      a[1] -= d[1];
-      c[0] -= d[2];
-      c[1] -= d[3];
-      *(f64x2*)x64 = a;
-      *(f64x2*)(x64 + 2) = c;
-      const f32x4 xo = {(float)a[0], (float)a[1], (float)c[0], (float)c[1]};
-      *(f32x4*)(aux + base + i) = xo;
+      f64x4 xv = md_load4(x64);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xv[e] -= d[e];
+      md_store4(x64, xv);
+      md_store4(aux + base + i, f32x4{(float)xv[0], (float)xv[1], (float)xv[2], (float)xv[3]});
     } else {
       float* x32 = (float*)state + base + i;
-      f32x4 xv = *(const f32x4*)x32;
+      f32x4 xv = md_load4(x32);
 #pragma unroll
       for (int e = 0; e < 4; ++e) xv[e] -= (float)d[e];
-      *(f32x4*)x32 = xv;
+      md_store4(x32, xv);
       if (aux) {
-        f32x4 xm = *(const f32x4*)(aux + base + i);
+        f32x4 xm = md_load4(aux + base + i);
 #pragma unroll
         for (int e = 0; e < 4; ++e) xm[e] -= (float)d[e];
-        *(f32x4*)(aux + base + i) = xm;
+        md_store4(aux + base + i, xm);
       }
     }
   }
@@ -304,7 +441,7 @@ __global__ __launch_bounds__(256) void md_guide_apply_kernel(void* __restrict__ 
 
 // ---- multistep exponential-integrator update (DPM-Solver++, Lu et al. 2022; ODE and SDE variants), one launch ----------------
 // coef[b] = {alpha_s, sigma_s, c_x, c_0, c_1, c_2, c_z, unused} as doubles, formed by the host from the half-log-SNR of the two
-// levels (sampling.dpmpp_tables).  Everything in double, in this order, no FMA contraction:
+// levels (sampling.dpmpp_tables).  Everything in double, in this order:
 //   x0 = (x - sigma_s*eps)/alpha_s ; x_new = c_x*x + c_0*x0 [+ c_1*h1] [+ c_2*h2] [+ c_z*z]    (added left to right)
 // then both times the grid mask, then on channel `ch` the replacement v*(1-pm) + partial*pm: the order of md_ddim_step.
 // x0 enters x_new as formed, before the mask; x0_out is the masked and replaced one, which the caller keeps as h1 / h2.
@@ -322,35 +459,33 @@ __global__ __launch_bounds__(256) void md_multistep_step_kernel(const double* __
   const double* row = coef + (int64_t)b * 8;
   const double alpha = row[0], sigma = row[1], cx = row[2], c0 = row[3], c1 = row[4], c2 = row[5], cz = row[6];
   const int64_t base = (int64_t)b * CP, lo = (int64_t)ch * P, hi = lo + P;
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < CP; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    const f64x2 xa = *(const f64x2*)(x + base + i), xb = *(const f64x2*)(x + base + i + 2);
-    const f32x4 ev = *(const f32x4*)(eps + base + i);
-    double xv[4] = {xa[0], xa[1], xb[0], xb[1]}, xn[4], x0[4];
+  MD_STREAM4(i, CP) {
+    const f64x4 xv = md_load4(x + base + i);
+    const f32x4 ev = md_load4(eps + base + i);
+    f64x4 xn, x0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       x0[e] = (xv[e] - sigma * (double)ev[e]) / alpha;
       xn[e] = cx * xv[e] + c0 * x0[e];
     }
     if constexpr (NH >= 1) {
-      const f64x2 a = *(const f64x2*)(h1 + base + i), c = *(const f64x2*)(h1 + base + i + 2);
-      const double hv[4] = {a[0], a[1], c[0], c[1]};
+      const f64x4 hv = md_load4(h1 + base + i);
 #pragma unroll
       for (int e = 0; e < 4; ++e) xn[e] = xn[e] + c1 * hv[e];
     }
     if constexpr (NH >= 2) {
-      const f64x2 a = *(const f64x2*)(h2 + base + i), c = *(const f64x2*)(h2 + base + i + 2);
-      const double hv[4] = {a[0], a[1], c[0], c[1]};
+      const f64x4 hv = md_load4(h2 + base + i);
 #pragma unroll
       for (int e = 0; e < 4; ++e) xn[e] = xn[e] + c2 * hv[e];
     }
     if constexpr (Z) {
-      const f32x4 zv = *(const f32x4*)(z + base + i);
+      const f32x4 zv = md_load4(z + base + i);
 #pragma unroll
       for (int e = 0; e < 4; ++e) xn[e] = xn[e] + cz * (double)zv[e];
     }
     const int64_t pos = i % P;                  // P % 4 == 0: four values never straddle two channels
     if constexpr (MASK) {
-      const f32x4 mv = *(const f32x4*)(mask + pos);
+      const f32x4 mv = md_load4(mask + pos);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         xn[e] = xn[e] * (double)mv[e];
@@ -359,7 +494,7 @@ __global__ __launch_bounds__(256) void md_multistep_step_kernel(const double* __
     }
     if constexpr (REP) {
       if (i >= lo && i < hi) {
-        const f32x4 pm = *(const f32x4*)(pmask + pos), pv = *(const f32x4*)(partial + pos);
+        const f32x4 pm = md_load4(pmask + pos), pv = md_load4(partial + pos);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const double m = (double)pm[e], v = (double)pv[e];
@@ -368,59 +503,88 @@ __global__ __launch_bounds__(256) void md_multistep_step_kernel(const double* __
         }
       }
     }
-    const f64x2 na = {xn[0], xn[1]}, nb = {xn[2], xn[3]}, pa = {x0[0], x0[1]}, pb = {x0[2], x0[3]};
-    *(f64x2*)(x_out + base + i) = na;
-    *(f64x2*)(x_out + base + i + 2) = nb;
-    *(f64x2*)(x0_out + base + i) = pa;
-    *(f64x2*)(x0_out + base + i + 2) = pb;
-    const f32x4 xo = {(float)xn[0], (float)xn[1], (float)xn[2], (float)xn[3]};
-    *(f32x4*)(x_f32 + base + i) = xo;
+    md_store4(x_out + base + i, xn);
+    md_store4(x0_out + base + i, x0);
+    md_store4(x_f32 + base + i, f32x4{(float)xn[0], (float)xn[1], (float)xn[2], (float)xn[3]});
   }
 }
 
-// one workgroup per 1024 values, at most 1024 workgroups in all (B*S <= 1024 keeps the slab prologue's L2 reads small)
-static int stream_blocks(int64_t CP, int batch) {
-  int64_t blocks = (CP / 4 + 255) / 256;
-  const int64_t cap = batch >= 1024 ? 1 : 1024 / batch;
-  return (int)(blocks < cap ? blocks : cap);
+// ---- exports ------------------------------------------------------------------------------------------------------------
+// The tail of an export: one launch of 256-thread workgroups on `stream`, the export's last parameter.
+#define MD_LAUNCH_STEP(kernel, grid, ...)                                                       \
+  do {                                                                                          \
+    MD_HIP_CLEAR_ERROR();                                                                       \
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);           \
+    MD_HIP_CHECK_LAUNCH();                                                                      \
+    return MD_OK;                                                                               \
+  } while (0)
+
+extern "C" int md_ancestral_step(const float* x, const float* eps, const float* z, const float* mask,
+                                 const float* coef, float* x_out, float* x_mean_out, int32_t batch,
+                                 int32_t C, int64_t P, void* stream) {
+  if (md_any_bad<16>(x, eps, z, x_out, x_mean_out) || md_any_bad<4>(coef) || md_any_misaligned<16>(mask)) return MD_ERR_BAD_ARG;
+  if (md_bad_dims(batch, C, P, true)) return MD_ERR_BAD_ARG;
+  const int64_t CP = (int64_t)C * P;
+  MD_LAUNCH_STEP(md_ancestral_step_kernel, dim3(md_grid_x(CP / 4, 2048), (unsigned)batch), x, eps, z, mask, coef, x_out,
+                 x_mean_out, CP, P);
+}
+
+extern "C" int md_ddim_step(const double* x, const float* eps, const float* mask, const double* coef, const float* partial,
+                            const float* pmask, int32_t ch, double* x_out, double* x0_out, float* x_f32, int32_t batch,
+                            int32_t C, int64_t P, void* stream) {
+  if (md_any_bad<8>(x, coef, x_out, x0_out) || md_any_bad<4>(eps, x_f32) || md_any_misaligned<4>(mask, partial, pmask))
+    return MD_ERR_BAD_ARG;
+  if (md_bad_dims(batch, C, P, false)) return MD_ERR_BAD_ARG;
+  if ((partial != nullptr) != (pmask != nullptr) || (partial != nullptr && (ch < 0 || ch >= C))) return MD_ERR_BAD_ARG;
+  const int64_t CP = (int64_t)C * P;
+  MD_LAUNCH_STEP(md_ddim_step_kernel, dim3(md_grid_x(CP, 4096), (unsigned)batch), x, eps, mask, coef, partial, pmask, ch, x_out,
+                 x0_out, x_f32, CP, P);
+}
+
+extern "C" int md_inpaint_blend(float* x, const float* src, const float* pmask, const float* gmask,
+                                int32_t batch, int32_t C, int32_t ch, int64_t P, int64_t src_bstride,
+                                void* stream) {
+  if (md_any_bad<4>(x, src, pmask) || md_any_misaligned<4>(gmask)) return MD_ERR_BAD_ARG;
+  if (md_bad_dims(batch, C, P, false) || ch < 0 || ch >= C) return MD_ERR_BAD_ARG;
+  MD_LAUNCH_STEP(md_inpaint_blend_kernel, dim3(md_grid_x(P, 1024), (unsigned)batch), x, src, pmask, gmask, C, ch, P, src_bstride);
+}
+
+extern "C" int md_inpaint_renoise(float* x, float* x_mean, const float* z, const float* pmask,
+                                  const float* gmask, const float* coef, int32_t batch, int32_t C,
+                                  int32_t ch, int64_t P, void* stream) {
+  if (md_any_bad<4>(x, z, pmask, coef) || md_any_misaligned<4>(x_mean, gmask)) return MD_ERR_BAD_ARG;
+  if (md_bad_dims(batch, C, P, false) || ch < 0 || ch >= C) return MD_ERR_BAD_ARG;
+  MD_LAUNCH_STEP(md_inpaint_renoise_kernel, dim3(md_grid_x(P, 1024), (unsigned)batch), x, x_mean, z, pmask, gmask, coef, C, ch, P);
 }
 
 extern "C" int md_langevin_norms(const float* eps, const float* z, int32_t batch, int32_t C, int64_t P, double* slabs,
                                  void* stream) {
-  if (!eps || !z || !slabs || batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_langevin_norms_kernel, dim3(MD_LANGEVIN_SLABS, (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
-                     eps, z, slabs, (int64_t)C * P);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  if (md_any_bad<16>(eps, z, slabs)) return MD_ERR_BAD_ARG;
+  if (md_bad_dims(batch, C, P, true)) return MD_ERR_BAD_ARG;
+  MD_LAUNCH_STEP(md_langevin_norms_kernel, dim3(MD_LANGEVIN_SLABS, (unsigned)batch), eps, z, slabs, (int64_t)C * P);
 }
 
 extern "C" int md_langevin_step(const float* x, const float* eps, const float* z, const float* mask, const float* coef,
                                 const double* slabs, float snr, int32_t mode, float* x_out, float* x_mean_out,
                                 float* step_out, int32_t batch, int32_t C, int64_t P, void* stream) {
-  if (!x || !eps || !z || !coef || !x_out || !x_mean_out || !step_out || batch <= 0 || C <= 0 || P <= 0 || (P % 4))
+  if (md_any_bad<16>(x, eps, z, x_out, x_mean_out) || md_any_bad<4>(coef, step_out) || md_any_misaligned<16>(mask, slabs))
     return MD_ERR_BAD_ARG;
+  if (md_bad_dims(batch, C, P, true)) return MD_ERR_BAD_ARG;
   if (mode != MD_CORRECTOR_LANGEVIN && mode != MD_CORRECTOR_ALD) return MD_ERR_BAD_ARG;
   if (mode == MD_CORRECTOR_LANGEVIN && !slabs) return MD_ERR_BAD_ARG;
   const int64_t CP = (int64_t)C * P;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_langevin_step_kernel, dim3((unsigned)stream_blocks(CP, batch), (unsigned)batch), dim3(256), 0,
-                     (hipStream_t)stream, x, eps, z, mask, coef, slabs, snr, (int)mode, x_out, x_mean_out, step_out, (int)batch,
-                     CP, P);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  MD_LAUNCH_STEP(md_langevin_step_kernel, dim3(stream_blocks(CP, batch), (unsigned)batch), x, eps, z, mask, coef, slabs, snr,
+                 (int)mode, x_out, x_mean_out, step_out, (int)batch, CP, P);
 }
 
 extern "C" int md_sde_step(const float* x, const float* eps, const float* z, const float* mask, const float* coef,
                            int32_t kind, float* x_out, float* x_mean_out, int32_t batch, int32_t C, int64_t P, void* stream) {
-  if (!x || !eps || !z || !coef || !x_out || !x_mean_out || batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<16>(x, eps, z, x_out, x_mean_out) || md_any_bad<4>(coef) || md_any_misaligned<16>(mask)) return MD_ERR_BAD_ARG;
+  if (md_bad_dims(batch, C, P, true)) return MD_ERR_BAD_ARG;
   if (kind != MD_SDE_REVERSE_DIFFUSION && kind != MD_SDE_EULER_MARUYAMA) return MD_ERR_BAD_ARG;
   const int64_t CP = (int64_t)C * P;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_sde_step_kernel, dim3((unsigned)stream_blocks(CP, batch), (unsigned)batch), dim3(256), 0,
-                     (hipStream_t)stream, x, eps, z, mask, coef, (int)kind, x_out, x_mean_out, CP, P);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  MD_LAUNCH_STEP(md_sde_step_kernel, dim3(stream_blocks(CP, batch), (unsigned)batch), x, eps, z, mask, coef, (int)kind, x_out,
+                 x_mean_out, CP, P);
 }
 
 extern "C" int md_pf_ode_rhs(const float* x, const float* eps_hat, const float* g, const float* probe, const float* mask,
@@ -428,24 +592,14 @@ extern "C" int md_pf_ode_rhs(const float* x, const float* eps_hat, const float* 
   if (md_any_bad<16>(x, eps_hat, drift) || md_any_bad<8>(coef) || md_any_misaligned<16>(g, probe, mask) ||
       md_any_misaligned<8>(slabs))
     return MD_ERR_BAD_ARG;
-  if (batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
+  if (md_bad_dims(batch, C, P, true)) return MD_ERR_BAD_ARG;
   if ((g == nullptr) != (probe == nullptr) || (g && !slabs)) return MD_ERR_BAD_ARG;     // the divergence needs both, and its slabs
   const int64_t CP = (int64_t)C * P;
-  MD_HIP_CLEAR_ERROR();
   if (g)
-    hipLaunchKernelGGL(md_pf_ode_rhs_kernel<true>, dim3(MD_LANGEVIN_SLABS, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, x,
-                       eps_hat, g, probe, mask, coef, drift, slabs, CP, P);
-  else
-    hipLaunchKernelGGL(md_pf_ode_rhs_kernel<false>, dim3((unsigned)stream_blocks(CP, batch), (unsigned)batch), dim3(256), 0,
-                       (hipStream_t)stream, x, eps_hat, g, probe, mask, coef, drift, slabs, CP, P);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
-}
-
-// an output of `na` bytes at `a` shares memory with an input (null: absent) of `nb` bytes at `b`
-static bool md_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return b && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+    MD_LAUNCH_STEP(md_pf_ode_rhs_kernel<true>, dim3(MD_LANGEVIN_SLABS, (unsigned)batch), x, eps_hat, g, probe, mask, coef, drift,
+                   slabs, CP, P);
+  MD_LAUNCH_STEP(md_pf_ode_rhs_kernel<false>, dim3(stream_blocks(CP, batch), (unsigned)batch), x, eps_hat, g, probe, mask, coef,
+                 drift, slabs, CP, P);
 }
 
 extern "C" int md_guide_residual(const float* x, const float* eps_hat, const float* src, int64_t src_bstride, const float* pmask,
@@ -453,21 +607,14 @@ extern "C" int md_guide_residual(const float* x, const float* eps_hat, const flo
                                  int32_t C, int64_t P, void* stream) {
   if (md_any_bad<16>(x, eps_hat, src, pmask, cot) || md_any_bad<8>(coef, slabs) || md_any_misaligned<16>(gmask))
     return MD_ERR_BAD_ARG;
-  if (batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
+  if (md_bad_dims(batch, C, P, true)) return MD_ERR_BAD_ARG;
   if (ch < 0 || ch >= C || (src_bstride != 0 && src_bstride != P)) return MD_ERR_BAD_ARG;
   const int64_t CP = (int64_t)C * P, n = 4 * CP * batch, np = 4 * P, ns = src_bstride ? np * batch : np;
-  const int64_t nc = 16LL * batch, nl = 8LL * MD_LANGEVIN_SLABS * batch;
-  if (md_overlap(cot, n, x, n) || md_overlap(cot, n, eps_hat, n) || md_overlap(cot, n, src, ns) || md_overlap(cot, n, pmask, np) ||
-      md_overlap(cot, n, gmask, np) || md_overlap(cot, n, coef, nc) || md_overlap(cot, n, slabs, nl))
-    return MD_ERR_BAD_ARG;
-  if (md_overlap(slabs, nl, x, n) || md_overlap(slabs, nl, eps_hat, n) || md_overlap(slabs, nl, src, ns) ||
-      md_overlap(slabs, nl, pmask, np) || md_overlap(slabs, nl, gmask, np) || md_overlap(slabs, nl, coef, nc))
-    return MD_ERR_BAD_ARG;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_guide_residual_kernel, dim3(MD_LANGEVIN_SLABS, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
-                     src, src_bstride, pmask, gmask, coef, (int)ch, cot, slabs, CP, P);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  const md_span out[] = {{cot, n}, {slabs, 8LL * MD_LANGEVIN_SLABS * batch}};
+  const md_span in[] = {{x, n}, {eps_hat, n}, {src, ns}, {pmask, np}, {gmask, np}, {coef, 16LL * batch}};
+  if (md_any_alias(out, in)) return MD_ERR_BAD_ARG;
+  MD_LAUNCH_STEP(md_guide_residual_kernel, dim3(MD_LANGEVIN_SLABS, (unsigned)batch), x, eps_hat, src, src_bstride, pmask, gmask,
+                 coef, (int)ch, cot, slabs, CP, P);
 }
 
 // the checks and the launch of both md_guide_apply exports: the state is float with x_mean as `aux`, or double with x_f32
@@ -476,20 +623,13 @@ static int md_guide_apply(void* state, float* aux, const float* cot, const float
                           const double* slabs, int32_t batch, int32_t C, int64_t P, void* stream) {
   if (md_any_bad<16>(state, cot, g) || md_any_bad<8>(coef, slabs) || md_any_misaligned<16>(aux, gmask)) return MD_ERR_BAD_ARG;
   if (F64 && !aux) return MD_ERR_BAD_ARG;
-  if (batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
-  const int64_t CP = (int64_t)C * P, n = 4 * CP * batch, nx = (F64 ? 8 : 4) * CP * batch, np = 4 * P;
-  const int64_t nc = 24LL * batch, nl = 8LL * MD_LANGEVIN_SLABS * batch;
-  if (md_overlap(state, nx, cot, n) || md_overlap(state, nx, g, n) || md_overlap(state, nx, gmask, np) ||
-      md_overlap(state, nx, coef, nc) || md_overlap(state, nx, slabs, nl) || md_overlap(state, nx, aux, n))
-    return MD_ERR_BAD_ARG;
-  if (aux && (md_overlap(aux, n, cot, n) || md_overlap(aux, n, g, n) || md_overlap(aux, n, gmask, np) ||
-              md_overlap(aux, n, coef, nc) || md_overlap(aux, n, slabs, nl)))
-    return MD_ERR_BAD_ARG;
-  MD_HIP_CLEAR_ERROR();
-  hipLaunchKernelGGL(md_guide_apply_kernel<F64>, dim3((unsigned)stream_blocks(CP, batch), (unsigned)batch), dim3(256), 0,
-                     (hipStream_t)stream, state, aux, cot, g, gmask, coef, slabs, CP, P);
-  MD_HIP_CHECK_LAUNCH();
-  return MD_OK;
+  if (md_bad_dims(batch, C, P, true)) return MD_ERR_BAD_ARG;
+  const int64_t CP = (int64_t)C * P, n = 4 * CP * batch;
+  const md_span out[] = {{state, (F64 ? 8 : 4) * CP * batch}, {aux, n}};
+  const md_span in[] = {{cot, n}, {g, n}, {gmask, 4 * P}, {coef, 24LL * batch}, {slabs, 8LL * MD_LANGEVIN_SLABS * batch}};
+  if (md_any_alias(out, in)) return MD_ERR_BAD_ARG;
+  MD_LAUNCH_STEP(md_guide_apply_kernel<F64>, dim3(stream_blocks(CP, batch), (unsigned)batch), state, aux, cot, g, gmask, coef,
+                 slabs, CP, P);
 }
 
 extern "C" int md_guide_apply_f32(float* x, float* x_mean, const float* cot, const float* g, const float* gmask, const double* coef,
@@ -521,19 +661,13 @@ extern "C" int md_multistep_step(const double* x, const float* eps, const double
                                  double* x_out, double* x0_out, float* x_f32, int32_t batch, int32_t C, int64_t P, void* stream) {
   if (md_any_bad<16>(x, eps, x_out, x0_out, x_f32) || md_any_bad<8>(coef) || md_any_misaligned<16>(h1, h2, z, mask, partial, pmask))
     return MD_ERR_BAD_ARG;
-  if (batch <= 0 || C <= 0 || P <= 0 || (P % 4)) return MD_ERR_BAD_ARG;
+  if (md_bad_dims(batch, C, P, true)) return MD_ERR_BAD_ARG;
   if (ch < 0 || ch >= C || (partial == nullptr) != (pmask == nullptr) || (h2 && !h1)) return MD_ERR_BAD_ARG;
-  const int64_t CP = (int64_t)C * P, n4 = 4 * CP * batch, n8 = 8 * CP * batch, np = 4 * P, nc = 64LL * batch;
-  const struct { const void* p; int64_t n; } in[] = {{x, n8}, {eps, n4}, {h1, n8}, {h2, n8}, {z, n4}, {mask, np}, {coef, nc},
-                                                     {partial, np}, {pmask, np}},
-                                             out[] = {{x_out, n8}, {x0_out, n8}, {x_f32, n4}};
-  for (int o = 0; o < 3; ++o) {
-    for (const auto& i : in)
-      if (md_overlap(out[o].p, out[o].n, i.p, i.n)) return MD_ERR_BAD_ARG;
-    for (int q = o + 1; q < 3; ++q)
-      if (md_overlap(out[o].p, out[o].n, out[q].p, out[q].n)) return MD_ERR_BAD_ARG;
-  }
-  const dim3 grid((unsigned)stream_blocks(CP, batch), (unsigned)batch);
+  const int64_t CP = (int64_t)C * P, n4 = 4 * CP * batch, n8 = 8 * CP * batch, np = 4 * P;
+  const md_span out[] = {{x_out, n8}, {x0_out, n8}, {x_f32, n4}};
+  const md_span in[] = {{x, n8}, {eps, n4}, {h1, n8}, {h2, n8}, {z, n4}, {mask, np}, {coef, 64LL * batch}, {partial, np}, {pmask, np}};
+  if (md_any_alias(out, in)) return MD_ERR_BAD_ARG;
+  const dim3 grid(stream_blocks(CP, batch), (unsigned)batch);
   const bool m = mask != nullptr, r = partial != nullptr;
   hipStream_t s = (hipStream_t)stream;
   MD_HIP_CLEAR_ERROR();

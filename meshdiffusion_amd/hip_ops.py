@@ -1194,17 +1194,40 @@ def softmax_keys(s, B, nk, nq):
     return p
 
 
+# ---- sampler updates (csrc/sde_steps.hip) ----------------------------------------------------------------------------------
+def _state_dims(x):
+    """(B, C, P) of a state tensor [B,C,D,H,W]."""
+    return x.shape[0], x.shape[1], x[0, 0].numel()
+
+
+def _operand(t, name, dtype, shape=None, numel=None, copy=False):
+    """A tensor handed to a sampler export: on the GPU, contiguous, of the stated dtype and shape (or element count).  None (an
+    absent optional operand) passes.  copy: a non-contiguous tensor is copied, not refused.  Returns the tensor to hand over."""
+    if t is None:
+        return None
+    _require_cuda(t, name)
+    if copy:
+        t = t.contiguous()
+    assert t.dtype == dtype and t.is_contiguous(), (name, t.dtype, t.is_contiguous())
+    assert shape is None or tuple(t.shape) == tuple(shape), (name, tuple(t.shape), tuple(shape))
+    assert numel is None or t.numel() == numel, (name, tuple(t.shape), numel)
+    return t
+
+
+def _step_operands(x, eps, z, mask, coef, ncoef):
+    """The fp32 operands of the one-launch predictor / corrector steps, copied where not contiguous, and (B, C, P)."""
+    B, Cc, P = _state_dims(x)
+    f32 = torch.float32
+    x = _operand(x, "x", f32, copy=True)
+    eps, z = _operand(eps, "eps", f32, shape=x.shape, copy=True), _operand(z, "z", f32, shape=x.shape, copy=True)
+    return x, eps, z, _operand(mask, "mask", f32, numel=P, copy=True), _operand(coef, "coef", f32, shape=(B, ncoef), copy=True), B, Cc, P
+
+
 def ancestral_step(x, eps, z, mask, coef):
     """x, eps, z: [B,C,D,H,W] fp32; mask [P] or None; coef [B,4] = beta, sigma, sqrt(1-beta), sqrt(beta)."""
-    lib = _lib.load()
-    for name, t in (("x", x), ("eps", eps), ("z", z)):
-        _require_cuda(t, name)
-    x, eps, z = x.contiguous(), eps.contiguous(), z.contiguous()
-    B, Cc = x.shape[0], x.shape[1]
-    P = x[0, 0].numel()
+    x, eps, z, mask, coef, B, Cc, P = _step_operands(x, eps, z, mask, coef, 4)
     x_out, xm_out = torch.empty_like(x), torch.empty_like(x)
-    check(lib.md_ancestral_step(_ptr(x), _ptr(eps), _ptr(z), _ptr(mask), _ptr(coef), _ptr(x_out),
-                                _ptr(xm_out), B, Cc, P, _stream()), "md_ancestral_step")
+    call("md_ancestral_step", x, eps, z, mask, coef, x_out, xm_out, B, Cc, P)
     return x_out, xm_out
 
 
@@ -1213,22 +1236,15 @@ def langevin_step(x, eps, z, mask, coef, snr, mode="langevin"):
     fp32; mask [P] or None; coef [B,3] = sigma, alpha, (snr*std)^2*2*alpha.  The Langevin step size couples the batch
     through its mean norms: two launches (md_langevin_norms, md_langevin_step), no host synchronisation.
     Returns (x, x_mean, step [B])."""
-    lib = _lib.load()
-    for name, t in (("x", x), ("eps", eps), ("z", z), ("coef", coef)):
-        _require_cuda(t, name)
-    x, eps, z, coef = x.contiguous(), eps.contiguous(), z.contiguous(), coef.contiguous()
-    B, Cc = x.shape[0], x.shape[1]
-    P = x[0, 0].numel()
-    assert coef.dtype == torch.float32 and coef.shape == (B, 3), coef.shape
+    x, eps, z, mask, coef, B, Cc, P = _step_operands(x, eps, z, mask, coef, 3)
     kind = {"langevin": _lib.CORRECTOR_LANGEVIN, "ald": _lib.CORRECTOR_ALD}[mode]
     x_out, xm_out = torch.empty_like(x), torch.empty_like(x)
     step = torch.empty(B, dtype=torch.float32, device=x.device)
     slabs = None
     if kind == _lib.CORRECTOR_LANGEVIN:
         slabs = torch.empty((B, _lib.LANGEVIN_SLABS, 2), dtype=torch.float64, device=x.device)
-        check(lib.md_langevin_norms(_ptr(eps), _ptr(z), B, Cc, P, _ptr(slabs), _stream()), "md_langevin_norms")
-    check(lib.md_langevin_step(_ptr(x), _ptr(eps), _ptr(z), _ptr(mask), _ptr(coef), _ptr(slabs), float(snr), kind,
-                               _ptr(x_out), _ptr(xm_out), _ptr(step), B, Cc, P, _stream()), "md_langevin_step")
+        call("md_langevin_norms", eps, z, B, Cc, P, slabs)
+    call("md_langevin_step", x, eps, z, mask, coef, slabs, float(snr), kind, x_out, xm_out, step, B, Cc, P)
     return x_out, xm_out, step
 
 
@@ -1236,17 +1252,10 @@ def sde_step(x, eps, z, mask, coef, kind):
     """One reverse-diffusion ('reverse_diffusion') or Euler-Maruyama ('euler_maruyama') predictor step, grid mask
     applied.  x, eps, z: [B,C,D,H,W] fp32; mask [P] or None; coef [B,5] (include/meshdiffusion_hip.h md_sde_step).
     Returns (x, x_mean)."""
-    lib = _lib.load()
-    for name, t in (("x", x), ("eps", eps), ("z", z), ("coef", coef)):
-        _require_cuda(t, name)
-    x, eps, z, coef = x.contiguous(), eps.contiguous(), z.contiguous(), coef.contiguous()
-    B, Cc = x.shape[0], x.shape[1]
-    P = x[0, 0].numel()
-    assert coef.dtype == torch.float32 and coef.shape == (B, 5), coef.shape
+    x, eps, z, mask, coef, B, Cc, P = _step_operands(x, eps, z, mask, coef, 5)
     k = {"reverse_diffusion": _lib.SDE_REVERSE_DIFFUSION, "euler_maruyama": _lib.SDE_EULER_MARUYAMA}[kind]
     x_out, xm_out = torch.empty_like(x), torch.empty_like(x)
-    check(lib.md_sde_step(_ptr(x), _ptr(eps), _ptr(z), _ptr(mask), _ptr(coef), k, _ptr(x_out), _ptr(xm_out), B, Cc, P,
-                          _stream()), "md_sde_step")
+    call("md_sde_step", x, eps, z, mask, coef, k, x_out, xm_out, B, Cc, P)
     return x_out, xm_out
 
 
@@ -1255,35 +1264,18 @@ def pf_ode_rhs(x, eps_hat, mask, coef, g=None, probe=None):
     None; coef [B,2] float64 = (-0.5*beta(t), 0.5*beta(t)/sigma(t)).  Returns (drift fp32 like x, div): with g = J^T probe and
     probe given, div [B] float64 = sum probe*(c_x*probe + c_e*g)*mask, the Hutchinson estimate of the drift's divergence (64
     slab sums per sample, added in a fixed order); without them div is None (the ODE sampler)."""
-    lib = _lib.load()
-    ts = [("x", x), ("eps_hat", eps_hat), ("coef", coef)] + ([("g", g), ("probe", probe)] if g is not None else [])
-    for name, t in ts:
-        _require_cuda(t, name)
     assert (g is None) == (probe is None)
-    x, eps_hat, coef = x.contiguous(), eps_hat.contiguous(), coef.contiguous()
-    B, Cc = x.shape[0], x.shape[1]
-    P = x[0, 0].numel()
-    assert x.dtype == eps_hat.dtype == torch.float32 and coef.dtype == torch.float64 and coef.shape == (B, 2), (coef.dtype, coef.shape)
-    if mask is not None:
-        _require_cuda(mask, "mask")
-        assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == P, (mask.dtype, tuple(mask.shape), P)
+    B, Cc, P = _state_dims(x)
+    f32 = torch.float32
+    x = _operand(x, "x", f32, copy=True)
+    eps_hat = _operand(eps_hat, "eps_hat", f32, shape=x.shape, copy=True)
+    coef = _operand(coef, "coef", torch.float64, shape=(B, 2), copy=True)
+    mask = _operand(mask, "mask", f32, numel=P)
+    g, probe = _operand(g, "g", f32, shape=x.shape, copy=True), _operand(probe, "probe", f32, shape=x.shape, copy=True)
     drift = torch.empty_like(x)
-    slabs = None
-    if g is not None:
-        g, probe = g.contiguous(), probe.contiguous()
-        assert g.dtype == probe.dtype == torch.float32 and g.shape == probe.shape == x.shape
-        slabs = torch.empty((B, _lib.LANGEVIN_SLABS), dtype=torch.float64, device=x.device)
-    check(lib.md_pf_ode_rhs(_ptr(x), _ptr(eps_hat), _ptr(g), _ptr(probe), _ptr(mask), _ptr(coef), _ptr(drift), _ptr(slabs), B, Cc, P,
-                            _stream()), "md_pf_ode_rhs")
+    slabs = torch.empty((B, _lib.LANGEVIN_SLABS), dtype=torch.float64, device=x.device) if g is not None else None
+    call("md_pf_ode_rhs", x, eps_hat, g, probe, mask, coef, drift, slabs, B, Cc, P)
     return drift, (slabs.sum(dim=1) if slabs is not None else None)
-
-
-def _guide_operand(t, name, dtype, shape=None, numel=None):
-    """A tensor of the guidance exports: on the GPU, contiguous, of the stated dtype and shape (or element count)."""
-    _require_cuda(t, name)
-    assert t.dtype == dtype and t.is_contiguous(), (name, t.dtype, t.is_contiguous())
-    assert shape is None or tuple(t.shape) == tuple(shape), (name, tuple(t.shape), tuple(shape))
-    assert numel is None or t.numel() == numel, (name, tuple(t.shape), numel)
 
 
 def guide_residual(x, eps_hat, src, pmask, gmask, coef, ch, src_bstride=0):
@@ -1292,39 +1284,31 @@ def guide_residual(x, eps_hat, src, pmask, gmask, coef, ch, src_bstride=0):
     coef [B,2] float64 = (alpha, sigma).
     Returns (cot fp32 like x: r = pmask*gmask*(x0_hat[ch] - src) in channel `ch`, +0 elsewhere; slabs [B, 64] float64, whose
     sum over a sample is ||r||^2 of the rounded r)."""
-    lib = _lib.load()
-    B, Cc = x.shape[0], x.shape[1]
-    P = x[0, 0].numel()
+    B, Cc, P = _state_dims(x)
     f32 = torch.float32
-    _guide_operand(x, "x", f32)
-    _guide_operand(eps_hat, "eps_hat", f32, shape=x.shape)
-    _guide_operand(pmask, "pmask", f32, numel=P)
-    _guide_operand(coef, "coef", torch.float64, shape=(B, 2))
+    _operand(x, "x", f32)
+    _operand(eps_hat, "eps_hat", f32, shape=x.shape)
+    _operand(pmask, "pmask", f32, numel=P)
+    _operand(coef, "coef", torch.float64, shape=(B, 2))
     assert src_bstride in (0, P), (src_bstride, P)
-    _guide_operand(src, "src", f32, numel=B * P if src_bstride else P)
-    if gmask is not None:
-        _guide_operand(gmask, "gmask", f32, numel=P)
+    _operand(src, "src", f32, numel=B * P if src_bstride else P)
+    _operand(gmask, "gmask", f32, numel=P)
     assert 0 <= int(ch) < Cc, (ch, Cc)
     cot = torch.empty_like(x)
     slabs = torch.empty((B, _lib.LANGEVIN_SLABS), dtype=torch.float64, device=x.device)
-    check(lib.md_guide_residual(_ptr(x), _ptr(eps_hat), _ptr(src), src_bstride, _ptr(pmask), _ptr(gmask), _ptr(coef), int(ch),
-                                _ptr(cot), _ptr(slabs), B, Cc, P, _stream()), "md_guide_residual")
+    call("md_guide_residual", x, eps_hat, src, src_bstride, pmask, gmask, coef, int(ch), cot, slabs, B, Cc, P)
     return cot, slabs
 
 
 def _guide_apply(name, state, sdtype, aux, cot, g, gmask, coef, slabs):
-    lib = _lib.load()
-    B, Cc = state.shape[0], state.shape[1]
-    P = state[0, 0].numel()
-    _guide_operand(state, "the state", sdtype)
-    for nm, t in (("cot", cot), ("g", g)) + ((("x_mean / x_f32", aux),) if aux is not None else ()):
-        _guide_operand(t, nm, torch.float32, shape=state.shape)
-    _guide_operand(coef, "coef", torch.float64, shape=(B, 3))
-    _guide_operand(slabs, "slabs", torch.float64, shape=(B, _lib.LANGEVIN_SLABS))
-    if gmask is not None:
-        _guide_operand(gmask, "gmask", torch.float32, numel=P)
-    check(getattr(lib, name)(_ptr(state), _ptr(aux), _ptr(cot), _ptr(g), _ptr(gmask), _ptr(coef), _ptr(slabs), B, Cc, P, _stream()),
-          name)
+    B, Cc, P = _state_dims(state)
+    _operand(state, "the state", sdtype)
+    for nm, t in (("cot", cot), ("g", g), ("x_mean / x_f32", aux)):
+        _operand(t, nm, torch.float32, shape=state.shape)
+    _operand(coef, "coef", torch.float64, shape=(B, 3))
+    _operand(slabs, "slabs", torch.float64, shape=(B, _lib.LANGEVIN_SLABS))
+    _operand(gmask, "gmask", torch.float32, numel=P)
+    call(name, state, aux, cot, g, gmask, coef, slabs, B, Cc, P)
 
 
 def guide_apply_(x, x_mean, cot, g, gmask, coef, slabs):
@@ -1346,17 +1330,15 @@ def guide_apply64_(x64, x_f32, cot, g, gmask, coef, slabs):
 def ddim_step(x64, eps, mask, coef, partial=None, pmask=None, ch=0):
     """x64 [B,C,D,H,W] float64 state, eps float32 U-Net output, mask [P] or None, coef [B,4] float64 = a1, a2, r1, r2;
     partial / pmask: [P] float32 each or None.  Returns (x_new f64, x0_pred f64, x_new as f32)."""
-    lib = _lib.load()
-    for name, t in (("x", x64), ("eps", eps)):
-        _require_cuda(t, name)
-    assert x64.dtype == torch.float64 and eps.dtype == torch.float32 and coef.dtype == torch.float64
-    x64, eps, coef = x64.contiguous(), eps.contiguous(), coef.contiguous()
-    B, Cc = x64.shape[0], x64.shape[1]
-    P = x64[0, 0].numel()
+    B, Cc, P = _state_dims(x64)
+    f32 = torch.float32
+    x64 = _operand(x64, "x", torch.float64, copy=True)
+    eps = _operand(eps, "eps", f32, shape=x64.shape, copy=True)
+    coef = _operand(coef, "coef", torch.float64, shape=(B, 4), copy=True)
+    mask, partial, pmask = (_operand(t, nm, f32, numel=P, copy=True) for nm, t in (("mask", mask), ("partial", partial), ("pmask", pmask)))
     x_out, x0_out = torch.empty_like(x64), torch.empty_like(x64)
     x_f32 = torch.empty_like(eps)
-    check(lib.md_ddim_step(_ptr(x64), _ptr(eps), _ptr(mask), _ptr(coef), _ptr(partial), _ptr(pmask), int(ch), _ptr(x_out),
-                           _ptr(x0_out), _ptr(x_f32), B, Cc, P, _stream()), "md_ddim_step")
+    call("md_ddim_step", x64, eps, mask, coef, partial, pmask, int(ch), x_out, x0_out, x_f32, B, Cc, P)
     return x_out, x0_out, x_f32
 
 
@@ -1366,52 +1348,49 @@ def multistep_step(x64, eps, hist, z, mask, coef, partial=None, pmask=None, ch=0
     noise or None; mask [P] fp32 or None; coef [B,8] float64 = alpha_s, sigma_s, c_x, c_0, c_1, c_2, c_z, 0; partial / pmask:
     [P] fp32 each or None.  out: (x_new f64, x0_pred f64, x_new as fp32) to write into -- the sampler's own buffers, none of them
     an input -- or None: allocated here.  Returns that triple."""
-    lib = _lib.load()
-    B, Cc = x64.shape[0], x64.shape[1]
-    P = x64.numel() // (B * Cc)
+    B, Cc, P = _state_dims(x64)
     f32, f64 = torch.float32, torch.float64
     hist = tuple(hist or ())
     assert len(hist) <= 2, len(hist)
-    _guide_operand(x64, "x", f64)
-    _guide_operand(eps, "eps", f32, shape=x64.shape)
-    _guide_operand(coef, "coef", f64, shape=(B, 8))
-    for t in hist:
-        _guide_operand(t, "history", f64, shape=x64.shape)
-    if z is not None:
-        _guide_operand(z, "z", f32, shape=x64.shape)
-    for nm, t in (("mask", mask), ("partial", partial), ("pmask", pmask)):
-        if t is not None:
-            _guide_operand(t, nm, f32, numel=P)
     if out is None:
         out = (torch.empty_like(x64), torch.empty_like(x64), torch.empty_like(eps))
     x_out, x0_out, x_f32 = out
-    _guide_operand(x_out, "x_out", f64, shape=x64.shape)
-    _guide_operand(x0_out, "x0_out", f64, shape=x64.shape)
-    _guide_operand(x_f32, "x_f32", f32, shape=x64.shape)
+    for nm, t in (("x", x64), ("x_out", x_out), ("x0_out", x0_out)) + tuple(("history", t) for t in hist):
+        _operand(t, nm, f64, shape=x64.shape)
+    for nm, t in (("eps", eps), ("z", z), ("x_f32", x_f32)):
+        _operand(t, nm, f32, shape=x64.shape)
+    _operand(coef, "coef", f64, shape=(B, 8))
+    for nm, t in (("mask", mask), ("partial", partial), ("pmask", pmask)):
+        _operand(t, nm, f32, numel=P)
     h1, h2 = (hist + (None, None))[:2]
-    check(lib.md_multistep_step(_ptr(x64), _ptr(eps), _ptr(h1), _ptr(h2), _ptr(z), _ptr(mask), _ptr(coef), _ptr(partial),
-                                _ptr(pmask), int(ch), _ptr(x_out), _ptr(x0_out), _ptr(x_f32), B, Cc, P, _stream()),
-          "md_multistep_step")
+    call("md_multistep_step", x64, eps, h1, h2, z, mask, coef, partial, pmask, int(ch), x_out, x0_out, x_f32, B, Cc, P)
     return x_out, x0_out, x_f32
 
 
 def inpaint_blend_(x, src, pmask, gmask, ch, src_bstride=0):
     """In place on channel `ch` of x: (x*(1-pmask) + src*pmask) * gmask."""
-    lib = _lib.load()
-    B, Cc = x.shape[0], x.shape[1]
-    P = x[0, 0].numel()
-    check(lib.md_inpaint_blend(_ptr(x), _ptr(src), _ptr(pmask), _ptr(gmask), B, Cc, ch, P, src_bstride,
-                               _stream()), "md_inpaint_blend")
+    B, Cc, P = _state_dims(x)
+    f32 = torch.float32
+    assert src_bstride in (0, P), (src_bstride, P)
+    _operand(x, "x", f32)
+    _operand(src, "src", f32, numel=B * P if src_bstride else P)
+    _operand(pmask, "pmask", f32, numel=P)
+    _operand(gmask, "gmask", f32, numel=P)
+    call("md_inpaint_blend", x, src, pmask, gmask, B, Cc, int(ch), P, src_bstride)
     return x
 
 
 def inpaint_renoise_(x, x_mean, z, pmask, gmask, coef, ch):
     """In place: re-noise channel `ch` inside pmask (see md_inpaint_renoise)."""
-    lib = _lib.load()
-    B, Cc = x.shape[0], x.shape[1]
-    P = x[0, 0].numel()
-    check(lib.md_inpaint_renoise(_ptr(x), _ptr(x_mean), _ptr(z), _ptr(pmask), _ptr(gmask), _ptr(coef), B, Cc,
-                                 ch, P, _stream()), "md_inpaint_renoise")
+    B, Cc, P = _state_dims(x)
+    f32 = torch.float32
+    _operand(x, "x", f32)
+    _operand(x_mean, "x_mean", f32, shape=x.shape)
+    _operand(z, "z", f32, numel=B * P)
+    _operand(pmask, "pmask", f32, numel=P)
+    _operand(gmask, "gmask", f32, numel=P)
+    _operand(coef, "coef", f32, shape=(B, 2))
+    call("md_inpaint_renoise", x, x_mean, z, pmask, gmask, coef, B, Cc, int(ch), P)
     return x
 
 

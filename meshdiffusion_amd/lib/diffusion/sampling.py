@@ -180,6 +180,41 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps, grid_mask=None, ret
                           eps=eps, device=config.device, grid_mask=grid_mask, return_traj=return_traj)
 
 
+def _grid_mask_operands(grid_mask, dev, P):
+    """(gm, gm_flat): the grid mask on `dev` as given, and as the contiguous float32 [P] the kernels read; both None without one."""
+    if grid_mask is None:
+        return None, None
+    gm = grid_mask.to(dev)
+    gm_flat = gm.reshape(-1).to(torch.float32).contiguous()
+    assert gm_flat.numel() == P, "grid_mask must broadcast over batch and channels"
+    return gm, gm_flat
+
+
+def prepare_run(sde, shape, dev, grid_mask=None, x0=None, partial=None, partial_mask=None, ch=0, replace=False):
+    """The operands of a DDIM / DPM-Solver++ run: (x, gm, gm_flat, part, pm).  x: x0 or a prior draw, on `dev`, times the grid
+    mask, always a fresh tensor (never the caller's x0); part / pm: `partial` / `partial_mask` as float32 [P], None without a
+    partial.  replace: channel `ch` of x starts as x*(1-pm) + part*pm."""
+    P = int(shape[2] * shape[3] * shape[4])
+    gm, gm_flat = _grid_mask_operands(grid_mask, dev, P)
+    x = (x0.to(dev) if x0 is not None else sde.prior_sampling(shape).to(dev))
+    x = x * gm if gm is not None else x.clone()
+    part = pm = None
+    if partial is not None:
+        part = partial.to(dev, torch.float32).reshape(-1).contiguous()
+        pm = partial_mask.to(dev, torch.float32).reshape(-1).contiguous()
+        assert part.numel() == P and pm.numel() == P, "partial / partial_mask: one grid shared by the batch"
+        if replace:
+            x[:, ch] = x[:, ch] * (1 - pm.view(shape[2:])) + part.view(shape[2:]) * pm.view(shape[2:])
+    return x, gm, gm_flat, part, pm
+
+
+def guidance_rows(alpha, sigma, scale):
+    """(alpha, sigma, zeta) rows [...,3] of md_guide_apply and their (alpha, sigma) prefix [...,2] of md_guide_residual, both
+    contiguous, in the dtype of `alpha` (float64 in every sampler)."""
+    gcoef = torch.stack([alpha, sigma, torch.full_like(alpha, float(scale))], dim=-1).contiguous()
+    return gcoef, gcoef[..., :2].contiguous()
+
+
 class AncestralStepper:
     """Per-iteration state of the N-step ancestral loop: label / coefficient tables built once with the
     reference's float32 ops (sampling.py:406, :224-226; models/utils.py:193-195), then one U-Net call and
@@ -201,14 +236,10 @@ class AncestralStepper:
         # per-iteration rows pre-expanded over the batch: no host-side tensor math inside the loop
         self.labels = labels_all[:, None].expand(sde.N, self.B).contiguous()
         self.coef = coef_all[:, None, :].expand(sde.N, self.B, 4).contiguous()
-        self.gm, self.gm_flat = None, None
-        if grid_mask is not None:
-            self.gm = grid_mask.to(dev)
-            self.gm_flat = self.gm.reshape(-1).to(torch.float32).contiguous()
-            assert self.gm_flat.numel() == self.P, "grid_mask must broadcast over batch and channels"
-            # a 0/1 mask makes the reference's pre-predictor `x * grid_mask` (sampling.py:476) an exact
-            # no-op on the already masked state, so one masked store per step suffices
-            assert bool(((self.gm_flat == 0) | (self.gm_flat == 1)).all()), "grid_mask must be binary"
+        self.gm, self.gm_flat = _grid_mask_operands(grid_mask, dev, self.P)
+        # a 0/1 mask makes the reference's pre-predictor `x * grid_mask` (sampling.py:476) an exact
+        # no-op on the already masked state, so one masked store per step suffices
+        assert self.gm is None or bool(((self.gm_flat == 0) | (self.gm_flat == 1)).all()), "grid_mask must be binary"
 
     def prior(self):
         """Initial sample: CPU generator like the reference (sde_lib.py:216-217), then masked."""
@@ -420,9 +451,7 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
                 # (alpha, sigma, zeta) of every iteration's level, from the float32 tables the step's own coefficients come from
                 k_all = (timesteps * (sde.N - 1) / sde.T).long()
                 a_all, s_all = sde.sqrt_alphas_cumprod.to(dev)[k_all].double(), sde.sqrt_1m_alphas_cumprod.to(dev)[k_all].double()
-                gcoef = torch.stack([a_all, s_all, torch.full_like(a_all, float(guidance_scale))], dim=1)
-                gcoef = gcoef[:, None, :].expand(sde.N, B, 3).contiguous()
-                rcoef = gcoef[:, :, :2].contiguous()
+                gcoef, rcoef = guidance_rows(a_all[:, None].expand(sde.N, B), s_all[:, None].expand(sde.N, B), guidance_scale)
             if replace:
                 # ---- initial conditioning (sampling.py:429-440), including its broadcasting quirk:
                 # `sampled_update` is [B,B,R,R,R] there and `[:, partial_channel]` indexes its SECOND batch
@@ -494,7 +523,6 @@ def get_ddim_sampler(sde, shape, predictor, inverse_scaler, n_steps=1, denoise=F
     if predictor is not DDIMPredictor:
         raise NotImplementedError("the DDIM sampler runs with the 'ddim' predictor")
     B = shape[0]
-    P = int(shape[2] * shape[3] * shape[4])
     dev = torch.device(device)
 
     def ddim_sampler(model, schedule="quad", num_steps=100, x0=None, partial=None, partial_mask=None, partial_channel=0,
@@ -504,22 +532,9 @@ def get_ddim_sampler(sde, shape, predictor, inverse_scaler, n_steps=1, denoise=F
         the step's own prediction.  guidance_replace off: no replacement of the known voxels, at the start or in the steps."""
         guided = _check_guidance(guidance_scale, partial)
         with torch.no_grad():
-            gm = grid_mask.to(dev) if grid_mask is not None else None
-            gm_flat = None
-            if gm is not None:
-                gm_flat = gm.reshape(-1).to(torch.float32).contiguous()
-                assert gm_flat.numel() == P, "grid_mask must broadcast over batch and channels"
-            x = (x0.to(dev) if x0 is not None else sde.prior_sampling(shape).to(dev))
-            if gm is not None:
-                x = x * gm
-            part = pm = None
             ch = partial_channel
-            if partial is not None:
-                part = partial.to(dev, torch.float32).reshape(-1).contiguous()
-                pm = partial_mask.to(dev, torch.float32).reshape(-1).contiguous()
-                assert part.numel() == P and pm.numel() == P, "partial / partial_mask: one grid shared by the batch"
-                if guidance_replace or not guided:
-                    x[:, ch] = x[:, ch] * (1 - pm.view(shape[2:])) + part.view(shape[2:]) * pm.view(shape[2:])
+            x, gm, gm_flat, part, pm = prepare_run(sde, shape, dev, grid_mask, x0, partial, partial_mask, ch,
+                                                   replace=guidance_replace or not guided)
             timesteps = ddim_schedule(sde.N, schedule, num_steps)
             pred = predictor(sde, None)
             model_fn = mutils.get_model_fn(model, train=False)
@@ -532,9 +547,9 @@ def get_ddim_sampler(sde, shape, predictor, inverse_scaler, n_steps=1, denoise=F
                 vec_tprev = torch.ones(B, device=dev) * timesteps[i - 1]
                 if guided:
                     coef = pred.coefficients(vec_t, vec_tprev)
-                    gcoef = torch.cat([coef[:, :2], torch.full_like(coef[:, :1], float(guidance_scale))], dim=1).contiguous()
-                    eps_hat, cot, g, slabs = guidance_terms(model, gcoef[:, :2].contiguous(), x32, vec_t.float() * (sde.N - 1), None,
-                                                            None, part, pm, gm_flat, ch, chunk=guidance_chunk)
+                    gcoef, rcoef = guidance_rows(coef[:, 0], coef[:, 1], guidance_scale)
+                    eps_hat, cot, g, slabs = guidance_terms(model, rcoef, x32, vec_t.float() * (sde.N - 1), None, None, part, pm,
+                                                            gm_flat, ch, chunk=guidance_chunk)
                     rep = (part, pm) if guidance_replace else (None, None)
                     x64, x0_pred, x32 = ops.ddim_step(x64, eps_hat, gm_flat, coef, rep[0], rep[1], ch)
                     ops.guide_apply64_(x64, x32, cot, g, gm_flat, gcoef, slabs)
@@ -673,14 +688,13 @@ def dpmpp_tables(sde, times, order=2, variant="taylor", tau=0, lower_order_final
 def get_dpmpp_sampler(sde, shape, inverse_scaler, steps=20, order=2, variant="taylor", tau=0, schedule="logsnr",
                       lower_order_final=True, denoise=False, eps=1e-3, device="cuda", grid_mask=None):
     """DPM-Solver++ sampler (`config.sampling.method = 'dpmpp'`): `steps` U-Net evaluations instead of DDIM's 99, each followed by
-    one md_multistep_step launch on the float64 state.  The loop is ddim_sampler's: masked prior draw (or x0), replacement of the
-    known voxels at the start and in every step, guidance_terms + md_guide_apply_f64 under guidance.  tau = 1: the SDE variant, one
+    one md_multistep_step launch on the float64 state.  Set up like ddim_sampler (prepare_run: masked prior draw or x0, replacement of
+    the known voxels at the start), then the same loop: replacement in every step, guidance_terms + md_guide_apply_f64 under guidance.  tau = 1: the SDE variant, one
     float32 draw(x_f32) per step taken before the launch.  denoise: return the last clean-grid prediction.  Returns (samples,
     number of evaluations)."""
     if not isinstance(sde, sde_lib.VPSDE):
         raise NotImplementedError(f"SDE class {sde.__class__.__name__} not yet supported.")
     B = shape[0]
-    P = int(shape[2] * shape[3] * shape[4])
     dev = torch.device(device)
     times = dpmpp_schedule(sde, steps, schedule, eps)
     rows, labels = dpmpp_tables(sde, times, order, variant, tau, lower_order_final)
@@ -690,29 +704,15 @@ def get_dpmpp_sampler(sde, shape, inverse_scaler, steps=20, order=2, variant="ta
                       guidance_replace=True, guidance_chunk=None, draw=torch.randn_like):
         guided = _check_guidance(guidance_scale, partial)
         with torch.no_grad():
-            gm = grid_mask.to(dev) if grid_mask is not None else None
-            gm_flat = None
-            if gm is not None:
-                gm_flat = gm.reshape(-1).to(torch.float32).contiguous()
-                assert gm_flat.numel() == P, "grid_mask must broadcast over batch and channels"
-            x = (x0.to(dev) if x0 is not None else sde.prior_sampling(shape).to(dev))
-            x = x * gm if gm is not None else x.clone()
-            part = pm = None
             ch = partial_channel
-            replace =partial is not None and (guidance_replace or not guided)
-            if partial is not None:
-                part = partial.to(dev, torch.float32).reshape(-1).contiguous()
-                pm = partial_mask.to(dev, torch.float32).reshape(-1).contiguous()
-                assert part.numel() == P and pm.numel() == P, "partial / partial_mask: one grid shared by the batch"
-                if replace:
-                    x[:, ch] = x[:, ch] * (1 - pm.view(shape[2:])) + part.view(shape[2:]) * pm.view(shape[2:])
+            replace = partial is not None and (guidance_replace or not guided)
+            x, gm, gm_flat, part, pm = prepare_run(sde, shape, dev, grid_mask, x0, partial, partial_mask, ch, replace)
             rep = (part, pm) if replace else (None, None)
             # per-step rows pre-expanded over the batch: no host-side tensor math inside the loop
             coef = rows.to(dev)[:, None, :].expand(steps, B, 8).contiguous()
             lab = labels.to(dev, torch.float32)[:, None].expand(steps, B).contiguous()
             if guided:
-                rcoef = coef[:, :, :2].contiguous()
-                gcoef = torch.cat([rcoef, torch.full_like(rcoef[:, :, :1], float(guidance_scale))], dim=2).contiguous()
+                gcoef, rcoef = guidance_rows(coef[:, :, 0], coef[:, :, 1], guidance_scale)
             model_fn = mutils.get_model_fn(model, train=False)
             # the sampler's own buffers, rotated: two float64 states, a ring of three clean-grid predictions, the U-Net input
             xa, x32 = x.double().contiguous(), x.float().contiguous()

@@ -163,3 +163,59 @@ def test_kernel_bars_leave_room_for_a_float64_chain():
         k = ref["keep"]
         assert np.all(np.abs(x0 - ref["x0"])[k] <= (4 * dc.U * ref["x0_bar"])[k])
         assert np.all(np.abs(xn - ref["x_new"])[k] <= (8 * dc.U * ref["terms"])[k])
+
+
+def test_multistep_step_refuses_aliased_outputs(hip_lib):
+    """The aliasing table of md_multistep_step on host addresses (nothing here may reach a kernel): every output against every
+    input and against the outputs after it, whole tensors and partial overlaps."""
+    import ctypes as C
+    from meshdiffusion_amd import _lib
+    B, Cc, P = 2, 4, 64                                                                # 4 KiB per float64 tensor, 2 KiB per float32 one
+    names = ["x", "eps", "h1", "h2", "z", "mask", "coef", "partial", "pmask", "x_out", "x0_out", "x_f32"]
+    buf = C.create_string_buffer(8192 * len(names) + 64)
+    base = (C.addressof(buf) + 63) & ~63
+    good = {n: base + 8192 * i for i, n in enumerate(names)}
+
+    def call(**change):
+        v = dict(good, **change)
+        p = lambda n: C.c_void_p(v[n])                                                   # noqa: E731
+        return hip_lib.md_multistep_step(p("x"), p("eps"), p("h1"), p("h2"), p("z"), p("mask"), p("coef"), p("partial"), p("pmask"), 0,
+                                         p("x_out"), p("x0_out"), p("x_f32"), B, Cc, P, C.c_void_p(0))
+
+    for out in ("x_out", "x0_out", "x_f32"):
+        for inp in names[:9]:
+            assert call(**{out: good[inp]}) == _lib.ERR_BAD_ARG, (out, inp)
+    assert call(x_out=good["x0_out"]) == _lib.ERR_BAD_ARG and call(x_out=good["x_f32"]) == _lib.ERR_BAD_ARG
+    assert call(x0_out=good["x_f32"]) == _lib.ERR_BAD_ARG
+    assert call(x0_out=good["x_out"] + 2048) == _lib.ERR_BAD_ARG                          # one output starts inside another
+    assert call(x_f32=good["x0_out"] + 4080) == _lib.ERR_BAD_ARG                          # ... in its last 16 bytes
+    assert call(x_out=good["h1"] - 4080) == _lib.ERR_BAD_ARG                              # an output's tail reaches into an input
+    assert call(x_f32=good["coef"] + 112) == _lib.ERR_BAD_ARG                             # the last 16 of the 128 coefficient bytes
+
+
+# ---- the samplers' shared setup ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("masked", [False, True])
+def test_prepare_run_never_hands_back_the_callers_x0(sde, masked):
+    """prepare_run on CPU tensors: the start state is a copy of x0 (times the grid mask), with and without a grid mask, so the
+    initial replacement -- and every in-place kernel after it -- leaves the caller's x0 as it was."""
+    shape = (2, 4, 4, 4, 4)
+    g = torch.Generator().manual_seed(3)
+    x0 = torch.randn(shape, generator=g)
+    keep = x0.clone()
+    gm = (torch.rand((1,) + shape[2:], generator=g) < 0.7).float() if masked else None
+    partial, pmask = torch.randn(shape[2:], generator=g), (torch.rand(shape[2:], generator=g) < 0.5).float()
+    dev = torch.device("cpu")
+    for replace in (False, True):
+        x, gm_dev, gm_flat, part, pm = sampling.prepare_run(sde, shape, dev, gm, x0, partial, pmask, ch=1, replace=replace)
+        assert x.untyped_storage().data_ptr() != x0.untyped_storage().data_ptr() and x.is_contiguous()
+        assert torch.equal(x0, keep)
+        want = keep * gm if masked else keep.clone()
+        if replace:
+            want[:, 1] = want[:, 1] * (1 - pmask) + partial * pmask
+        assert torch.equal(x, want)
+        assert (gm_flat is None and gm_dev is None) if not masked else (gm_flat.shape == (64,) and gm_flat.dtype == torch.float32)
+        assert part.shape == pm.shape == (64,) and torch.equal(part.view(4, 4, 4), partial) and torch.equal(pm.view(4, 4, 4), pmask)
+        x.zero_()                                                                        # what an in-place kernel would do
+        assert torch.equal(x0, keep)
+    x, _, _, part, pm = sampling.prepare_run(sde, shape, dev, gm)                        # no x0: a prior draw; no partial
+    assert x.shape == shape and part is None and pm is None

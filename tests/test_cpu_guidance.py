@@ -142,6 +142,8 @@ def test_exports_refuse_bad_arguments_in_order(hip_lib):
         assert residual(cot=ptr[name]) == bad, name                         # the cotangent written over an input
     assert residual(slabs=coef) == bad
     assert residual(cot=C.c_void_p(x.value + 1024)) == bad                        # inside x's [B][C][P] floats
+    assert residual(slabs=C.c_void_p(cot.value + 1024)) == bad                    # one output starts inside the other
+    assert residual(slabs=C.c_void_p(x.value - 512)) == bad                       # the slabs' tail reaches into an input
 
     for fname, state_bytes in (("md_guide_apply_f32", 4), ("md_guide_apply_f64", 8)):
         fn = getattr(hip_lib, fname)
@@ -162,6 +164,7 @@ def test_exports_refuse_bad_arguments_in_order(hip_lib):
         for name, val in (("cot", cot), ("g", g), ("gm", gm)):
             assert apply(x=val) == bad and apply(aux=val) == bad, (fname, name)  # a state written over an input
         assert apply(aux=x) == bad                                               # the two outputs are one tensor
+        assert apply(aux=C.c_void_p(x.value + 64)) == bad                        # one output starts inside the other
         assert apply(x=C.c_void_p(cot.value - 16 * state_bytes)) == bad          # the state's tail reaches into cot
 
 

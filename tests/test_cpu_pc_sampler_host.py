@@ -121,3 +121,69 @@ def test_new_entry_points_reject_bad_arguments(hip_lib):
     assert hip_lib.md_langevin_step(one, one, one, nul, one, one, 0.075, 7, one, one, one, 2, 4, 4096, nul) == -1  # unknown mode
     assert hip_lib.md_sde_step(one, one, one, nul, one, 2, one, one, 2, 4, 4096, nul) == -1                       # unknown kind
     assert hip_lib.md_sde_step(one, one, one, nul, one, 0, one, one, 0, 4, 4096, nul) == -1                       # empty batch
+
+
+# The exports that took their argument checks from md_args.h last.  Per export: the arguments in order -- a pointer as (name,
+# required, alignment), a scalar as its name -- and whether the kernel moves four values at a time (P % 4 refused).
+_PTR16 = lambda *names: [(n, True, 16) for n in names]                                   # noqa: E731
+STEP_EXPORTS = {
+    "md_ancestral_step": (_PTR16("x", "eps", "z") + [("mask", False, 16), ("coef", True, 4)] + _PTR16("x_out", "x_mean_out")
+                          + ["batch", "C", "P"], True),
+    "md_ddim_step": ([("x", True, 8), ("eps", True, 4), ("mask", False, 4), ("coef", True, 8), ("partial", False, 4),
+                      ("pmask", False, 4), "ch", ("x_out", True, 8), ("x0_out", True, 8), ("x_f32", True, 4), "batch", "C", "P"], False),
+    "md_inpaint_blend": ([("x", True, 4), ("src", True, 4), ("pmask", True, 4), ("gmask", False, 4), "batch", "C", "ch", "P",
+                          "src_bstride"], False),
+    "md_inpaint_renoise": ([("x", True, 4), ("x_mean", False, 4), ("z", True, 4), ("pmask", True, 4), ("gmask", False, 4),
+                            ("coef", True, 4), "batch", "C", "ch", "P"], False),
+    "md_langevin_norms": (_PTR16("eps", "z") + ["batch", "C", "P"] + _PTR16("slabs"), True),
+    "md_langevin_step": (_PTR16("x", "eps", "z") + [("mask", False, 16), ("coef", True, 4), ("slabs", False, 16), "snr", "mode"]
+                         + _PTR16("x_out", "x_mean_out") + [("step_out", True, 4), "batch", "C", "P"], True),
+    "md_sde_step": (_PTR16("x", "eps", "z") + [("mask", False, 16), ("coef", True, 4), "kind"] + _PTR16("x_out", "x_mean_out")
+                    + ["batch", "C", "P"], True),
+}
+
+
+@pytest.mark.parametrize("export", sorted(STEP_EXPORTS))
+def test_step_exports_refuse_bad_arguments_in_order(hip_lib, export):
+    """Null required pointers, a 16-byte operand at 8 mod 16, an element 2 bytes off, batch / C / P <= 0, P % 4 where the kernel
+    is four-wide, ch outside [0, C): MD_ERR_BAD_ARG before any launch.  Host addresses: nothing here may reach a kernel, so
+    what must be ACCEPTED -- a coefficient row 4 bytes into a 16-byte line, as coef[i] of a [N,B,3] table is; P % 4 != 0 in the
+    scalar kernels -- is probed only where no GPU is visible: there the launch itself fails, with another code."""
+    import ctypes as C
+    from meshdiffusion_amd import _lib
+    args, four_wide = STEP_EXPORTS[export]
+    buf = C.create_string_buffer(8192 * len(args) + 64)
+    base = (C.addressof(buf) + 63) & ~63
+    scalars = dict(batch=2, C=4, P=64, ch=0, src_bstride=0, snr=0.075, mode=0, kind=0)
+    good = {a[0]: base + 8192 * i for i, a in enumerate(args) if not isinstance(a, str)}   # distinct 8 KiB regions, 64-byte aligned
+    bad, fn = _lib.ERR_BAD_ARG, getattr(hip_lib, export)
+
+    def call(**change):
+        v = dict(scalars, **good)
+        v.update(change)
+        return fn(*[v[a] if isinstance(a, str) else C.c_void_p(v[a[0]]) for a in args], C.c_void_p(0))
+
+    for name, required, align in (a for a in args if not isinstance(a, str)):
+        if required:
+            assert call(**{name: 0}) == bad, (name, "null")
+        if align == 16:
+            assert call(**{name: good[name] + 8}) == bad, (name, "8 mod 16")
+        assert call(**{name: good[name] + 2}) == bad, (name, "2 bytes into an element")
+    for name in ("batch", "C", "P"):
+        assert call(**{name: 0}) == bad and call(**{name: -1}) == bad, name
+    if four_wide:
+        assert call(P=66) == bad
+    if "ch" in args:                                                                      # (md_ddim_step: with its partial, as here)
+        assert call(ch=-1) == bad and call(ch=4) == bad
+    if export == "md_ddim_step":
+        assert call(partial=0) == bad and call(pmask=0) == bad                            # one without the other
+    if export == "md_langevin_step":
+        assert call(mode=7) == bad and call(slabs=0) == bad and call(slabs=0, mode=1, P=66) == bad
+    if export == "md_sde_step":
+        assert call(kind=2) == bad
+    if not torch.cuda.is_available():
+        probes = [dict(coef=good["coef"] + 4)] if "coef" in good and export != "md_ddim_step" else []
+        probes += [dict(P=66), dict(P=1)] if not four_wide else []
+        probes += [dict(slabs=0, mode=1)] if export == "md_langevin_step" else []         # ALD reads no slabs
+        for change in probes:
+            assert call(**change) not in (bad, _lib.OK), change

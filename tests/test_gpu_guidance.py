@@ -15,13 +15,19 @@ from conftest import ROOT, rel_l2
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 4), (3, 64), (2, 16 ** 3)]
+# the last two: one channel of 1028 values (257 threads: a last workgroup of one lane), and B = 8 with C*P = 4*(32^3 + 4) =
+# 131088 values, 16 past the 131072 that one trip of md_guide_apply's 128 workgroups covers
+SHAPES = [(1, 4), (3, 64), (2, 16 ** 3), (1, 1028), (8, 32 ** 3 + 4)]
 C = 4
 
 
+def _channels(P):
+    return 1 if P == 1028 else C
+
+
 def _levels(B):
-    """(alpha, sigma) rows of the levels t = 1e-3, 0.5, 1 (one per sample)."""
-    return np.array([lc.vp_coefficients_f64(t)[2:] for t in (1e-3, 0.5, 1.0)][:B])
+    """(alpha, sigma) rows of the levels t = 1e-3, 0.5, 1, ... (one per sample)."""
+    return np.array([lc.vp_coefficients_f64(t)[2:] for t in (1e-3, 0.5, 1.0, 0.25, 0.75, 0.1, 0.9, 0.6)][:B])
 
 
 # ---- md_guide_residual ------------------------------------------------------------------------------------------------------
@@ -32,6 +38,8 @@ def _levels(B):
 def test_guide_residual_kernel(hip_lib, B, P, ch, masked, per_sample):
     from meshdiffusion_amd import hip_ops as ops
     g = torch.Generator().manual_seed(B * 1000 + P + ch)
+    C = _channels(P)
+    ch = min(ch, C - 1)
     x, e = (torch.randn((B, C, P), generator=g) for _ in range(2))
     src = torch.sign(torch.randn((B, P) if per_sample else (P,), generator=g))
     pm = (torch.rand(P, generator=g) < 0.5).float()
@@ -71,13 +79,14 @@ def test_guide_apply_kernels(hip_lib, B, P, masked):
     """The slabs are GIVEN (arbitrary positive doubles), so that the two kernels are pinned apart from md_guide_residual."""
     from meshdiffusion_amd import hip_ops as ops
     g = torch.Generator().manual_seed(B * 77 + P)
+    C = _channels(P)
     x, xm, cot, jt = (torch.randn((B, C, P), generator=g) for _ in range(4))
     gm = (torch.rand(P, generator=g) < 0.6).float() if masked else None
     if masked:
         gm[0] = 1.0
     gm_np, gm_cu = (gm.numpy(), gm.cuda()) if masked else (None, None)
     slabs = torch.rand((B, gc.SLABS), generator=g, dtype=torch.float64) * 10.0 ** torch.randint(-3, 4, (B, gc.SLABS), generator=g).double()
-    coef = np.concatenate([_levels(B), np.array([[1.0], [0.3], [2.5]])[:B]], axis=1)
+    coef = np.concatenate([_levels(B), np.array([[1.0], [0.3], [2.5], [0.7], [1.5], [0.1], [4.0], [0.9]])[:B]], axis=1)
     x64 = (x.double() + 1e-9 * torch.randn((B, C, P), generator=g, dtype=torch.float64))
 
     def run32(coef, slabs, with_mean=True):

@@ -295,17 +295,19 @@ def test_temb_and_linear(ops):
 
 
 def test_ancestral_step_bit_exact(ops):
+    """An 8^3 grid, then flat grids at the edges of the launch: 1028 values (257 threads: a last workgroup of one lane), 131088
+    values per sample, and 2097156, four past what one trip of the kernel's 2048 workgroups covers."""
     from oracle import unet_oracle as uo
-    B, Cc, S = 2, 4, 8
-    x, e, z = _rand((B, Cc, S, S, S), 28), _rand((B, Cc, S, S, S), 29), _rand((B, Cc, S, S, S), 30)
-    mask = (torch.rand(S, S, S, generator=torch.Generator().manual_seed(31)) < 0.3).float()
     t = torch.tensor(0.731)
     betas, _, sq1m = uo.vpsde_tables()
     k = (t * 999).long()
-    coef = torch.stack([betas[k], sq1m[k], torch.sqrt(1.0 - betas[k]), torch.sqrt(betas[k])]).expand(B, 4).contiguous()
-    xn, xm = ops.ancestral_step(x.cuda(), e.cuda(), z.cuda(), mask.reshape(-1).cuda(), coef.cuda())
-    rn, rm = uo.ancestral_step(x, e, z, t, mask)
-    assert torch.equal(xm.cpu(), rm) and torch.equal(xn.cpu(), rn)
+    for B, Cc, grid in ((2, 4, (8, 8, 8)), (1, 1, (1, 1, 1028)), (8, 4, (1, 1, 32 ** 3 + 4)), (1, 1, (1, 1, 2097156))):
+        x, e, z = _rand((B, Cc) + grid, 28), _rand((B, Cc) + grid, 29), _rand((B, Cc) + grid, 30)
+        mask = (torch.rand(grid, generator=torch.Generator().manual_seed(31)) < 0.3).float()
+        coef = torch.stack([betas[k], sq1m[k], torch.sqrt(1.0 - betas[k]), torch.sqrt(betas[k])]).expand(B, 4).contiguous()
+        xn, xm = ops.ancestral_step(x.cuda(), e.cuda(), z.cuda(), mask.reshape(-1).cuda(), coef.cuda())
+        rn, rm = uo.ancestral_step(x, e, z, t, mask)
+        assert torch.equal(xm.cpu(), rm) and torch.equal(xn.cpu(), rn), (B, Cc, grid)
 
 
 def test_inpaint_blend_and_renoise(ops):

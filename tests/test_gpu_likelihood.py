@@ -17,17 +17,19 @@ pytestmark = pytest.mark.gpu
 # ---- md_pf_ode_rhs ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("with_div", [False, True])
 @pytest.mark.parametrize("masked", [False, True])
-@pytest.mark.parametrize("B,P", [(3, 64), (2, 16 ** 3)])
+@pytest.mark.parametrize("B,P", [(3, 64), (2, 16 ** 3), (1, 1028), (8, 32 ** 3 + 4)])
 def test_pf_ode_rhs_kernel(hip_lib, B, P, masked, with_div):
+    """The last two shapes are flat grids.  P = 1028 with one channel: 257 threads, a last workgroup of one lane.  B = 8, C = 4,
+    P = 32^3 + 4: C*P = 131088 is 16 past the 131072 values one trip of the 128 workgroups covers (without the divergence)."""
     from meshdiffusion_amd import _lib, hip_ops as ops
     g = torch.Generator().manual_seed(B * 1000 + P)
-    C = 4
+    C = 1 if P == 1028 else 4
     side = round(P ** (1 / 3))
-    shape = (B, C, side, side, side)
+    shape = (B, C, side, side, side) if side ** 3 == P else (B, C, 1, 1, P)
     x, e, jt = (torch.randn(shape, generator=g) for _ in range(3))
     probe = torch.randint(0, 2, shape, generator=g).float() * 2 - 1
     mask = (torch.rand(P, generator=g) < 0.3).float() if masked else None
-    coef = np.array([lc.vp_coefficients_f64(t)[:2] for t in (1e-3, 0.5, 1.0)][:B])
+    coef = np.array([lc.vp_coefficients_f64(t)[:2] for t in (1e-3, 0.5, 1.0, 0.25, 0.75, 0.1, 0.9, 0.6)][:B])
     kw = dict(g=jt.cuda(), probe=probe.cuda()) if with_div else {}
     args = (x.cuda(), e.cuda(), mask.cuda() if masked else None, torch.from_numpy(coef).cuda())
     drift, div = ops.pf_ode_rhs(*args, **kw)

@@ -25,13 +25,20 @@ def env(hip_lib):
     return dict(synth=synth, mutils=mutils, ops=hip_ops, sampling=sampling, sde_lib=sde_lib)
 
 
+# flat grids (C, P) next to the cubes: 1028 values end in a workgroup of one wave's first lane (1028 / 4 = 257 threads), and
+# 4 * (32^3 + 4) = 131088 values are 16 past the 131072 that one trip of stream_blocks' 128 workgroups covers at B = 8
+FLAT_ODD, FLAT_TWO_TRIPS = (1, 1028), (4, 32 ** 3 + 4)
+
+
 def _inputs(B, R, seed, masked):
+    """R: the edge of a cubic grid of 4 channels, or (C, P) for a flat grid [1, 1, P] of C channels."""
     g = torch.Generator().manual_seed(seed)
-    x, eps, z = (torch.randn((B, 4, R, R, R), generator=g).cuda() for _ in range(3))
+    Cc, grid = (4, (R, R, R)) if isinstance(R, int) else (R[0], (1, 1, R[1]))
+    x, eps, z = (torch.randn((B, Cc) + grid, generator=g).cuda() for _ in range(3))
     mask = None
     if masked:
         from meshdiffusion_amd import synth
-        mask = synth.synthetic_grid_mask(R).cuda()
+        mask = synth.synthetic_grid_mask(R).cuda() if isinstance(R, int) else (torch.rand(grid, generator=g) < 0.6).float().cuda()
         x = x * mask
     return x, eps, z, mask
 
@@ -43,20 +50,24 @@ def _rows(env, B, pred, corr, snr, pf, seed):
     ts = torch.linspace(1.0, 1e-3, 1000, device="cuda")
     pc, cc = sampling._pc_tables(sde, ts, 1, pred, corr, snr, pf)
     idx = torch.randint(0, 999, (B,), generator=torch.Generator().manual_seed(seed)).cuda()
-    return (None if pc is None else pc[idx, 0].contiguous()), (None if cc is None else cc[idx, 0].contiguous())
+    # the rows start 4 bytes into their allocation, as a sampler's coef[i] may: the exports ask the coefficients for no more
+    off4 = lambda t: None if t is None else torch.cat([t.new_zeros(1), t[idx, 0].reshape(-1)])[1:].view(B, -1)   # noqa: E731
+    return off4(pc), off4(cc)
 
 
 def _masked(t, mask):
     return t if mask is None else t * mask.view(1, 1, *mask.shape)
 
 
-@pytest.mark.parametrize("B", [1, 3, 8])
+@pytest.mark.parametrize("dims", [1, 3, 8, pytest.param((1, FLAT_ODD), id="1x1x1028"), pytest.param((8, FLAT_TWO_TRIPS), id="8x4x32772")])
 @pytest.mark.parametrize("masked", [False, True])
 @pytest.mark.parametrize("kind,pf", [("reverse_diffusion", False), ("reverse_diffusion", True), ("euler_maruyama", False)])
-def test_sde_step_bit_identical_to_reference_expression(env, B, masked, kind, pf):
+def test_sde_step_bit_identical_to_reference_expression(env, dims, masked, kind, pf):
+    """dims: B on the 16^3 grid, or (B, (C, P)) on a flat one."""
     sampling, ops = env["sampling"], env["ops"]
     pred = sampling.get_predictor(kind)
-    x, eps, z, mask = _inputs(B, 16, seed=10 + B, masked=masked)
+    B, R = (dims, 16) if isinstance(dims, int) else dims
+    x, eps, z, mask = _inputs(B, R, seed=10 + B, masked=masked)
     coef, _ = _rows(env, B, pred, sampling.NoneCorrector, 0.075, pf, seed=B)
     with torch.no_grad():
         torch.cuda.set_sync_debug_mode("error")
@@ -91,14 +102,17 @@ def _langevin_expr(x, eps, z, sigma, step, mask):
     return _masked(xn, mask), _masked(x_mean, mask)
 
 
-@pytest.mark.parametrize("B,R,masked", [(1, 16, False), (3, 16, True), (8, 16, True), (8, 64, True)])
+@pytest.mark.parametrize("B,R,masked", [(1, 16, False), (3, 16, True), (8, 16, True), (8, 64, True),
+                                        pytest.param(1, FLAT_ODD, True, id="1-1x1028-True"),
+                                        pytest.param(8, FLAT_TWO_TRIPS, False, id="8-4x32772-False")])
 @pytest.mark.parametrize("mode", ["langevin", "ald"])
 def test_langevin_step_vs_reference_and_deterministic(env, B, R, masked, mode):
     sampling, ops = env["sampling"], env["ops"]
     snr = 0.16
-    x, eps, z, mask = _inputs(B, R, seed=20 + B + R, masked=masked)
+    salt = R if isinstance(R, int) else R[1]
+    x, eps, z, mask = _inputs(B, R, seed=20 + B + salt, masked=masked)
     eps = eps * torch.linspace(0.5, 2.0, B, device="cuda")[B5]       # samples of different norm: the mean is not trivial
-    _, coef = _rows(env, B, sampling.AncestralSamplingPredictor, sampling.get_corrector(mode), snr, False, seed=B + R)
+    _, coef = _rows(env, B, sampling.AncestralSamplingPredictor, sampling.get_corrector(mode), snr, False, seed=B + salt)
     gm = None if mask is None else mask.reshape(-1).float().contiguous()
     with torch.no_grad():
         torch.cuda.set_sync_debug_mode("error")
@@ -113,7 +127,7 @@ def test_langevin_step_vs_reference_and_deterministic(env, B, R, masked, mode):
             nn_ = z.double().reshape(B, -1).norm(dim=1).mean()
             want = (snr * nn_ / gn) ** 2 * 2 * alpha.double()
             err = float(((step.double() - want).abs() / want).max())
-            print(f"Langevin step size vs fp64 restatement (B={B}, R={R}): max rel {err:.2e}")
+            print(f"Langevin step size vs fp64 restatement (B={B}, grid {R}): max rel {err:.2e}")
             assert err <= 1e-6
         else:
             assert torch.equal(step, coef[:, 2])

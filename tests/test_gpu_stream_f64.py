@@ -1,5 +1,6 @@
 """The streaming kernels on their own, against float64, at their edges: GroupNorm (csrc/norm.hip), the training step
-(csrc/train.hip) and the small kernels of csrc/elementwise.hip.
+(csrc/train.hip) and the small kernels of csrc/elementwise.hip: dense layer, timestep embedding, layout conversion (the sampler
+updates are in csrc/sde_steps.hip and have their own tests).
 
 Everything is called through hip_ops, losses and _lib.load().  Inputs, float64 references and the bounds live in
 tests/stream_cases.py; every bound is derived by counting the roundings of the kernel source (its docstring has the count),
