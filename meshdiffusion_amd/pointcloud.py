@@ -6,8 +6,9 @@ The reference's fitting step adds one loss that needs no renderer (nvdiffrec/lib
     chamfer     = kaolin.metrics.pointcloud.chamfer_distance(pred_points[None], target['spts'][None]).mean()
 
 `sample_points` has the signature and return shapes of the reference's pure-torch copy (geometry/utils.py:55),
-`chamfer_distance` / `sided_distance` those of kaolin.metrics.pointcloud, and `fit_to_points` is the geometry part of
-`DMTetGeometry.tick` (chamfer + the SDF regulariser with its schedule).  Everything runs on the GPU only: a CPU tensor is an
+`chamfer_distance` / `sided_distance` those of kaolin.metrics.pointcloud.  The loop around them, `fit_to_points` (the geometry
+part of `DMTetGeometry.tick`: chamfer + the SDF regulariser with its schedule, `sdf_regularizer_weight`), lives with the other
+fits in fit.py and is still found here by name.  Everything runs on the GPU only: a CPU tensor is an
 error, not a fallback.  Gradients are gathers over a CSR built with torch ops on the device (stable sort of the dynamic
 indices); the summation is the kernel, so two backward passes agree bit for bit.
 """
@@ -207,41 +208,12 @@ def sample_points(vertices, faces, num_samples, areas=None, face_features=None, 
     return points, choices, feats
 
 
-# ---- the fitting loop -----------------------------------------------------------------------------------------------------
-def sdf_regularizer_weight(iteration, iters, sdf_regularizer):
-    """dmtet.py:440-441: falls linearly from `sdf_regularizer` to 0.01 over the first quarter of the run."""
-    return sdf_regularizer - (sdf_regularizer - 0.01) * min(1.0, 4.0 * (iteration / iters))
+_IN_FIT = ("sdf_regularizer_weight", "fit_to_points")
 
 
-def fit_to_points(geometry, target_points, iters, *, num_samples=50000, lr=0.01, sdf_regularizer=0.2, generator=None,
-                  callback=None, uniforms=None):
-    """Fit a `DMTetGeometry` to target points [P,3] without a renderer: per iteration
-        getMesh -> sample_points(num_samples) -> chamfer_distance(pred, target) + sdf_reg_loss(masked sdf) * weight * 0.1
-        -> Adam step on (sdf, deform) -> clamp_deform,
-    with the reference's regulariser schedule and `valid_vert_idx` detach mask (dmtet.py:441-446, 454-459).
-    `uniforms(it)` may supply the iteration's (r_face, r_u, r_v), each [1,num_samples]; else torch.rand(generator=generator).
-    `callback(it, chamfer, mesh)` is called after each step.  Returns the chamfer values, float32 [iters] on the device."""
-    from .dmtet import sdf_reg_loss
-    _gpu_only(target_points, "fit_to_points")
-    target = target_points.detach().to(torch.float32).reshape(1, -1, 3).contiguous()
-    opt = torch.optim.Adam([geometry.sdf, geometry.deform], lr=lr)
-    history = []
-    for it in range(iters):
-        opt.zero_grad(set_to_none=True)
-        mesh = geometry.getMesh()
-        if mesh.t_pos_idx.shape[0] == 0:
-            raise _lib.MeshDiffusionHipError(f"fit_to_points: the mesh of iteration {it} has no faces")
-        u = uniforms(it) if uniforms is not None else None
-        pred = sample_points(mesh.v_pos[None], mesh.t_pos_idx, num_samples, uniforms=u, generator=generator)[0]
-        chamfer = chamfer_distance(pred, target).mean()
-        sdf_mask = torch.zeros_like(geometry.sdf)
-        sdf_mask[mesh.valid_vert_idx] = 1.0
-        sdf_masked = geometry.sdf.detach() * sdf_mask + geometry.sdf * (1 - sdf_mask)
-        reg = sdf_reg_loss(sdf_masked, geometry.all_edges).mean() * sdf_regularizer_weight(it, iters, sdf_regularizer) * 0.1
-        (chamfer + reg).backward()
-        opt.step()
-        geometry.clamp_deform()
-        history.append(chamfer.detach())
-        if callback is not None:
-            callback(it, history[-1], mesh)
-    return torch.stack(history) if history else torch.empty(0, device=target.device)
+def __getattr__(name):
+    """The fitting loop is in fit.py, which imports this module: its names are handed out from there on first use."""
+    if name in _IN_FIT:
+        from . import fit
+        return getattr(fit, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -3,22 +3,23 @@
 The reference gets its depth buffers from nvdiffrast (nvdiffrec/lib/render/render.py:287-329): `xfm_points` -> two depth-peeled
 layers -> `interpolate(v_pos)` -> |gb_pos - campos|, and supervises the geometry with the depth terms of `DMTetGeometry.tick`
 (nvdiffrec/lib/geometry/dmtet.py:402-434) and the silhouette carve (:366-378).  This module is that path: `rasterize` and
-`render_depth` follow the rasterisation contract in the header comment of csrc/raster.hip, `depth_loss`, `make_targets`,
-`carve_outside_silhouette` and `fit_to_views` are the loop around it.  `edge_neighbours` and `antialias` follow the antialiasing
+`render_depth` follow the rasterisation contract in the header comment of csrc/raster.hip and `make_targets` renders what a fit
+is supervised with; the losses, the carve and the loops around them (`depth_loss`, `carve_outside_silhouette`, `fit_to_views`, ...)
+are plain torch and live in fit.py, still found here by name.  `edge_neighbours` and `antialias` follow the antialiasing
 contract in the header comment of csrc/antialias.hip: silhouette antialiasing in the manner of dr.antialias (render.py:256-276),
 not equal to it, with gradients for the colour and the clip-space vertices.  `render_depth(antialias=True)` adds the antialiased
-coverage of both layers and `silhouette_loss` is the coverage term of tick (dmtet.py:394,399), the one path from a silhouette to
-the vertices.  `interpolate`, `rasterize(grad=True)` and `dmtet.vertex_normals` follow the interpolation contract in the header
+coverage of both layers, the one path from a silhouette to the vertices (the coverage term of tick, dmtet.py:394,399, is
+`fit.silhouette_loss`).  `interpolate`, `rasterize(grad=True)` and `dmtet.vertex_normals` follow the interpolation contract in the header
 comment of csrc/interp.hip: dr.interpolate, the `rast` gradient of dr.rasterize and auto_normals under autograd.  On top of them
-`render_buffers` is the reference's `bsdf == 'normal'` renderer (render.py:105-106, 177-264) and `image_loss` / `color_loss` the
-colour term of tick (dmtet.py:391-400).  `laplace_regularizer_const`, `depth_loss_fixedtopo` and `fit_fixed_topology` are pass 2 of
-the reference's fit (fit_dmtets.py:758-793) on a `dmtet.DMTetGeometryFixedTopo`, by the fixed-topology contract in the header
-comment of csrc/fixedtopo.hip.  `shade_diffuse` and `render_preview` are the quick-look image the reference renders of every sampled
+`render_buffers` is the reference's `bsdf == 'normal'` renderer (render.py:105-106, 177-264), which the colour term of tick
+(dmtet.py:391-400: `fit.image_loss` / `fit.color_loss`) reads.  `laplace_regularizer_const` is the regulariser of pass 2 of the
+reference's fit (fit_dmtets.py:758-793: `fit.fit_fixed_topology`), by the fixed-topology contract in the header comment of
+csrc/fixedtopo.hip.  `shade_diffuse` and `render_preview` are the quick-look image the reference renders of every sampled
 mesh (nvdiffrec/eval.py:421-438: `bsdf == 'diffuse'`, kd = (0.75, 0.3, 0.6), an environment light, the two-sided geometric normal)
 by the shading part of the mesh post-processing contract in the header comment of csrc/meshpost.hip: in the manner of that image,
 not equal to it -- the environment comes in as nine spherical-harmonic coefficients (`sh9_from_latlong`, `default_light`), which
 stand in for the reference's cosine-convolved cube map, and `preview_camera` is its `rotate_scene`.  The kernels run on the GPU
-only: a CPU tensor is an error, not a fallback.  The camera helpers, `xfm_points`, `shading_normal`, the losses and the carve are plain torch and run
+only: a CPU tensor is an error, not a fallback.  The camera helpers, `xfm_points` and `shading_normal` are plain torch and run
 anywhere; `sh9_from_latlong` and `default_light` are numpy on the host.
 
 Not built: materials beyond one diffuse colour, specular / PBR shading, cube maps and `.hdr` loading,
@@ -599,58 +600,21 @@ def render_buffers(verts, faces, mvp, campos, resolution, v_nrm=None, neighbours
     return out
 
 
-# ---- losses and the fitting loop ---------------------------------------------------------------------------------------------------
-def depth_loss(buffers, target, iteration):
-    """The depth terms of DMTetGeometry.tick (dmtet.py:402-434) with no_depth_thin: elementwise torch.
-    buffers: `depth`, `depth_second`; target: `depth`, `depth_second`, `mask_cont`, all [B,H,W,1]."""
-    mask = (target["mask_cont"][..., 0] == 1.0).float().unsqueeze(-1)
-    valid = (target["depth_second"] >= 0).float()
-    prox = ((target["depth_second"] - target["depth"]).abs() >= 5e-3).float()
-    d1 = (buffers["depth"][..., :1] - target["depth"][..., :1]).abs() * mask * valid
-    d2 = (buffers["depth_second"][..., :1] - target["depth_second"][..., :1]).abs() * mask * valid * prox * 0.1
-    scale = 100.0 if iteration < 10000 else 1.0
-
-    def huber(d):
-        return torch.where(d < 1.0, d, d * d)
-    return (huber(d1).mean() + huber(d2).mean()) * scale
+# ---- the targets of a fit (the losses and the loops are in fit.py) ------------------------------------------------------------------
+_IN_FIT = ("depth_loss", "depth_loss_fixedtopo", "silhouette_loss", "color_loss", "image_loss", "IMAGE_LOSSES", "lr_schedule_fixedtopo",
+           "_select_views", "carve_outside_silhouette", "fit_to_views", "fit_fixed_topology")
 
 
-def silhouette_loss(buffers, target):
-    """The coverage term of DMTetGeometry.tick (dmtet.py:394,399): mse(alpha) + 0.1 mse(alpha_second), all [B,H,W,1]."""
-    mse = torch.nn.functional.mse_loss
-    return mse(buffers["alpha"], target["alpha"]) + 0.1 * mse(buffers["alpha_second"], target["alpha_second"])
-
-
-IMAGE_LOSSES = ("smape", "mse", "logl1", "logl2", "relmse")
+def __getattr__(name):
+    """The fitting stack moved to fit.py, which imports this module: its names are handed out from there on first use."""
+    if name in _IN_FIT:
+        from . import fit
+        return getattr(fit, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _tonemap_srgb(f):
     return torch.where(f > 0.0031308, torch.pow(torch.clamp(f, min=0.0031308), 1.0 / 2.4) * 1.055 - 0.055, 12.92 * f)
-
-
-def image_loss(img, ref, kind):
-    """The reference's createLoss(kind)(img, ref) (fit_dmtets.py:65-77, renderutils/loss.py): `smape`, `mse`, `relmse` on the
-    images as they are, `logl1` / `logl2` the L1 / MSE of tonemap_srgb(log(clamp(x, 0, 65535) + 1)).  Plain torch."""
-    if kind not in IMAGE_LOSSES:
-        raise ValueError(f"image_loss: kind must be one of {IMAGE_LOSSES}, got {kind!r}")
-    if kind in ("logl1", "logl2"):
-        img = _tonemap_srgb(torch.log(torch.clamp(img, min=0, max=65535) + 1))
-        ref = _tonemap_srgb(torch.log(torch.clamp(ref, min=0, max=65535) + 1))
-    if kind in ("mse", "logl2"):
-        return torch.nn.functional.mse_loss(img, ref)
-    if kind == "smape":
-        return torch.mean(torch.abs(img - ref) / (torch.abs(img) + torch.abs(ref) + 0.01))
-    if kind == "relmse":
-        return torch.mean((img - ref) * (img - ref) / (img * img + ref * ref + 0.1))
-    return torch.nn.functional.l1_loss(img, ref)
-
-
-def color_loss(buffers, target, kind="logl1"):
-    """The colour term of DMTetGeometry.tick (dmtet.py:395,400): image_loss(shaded rgb x ref alpha, ref rgb x ref alpha) of layer
-    1 plus 0.1 times that of `shaded_second` / `img_second`.  The alpha terms of those lines are `silhouette_loss`."""
-    ref, ref2 = target["img"], target["img_second"]
-    return (image_loss(buffers["shaded"][..., 0:3] * ref[..., 3:], ref[..., 0:3] * ref[..., 3:], kind)
-            + 0.1 * image_loss(buffers["shaded_second"][..., 0:3] * ref2[..., 3:], ref2[..., 0:3] * ref2[..., 3:], kind))
 
 
 @torch.no_grad()
@@ -672,116 +636,6 @@ def make_targets(verts, faces, mvp, campos, resolution, antialias=False, shaded=
     if shaded:
         tgt["img"], tgt["img_second"] = out["shaded"], out["shaded_second"]
     return tgt
-
-
-@torch.no_grad()
-def carve_outside_silhouette(geometry, target, kernel_size=11):
-    """The carve of tick (dmtet.py:366-378): project the deformed grid vertices, round to pixels, dilate `mask_cont` with a
-    `kernel_size` box; where a vertex lands on a pixel whose dilated mask is 0 in ANY view, sdf = 1e-2 and deform = 0.
-    x is scaled with the width and y with the height.  Returns the number of vertices carved."""
-    v = geometry.get_deformed().detach()
-    H, W = target["resolution"]
-    clip = xfm_points(v[None], target["mvp"])
-    ndc = clip[..., :2] / clip[..., 3:4]
-    px = torch.round((ndc[..., 0] * 0.5 + 0.5).clip(0, 1) * (W - 1)).long()
-    py = torch.round((ndc[..., 1] * 0.5 + 0.5).clip(0, 1) * (H - 1)).long()
-    m = target["mask_cont"][..., 0].unsqueeze(1)
-    box = torch.ones((1, 1, kernel_size, kernel_size), dtype=m.dtype, device=m.device) / (kernel_size * kernel_size)
-    dilated = torch.nn.functional.conv2d(m, box, stride=1, padding=kernel_size // 2)[:, 0]
-    outside = dilated == 0
-    carved = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
-    for k in range(outside.shape[0]):
-        carved |= outside[k, py[k], px[k]]
-    geometry.sdf.data[carved] = 1e-2
-    geometry.deform.data[carved] = 0.0
-    return int(carved.sum())
-
-
-def _select_views(targets, n_views, views_per_iter, generator, dev):
-    """The targets of one iteration: all of them, or `views_per_iter` views drawn without replacement (one torch.randperm)."""
-    if views_per_iter is None or views_per_iter >= n_views:
-        return targets
-    sel = torch.randperm(n_views, generator=generator, device=generator.device if generator is not None else "cpu")
-    sel = sel[:views_per_iter].to(dev)
-    return {key: (val[sel] if torch.is_tensor(val) and val.shape[0] == n_views else val) for key, val in targets.items()}
-
-
-def fit_to_views(geometry, targets, iters, *, lr=0.01, sdf_regularizer=0.2, views_per_iter=None, generator=None,
-                 target_points=None, num_samples=50000, carve=True, callback=None, start_iteration=0, alpha_weight=0.0,
-                 return_terms=False, color_weight=0.0, color_loss_kind="logl1"):
-    """Fit a `DMTetGeometry` to rendered targets (`make_targets`) the way the reference's tick supervises geometry: per
-    iteration
-        [carve, for 200 < it < 2000 and it % 20 == 0] -> [deform *= 0.4, for it % 300 == 0 and it < 1790]
-        -> getMesh -> render_depth on `views_per_iter` views -> depth_loss + sdf_reg_loss(masked sdf) * weight * 0.1
-        [+ alpha_weight * silhouette_loss, for alpha_weight > 0; the reference's weight is 1.0]
-        [+ color_weight * color_loss(color_loss_kind), for color_weight > 0: the mesh then comes from getMesh(normals_grad=True)
-           and is rendered with render_buffers; the reference's weight is 1.0 and its loss logl1]
-        [+ chamfer(sample_points(num_samples), target_points)] -> Adam step on (sdf, deform) -> clamp_deform.
-    views_per_iter: None = every view each iteration, else that many drawn without replacement (torch.randperm, `generator`).
-    `callback(it, loss, mesh)` after each step.  Returns the depth-loss values, float32 [iters] on the device; with
-    return_terms=True the dict {"depth": [iters], "alpha": [iters]} of both terms.  alpha_weight > 0 and return_terms need
-    targets made with `make_targets(..., antialias=True)`; color_weight > 0 needs `make_targets(..., shaded=True)` and adds
-    "color": [iters] to the dict of return_terms."""
-    from .dmtet import sdf_reg_loss
-    from .pointcloud import chamfer_distance, sample_points, sdf_regularizer_weight
-    dev = geometry.sdf.device
-    _gpu_only(geometry.sdf, "fit_to_views")
-    n_views = targets["mvp"].shape[0]
-    with_alpha = alpha_weight > 0 or return_terms
-    if with_alpha and not ("alpha" in targets and "alpha_second" in targets):
-        raise ValueError("fit_to_views: the alpha term needs targets made with make_targets(..., antialias=True)")
-    with_color = color_weight > 0
-    if with_color and not ("img" in targets and "img_second" in targets):
-        raise ValueError("fit_to_views: the colour term needs targets made with make_targets(..., shaded=True)")
-    pts = None if target_points is None else target_points.detach().to(device=dev, dtype=torch.float32).reshape(1, -1, 3).contiguous()
-    opt = torch.optim.Adam([geometry.sdf, geometry.deform], lr=lr)
-    history, alpha_history, color_history = [], [], []
-    for k in range(iters):
-        it = start_iteration + k
-        tgt = _select_views(targets, n_views, views_per_iter, generator, dev)
-        if carve and 200 < it < 2000 and it % 20 == 0:
-            carve_outside_silhouette(geometry, tgt)
-        if it % 300 == 0 and it < 1790:
-            with torch.no_grad():
-                geometry.deform.data[:] *= 0.4
-        opt.zero_grad(set_to_none=True)
-        mesh = geometry.getMesh(normals_grad=True) if with_color else geometry.getMesh()
-        if mesh.t_pos_idx.shape[0] == 0:
-            raise _lib.MeshDiffusionHipError(f"fit_to_views: the mesh of iteration {it} has no faces")
-        if with_color:
-            buffers = render_buffers(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"], v_nrm=mesh.v_nrm)
-        else:
-            buffers = render_depth(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"], antialias=with_alpha)
-        loss = depth_loss(buffers, tgt, it)
-        sdf_mask = torch.zeros_like(geometry.sdf)
-        sdf_mask[mesh.valid_vert_idx] = 1.0
-        sdf_masked = geometry.sdf.detach() * sdf_mask + geometry.sdf * (1 - sdf_mask)
-        total = loss + sdf_reg_loss(sdf_masked, geometry.all_edges).mean() * sdf_regularizer_weight(it, start_iteration + iters, sdf_regularizer) * 0.1
-        if with_alpha:
-            alpha = silhouette_loss(buffers, tgt)
-            alpha_history.append(alpha.detach())
-            if alpha_weight > 0:
-                total = total + alpha * alpha_weight
-        if with_color:
-            color = color_loss(buffers, tgt, color_loss_kind)
-            color_history.append(color.detach())
-            total = total + color * color_weight
-        if pts is not None:
-            pred = sample_points(mesh.v_pos[None], mesh.t_pos_idx, num_samples, generator=generator)[0]
-            total = total + chamfer_distance(pred, pts).mean()
-        total.backward()
-        opt.step()
-        geometry.clamp_deform()
-        history.append(loss.detach())
-        if callback is not None:
-            callback(it, history[-1], mesh)
-    depth_terms = torch.stack(history) if history else torch.empty(0, device=dev)
-    if return_terms:
-        terms = {"depth": depth_terms, "alpha": torch.stack(alpha_history) if alpha_history else torch.empty(0, device=dev)}
-        if with_color:
-            terms["color"] = torch.stack(color_history) if color_history else torch.empty(0, device=dev)
-        return terms
-    return depth_terms
 
 
 # ---- the fixed-topology second pass (fit_dmtets.py:758-793) --------------------------------------------------------------------------
@@ -834,103 +688,6 @@ def laplace_regularizer_const(v_pos, t_pos_idx, base=None, corner_csr=None):
         f = t_pos_idx.to(device=dev, dtype=torch.int64).contiguous()
         ptr, order = _check_corner_csr(corner_csr, V, f.shape[0], dev, "laplace_regularizer_const")
     return _LaplaceUmbrellaFn.apply(x, b, f, ptr, order)
-
-
-def depth_loss_fixedtopo(buffers, target):
-    """The depth term of DMTetGeometryFixedTopo.tick (dmtet_fixedtopo.py:326-337) as written there: the line that forms the
-    layer-1 difference (:333) is overwritten by the next one (:334), so the term is the SECOND layer only,
-        d = |depth_second - target depth_second| * mask * [target depth_second >= 0] * [|target depth_second - target depth| >= 5e-3] * 0.1,
-    Huber at 1 (d below 1, d^2 from there), mean, times 100; `buffers['depth']` does not enter.  Kept, not fixed.  The mask is
-    `target['mask_cont'][..., 0]` (the reference's `target['mask']`) as it is.  Elementwise torch."""
-    mask = target["mask_cont"][..., 0].unsqueeze(-1)
-    valid = ((target["depth_second"] >= 0).float() * ((target["depth_second"] - target["depth"]).abs() >= 5e-3).float()).detach()
-    d = (buffers["depth_second"][..., :1] - target["depth_second"][..., :1]).abs() * mask * valid * 1e-1
-    l1 = (d < 1.0).float()
-    return (l1 * d + (1 - l1) * d.pow(2)).mean() * 100.0
-
-
-def lr_schedule_fixedtopo(it, warmup_iter=100):
-    """fit_dmtets.py:396-399: it / warmup below warmup_iter, then 10^(-0.0002 (it - warmup))."""
-    if it < warmup_iter:
-        return it / warmup_iter
-    return max(0.0, 10 ** (-(it - warmup_iter) * 0.0002))
-
-
-def fit_fixed_topology(geometry, targets, iters, *, lr=0.01, laplace_scale=10000.0, warmup_iter=100, views_per_iter=None,
-                       generator=None, target_points=None, num_samples=50000, callback=None, alpha_weight=0.0,
-                       return_terms=False, color_weight=0.0, color_loss_kind="logl1"):
-    """Pass 2 of the reference's fit (fit_dmtets.py:758-793, DMTetGeometryFixedTopo.tick): fine-tune the `deform` of a
-    `dmtet.DMTetGeometryFixedTopo` on its frozen topology.  Per iteration
-        getMesh (through the plan) -> render_depth, or render_buffers when color_weight > 0, on `views_per_iter` views, with the
-        plan's neighbours and corner CSR -> depth_loss_fixedtopo
-        [+ laplace_regularizer_const(v_pos, faces, base=initial_guess_v_pos) * laplace_scale * (1 - it / iters) * 1e-2, for laplace_scale > 0]
-        [+ alpha_weight * mse(alpha), layer 1 only (:318)] [+ color_weight * image_loss(color_loss_kind), layer 1 only (:319-322)]
-        [+ chamfer(sample_points(num_samples), target_points)]
-        -> Adam step on deform, LambdaLR(lr_schedule_fixedtopo) step -> clamp_deform.
-    `callback(it, loss, mesh)` after each step.  Returns the depth terms, float32 [iters] on the device; with return_terms=True
-    the dict {"depth", "laplace", "alpha"[, "color"]} of the unweighted terms per iteration (device tensors; the Laplacian and
-    alpha terms are then computed even at weight 0, and added to the loss only above it).  The alpha term needs targets made
-    with `make_targets(..., antialias=True)`, the colour term `make_targets(..., shaded=True)`."""
-    from .pointcloud import chamfer_distance, sample_points
-    _gpu_only(geometry.deform, "fit_fixed_topology")
-    dev = geometry.deform.device
-    n_views = targets["mvp"].shape[0]
-    with_alpha = alpha_weight > 0 or return_terms
-    if with_alpha and "alpha" not in targets:
-        raise ValueError("fit_fixed_topology: the alpha term needs targets made with make_targets(..., antialias=True)")
-    with_color = color_weight > 0
-    if with_color and "img" not in targets:
-        raise ValueError("fit_fixed_topology: the colour term needs targets made with make_targets(..., shaded=True)")
-    with_laplace = laplace_scale > 0 or return_terms
-    pts = None if target_points is None else target_points.detach().to(device=dev, dtype=torch.float32).reshape(1, -1, 3).contiguous()
-    opt = torch.optim.Adam([geometry.deform], lr=lr)
-    sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda it: lr_schedule_fixedtopo(it, warmup_iter))
-    hist = {"depth": [], "laplace": [], "alpha": [], "color": []}
-    for it in range(iters):
-        tgt = _select_views(targets, n_views, views_per_iter, generator, dev)
-        opt.zero_grad(set_to_none=True)
-        plan = geometry.plan
-        mesh = geometry.getMesh(normals_grad=True) if with_color else geometry.getMesh()
-        if with_color:
-            buffers = render_buffers(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"], v_nrm=mesh.v_nrm,
-                                     neighbours=plan.neighbours, corner_csr=plan.corner_csr)
-        else:
-            buffers = render_depth(mesh.v_pos, mesh.t_pos_idx, tgt["mvp"], tgt["campos"], tgt["resolution"], antialias=with_alpha,
-                                   neighbours=plan.neighbours)
-        loss = depth_loss_fixedtopo(buffers, tgt)
-        total = loss
-        if with_laplace:
-            lap = laplace_regularizer_const(mesh.v_pos, mesh.t_pos_idx, base=geometry.initial_guess_v_pos, corner_csr=plan.corner_csr)
-            hist["laplace"].append(lap.detach())
-            if laplace_scale > 0:
-                total = total + lap * (laplace_scale * (1 - it / iters) * 1e-2)
-        if with_alpha:
-            alpha = torch.nn.functional.mse_loss(buffers["alpha"], tgt["alpha"])
-            hist["alpha"].append(alpha.detach())
-            if alpha_weight > 0:
-                total = total + alpha * alpha_weight
-        if with_color:
-            ref = tgt["img"]
-            color = image_loss(buffers["shaded"][..., 0:3] * ref[..., 3:], ref[..., 0:3] * ref[..., 3:], color_loss_kind)
-            hist["color"].append(color.detach())
-            total = total + color * color_weight
-        if pts is not None:
-            pred = sample_points(mesh.v_pos[None], mesh.t_pos_idx, num_samples, generator=generator)[0]
-            total = total + chamfer_distance(pred, pts).mean()
-        total.backward()
-        opt.step()
-        sched.step()
-        geometry.clamp_deform()
-        hist["depth"].append(loss.detach())
-        if callback is not None:
-            callback(it, hist["depth"][-1], mesh)
-
-    def stacked(xs):
-        return torch.stack(xs) if xs else torch.empty(0, device=dev)
-    if return_terms:
-        keys = ("depth", "laplace", "alpha") + (("color",) if with_color else ())
-        return {k: stacked(hist[k]) for k in keys}
-    return stacked(hist["depth"])
 
 
 # ---- the diffuse preview (nvdiffrec/eval.py:421-438) ---------------------------------------------------------------------------------

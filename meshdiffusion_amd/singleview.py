@@ -9,16 +9,16 @@ fixed-topology pass and a labelling of every tetrahedron as seen or occluded fro
                                 kernels run on the GPU only: a CPU tensor is an error, not a fallback
   single_view_partial           geometry + one view (or several: their union) -> the dict, on the CPU
   init_with_gt_surface          dmtet_singleview.py:421-435, the nearest visible face through `pointcloud._nn` (md_nn_sided)
-  carve_single_view             the carve of the single-view tick (:447-458), plain torch
-  fit_single_view               the reference's loop (fit_singleview.py:489-502) around that tick (:438-516)
 
-tools/fit_singleview.py is the command line around them.
+The rest of the single-view tick is plain torch and lives with the other fits in fit.py: `carve_single_view` (:447-458),
+`depth_loss_single_view` (:474-490) and `fit_single_view`, the reference's loop (fit_singleview.py:489-502) around that tick
+(:438-516); they are still found here by name.  tools/fit_singleview.py is the command line around them.
 """
 import torch
 
 from . import _lib
 from .hip_ops import call
-from .render import MAX_RES, MAX_VIEWS, _gpu_only, image_loss, rasterize, render_buffers, render_depth, xfm_points
+from .render import MAX_RES, MAX_VIEWS, _gpu_only, rasterize, xfm_points
 
 MAX_RADIUS = 15                          # VS_MAX_RADIUS of csrc/visibility.hip
 EMPTY_DEPTH = 100.0                      # VS_EMPTY
@@ -174,107 +174,12 @@ def init_with_gt_surface(geometry, gt_verts, surface_faces, campos):
     return int(outside.sum())
 
 
-@torch.no_grad()
-def carve_single_view(geometry, target):
-    """The carve of the single-view tick (dmtet_singleview.py:447-458): project the deformed grid vertices, clip the unit
-    coordinates to [0, 1], scale and TRUNCATE them to pixels (`.long()`: no rounding, no dilation); where a vertex lands on a
-    pixel whose `mask_cont` is 0 in a view, sdf = |sdf|.clamp(0, 1), view after view.  x is scaled with the width and y with
-    the height (the reference asserts a square image).  Plain torch.  Returns the number of vertices carved."""
-    v = geometry.get_deformed().detach()
-    H, W = target["resolution"]
-    clip = xfm_points(v[None], target["mvp"])
-    ndc = clip[..., :2] / clip[..., 3:4]
-    px = ((ndc[..., 0] * 0.5 + 0.5).clip(0, 1) * (W - 1)).long()
-    py = ((ndc[..., 1] * 0.5 + 0.5).clip(0, 1) * (H - 1)).long()
-    empty = target["mask_cont"][..., 0] == 0
-    carved = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
-    for k in range(empty.shape[0]):
-        m = empty[k, py[k], px[k]]
-        geometry.sdf.data[m] = geometry.sdf.data[m].abs().clamp(0.0, 1.0)
-        carved |= m
-    return int(carved.sum())
+_IN_FIT = ("carve_single_view", "depth_loss_single_view", "fit_single_view")
 
 
-def depth_loss_single_view(buffers, target):
-    """The depth term of the single-view tick (dmtet_singleview.py:474-490): layer 1 only,
-        d = |depth - target depth| * [mask_cont == 1] * [target depth_second >= 0] * [|target depth_second - target depth| >= 5e-3],
-    Huber at 1 (d below 1, d^2 from there), mean, times 100.  Elementwise torch."""
-    mask = (target["mask_cont"][..., 0] == 1.0).float().unsqueeze(-1)
-    valid = ((target["depth_second"] >= 0).float() * ((target["depth_second"] - target["depth"]).abs() >= 5e-3).float()).detach()
-    d = (buffers["depth"][..., :1] - target["depth"][..., :1]).abs() * mask * valid
-    l1 = (d < 1.0).float()
-    return (l1 * d + (1 - l1) * d.pow(2)).mean() * 100.0
-
-
-def fit_single_view(geometry, target, iters, *, lr=0.01, sdf_regularizer=0.2, target_points=None, gt_mesh=None, num_samples=50000,
-                    generator=None, color_loss_kind="logl1", callback=None, start_iteration=0, total_iters=None):
-    """Fit a `DMTetGeometry` to ONE view the way the reference's single-view loop does (fit_singleview.py:489-502 around
-    dmtet_singleview.DMTetGeometry.tick, :438-516).  target: `make_targets(..., shaded=True)` of the view.  Per iteration `it`
-        [init_with_gt_surface, for it < 300 and it % 10 == 0, with the faces of gt_mesh = (verts, faces) that the view sees: the
-         `rast_triangle_id` of `render_depth` on it, found once]
-        -> deform.requires_grad = (it >= 100) -> [carve_single_view, for 200 < it < 2000 and it % 20 == 0]
-        -> [deform *= 0.4, for it % 300 == 0 and it < 1790] -> getMesh(normals_grad=True) -> render_buffers
-        -> mse(alpha) + image_loss(shaded rgb x ref alpha, ref rgb x ref alpha) of layer 1 + depth_loss_single_view
-           + sdf_reg_loss(masked sdf) * weight * 2.5 [+ chamfer(sample_points(num_samples), target_points)]
-        -> Adam step on (sdf, deform) -> clamp_deform.
-    The regulariser's weight falls from `sdf_regularizer` to 0.01 over the first quarter of `total_iters` (default:
-    start_iteration + iters).  `callback(it, depth term, mesh)` after each step.  Returns the per-iteration terms as
-    `fit_to_views(return_terms=True)` does: {"depth", "alpha", "color"}, float32 [iters] each on the device.
-    Not built: the reference's `kd_grad` and `occlusion` regularisers (they need materials), `msaa`, and its random background
-    (the targets and the prediction are rendered on a zero background)."""
-    from .dmtet import sdf_reg_loss
-    from .pointcloud import chamfer_distance, sample_points, sdf_regularizer_weight
-    _gpu_only(geometry.sdf, "fit_single_view")
-    dev = geometry.sdf.device
-    for key in ("img", "alpha", "depth", "depth_second", "mask_cont", "mvp", "campos", "resolution"):
-        if key not in target:
-            raise ValueError(f"fit_single_view: the target has no {key!r}; make it with make_targets(..., shaded=True)")
-    total_iters = start_iteration + iters if total_iters is None else total_iters
-    pts = None if target_points is None else target_points.detach().to(device=dev, dtype=torch.float32).reshape(1, -1, 3).contiguous()
-    surface_faces = gt_verts = None
-    if gt_mesh is not None:
-        gt_verts = gt_mesh[0].detach().to(device=dev, dtype=torch.float32)
-        gt_faces = gt_mesh[1].to(dev).long()
-        with torch.no_grad():
-            seen = render_depth(gt_verts, gt_faces, target["mvp"], target["campos"], target["resolution"])["rast_triangle_id"]
-        surface_faces = None if seen is None else gt_faces[seen]
-    opt = torch.optim.Adam([geometry.sdf, geometry.deform], lr=lr)
-    hist = {"depth": [], "alpha": [], "color": []}
-    ref = target["img"]
-    try:
-        for k in range(iters):
-            it = start_iteration + k
-            if surface_faces is not None and it < 300 and it % 10 == 0:
-                init_with_gt_surface(geometry, gt_verts, surface_faces, target["campos"][0])
-            geometry.deform.requires_grad_(it >= 100)
-            if 200 < it < 2000 and it % 20 == 0:
-                carve_single_view(geometry, target)
-            if it % 300 == 0 and it < 1790:
-                with torch.no_grad():
-                    geometry.deform.data[:] *= 0.4
-            opt.zero_grad(set_to_none=True)
-            mesh = geometry.getMesh(normals_grad=True)
-            if mesh.t_pos_idx.shape[0] == 0:
-                raise _lib.MeshDiffusionHipError(f"fit_single_view: the mesh of iteration {it} has no faces")
-            buffers = render_buffers(mesh.v_pos, mesh.t_pos_idx, target["mvp"], target["campos"], target["resolution"], v_nrm=mesh.v_nrm)
-            alpha = torch.nn.functional.mse_loss(buffers["shaded"][..., 3:], ref[..., 3:])
-            color = image_loss(buffers["shaded"][..., 0:3] * ref[..., 3:], ref[..., 0:3] * ref[..., 3:], color_loss_kind)
-            depth = depth_loss_single_view(buffers, target)
-            sdf_mask = torch.zeros_like(geometry.sdf)
-            sdf_mask[mesh.valid_vert_idx] = 1.0
-            sdf_masked = geometry.sdf.detach() * sdf_mask + geometry.sdf * (1 - sdf_mask)
-            reg = sdf_reg_loss(sdf_masked, geometry.all_edges).mean() * sdf_regularizer_weight(it, total_iters, sdf_regularizer) * 2.5
-            total = alpha + color + depth + reg
-            if pts is not None:
-                pred = sample_points(mesh.v_pos[None], mesh.t_pos_idx, num_samples, generator=generator)[0]
-                total = total + chamfer_distance(pred, pts).mean()
-            total.backward()
-            opt.step()
-            geometry.clamp_deform()
-            for name, val in (("depth", depth), ("alpha", alpha), ("color", color)):
-                hist[name].append(val.detach())
-            if callback is not None:
-                callback(it, hist["depth"][-1], mesh)
-    finally:
-        geometry.deform.requires_grad_(True)
-    return {name: (torch.stack(v) if v else torch.empty(0, device=dev)) for name, v in hist.items()}
+def __getattr__(name):
+    """The carve, the depth term and the loop of the tick are in fit.py, which imports this module: handed out from there on first use."""
+    if name in _IN_FIT:
+        from . import fit
+        return getattr(fit, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -74,6 +74,7 @@ def test_python_entry_points_refuse_cpu_tensors_bad_radii_and_bad_shapes(monkeyp
     with pytest.raises(_lib.MeshDiffusionHipError):
         sv.fit_single_view(geo, {}, 1)
     monkeypatch.setattr(sv, "_gpu_only", lambda t, what: None)                 # the shape checks come before any launch
+    monkeypatch.setattr("meshdiffusion_amd.fit._gpu_only", lambda t, what: None)    # where fit_single_view lives
     for call in (lambda: sv.window_min_depth(rast[0]), lambda: sv.window_min_depth(rast[..., :3]), lambda: sv.window_min_depth(rast, -1),
                  lambda: sv.window_min_depth(rast, 2.5), lambda: sv.visible_tets(rast, torch.zeros(5), mvp),
                  lambda: sv.visible_tets(rast, torch.zeros(0, 3), mvp), lambda: sv.visible_tets(rast, centres, torch.eye(4)),
