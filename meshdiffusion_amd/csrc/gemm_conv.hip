@@ -752,6 +752,14 @@ static void cfg_info(int32_t* nt, int32_t* kc, int32_t* cols, int32_t* taps, int
 #endif
 
 int md_launch_conv3_main(const MdGemmConvArgs& a, hipStream_t stream);  // conv3_main.hip
+// conv3_low.hip: the 4^3-level launches of MD_CFG_C3_LOW (fp32 parts, split-K) with the batch folded into the columns; writes the
+// same words to `partial` as the generic tile
+bool md_conv3_low_takes(const MdGemmConvArgs& a);
+int md_launch_conv3_low(const MdGemmConvArgs& a, hipStream_t stream);
+// gemm_stream.hip: the MD_CFG_G1_128 launches with packed weights, F32B output and K a multiple of 128, positions streamed past
+// LDS; writes the same words to `out` as the generic tile
+bool md_gemm_stream_takes(const MdGemmConvArgs& a);
+int md_launch_gemm_stream(const MdGemmConvArgs& a, hipStream_t stream);
 
 extern "C" int md_gemm_conv(const MdGemmConvArgs* args, void* stream) {
   if (args == nullptr || args->a == nullptr || args->b == nullptr || args->out == nullptr)
@@ -761,6 +769,13 @@ extern "C" int md_gemm_conv(const MdGemmConvArgs* args, void* stream) {
   if (args->cfg == MD_CFG_C3_128_FAST || MD_CFG_IS_TIMING_FAST(args->cfg)) return md_launch_conv3_main(*args, st);
   if (args->stats != nullptr && !(args->ksplit > 1 && args->out_mode == MD_OUT_F32B))
     return MD_ERR_UNSUPPORTED;   // statistics: the dedicated 3x3x3 kernel's epilogue, or the split-K finish (md_splitk_reduce_stats_kernel)
+#ifndef MD_BUILD_ABLATIONS       // ablation builds time the generic tile on every shape
+  if (md_conv3_low_takes(*args)) {
+    rc = md_launch_conv3_low(*args, st);
+    return rc != MD_OK ? rc : md_launch_splitk_reduce(*args, st);
+  }
+  if (md_gemm_stream_takes(*args)) return md_launch_gemm_stream(*args, st);
+#endif
   MD_CFG_SWITCH_LAUNCH(args->cfg, rc = launch_cfg, *args, st);
   return rc;
 }
