@@ -625,6 +625,32 @@ int md_multistep_step(const double* x, const float* eps, const double* h1, const
                       const float* mask, const double* coef, const float* partial, const float* pmask, int32_t ch,
                       double* x_out, double* x0_out, float* x_f32, int32_t batch, int32_t C, int64_t P, void* stream);
 /*
+ * Spherical interpolation between pairs of latents (evaler.py:63-71 `slerp`, the reference's formula evaluated in double; the
+ * reference itself runs it in the tensors' float32).  Two launches on one stream, deterministic (no atomics):
+ *   a, b : fp32 [pairs][C][P], the two endpoints of each pair;  mask: fp32 [P] binary, shared by pairs and channels, or NULL
+ *   md_slerp_dots: slabs[p][s][0..3] = {sum a*b, sum a*a, sum b*b, 0} (fp64 products and sums of the masked values) over
+ *                  workgroup s's share of pair p (written, not added to); slabs is double[pairs][MD_LANGEVIN_SLABS][4]
+ *   md_slerp_mix : adds pair p's slabs in ascending order in double ; c = sum ab / (sqrt(sum aa)*sqrt(sum bb)) clamped to [-1, 1] ;
+ *                  theta = acos(c) ; with alpha double[K] on the device, for every k < K
+ *                    w1_k = sin((1-alpha_k) theta)/sin(theta) ; w2_k = sin(alpha_k theta)/sin(theta)
+ *                    out[p][k] = float((w1_k*a + w2_k*b)*mask), formed in double and rounded once ; out is fp32 [pairs][K][C][P]
+ *                  theta_out (double[pairs], may be NULL) receives theta.  a and b are read once for all K.
+ * Endpoints: alpha = 0 gives a*mask and alpha = 1 gives b*mask bit for bit (sin(theta)/sin(theta) is exactly 1, sin(0) exactly 0;
+ * no special case).  Degenerate pairs, the one deviation from the reference, which returns NaN there: where
+ * (1-c)(1+c) < 2^-40 the endpoints are parallel or antiparallel and the weights are (1-alpha_k, alpha_k), linear interpolation;
+ * theta is still reported.  A zero endpoint (sum aa or sum bb = 0) makes the pair NaN, as in the reference.  A non-finite value
+ * anywhere in an endpoint makes theta and every output of that pair NaN; other pairs of the launch are not touched by it.
+ * The mask multiplies the result, as in md_ddim_step: outside it a finite pair gives (signed) zero, a NaN pair NaN.
+ * MD_ERR_BAD_ARG, before any launch: K < 1 or K > MD_SLERP_MAX_K; P % 4 != 0; pairs < 1 or C < 1; a, b or out null or not
+ * 16-byte aligned (mask: 16 when given); slabs or alpha null or not 8-byte aligned (theta_out: 8 when given); an output
+ * sharing memory with an input or with the other output.  Two runs give the same bits.  Purely additive: MD_ABI_VERSION stays 16.
+ */
+#define MD_SLERP_MAX_K 256
+int md_slerp_dots(const float* a, const float* b, const float* mask, int32_t pairs, int32_t C, int64_t P,
+                  double* slabs, void* stream);
+int md_slerp_mix(const float* a, const float* b, const float* mask, const double* slabs, const double* alpha, int32_t K,
+                 float* out, double* theta_out, int32_t pairs, int32_t C, int64_t P, void* stream);
+/*
  * Inpainting blend of one channel (sampling.py:443-467):
  *   v = (x*(1-m) + src*m) * gm     applied in place to channel `ch` of x [B][C][P];
  *   src has batch stride src_bstride (0 = shared partial grid).

@@ -11,6 +11,9 @@ probability-flow ODE (`--config.eval.ode_rtol=1e-5 --config.eval.ode_atol=1e-5 -
 conditional samplers (`--config.sampling.method=ddim` is the form to run: 99 guided evaluations instead of 1000).
 `--config.sampling.method=dpmpp [--config.sampling.dpmpp_steps=20 --config.sampling.dpmpp_order=2 --config.sampling.dpmpp_tau=0]`
 samples with DPM-Solver++ in 20 evaluations, in uncond_gen and cond_gen (with or without guidance), under torchrun as well.
+`--mode=interp --config.sampling.method=ddim|dpmpp|ode [--config.eval.interp_points=K --config.eval.interp_pairs=Np]` writes
+{eval_dir}/interp.npy: K shapes per pair on the walk between two latents; `--config.eval.interp_sources=grids.npy` walks between
+given grids instead of prior draws, encoded by DDIM (method ddim) or ODE (method ode) inversion.
 """
 import sys
 
@@ -36,8 +39,8 @@ def parse(argv):
         i += 1
     if cfg_path is None or mode is None:
         raise SystemExit("flags --config and --mode are required")
-    if mode not in ("train", "uncond_gen", "cond_gen", "likelihood"):
-        raise SystemExit(f"--mode must be one of train|uncond_gen|cond_gen|likelihood, got {mode}")
+    if mode not in ("train", "uncond_gen", "cond_gen", "likelihood", "interp"):
+        raise SystemExit(f"--mode must be one of train|uncond_gen|cond_gen|likelihood|interp, got {mode}")
     if cfg_path in ("res64", "res128"):
         config = getattr(mdconfig, f"get_config_{cfg_path}")()
     else:
@@ -57,6 +60,11 @@ def main(argv=None):
         evaler.cond_gen(config)
     elif mode == "likelihood":
         evaler.likelihood(config)
+    elif mode == "interp":
+        try:
+            evaler.interp(config)
+        except (ValueError, NotImplementedError) as e:      # a run this mode refuses: the message names what it takes
+            raise SystemExit(f"--mode=interp: {e}") from e
     else:
         from meshdiffusion_amd.lib.diffusion import trainer
         trainer.train(config)

@@ -509,6 +509,107 @@ __global__ __launch_bounds__(256) void md_multistep_step_kernel(const double* __
   }
 }
 
+// ---- spherical interpolation between latents (reference lib/diffusion/evaler.py:63-71 `slerp`), launch 1 -------------------------
+// grid (MD_LANGEVIN_SLABS, pairs): workgroup (s, p) writes slabs[p][s] = {sum a*b, sum a*a, sum b*b, 0} over its strided share of
+// pair p, of the masked values.  A product of two floats is exact in double; fixed grid and fixed per-thread order as in
+// md_langevin_norms: the partial sums do not depend on scheduling.
+__global__ __launch_bounds__(256) void md_slerp_dots_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                            const float* __restrict__ mask, double* __restrict__ slabs, int64_t CP,
+                                                            int64_t P) {
+  const int p = blockIdx.y;
+  const int64_t base = (int64_t)p * CP;
+  double acc[3] = {0.0, 0.0, 0.0};
+  MD_STREAM4(i, CP) {
+    const f32x4 av = md_load4(a + base + i), bv = md_load4(b + base + i);
+    const f32x4 mv = md_mask4(mask, i % P);
+    double ab[4], aa[4], bb[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double x = (double)av[e] * (double)mv[e], y = (double)bv[e] * (double)mv[e];
+      ab[e] = x * y;
+      aa[e] = x * x;
+      bb[e] = y * y;
+    }
+    acc[0] += (ab[0] + ab[1]) + (ab[2] + ab[3]);
+    acc[1] += (aa[0] + aa[1]) + (aa[2] + aa[3]);
+    acc[2] += (bb[0] + bb[1]) + (bb[2] + bb[3]);
+  }
+  if (md_block_sum(acc)) {
+    double* row = slabs + ((int64_t)p * MD_LANGEVIN_SLABS + blockIdx.x) * 4;      // 8-byte aligned: one double at a time
+    row[0] = acc[0];
+    row[1] = acc[1];
+    row[2] = acc[2];
+    row[3] = 0.0;
+  }
+}
+
+// launch 2.  Prologue, in double: the pair's slabs added in ascending order (thread 0), c = sum ab / (sqrt(sum aa)*sqrt(sum bb))
+// clamped to [-1, 1] by comparisons (a NaN stays a NaN), theta = acos(c); thread k < K then forms
+//   w1_k = sin((1-alpha_k) theta)/sin(theta), w2_k = sin(alpha_k theta)/sin(theta)      (evaler.py:67-70)
+// or, where (1-c)(1+c) = sin^2(theta) < 2^-40 (parallel or antiparallel endpoints, where the reference divides 0 by 0),
+//   w1_k = 1-alpha_k, w2_k = alpha_k.
+// alpha = 0 gives w = (1, 0) and alpha = 1 gives (0, 1) exactly, because sin(theta)/sin(theta) is 1 and sin(0) is 0: the endpoints
+// need no branch.  Then out[p][k] = float((w1_k*a + w2_k*b)*mask), formed in double and rounded once: a and b are read once for all K.
+static_assert(MD_SLERP_MAX_K <= 256, "the prologue forms one weight pair per thread of a workgroup");
+
+__global__ __launch_bounds__(256) void md_slerp_mix_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                           const float* __restrict__ mask, const double* __restrict__ slabs,
+                                                           const double* __restrict__ alpha, int K, float* __restrict__ out,
+                                                           double* __restrict__ theta_out, int64_t CP, int64_t P) {
+  const int p = blockIdx.y;
+  __shared__ double s_slab[MD_LANGEVIN_SLABS][3];
+  __shared__ double s_theta;
+  __shared__ int s_linear;
+  __shared__ double s_w[MD_SLERP_MAX_K][2];
+  if (threadIdx.x < MD_LANGEVIN_SLABS) {
+    const double* row = slabs + ((int64_t)p * MD_LANGEVIN_SLABS + threadIdx.x) * 4;
+    s_slab[threadIdx.x][0] = row[0];
+    s_slab[threadIdx.x][1] = row[1];
+    s_slab[threadIdx.x][2] = row[2];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double ab = 0.0, aa = 0.0, bb = 0.0;
+    for (int s = 0; s < MD_LANGEVIN_SLABS; ++s) {
+      ab += s_slab[s][0];
+      aa += s_slab[s][1];
+      bb += s_slab[s][2];
+    }
+    double c = ab / (sqrt(aa) * sqrt(bb));
+    c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
+    const double theta = acos(c);
+    s_theta = theta;
+    s_linear = ((1.0 - c) * (1.0 + c) < 0x1p-40) ? 1 : 0;
+    if (blockIdx.x == 0 && theta_out) theta_out[p] = theta;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < K) {
+    const double al = alpha[threadIdx.x], theta = s_theta;
+    double w1 = 1.0 - al, w2 = al;
+    if (!s_linear) {
+      const double st = sin(theta);
+      w1 = sin((1.0 - al) * theta) / st;
+      w2 = sin(al * theta) / st;
+    }
+    s_w[threadIdx.x][0] = w1;
+    s_w[threadIdx.x][1] = w2;
+  }
+  __syncthreads();
+  const int64_t base = (int64_t)p * CP;
+  float* po = out + (int64_t)p * K * CP;
+  MD_STREAM4(i, CP) {
+    const f32x4 av = md_load4(a + base + i), bv = md_load4(b + base + i);
+    const f32x4 mv = md_mask4(mask, i % P);
+    for (int k = 0; k < K; ++k) {
+      const double w1 = s_w[k][0], w2 = s_w[k][1];
+      f32x4 v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = (float)((w1 * (double)av[e] + w2 * (double)bv[e]) * (double)mv[e]);
+      md_store4(po + (int64_t)k * CP + i, v);
+    }
+  }
+}
+
 // ---- exports ------------------------------------------------------------------------------------------------------------
 // The tail of an export: one launch of 256-thread workgroups on `stream`, the export's last parameter.
 #define MD_LAUNCH_STEP(kernel, grid, ...)                                                       \
@@ -678,4 +779,28 @@ extern "C" int md_multistep_step(const double* x, const float* eps, const double
 #undef MD_MULTISTEP_ARGS
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
+}
+
+extern "C" int md_slerp_dots(const float* a, const float* b, const float* mask, int32_t pairs, int32_t C, int64_t P, double* slabs,
+                             void* stream) {
+  if (md_any_bad<16>(a, b) || md_any_bad<8>(slabs) || md_any_misaligned<16>(mask)) return MD_ERR_BAD_ARG;
+  if (md_bad_dims(pairs, C, P, true)) return MD_ERR_BAD_ARG;
+  const int64_t CP = (int64_t)C * P, n = 4 * CP * pairs;
+  const md_span out[] = {{slabs, 32LL * MD_LANGEVIN_SLABS * pairs}};
+  const md_span in[] = {{a, n}, {b, n}, {mask, 4 * P}};
+  if (md_any_alias(out, in)) return MD_ERR_BAD_ARG;
+  MD_LAUNCH_STEP(md_slerp_dots_kernel, dim3(MD_LANGEVIN_SLABS, (unsigned)pairs), a, b, mask, slabs, CP, P);
+}
+
+extern "C" int md_slerp_mix(const float* a, const float* b, const float* mask, const double* slabs, const double* alpha, int32_t K,
+                            float* out, double* theta_out, int32_t pairs, int32_t C, int64_t P, void* stream) {
+  if (md_any_bad<16>(a, b, out) || md_any_bad<8>(slabs, alpha) || md_any_misaligned<16>(mask) || md_any_misaligned<8>(theta_out))
+    return MD_ERR_BAD_ARG;
+  if (md_bad_dims(pairs, C, P, true) || K < 1 || K > MD_SLERP_MAX_K) return MD_ERR_BAD_ARG;
+  const int64_t CP = (int64_t)C * P, n = 4 * CP * pairs;
+  const md_span outs[] = {{out, n * K}, {theta_out, 8LL * pairs}};
+  const md_span in[] = {{a, n}, {b, n}, {mask, 4 * P}, {slabs, 32LL * MD_LANGEVIN_SLABS * pairs}, {alpha, 8LL * K}};
+  if (md_any_alias(outs, in)) return MD_ERR_BAD_ARG;
+  MD_LAUNCH_STEP(md_slerp_mix_kernel, dim3(stream_blocks(CP, pairs), (unsigned)pairs), a, b, mask, slabs, alpha, (int)K, out,
+                 theta_out, CP, P);
 }

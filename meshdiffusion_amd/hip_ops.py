@@ -1367,6 +1367,29 @@ def multistep_step(x64, eps, hist, z, mask, coef, partial=None, pmask=None, ch=0
     return x_out, x0_out, x_f32
 
 
+def slerp(a, b, alphas, mask=None):
+    """Spherical interpolation between pairs of latents (md_slerp_dots + md_slerp_mix: two launches, no host synchronisation).
+    a, b: [pairs,C,D,H,W] fp32, the endpoints; alphas: K positions in [0, 1] (a sequence, or a float64 tensor); mask [P] fp32 or
+    None.  Returns (out [pairs,K,C,D,H,W] fp32, theta [pairs] float64): out[p,k] = slerp(a[p], b[p], alphas[k]) times the mask,
+    with the angle taken over the masked values; parallel endpoints interpolate linearly (include/meshdiffusion_hip.h)."""
+    pairs, Cc, P = _state_dims(a)
+    f32, f64 = torch.float32, torch.float64
+    a = _operand(a, "a", f32, copy=True)
+    b = _operand(b, "b", f32, shape=a.shape, copy=True)
+    mask = _operand(mask, "mask", f32, numel=P, copy=True)
+    if not torch.is_tensor(alphas):
+        alphas = torch.tensor([float(v) for v in alphas], dtype=f64)
+    alphas = _operand(alphas.to(a.device), "alphas", f64, copy=True)
+    K = alphas.numel()
+    assert alphas.dim() == 1 and 1 <= K <= _lib.SLERP_MAX_K, (tuple(alphas.shape), _lib.SLERP_MAX_K)
+    slabs = torch.empty((pairs, _lib.LANGEVIN_SLABS, 4), dtype=f64, device=a.device)
+    out = torch.empty((pairs, K) + tuple(a.shape[1:]), dtype=f32, device=a.device)
+    theta = torch.empty(pairs, dtype=f64, device=a.device)
+    call("md_slerp_dots", a, b, mask, pairs, Cc, P, slabs)
+    call("md_slerp_mix", a, b, mask, slabs, alphas, K, out, theta, pairs, Cc, P)
+    return out, theta
+
+
 def inpaint_blend_(x, src, pmask, gmask, ch, src_bstride=0):
     """In place on channel `ch` of x: (x*(1-pmask) + src*pmask) * gmask."""
     B, Cc, P = _state_dims(x)

@@ -1,5 +1,5 @@
 """Generation drivers -- mirror of the reference's lib/diffusion/evaler.py
-(`uncond_gen` :14-60, `cond_gen` :134-211).  Same behaviour and file outputs
+(`uncond_gen` :14-60, `cond_gen` :134-211, `slerp` + `uncond_gen_interp` :63-131 repaired as `interp`).  Same behaviour and file outputs
 (`{eval_dir}/{idx}.npy`, float32 [B,4,R,R,R]); the grid mask is read from
 `./data/grid_mask_{R}.pt` relative to the cwd like the reference, with `map_location` so that the
 CUDA-saved tensor loads on any host.
@@ -59,12 +59,16 @@ def _setup(config, mask_shape, local_batch=None):
     # the checkpoint's weights meet the reduced-precision conv formats here for the first time: measure every conv's operand on a
     # few noise batches, rebuild the equalisers from the measurement, audit each conv against its bf16x3 form and demote the ones
     # above the bar (models/utils.calibrate_model; config.eval.calibrate = False skips it)
+    _calibrate(score_model, config, shape[0])
+    return score_model, sampling_fn, eval_dir
+
+
+def _calibrate(score_model, config, batch):
     if getattr(config.eval, "calibrate", True) and torch.device(config.device).type == "cuda":
-        rep = mutils.calibrate_model(score_model, config, batch=shape[0])      # at the sampling batch: which convs take the Winograd path depends on it
+        rep = mutils.calibrate_model(score_model, config, batch=batch)      # at the sampling batch: which convs take the Winograd path depends on it
         if rep is not None:
             print(f"calibrated the {score_model.module.hip_precision} convs: {rep['measured']} measured, worst kept {rep['worst']:.2e}, "
                   f"demoted to bf16x3: {rep['demoted']}")
-    return score_model, sampling_fn, eval_dir
 
 
 def _ranks(config):
@@ -108,6 +112,92 @@ def ops_release():
 def uncond_gen(config, idx=0):
     """Unconditional generation: N-1 ancestral steps from the masked prior, saves {idx}.npy."""
     return _generate(config, lambda R: (1, R, R, R), idx, lambda model, sampling_fn: sampling_fn(model)[0])
+
+
+def interp_plan(config, source_rows=None, fields=True):
+    """What an interpolation run of `config` does, decided before any GPU work: (pairs Np, points per pair K, sampling method,
+    encoded).  Reads config.eval.interp_sources / interp_pairs / interp_points, all optional; source_rows: the rows of the
+    interp_sources file (needed when the field is set); fields off: the three fields are not read.  Raises ValueError on a count
+    out of range and NotImplementedError on a sampler that cannot run it."""
+    from ..._lib import SLERP_MAX_K
+    ev = config.eval if fields else {}
+    method = str(getattr(config.sampling, "method", "pc")).lower()
+    encoded = bool(getattr(ev, "interp_sources", None))
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NotImplementedError("interp runs in a single process: sharding pairs over ranks is not implemented")
+    if encoded:
+        if method not in ("ddim", "ode"):
+            raise NotImplementedError(f"interp_sources are encoded by the inverse of the configured sampler: sampling.method must be "
+                                      f"'ddim' (DDIM inversion) or 'ode' (ODE inversion), got {method!r}")
+        if source_rows is None or source_rows < 2 or source_rows % 2:
+            raise ValueError(f"interp_sources must hold 2*Np grids (rows 2p and 2p+1 form pair p), got {source_rows} rows")
+    elif method == "dpmpp" and int(getattr(config.sampling, "dpmpp_tau", 0)) != 0:
+        raise NotImplementedError("interp needs a deterministic sampler: 'dpmpp' runs it with sampling.dpmpp_tau = 0 only")
+    elif method not in ("ddim", "dpmpp", "ode"):
+        raise NotImplementedError(f"interp needs a sampler that starts from a given latent (x0=): sampling.method 'ddim', 'dpmpp' "
+                                  f"with dpmpp_tau = 0, or 'ode', got {method!r}")
+    pairs = getattr(ev, "interp_pairs", None)
+    pairs = int(pairs) if pairs is not None else (source_rows // 2 if encoded else 1)
+    if pairs < 1 or (encoded and 2 * pairs > source_rows):
+        raise ValueError(f"interp_pairs = {pairs}: at least 1" + (f", and interp_sources holds {source_rows // 2} pairs" if encoded else ""))
+    points = getattr(ev, "interp_points", None)
+    points = int(points) if points is not None else int(config.eval.batch_size) // pairs
+    if not 2 <= points <= SLERP_MAX_K:
+        raise ValueError(f"interp_points = {points}: between 2 (both ends) and {SLERP_MAX_K} per pair")
+    return pairs, points, method, encoded
+
+
+def _interp(config, fname, plan, sources=None):
+    from ... import hip_ops as ops
+    pairs, K, method, encoded = plan
+    dev, R, C = config.device, config.data.image_size, config.data.num_channels
+    with torch.no_grad():
+        score_model, sde = _load_model(config)
+        grid_mask = _grid_mask(config, (1, R, R, R))
+        fn_for = lambda batch: sampling.get_sampling_fn(config, sde, (batch, C, R, R, R), lambda x: x, 1e-3, grid_mask=grid_mask)   # noqa: E731
+        decode = fn_for(K)
+        _calibrate(score_model, config, K)
+        if encoded:
+            encode = fn_for(2)
+            ends = torch.cat([encode(score_model, x0=sources[2 * p:2 * p + 2].to(dev), encode=True)[0].float() for p in range(pairs)])
+        else:
+            ends = sde.prior_sampling((2 * pairs, C, R, R, R)).to(dev)
+        alpha = np.arange(K, dtype=np.float64) / float(K - 1)                    # evaler.py:127
+        mix, theta = ops.slerp(ends[0::2], ends[1::2], torch.from_numpy(alpha), grid_mask.reshape(-1).float().contiguous())
+        samples = torch.cat([decode(score_model, x0=mix[p])[0].float().cpu() for p in range(pairs)])
+    os.makedirs(config.eval.eval_dir, exist_ok=True)
+    np.save(os.path.join(config.eval.eval_dir, f"{fname}.npy"), samples.numpy())
+    np.savez(os.path.join(config.eval.eval_dir, f"{fname}_meta.npz"), theta=theta.cpu().numpy(), alpha=alpha, method=method,
+             encoded=encoded)
+    ops_release()
+    return samples
+
+
+def interp(config, save_fname="interp"):
+    """Walks between pairs of shapes (`--mode=interp`; the reference's `slerp` + `uncond_gen_interp`, evaler.py:63-131, which reads
+    undefined names and cannot run): K latents on the great circle between the two endpoints of every pair (hip_ops.slerp), each
+    decoded by the configured deterministic sampler.  Optional config.eval fields:
+        interp_sources  unset: the endpoints are prior draws on the grid mask.  Set: a .npy [2*Np, C, R, R, R] of data grids; rows
+                        2p, 2p+1 form pair p and are encoded first, by the inverse of the configured sampler (sampling.method
+                        'ddim': DDIM inversion, first order; 'ode': ODE inversion, to the solver's tolerance)
+        interp_pairs    Np (default 1; with sources: rows / 2)
+        interp_points   K per pair, both ends included (default eval.batch_size // Np); alpha_k = k/(K-1)
+    The checkpoint is loaded once and calibrated once at batch K; encoding runs at batch 2, decoding pair by pair at batch K.
+    Writes {eval_dir}/{save_fname}.npy, float32 [Np*K, C, R, R, R] pair-major (mesh_export input as it stands), and
+    {save_fname}_meta.npz: theta [Np], alpha [K], method, encoded.  Single process."""
+    path = getattr(config.eval, "interp_sources", None)
+    sources = torch.from_numpy(np.load(path)).float() if path else None
+    if sources is not None:
+        R, C = config.data.image_size, config.data.num_channels
+        if sources.dim() != 5 or tuple(sources.shape[1:]) != (C, R, R, R):
+            raise ValueError(f"interp_sources must be [2*Np, {C}, {R}, {R}, {R}], got {tuple(sources.shape)}")
+    return _interp(config, save_fname, interp_plan(config, None if sources is None else sources.shape[0]), sources)
+
+
+def uncond_gen_interp(config, idx=0):
+    """The reference's entry point (evaler.py:73-131) as it was meant: one pair of prior draws, K = config.eval.batch_size points,
+    whatever the interp_* fields say; saves {idx}.npy (and {idx}_meta.npz)."""
+    return _interp(config, idx, interp_plan(config, fields=False))
 
 
 def tet_vertices_to_grid_index(vertices):

@@ -348,7 +348,8 @@ def _check_pc_pair(sde, predictor, corrector, n_steps, probability_flow, continu
     if corrector is not NoneCorrector and n_steps < 1:
         raise NotImplementedError("a corrector needs n_steps_each >= 1 (the reference returns an unbound x_mean)")
     if return_traj:
-        raise NotImplementedError("return_traj is only used by the reference's unreachable uncond_gen_interp")
+        raise NotImplementedError("return_traj (sampling trajectories) is not implemented; latent interpolation does not need "
+                                  "it: evaler.interp / --mode=interp")
 
 
 def _check_guidance(guidance_scale, partial, predictor=None, corrector=None, probability_flow=False):
@@ -526,12 +527,37 @@ def get_ddim_sampler(sde, shape, predictor, inverse_scaler, n_steps=1, denoise=F
     dev = torch.device(device)
 
     def ddim_sampler(model, schedule="quad", num_steps=100, x0=None, partial=None, partial_mask=None, partial_channel=0,
-                     n_iters=None, guidance_scale=0.0, guidance_replace=True, guidance_chunk=None):
+                     n_iters=None, guidance_scale=0.0, guidance_replace=True, guidance_chunk=None, encode=False):
         """guidance_scale > 0 (reconstruction guidance; needs `partial`): each update is guidance_terms at the float32 state the
         U-Net sees, md_ddim_step with that eps_hat, then md_guide_apply_f64 on the float64 state and its float32 copy; x0_pred stays
-        the step's own prediction.  guidance_replace off: no replacement of the known voxels, at the start or in the steps."""
+        the step's own prediction.  guidance_replace off: no replacement of the known voxels, at the start or in the steps.
+        encode (DDIM inversion; the meaning given to the name the reference reads at sampling.py:569 and never defines): x0 holds
+        data grids, and the same schedule is walked upward, i = 1 .. len-1: the U-Net is evaluated at the current level
+        timesteps[i-1] and md_ddim_step moves the state to timesteps[i] with coefficients(current, next), whose row works in either
+        direction of time.  n_iters limits the upward steps.  Returns the float64 state at the top level -- what
+        ddim_sampler(x0=latent) starts from -- whatever `denoise` says, without the inverse scaler: a latent is no data grid."""
+        if encode:
+            if x0 is None:
+                raise ValueError("encode=True needs x0: the data grids to invert")
+            if partial is not None or float(guidance_scale) != 0.0:
+                raise NotImplementedError("DDIM inversion (encode=True) of a partial grid or under guidance is not implemented")
         guided = _check_guidance(guidance_scale, partial)
         with torch.no_grad():
+            if encode:
+                x, gm, gm_flat, _, _ = prepare_run(sde, shape, dev, grid_mask, x0)
+                timesteps = ddim_schedule(sde.N, schedule, num_steps)
+                pred = predictor(sde, None)
+                model_fn = mutils.get_model_fn(model, train=False)
+                x64, x32 = x.double(), x.float().contiguous()
+                order = list(range(1, len(timesteps)))
+                if n_iters is not None:
+                    order = order[:int(n_iters)]
+                for i in order:
+                    vec_t = torch.ones(B, device=dev) * timesteps[i - 1]
+                    vec_tnext = torch.ones(B, device=dev) * timesteps[i]
+                    eps_hat = model_fn(x32, vec_t.float() * (sde.N - 1))
+                    x64, _, x32 = ops.ddim_step(x64, eps_hat, gm_flat, pred.coefficients(vec_t, vec_tnext))
+                return x64, sde.N * (n_steps + 1)
             ch = partial_channel
             x, gm, gm_flat, part, pm = prepare_run(sde, shape, dev, grid_mask, x0, partial, partial_mask, ch,
                                                    replace=guidance_replace or not guided)
@@ -745,14 +771,18 @@ def get_ode_sampler(sde, shape, inverse_scaler, rtol=1e-5, atol=1e-5, eps=1e-3, 
     the ODE of likelihood.get_likelihood_fn without the log-density entries, so no divergence and no backward -- the model's
     inference path, one md_pf_ode_rhs launch per evaluation, likelihood.rk45 as the integrator (float64 state on the device).
     ode_sampler(model, x0=None) -> (samples, nfe); x0: the latent to start from (likelihood_fn's z decodes back to its data)
-    instead of a prior draw.  get_sampling_fn reads rtol / atol from config.sampling.ode_rtol / ode_atol (default 1e-5)."""
+    instead of a prior draw.  get_sampling_fn reads rtol / atol from config.sampling.ode_rtol / ode_atol (default 1e-5).
+    ode_sampler(model, x0=grids, encode=True) -> (latent, nfe): the same drift integrated upward, eps -> T (ODE inversion; no
+    divergence, no backward), from data grids; the latent is returned as it is, without the inverse scaler."""
     from . import likelihood
     shape = tuple(shape)
     dev = torch.device(device)
 
-    def ode_sampler(model, x0=None, partial=None, **unknown):
+    def ode_sampler(model, x0=None, partial=None, encode=False, **unknown):
         if partial is not None or unknown:
             raise NotImplementedError(f"the ODE sampler takes no conditioning or other options ({['partial'] * (partial is not None) + sorted(unknown)})")
+        if encode and x0 is None:
+            raise ValueError("encode=True needs x0: the data grids to invert")
         with torch.no_grad():
             x = (x0 if x0 is not None else sde.prior_sampling(shape)).to(dev)
             if x.dtype not in (torch.float32, torch.float64):
@@ -760,7 +790,9 @@ def get_ode_sampler(sde, shape, inverse_scaler, rtol=1e-5, atol=1e-5, eps=1e-3, 
             if grid_mask is not None:
                 x = x * grid_mask.to(dev).reshape((1, 1) + shape[2:]).to(x.dtype)
             fun = likelihood.get_ode_rhs(sde, model, shape, x, grid_mask=grid_mask)
-            y, nfe, _ = likelihood.rk45(fun, (sde.T, eps), x.double().reshape(-1), rtol=rtol, atol=atol)
-            return inverse_scaler(y.view(shape).to(x.dtype)), nfe
+            span = (eps, sde.T) if encode else (sde.T, eps)
+            y, nfe, _ = likelihood.rk45(fun, span, x.double().reshape(-1), rtol=rtol, atol=atol)
+            y = y.view(shape).to(x.dtype)
+            return (y if encode else inverse_scaler(y)), nfe
 
     return ode_sampler
