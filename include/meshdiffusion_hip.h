@@ -1324,6 +1324,52 @@ int md_lfd_describe(const uint8_t* mask, int32_t n, int32_t R, uint8_t* desc, fl
 int md_lfd_matrix(const uint8_t* x, const uint8_t* y, const uint8_t* perm, int32_t nx, int32_t ny, int32_t L, int32_t G,
                   int32_t triangular, int32_t* out, void* stream);
 
+/*
+ * Textures for meshes (csrc/texture.hip): the bilinear fetch of dr.texture (filter_mode = 'linear', no mip levels) with gradients
+ * for the texture and the uv, one dilation step of a baked atlas, and the multi-view projection bake
+ * (meshdiffusion_amd/texture.py, render.render_textured, fit.fit_texture).  Purely additive: MD_ABI_VERSION stays 16.
+ *
+ * THE TEXTURE CONTRACT (the header comment of csrc/texture.hip has it in full; tests/texture_cases.py restates it in numpy)
+ * tex float32 [T][Ht][Wt][C], T = 1 or B, 1 <= C <= 8, Ht, Wt <= MD_TEXTURE_MAX_RES; uv float32 [B][H][W][2]; rast float32
+ *   [B][H][W][4] or NULL.  A pixel with rast id 0, or whose x = u Wt - 0.5 or y = v Ht - 0.5 is not finite, is skipped: zeros out,
+ *   nothing to any gradient.  Texel (row i, column j) has its centre at ((j + 0.5) / Wt, (i + 0.5) / Ht); row 0 is v = 0.
+ *   fp32 without contraction: x0 = floor(x), fx = x - x0 (y likewise), out = (t00 (1 - fx) + t10 fx) (1 - fy) + (t01 (1 - fx) + t11
+ *   fx) fy; boundary MD_TEXTURE_CLAMP clamps the four indices, MD_TEXTURE_WRAP takes them modulo the size.
+ * md_texture_sample: the fetch.  tex and out 16-byte aligned, uv 8, rast 16.
+ * md_texture_codes: dest int32 [B H W][4] (16-byte aligned), the texel row (t Ht + iy) Wt + ix of the code 4 pixel + corner, corners
+ *   (t00, t10, t01, t11), and T Ht Wt for the codes of a skipped pixel: the host sorts the codes stably by row into (ptr int32
+ *   [T Ht Wt + 2], order int32 [4 B H W]).
+ * md_texture_sample_bwd: dtex (may be NULL; needs ptr and order) = per texel the Kahan sum of w_k grad_out[pixel] in the order of
+ *   the CSR, every element written; duv (may be NULL) = (Wt sum_c g ((t10 - t00)(1 - fy) + (t11 - t01) fy), Ht sum_c g ((t01 - t00)
+ *   (1 - fx) + (t11 - t10) fx)), zeros where skipped.  One of the two at least.  No atomics: two runs agree bit for bit.
+ * md_texture_dilate: one step.  A texel with mask <= 0.5 and a covered 8-neighbour becomes the mean of those neighbours (summed in
+ *   row-major order) and gets mask 1; the rest is copied.  tex float32 [Ht][Wt][C], mask float32 [Ht][Wt]; no output may overlap
+ *   an input or the other output (MD_ERR_BAD_ARG).
+ * md_texture_project: per texel with texmask > 0.5 the cos^power-weighted mean over the views (ascending, V <=
+ *   MD_TEXTURE_MAX_VIEWS) of the bilinear fetch of image [V][H][W][3] at the texel's projection, a view counting only if w > 0,
+ *   ndc in [-1, 1]^2, the four footprint pixels inside the image with viewmask > 0.5, |p - campos| - depth[nearest pixel] <=
+ *   depth_bias and cos > cos_min.  color float32 [Ht][Wt][3] (zeros where the weights sum to 0), weight float32 [Ht][Wt].
+ * Every export, in this order: null or misaligned pointers: MD_ERR_BAD_ARG; a size < 1, T not 1 or B, an unknown boundary, a NaN
+ *   scalar: MD_ERR_BAD_ARG; C outside 1..8, Ht or Wt > MD_TEXTURE_MAX_RES, B or H or W beyond the rasteriser's limits, V >
+ *   MD_TEXTURE_MAX_VIEWS: MD_ERR_UNSUPPORTED; aliasing: MD_ERR_BAD_ARG.  Nothing is allocated, nothing synchronises.
+ */
+#define MD_TEXTURE_CLAMP 0
+#define MD_TEXTURE_WRAP 1
+#define MD_TEXTURE_MAX_RES 2048
+#define MD_TEXTURE_MAX_VIEWS 64
+int md_texture_sample(const float* tex, const float* uv, const float* rast, int32_t T, int32_t Ht, int32_t Wt, int32_t C, int32_t B,
+                      int32_t H, int32_t W, int32_t boundary, float* out, void* stream);
+int md_texture_codes(const float* uv, const float* rast, int32_t T, int32_t Ht, int32_t Wt, int32_t B, int32_t H, int32_t W,
+                     int32_t boundary, int32_t* dest, void* stream);
+int md_texture_sample_bwd(const float* tex, const float* uv, const float* rast, const float* grad_out, const int32_t* ptr,
+                          const int32_t* order, int32_t T, int32_t Ht, int32_t Wt, int32_t C, int32_t B, int32_t H, int32_t W,
+                          int32_t boundary, float* dtex, float* duv, void* stream);
+int md_texture_dilate(const float* tex, const float* mask, int32_t Ht, int32_t Wt, int32_t C, float* out_tex, float* out_mask,
+                      void* stream);
+int md_texture_project(const float* pos, const float* nrm, const float* texmask, const float* image, const float* depth,
+                       const float* viewmask, const float* mvp, const float* campos, int32_t Ht, int32_t Wt, int32_t V, int32_t H,
+                       int32_t W, float depth_bias, float cos_min, float power, float* color, float* weight, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

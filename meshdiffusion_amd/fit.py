@@ -11,7 +11,7 @@ The four loops supervise a `DMTetGeometry` (or, `fit_fixed_topology`, a `DMTetGe
 Each is a step function handed to `_optimise`, which owns what they share: zero_grad -> step(it) -> backward -> opt.step [->
 sched.step] -> clamp_deform -> the history of the detached terms -> callback(it, headline term, mesh) -> the stacked history.  The
 pieces of a step that more than one loop needs are written once: `_masked_sdf_reg`, `_chamfer_term`, `_pre_step`, `_huber_depth`,
-`_vertex_pixels`, `_layer1_image_terms`, `_need_targets`, `_get_mesh`.  `render`, `pointcloud` and `singleview` hand out the
+`_vertex_pixels`, `_layer1_image_terms`, `_need_targets`, `_get_mesh`.  `fit_texture` runs the same driver on a `kd` texture of a fixed mesh (`render.render_textured`).  `render`, `pointcloud` and `singleview` hand out the
 public names below under their old addresses.  tools/fit_views.py, fit_singleview.py and fit_pointcloud.py build their command
 lines from `add_fit_arguments`, `load_normalised_obj`, `look_at_cameras`, `make_geometry`, `progress` and `second_pass`.
 """
@@ -249,6 +249,50 @@ def _optimise(geometry, opt, iters, step, names, callback, dev, start_iteration=
         if callback is not None:
             callback(it, history[names[0]][-1], mesh)
     return {name: (torch.stack(xs) if xs else torch.empty(0, device=dev)) for name, xs in history.items()}
+
+
+class _TextureParam:
+    """What `_optimise` asks of a geometry, for a texture: nothing to clamp."""
+
+    def clamp_deform(self):
+        pass
+
+
+def fit_texture(verts, faces, uvs, uv_idx, targets, resolution_tex, iters, lr=0.01, init=None, light=None, shade=True, callback=None):
+    """Adam on a `kd` texture float32 [Ht,Wt,3] of a fixed mesh under the masked L1 between `render.render_textured` and posed images
+    (the colour term of the reference's fit with the geometry frozen).  targets: dict of `images` [B,H,W,3], `viewmask` [B,H,W] or
+    [B,H,W,1], `mvp` [B,4,4], `campos` [B,3].  loss = sum(|render.rgb - images| * viewmask) / (3 sum(viewmask)).  init: the starting
+    texture (e.g. `texture.bake_from_views(...)["tex"]`), None: 0.5 everywhere.  Everything that does not depend on the texture (the
+    layer, the texture coordinates, the irradiance, the antialiasing pairs' inputs, the `SamplePlan`) is computed once
+    (`render.textured_fixed`).  Returns (texture, {"loss": float32 [iters]})."""
+    from .render import _resolution, render_textured, textured_fixed
+    _gpu_only(verts, "fit_texture")
+    dev = verts.device
+    Ht, Wt = _resolution(resolution_tex)
+    images = targets["images"].detach().to(device=dev, dtype=torch.float32)
+    vm = targets["viewmask"].detach().to(device=dev, dtype=torch.float32)
+    vm = vm[..., None] if vm.dim() == 3 else vm
+    if images.dim() != 4 or images.shape[-1] != 3 or tuple(vm.shape) != tuple(images.shape[:3]) + (1,):
+        raise ValueError(f"fit_texture: expected images [B,H,W,3] and viewmask [B,H,W], got {tuple(images.shape)} and {tuple(targets['viewmask'].shape)}")
+    H, W = images.shape[1], images.shape[2]
+    if init is None:
+        tex = torch.full((Ht, Wt, 3), 0.5, dtype=torch.float32, device=dev)
+    else:
+        if tuple(init.shape) != (Ht, Wt, 3):
+            raise ValueError(f"fit_texture: expected init [{Ht},{Wt},3], got {tuple(init.shape)}")
+        tex = init.detach().to(device=dev, dtype=torch.float32).clone()
+    tex.requires_grad_(True)
+    fixed = textured_fixed(verts, faces, uvs, uv_idx, (Ht, Wt, 3), targets["mvp"], targets["campos"], (H, W), light, shade)
+    norm = 3.0 * vm.sum().clamp_min(1.0)
+    opt = torch.optim.Adam([tex], lr=lr)
+
+    def step(it):
+        img = render_textured(verts, faces, uvs, uv_idx, tex, targets["mvp"], targets["campos"], (H, W), light, shade, _fixed=fixed)
+        loss = ((img[..., :3] - images).abs() * vm).sum() / norm
+        return loss, {"loss": loss}, None
+
+    history = _optimise(_TextureParam(), opt, iters, step, ("loss",), callback, dev)
+    return tex.detach(), history
 
 
 # ---- the four fits ------------------------------------------------------------------------------------------------------------------

@@ -18,13 +18,17 @@ csrc/fixedtopo.hip.  `shade_diffuse` and `render_preview` are the quick-look ima
 mesh (nvdiffrec/eval.py:421-438: `bsdf == 'diffuse'`, kd = (0.75, 0.3, 0.6), an environment light, the two-sided geometric normal)
 by the shading part of the mesh post-processing contract in the header comment of csrc/meshpost.hip: in the manner of that image,
 not equal to it -- the environment comes in as nine spherical-harmonic coefficients (`sh9_from_latlong`, `default_light`), which
-stand in for the reference's cosine-convolved cube map, and `preview_camera` is its `rotate_scene`.  The kernels run on the GPU
+stand in for the reference's cosine-convolved cube map, and `preview_camera` is its `rotate_scene`.  `render_textured` is the same
+image with a `kd` texture in place of the one colour (the reference's `Texture2D.sample` inside render.py:shade): `rasterize` ->
+`interpolate` of the texture coordinates -> `texture.sample` (the texture contract, csrc/texture.hip) -> times the irradiance of
+`shade_diffuse` -> `antialias`, differentiable in the texture (`fit.fit_texture`).  The kernels run on the GPU
 only: a CPU tensor is an error, not a fallback.  The camera helpers, `xfm_points` and `shading_normal` are plain torch and run
 anywhere; `sh9_from_latlong` and `default_light` are numpy on the host.
 
-Not built: materials beyond one diffuse colour, specular / PBR shading, cube maps and `.hdr` loading,
-camera-space lights, gradients of the preview, textures, spp > 1 / MSAA, clipping of triangles that cross w = 0, more than
-two layers, gradients for mvp / campos and zf, a silhouette search beyond the covering triangle.
+Not built: materials beyond a diffuse colour or `kd` texture (`ks`, normal maps), specular / PBR shading,
+cube maps and `.hdr` loading, mip maps and trilinear filtering (no uv screen derivatives leave the rasteriser), MLP textures,
+camera-space lights, gradients of the preview and of the textured render w.r.t. the geometry, spp > 1 / MSAA, clipping of triangles
+that cross w = 0, more than two layers, gradients for mvp / campos and zf, a silhouette search beyond the covering triangle.
 """
 import numpy as np
 import torch
@@ -845,3 +849,66 @@ def render_preview(verts, faces, mvp, campos, resolution, *, kd=PREVIEW_KD, ligh
             col = _AntialiasFn.apply(col, clip, rast, f, edge_neighbours(f, v.shape[0]))[0]
         rgb = col[..., 0:3] + (1 - col[..., 3:4]) * bg
     return torch.clamp(_tonemap_srgb(rgb), 0.0, 1.0).contiguous()
+
+
+# ---- the textured render (Texture2D.sample inside the reference's shade, render.py:57-80) ---------------------------------------------
+@torch.no_grad()
+def textured_fixed(verts, faces, uvs, uv_idx, tex_shape, mvp, campos, resolution, light=None, shade=True):
+    """Everything of `render_textured` that does not depend on the texture, for its `_fixed=`: a dict of `rast` (layer 1), `uv`
+    float32 [B,H,W,2] (`interpolate(uvs, rast, uv_idx)`), `irradiance` float32 [B,H,W,4] (`shade_diffuse` with kd = 1: rgb and the
+    coverage; with shade=False rgb is 1 where covered), `plan` (the `texture.SamplePlan` of uv, rast and tex_shape), and `clip`,
+    `faces`, `neighbours` for the antialiasing.  A fit on a fixed mesh and fixed cameras builds it once."""
+    from . import texture
+    _gpu_only(verts, "render_textured")
+    H, W = _resolution(resolution)
+    dev = verts.device
+    if mvp.dim() != 3 or mvp.shape[1:] != (4, 4) or tuple(campos.shape) != (mvp.shape[0], 3):
+        raise ValueError(f"render_textured: expected mvp [B,4,4] and campos [B,3], got {tuple(mvp.shape)} and {tuple(campos.shape)}")
+    if verts.dim() != 2 or verts.shape[-1] != 3 or verts.shape[0] < 1 or uvs.dim() != 2 or uvs.shape[-1] != 2 or uvs.shape[0] < 1:
+        raise ValueError(f"render_textured: expected verts [V,3] and uvs [N,2], got {tuple(verts.shape)} and {tuple(uvs.shape)}")
+    if tuple(uv_idx.shape) != tuple(faces.shape):
+        raise ValueError(f"render_textured: uv_idx {tuple(uv_idx.shape)} and faces {tuple(faces.shape)} must have one shape")
+    v = verts.detach().to(torch.float32).contiguous()
+    f = _check_faces(faces.to(dev), v.shape[0])
+    uv_attr = uvs.detach().to(device=dev, dtype=torch.float32).contiguous()
+    ui = _check_tri(uv_idx.to(dev), uv_attr.shape[0])
+    m = mvp.detach().to(device=dev, dtype=torch.float32).contiguous()
+    cam = campos.detach().to(device=dev, dtype=torch.float32).contiguous()
+    clip = xfm_points(v[None], m).contiguous()
+    _check_clip(clip)
+    rast = _rasterize(clip, f, H, W)[0]
+    uv = interpolate(uv_attr, rast, ui).contiguous()
+    sh = _device_constant(None, dev) if light is None else torch.as_tensor(light).detach().to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(sh.shape) != (9, 3):
+        raise ValueError(f"render_textured: expected light [9,3], got {tuple(sh.shape)}")
+    irr = _shade_diffuse(rast, v, f, cam, sh, torch.ones(3, dtype=torch.float32, device=dev))
+    if not shade:
+        irr = irr[..., 3:4].expand(-1, -1, -1, 4).contiguous()
+    return {"rast": rast, "uv": uv, "irradiance": irr, "plan": texture.SamplePlan(uv, rast, tex_shape), "clip": clip, "faces": f,
+            "neighbours": edge_neighbours(f, v.shape[0])}
+
+
+def render_textured(verts, faces, uvs, uv_idx, tex, mvp, campos, resolution, light=None, shade=True, antialias=True, _fixed=None):
+    """The diffuse image of a textured mesh, float32 [B,H,W,4] (rgb, coverage): `rasterize` layer 1 of xfm_points(verts, mvp) ->
+    `interpolate(uvs, rast, uv_idx)` -> `texture.sample(tex, uv, rast)` (tex float32 [Ht,Wt,3], boundary clamp) -> times the
+    irradiance of `shade_diffuse(kd = 1)` under `light` (sh [9,3], None = `default_light()`; shade=False: the raw kd) -> the existing
+    `antialias` on the four channels.  Linear colour, zero background, no tone mapping.  uvs [N,2] and uv_idx [F,3] are any atlas:
+    the per-tet one of `DMTet()` or `texture.face_atlas`.  Differentiable in `tex`; the geometry and the irradiance are constants.
+    An empty mesh gives zeros.  _fixed: the dict of `textured_fixed` for these arguments, computed once for a fit."""
+    from . import texture
+    _gpu_only(verts, "render_textured")
+    H, W = _resolution(resolution)
+    t = tex[0] if tex.dim() == 4 and tex.shape[0] == 1 else tex
+    if t.dim() != 3 or t.shape[-1] != 3:
+        raise ValueError(f"render_textured: expected tex [Ht,Wt,3], got {tuple(tex.shape)}")
+    if verts.shape[0] == 0 or faces.shape[0] == 0:
+        return torch.zeros((mvp.shape[0], H, W, 4), dtype=torch.float32, device=verts.device)
+    fx = _fixed if _fixed is not None else textured_fixed(verts, faces, uvs, uv_idx, t.shape, mvp, campos, (H, W), light, shade)
+    if tuple(fx["rast"].shape[1:3]) != (H, W) or fx["rast"].shape[0] != mvp.shape[0]:
+        raise ValueError("render_textured: _fixed belongs to other views")
+    kd = texture.sample(t, fx["uv"], fx["rast"], plan=fx["plan"])
+    irr = fx["irradiance"]
+    col = torch.cat([kd * irr[..., :3], irr[..., 3:4]], -1)
+    if antialias:
+        col = _AntialiasFn.apply(col, fx["clip"], fx["rast"], fx["faces"], fx["neighbours"])[0]
+    return col
