@@ -212,8 +212,9 @@ extern "C" int md_dropout_scale(float* out, int32_t batch, int32_t C, int64_t P,
     return MD_ERR_BAD_ARG;
   dim3 grid((unsigned)((P * 2 + 255) / 256), (unsigned)(C / 8), (unsigned)batch);
   MD_HIP_CLEAR_ERROR();
+  const uint32_t thr16 = md_drop_thr16(drop_p);   // thr16 == 0: no mask and no scale, as in every user of the mask
   hipLaunchKernelGGL(md_dropout_scale_kernel, grid, dim3(256), 0, (hipStream_t)stream, out, C, P, c_total, c_off,
-                     md_drop_thr16(drop_p), 1.0f / (1.0f - drop_p), (uint64_t)drop_seed);
+                     thr16, thr16 ? 1.0f / (1.0f - drop_p) : 1.0f, (uint64_t)drop_seed);
   MD_HIP_CHECK_LAUNCH();
   return MD_OK;
 }

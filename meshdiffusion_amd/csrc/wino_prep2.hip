@@ -363,7 +363,7 @@ static int md_wino_prep2_launch(const float* x1, const float* x2, int32_t c1, in
   if (!x1 || !t_out || batch <= 0 || c1 <= 0 || c2 < 0 || (c1 & 7) || (c2 & 7) || (c2 > 0 && !x2)) return MD_ERR_BAD_ARG;
   if (silu && !ac) return MD_ERR_BAD_ARG;      // SiLU is applied together with the folded GroupNorm affine only
   if (D <= 0 || H <= 0 || W <= 0 || (W & 1) || (ups && ((D | H | W) & 1))) return MD_ERR_BAD_ARG;
-  if (!(drop_p >= 0.f && drop_p < 1.f) || (drop_p > 0.f && (ups || c2 > 0))) return MD_ERR_BAD_ARG;
+  if (!(drop_p >= 0.f && drop_p < 1.f)) return MD_ERR_BAD_ARG;
   const int64_t P = (int64_t)D * H * W;
   if ((P2_POS % W) || (P % P2_POS)) return MD_ERR_UNSUPPORTED;      // whole rows per workgroup
   const int64_t blocks = (int64_t)batch * ((c1 + c2) / 8) * (P / P2_POS);

@@ -17,6 +17,7 @@ outputs are stored):
   train_grads.npz    reference loss function (train mode): loss + per-parameter gradient norms / samples
   train_grads_b2.npz the same for the real res64 network at B = 2 (--only train_b2)
   train_grads_trained.npz the same at B = 1 on the adversarial trained-like weights (--only train_trained)
+  train_grads_drop.npz the res64 B = 2 recipe with dropout 0.1 under seeded masks, and the seed list (--only train_drop)
   dataset.npz        reference ShapeNetDMTetDataset items (augmentation on/off) for seeded on-disk grids
   dmtet.npz          reference DMTet.__call__ on the shipped 64-grid: counts, hashes, samples
   tetgrid.npz        reference DMTet.__call__ on the small synthetic grids of tests/tetgrid_cases.py: counts and hashes
@@ -570,10 +571,35 @@ class fixed_draws:
         torch.randint, torch.randn_like = self.ri, self.rl
 
 
-def gen_train(full, b2_only=False, trained_only=False):
+DROP_P = 0.1            # train_grads_drop.npz: the shipped configurations' dropout
+DROP_SEED_SEED = 777    # the generator seed its mask seeds are drawn from
+
+
+class SeededDropout(torch.nn.Module):
+    """Stands in for one `Dropout_0` of the reference: multiplies by the {0, 1/(1-p)} factors of the counter-based training mask
+    (tests/dropout_cases.py, the host restatement of csrc/md_common.h).  Every instance pops the next seed of the shared list when
+    it RUNS, so the k-th seed belongs to the k-th ResnetBlock in forward order."""
+
+    def __init__(self, p, seeds):
+        super().__init__()
+        self.p, self.seeds = p, seeds
+
+    def forward(self, h):
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import dropout_cases as dc
+        assert self.training
+        B, C = h.shape[:2]
+        P = h[0, 0].numel()
+        f = dc.factor(self.seeds.pop(0), self.p, B, C, 0, C, P)
+        return h * torch.from_numpy(f).reshape(h.shape)
+
+
+def gen_train(full, b2_only=False, trained_only=False, drop_only=False):
     """Loss and parameter gradients of the UNMODIFIED reference loss function (lib/diffusion/losses.py:54-85, train
     mode, dropout 0) for the small res64/res128 configs and -- `full` -- the real res64 network at B=1.
-    Stored per parameter: gradient norm and a strided sample of <= 256 entries."""
+    Stored per parameter: gradient norm and a strided sample of <= 256 entries.
+    drop_only: train_grads_drop.npz -- the `res64_b2` recipe with dropout 0.1, every block's `Dropout_0` instance replaced by a
+    SeededDropout; the seed list is stored next to the results."""
     rsampling, rsde, rmutils = import_reference()
     from lib.diffusion import losses as rlosses
     cases = [("small_res64", synth.small_config(), 8, 1234), ("small_res128", synth.small_config_res128(), 8, 4321)]
@@ -591,10 +617,15 @@ def gen_train(full, b2_only=False, trained_only=False):
         # bf16x3, which has no block scale to upset: this pins that claim to the reference's autograd)
         from meshdiffusion_amd.config import get_config_res64
         cases = [("res64_trained", get_config_res64(), 1, 4321)]
+    if drop_only:
+        # train_grads_drop.npz: the path bench.py times (dropout 0.1; the mask inside the kept Winograd operand, md_wgrad_wino,
+        # the f16f6 data gradients) on the reference's autograd
+        from meshdiffusion_amd.config import get_config_res64
+        cases = [("res64_b2_drop", get_config_res64(), 2, 1234)]
     out = {}
     for name, cfg, B, sd_seed in cases:
         cfg.device = torch.device("cpu")
-        cfg.model.dropout = 0.0
+        cfg.model.dropout = DROP_P if drop_only else 0.0
         R = cfg.data.image_size
         if name.endswith("_trained"):
             from meshdiffusion_amd.lib.diffusion.models import ddpm_res64, utils as mutils  # noqa: F401
@@ -604,6 +635,14 @@ def gen_train(full, b2_only=False, trained_only=False):
         else:
             sd = make_sd(cfg, R, seed=sd_seed)
         model = ref_model(rmutils, cfg, sd)
+        if drop_only:
+            blocks = [m for m in model.modules() if isinstance(getattr(m, "Dropout_0", None), torch.nn.Dropout)]
+            assert blocks and all(m.Dropout_0.p == DROP_P for m in blocks)
+            seeds = torch.randint(0, 2 ** 62, (len(blocks),), generator=torch.Generator().manual_seed(DROP_SEED_SEED)).tolist()
+            assert len(set(seeds)) == len(seeds)
+            out[f"{name}_seeds"], out[f"{name}_p"] = np.array(seeds, dtype=np.int64), np.float64(DROP_P)
+            for m in blocks:
+                m.Dropout_0 = SeededDropout(DROP_P, seeds)
         batch, labels, noise, mask = train_step_inputs(B, R, seed=2024)
         sde = rsde.VPSDE(beta_min=cfg.model.beta_min, beta_max=cfg.model.beta_max, N=cfg.model.num_scales)
         loss_fn = rlosses.get_ddpm_loss_fn(sde, train=True, mask=mask)
@@ -611,6 +650,7 @@ def gen_train(full, b2_only=False, trained_only=False):
         with fixed_draws(labels, noise):
             loss = loss_fn(model, batch)
         loss.backward()
+        assert not drop_only or not seeds, "a Dropout_0 did not run"
         print(f"[train {name}] reference loss {float(loss):.6f}  ({time.time() - t0:.1f} s)")
         out[f"{name}_loss"] = np.float64(float(loss))
         out[f"{name}_B"], out[f"{name}_sd_seed"] = np.int64(B), np.int64(sd_seed)
@@ -624,7 +664,8 @@ def gen_train(full, b2_only=False, trained_only=False):
             out[f"{name}/{n}/sample"] = g[::stride][:256].numpy().copy()
             gsq += float(g.double().square().sum())
         out[f"{name}_gnorm"] = np.float64(gsq ** 0.5)
-    fname = "train_grads_trained.npz" if trained_only else ("train_grads_b2.npz" if b2_only else "train_grads.npz")
+    fname = "train_grads_drop.npz" if drop_only else \
+        "train_grads_trained.npz" if trained_only else ("train_grads_b2.npz" if b2_only else "train_grads.npz")
     np.savez_compressed(os.path.join(GOLD, fname), **out)
 
 
@@ -669,7 +710,7 @@ def gen_dataset():
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-res64", action="store_true")
-    ap.add_argument("--only", choices=["unet", "dmtet", "tetgrid", "dataset", "train", "train_b2", "train_trained", "graded", "ddim", "trained"], default=None)
+    ap.add_argument("--only", choices=["unet", "dmtet", "tetgrid", "dataset", "train", "train_b2", "train_trained", "train_drop", "graded", "ddim", "trained"], default=None)
     ap.add_argument("--graded", default="config1,cond32,res128", help="which graded-size sampler fixtures to (re)generate")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
@@ -686,6 +727,8 @@ if __name__ == "__main__":
         gen_train(full=False, b2_only=True)
     if a.only == "train_trained" or (a.only is None and not a.skip_res64):
         gen_train(full=False, trained_only=True)
+    if a.only == "train_drop" or (a.only is None and not a.skip_res64):
+        gen_train(full=False, drop_only=True)
     if a.only in (None, "unet"):
         gen_unet_and_sampler(a.skip_res64)
     if a.only in (None, "ddim"):

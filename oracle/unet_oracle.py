@@ -91,8 +91,12 @@ def upsample(p, x):
     return F.conv3d(h, p["Conv_0.weight"], p["Conv_0.bias"], padding=1)
 
 
-def unet_res64_forward(sd, cfg, x, labels):
+def unet_res64_forward(sd, cfg, x, labels, drops=None):
     """lib/diffusion/models/ddpm_res64.py:126-199 and ddpm_res128.py:137-215 driven by a state dict.
+
+    drops (training mode): one entry per ResnetBlock in execution order, each the explicit {0, 1/(1-p)} factor tensor of
+    that block's dropout (`resnet_block(drop=...)`), or a callable (B, C, D, H, W) -> that tensor, called with the shape
+    of the activation it multiplies.  None: eval mode, dropout is the identity.
 
     cfg: dict(nf, ch_mult, num_res_blocks, attn_resolutions, image_size[, level0_blocks]); sd keys may
     carry a leading 'module.' (DataParallel) prefix.  The res128 variant is recognised from the state
@@ -108,6 +112,17 @@ def unet_res64_forward(sd, cfg, x, labels):
     nres = len(ch_mult)
     blocks_at = lambda lvl: cfg.get("level0_blocks") or nrb if lvl == 0 else nrb  # noqa: E731
     i = 0
+    drops = list(drops) if drops is not None else None
+    n_drops = len(drops) if drops is not None else 0
+
+    def res(p, xin):
+        if drops is None:
+            return resnet_block(p, xin, temb)
+        d = drops.pop(0)
+        if callable(d):
+            d = d((xin.shape[0], p["Conv_1.weight"].shape[0]) + tuple(xin.shape[2:]))
+        return resnet_block(p, xin, temb, drop=d)
+
     temb = timestep_embedding(labels, nf)
     temb = F.linear(temb, mod(i)["weight"], mod(i)["bias"]); i += 1
     temb = F.linear(F.silu(temb), mod(i)["weight"], mod(i)["bias"]); i += 1
@@ -119,24 +134,25 @@ def unet_res64_forward(sd, cfg, x, labels):
     hs = [h0]
     for lvl in range(nres):
         for _ in range(blocks_at(lvl)):
-            h = resnet_block(mod(i), hs[-1], temb); i += 1
+            h = res(mod(i), hs[-1]); i += 1
             if h.shape[-1] in attn_res:
                 h = attn_block(mod(i), h); i += 1
             hs.append(h)
         if lvl != nres - 1:
             hs.append(downsample(mod(i), hs[-1])); i += 1
     h = hs[-1]
-    h = resnet_block(mod(i), h, temb); i += 1
+    h = res(mod(i), h); i += 1
     h = attn_block(mod(i), h); i += 1
-    h = resnet_block(mod(i), h, temb); i += 1
+    h = res(mod(i), h); i += 1
     for lvl in reversed(range(nres)):
         for _ in range(blocks_at(lvl) + 1):
-            h = resnet_block(mod(i), torch.cat([h, hs.pop()], dim=1), temb); i += 1
+            h = res(mod(i), torch.cat([h, hs.pop()], dim=1)); i += 1
         if h.shape[-1] in attn_res:
             h = attn_block(mod(i), h); i += 1
         if lvl != 0:
             h = upsample(mod(i), h); i += 1
     assert not hs
+    assert not drops, f"{n_drops} dropout factors for {n_drops - len(drops)} ResnetBlocks"
     h = F.silu(group_norm(h, mod(i)["weight"], mod(i)["bias"])); i += 1
     h = F.conv3d(h, mod(i)["weight"], mod(i)["bias"], padding=mod(i)["weight"].shape[-1] // 2); i += 1
     assert f"all_modules.{i}.weight" not in sd

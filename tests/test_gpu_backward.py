@@ -3,6 +3,7 @@ Tolerance 2e-4 rel-L2: the gradients go through bf16x3 contractions twice (dgrad
 import pytest
 import torch
 
+import dropout_cases as dc
 from conftest import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -137,19 +138,29 @@ def test_resnet_block_training_through_winograd_path(hip_lib):
         tape = []
         torch.manual_seed(99)
         ops.PROFILE = []
+        real_gn, real_prep = ops.gn_apply, ops.wino_prep
+        ops.gn_apply = lambda *a, **k: (masked["gn_apply"].append(k.get("drop")), real_gn(*a, **k))[1]
+        ops.wino_prep = lambda *a, **k: (masked["wino_prep"].append(k.get("drop")), real_prep(*a, **k))[1]
         try:
             with torch.no_grad():
                 y = blk.forward_blocked(parts, B, P, temb.cuda(), tape=tape)
                 dparts, _ = blk.backward_blocked(tape[0], _f32b(ops, dy))
             tags = [e[0] for e in ops.PROFILE]
         finally:
-            ops.PROFILE = None
+            ops.PROFILE, ops.gn_apply, ops.wino_prep = None, real_gn, real_prep
         grads = {n: q.grad.clone() for n, q in blk.named_parameters() if q.grad is not None}
-        return y, dparts, grads, tape[0]["drop"], tags
+        return y, dparts, grads, tape[0], tags
 
-    y, dparts, grads, (pd, seed), tags = run()
+    masked = dict(gn_apply=[], wino_prep=[])
+    y, dparts, grads, tp, tags = run()
+    (pd, seed) = tp["drop"]
     assert tags.count("wino") == 4 and tags.count("wino_prep") == 4        # Conv_0, Conv_1 forward + their two data gradients
-    scale = ops.f32b_to_ncdhw(ops.dropout_scale(B, cout, P, p, seed, torch.device("cuda", 0)), (S, S, S)).cpu()
+    # this route: md_gn_apply(drop) writes the masked S16B activation (direct weight gradient) AND md_wino_prep(drop) the masked
+    # operand of the forward conv -- two launches that must agree on one mask; no T is kept, md_wgrad_wino does not run
+    assert masked["gn_apply"].count((p, seed)) == 1 and masked["wino_prep"].count((p, seed)) == 1
+    assert tp["a1"] is not None and tp["t1"] is None and tp["t0"] is None and "wgrad_wino" not in tags
+    # the mask of the oracle is the host restatement of the contract (tests/dropout_cases.py), not a kernel's
+    scale = torch.from_numpy(dc.factor(seed, p, B, cout, 0, cout, P)).reshape(B, cout, S, S, S)
     sdr = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     xr = [x.clone().requires_grad_(True) for x in xs]
     tr = temb.clone().requires_grad_(True)
@@ -163,10 +174,10 @@ def test_resnet_block_training_through_winograd_path(hip_lib):
     # the direct kernels on the same inputs and mask
     ops.WINO = False
     try:
-        y2, dparts2, grads2, drop2, tags2 = run()
+        y2, dparts2, grads2, tp2, tags2 = run()
     finally:
         ops.WINO = True
-    assert "wino" not in tags2 and drop2 == (pd, seed)
+    assert "wino" not in tags2 and tp2["drop"] == (pd, seed)
     assert rel_l2(y.cpu(), y2.cpu()) < 2e-5
     for g, g2 in zip(dparts, dparts2):
         assert rel_l2(g.cpu(), g2.cpu()) < 5e-5

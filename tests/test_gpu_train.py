@@ -191,7 +191,7 @@ def test_whole_unet_backward_and_train_step_vs_oracle_autograd(hip_lib, arch, B)
     assert len(moved) == len(grads) and state["step"] == 2 and ema.num_updates == 1
 
 
-@pytest.mark.parametrize("case", ["small_res64", "small_res128", "res64", "res64_b2", "res64_trained"])
+@pytest.mark.parametrize("case", ["small_res64", "small_res128", "res64", "res64_b2", "res64_trained", "res64_b2_drop"])
 def test_loss_and_gradients_vs_reference_golden(hip_lib, case):
     """The UNMODIFIED reference loss function run on the CPU by oracle/gen_golden.py (train mode, dropout 0, fixed
     labels/noise) pins loss and every parameter gradient of the HIP path -- `res64` is the real 364 M-parameter
@@ -199,7 +199,11 @@ def test_loss_and_gradients_vs_reference_golden(hip_lib, case):
     `res64_b2` (train_grads_b2.npz) the same at B = 2, where the 32^3 levels run through the Winograd forward /
     data-gradient kernels as well (hip_ops.wino_ok), so those are pinned to the reference's autograd at two grid sizes;
     `res64_trained` (train_grads_trained.npz) the real network at B = 1 on the adversarial trained-like weights of round 5 (heavy tails,
-    2^U(-3,3) GroupNorm gammas): training runs bf16x3, which has no block scale to upset."""
+    2^U(-3,3) GroupNorm gammas): training runs bf16x3, which has no block scale to upset.
+    `res64_b2_drop` (train_grads_drop.npz) is `res64_b2` with dropout 0.1, the setting both shipped configurations train with and
+    bench.py times: the reference ran with every block's Dropout_0 replaced by the seeded mask of tests/dropout_cases.py, and the
+    HIP path pops the stored seeds, one per ResnetBlock in forward order, through a patched hip_ops.next_dropout_seed.  The mask
+    inside the kept Winograd operand, md_wgrad_wino and the f16f6 data gradients are on the reference's autograd here."""
     import os
     from conftest import GOLD
     from oracle.gen_golden import fixed_draws, train_step_inputs
@@ -207,14 +211,17 @@ def test_loss_and_gradients_vs_reference_golden(hip_lib, case):
     from meshdiffusion_amd.config import get_config_res64
     from meshdiffusion_amd.lib.diffusion import losses, sde_lib
     from meshdiffusion_amd.lib.diffusion.models import ddpm_res64, ddpm_res128, utils as mutils  # noqa: F401
-    gfile = {"res64_b2": "train_grads_b2.npz", "res64_trained": "train_grads_trained.npz"}.get(case, "train_grads.npz")
+    gfile = {"res64_b2": "train_grads_b2.npz", "res64_trained": "train_grads_trained.npz",
+             "res64_b2_drop": "train_grads_drop.npz"}.get(case, "train_grads.npz")
     if not os.path.exists(os.path.join(GOLD, gfile)):
         pytest.skip(f"{gfile} not generated")
     gold = np.load(os.path.join(GOLD, gfile))
     cfg = {"small_res64": synth.small_config, "small_res128": synth.small_config_res128, "res64": get_config_res64,
-           "res64_b2": get_config_res64, "res64_trained": get_config_res64}[case]()
+           "res64_b2": get_config_res64, "res64_trained": get_config_res64, "res64_b2_drop": get_config_res64}[case]()
     cfg.device = torch.device("cuda")
-    cfg.model.dropout = 0.0
+    drop_seeds = [int(s) for s in gold[f"{case}_seeds"]] if case == "res64_b2_drop" else None
+    cfg.model.dropout = float(gold[f"{case}_p"]) if drop_seeds else 0.0
+    assert not drop_seeds or cfg.model.dropout == 0.1
     R, B = cfg.data.image_size, int(gold[f"{case}_B"])
     model = mutils.create_model(cfg)
     make = synth.trained_like_state_dict if case.endswith("_trained") else synth.sensitised_state_dict
@@ -228,14 +235,24 @@ def test_loss_and_gradients_vs_reference_golden(hip_lib, case):
     wino_launches = []
     real_wino = hip_ops.conv3_wino
     hip_ops.conv3_wino = lambda ww, t, B_, S_, **kw: (wino_launches.append(S_), real_wino(ww, t, B_, S_, **kw))[1]
+    wgrad_launches = []
+    real_wgrad, real_seed = hip_ops.wgrad_wino, hip_ops.next_dropout_seed
+    hip_ops.wgrad_wino = lambda u, t, B_, co, ci, S_, dw, **kw: (wgrad_launches.append(S_), real_wgrad(u, t, B_, co, ci, S_, dw, **kw))[1]
+    if drop_seeds:
+        left = list(drop_seeds)
+        hip_ops.next_dropout_seed = lambda: left.pop(0)       # IndexError if the net asks for more masks than the reference had blocks
     try:
         with fixed_draws(labels.cuda(), noise.cuda()):
             loss = loss_fn(model, batch.cuda())
         loss.backward()
     finally:
-        hip_ops.conv3_wino = real_wino
-    if case == "res64_b2":      # the point of this case: Winograd launches (forward and data gradient) at both grid sizes
+        hip_ops.conv3_wino, hip_ops.wgrad_wino, hip_ops.next_dropout_seed = real_wino, real_wgrad, real_seed
+    if case in ("res64_b2", "res64_b2_drop"):      # the point of these cases: Winograd launches (forward and data gradient) at both grid sizes
         assert hip_ops.WINO and wino_launches.count(64) >= 20 and wino_launches.count(32) >= 20, sorted(set(wino_launches))
+    if drop_seeds:
+        assert not left, f"{len(left)} of {len(drop_seeds)} stored seeds were not drawn"
+        print(f"{case}: md_wgrad_wino launches at 64^3: {wgrad_launches.count(64)}, at 32^3: {wgrad_launches.count(32)}")
+        assert wgrad_launches.count(64) > 0 and wgrad_launches.count(32) > 0, wgrad_launches
     ref_loss = float(gold[f"{case}_loss"])
     assert abs(float(loss.detach()) - ref_loss) / ref_loss < 2e-5
     gnorm = float(gold[f"{case}_gnorm"])
