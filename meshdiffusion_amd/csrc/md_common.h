@@ -43,10 +43,12 @@ __device__ __forceinline__ void md_split2(float x0, float x1, uint32_t& hi, uint
 }
 
 // fp16x2 mode ("weights split, activations single"): w ~= hi + lo with hi = fp16(w), lo = fp16(w - hi);
-// activations are one fp16 (saturated to the finite range).
+// activations are one fp16.  FINITE values saturate at the fp16 range; NaN and +-inf pass as what they are (fminf(fmaxf(..)) alone
+// maps NaN to -65504 and inf to +-65504: a non-finite operand would reach the MFMA as a large finite number,
+// tests/test_gpu_nonfinite_kernels.py).  The same rule as md_sat_f16_finite below.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ uint32_t md_f2h(float f) {
-  f = fminf(fmaxf(f, -65504.f), 65504.f);
+  if (__builtin_isfinite(f)) f = fminf(fmaxf(f, -65504.f), 65504.f);
   return (uint32_t)__half_as_ushort(__float2half_rn(f));
 }
 __device__ __forceinline__ float md_h2f(uint32_t h) { return __half2float(__ushort_as_half((unsigned short)h)); }

@@ -176,7 +176,10 @@ __global__ __launch_bounds__(WG_THREADS) void md_wgrad_kernel(const WgArgs g) {
 #pragma unroll
     for (int i = 0; i < B_ITERS; ++i) {
       uint4 x = make_uint4(0, 0, 0, 0);
-      if (FULL || b_ok) x = *(const uint4*)(pb + 2 * i * b_pos);
+      // window position j meets dY position q with tap t = j - q: beyond valid + NTAP - 2 only MASKED dY positions read it.  Those
+      // are zeroed as well: a zero of dY times a NaN / inf of A (the next row's voxels) would put a NaN into taps that never reach it
+      // (tests/test_gpu_nonfinite_kernels.py); finite products were zeros either way.
+      if (FULL || (b_ok && fpos + 2 * i < valid + NTAP - 1)) x = *(const uint4*)(pb + 2 * i * b_pos);
       rb[i] = x;
     }
   };

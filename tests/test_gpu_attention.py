@@ -23,7 +23,7 @@ Which path of the online softmax each case owns (waves x tiles; "live" = rescale
   randn-N4096-B2                    ordinary operands (lo planes in use), logit spread ~37 log2, most waves rescale
 
 Measured on an MI355X: see DESIGN.md, "Direct tests of the attention kernels".
-Non-finite operands to the attention kernels are not covered here: that gap of tests/test_gpu_nonfinite.py stays open.
+Non-finite operands to the attention kernels: tests/test_gpu_nonfinite_kernels.py (on the exact cases of this module).
 """
 import pytest
 import torch

@@ -111,9 +111,8 @@ XFOLD_CFGS = ("CFG_C3X_128_K16", "CFG_C5X_128")       # operand from md_ncdhw_to
 FOLD_CFGS = ("CFG_C3X_32", "CFG_C5X_32_K16")           # result through md_fold_dx
 
 
-@pytest.mark.parametrize("case_id", _ids("gemm"))
-def test_gemm_conv_exact(ops, case_id):
-    spec = cc.spec_of(case_id)
+def gemm_run(ops, spec):
+    """The md_gemm_conv launcher of a "gemm" spec (tests/test_gpu_nonfinite_kernels.py launches poisoned cases through it too)."""
     cfg = getattr(ops, spec["cfg"])
     fast = spec["cfg"] == "CFG_C3_128_FAST"
     prec = ops.PREC_FP16X2 if spec.get("prec") == "fp16x2" else ops.PREC_BF16X3
@@ -163,15 +162,19 @@ def test_gemm_conv_exact(ops, case_id):
             return ops.fold_dx(out, case["bias"].reshape(-1).cuda() if case["bias"] is not None else None, B, cout, k, rows_alloc, None, dims=dims), None
         return ops.f32b_to_ncdhw(out, dims), st
 
-    _drive(spec, run)
+    return run
+
+
+@pytest.mark.parametrize("case_id", _ids("gemm"))
+def test_gemm_conv_exact(ops, case_id):
+    spec = cc.spec_of(case_id)
+    _drive(spec, gemm_run(ops, spec))
 
 
 # ---------------------------------------------------------------------------------------------------------------
 # the dedicated kernels
 # ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case_id", _ids("s2"))
-def test_conv3_s2_exact(ops, case_id):
-    """md_conv3_s2 on the raw fp32 tensor; the far-face zero padding sits in every tile position of the non-cubic grids."""
+def s2_run(ops, spec=None):
     def run(case, stats, ksplit):
         B, cout, dims = case["B"], case["cout"], case["dims"]
         pw = ops.PackedWeight(case["w"].cuda(), "conv", ops.CFG_S2_PACK, "cuda")
@@ -181,12 +184,16 @@ def test_conv3_s2_exact(ops, case_id):
                            out=_nan_f32b(ops, B, cout, dims[0] * dims[1] * dims[2]), dims=dims)
         return ops.f32b_to_ncdhw(out, dims), st
 
-    _drive(cc.spec_of(case_id), run)
+    return run
 
 
-@pytest.mark.parametrize("case_id", _ids("stem"))
-def test_conv3_stem_exact(ops, case_id):
-    """md_ncdhw_to_s16b_xfold + md_conv3_stem with the batch-shared residual and the GroupNorm sums."""
+@pytest.mark.parametrize("case_id", _ids("s2"))
+def test_conv3_s2_exact(ops, case_id):
+    """md_conv3_s2 on the raw fp32 tensor; the far-face zero padding sits in every tile position of the non-cubic grids."""
+    _drive(cc.spec_of(case_id), s2_run(ops))
+
+
+def stem_run(ops, spec=None):
     def run(case, stats, ksplit):
         B, cout, dims = case["B"], case["cout"], case["dims"]
         w2 = case["w"].permute(0, 1, 4, 2, 3).reshape(cout, 12, 3, 3, 1).contiguous().cuda()
@@ -197,19 +204,29 @@ def test_conv3_stem_exact(ops, case_id):
         out = ops.conv3_stem(pw, ops.ncdhw_to_s16b_xfold(case["x"].cuda(), 3, 16), B, None, bias=bias, residual=res, stats=st, dims=dims)
         return ops.f32b_to_ncdhw(out, dims), st
 
-    _drive(cc.spec_of(case_id), run)
+    return run
 
 
-@pytest.mark.parametrize("case_id", _ids("nin"))
-def test_nin_f32_exact(ops, case_id):
-    """md_nin_f32: one and two parts, 128 and 256 channels, more tiles than workgroups (ragged) and fewer."""
+@pytest.mark.parametrize("case_id", _ids("stem"))
+def test_conv3_stem_exact(ops, case_id):
+    """md_ncdhw_to_s16b_xfold + md_conv3_stem with the batch-shared residual and the GroupNorm sums."""
+    _drive(cc.spec_of(case_id), stem_run(ops))
+
+
+def nin_run(ops, spec=None):
     def run(case, stats, ksplit):
         pw = ops.PackedWeight(case["w"][:, :, 0, 0, 0].t().contiguous().cuda(), "nin", ops.CFG_G1_128, "cuda")
         B, P = case["B"], case["dims"][2]
         out = ops.nin_f32(_parts(ops, case), pw, case["bias"].reshape(-1).cuda(), B, P, out=_nan_f32b(ops, B, 128, P))
         return ops.f32b_to_ncdhw(out, case["dims"]), None
 
-    _drive(cc.spec_of(case_id), run)
+    return run
+
+
+@pytest.mark.parametrize("case_id", _ids("nin"))
+def test_nin_f32_exact(ops, case_id):
+    """md_nin_f32: one and two parts, 128 and 256 channels, more tiles than workgroups (ragged) and fewer."""
+    _drive(cc.spec_of(case_id), nin_run(ops))
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -133,7 +133,9 @@ def _wino_T_direct(ops, fn, x_f, c, B, dims):
     return t
 
 
-def _prepare_wino(ops):
+def _prepare_wino(ops, verify=True):
+    """verify=False (tests/test_gpu_nonfinite_kernels.py: a NaN operand, whose payload and sign bits the host does not restate)
+    leaves out the bit-for-bit comparison of T and U with the host's planes."""
     from meshdiffusion_amd import _lib
     from meshdiffusion_amd.hip_ops import _ptr, _stream
     lib = _lib.load()
@@ -148,8 +150,9 @@ def _prepare_wino(ops):
         _, u_dy = ops.wino_prep([(dy_f, co)], None, False, False, B, 0, dual=True, dims=dims)
         # the operands in the kernel's own domain, bit for bit: a mismatch below is then md_wgrad_wino's
         shape = (B, -1, 4, 2, dims[0], dims[1], dims[2] // 2, 8)
-        assert torch.equal(t_act.view(torch.int16).cpu().view(shape), wc.t_layout(_planes(wc.wino_T(case["a"])), B, ci)), f"{spec['id']}: T"
-        assert torch.equal(u_dy.view(torch.int16).cpu().view(shape), wc.t_layout(_planes(wc.wino_U(case["dy"])), B, co)), f"{spec['id']}: U"
+        if verify:
+            assert torch.equal(t_act.view(torch.int16).cpu().view(shape), wc.t_layout(_planes(wc.wino_T(case["a"])), B, ci)), f"{spec['id']}: T"
+            assert torch.equal(u_dy.view(torch.int16).cpu().view(shape), wc.t_layout(_planes(wc.wino_U(case["dy"])), B, co)), f"{spec['id']}: U"
 
         def launch(dw, ks):
             if case["strides"] == (ci * 27, 27, 1):
