@@ -652,6 +652,28 @@ int md_slerp_dots(const float* a, const float* b, const float* mask, int32_t pai
 int md_slerp_mix(const float* a, const float* b, const float* mask, const double* slabs, const double* alpha, int32_t K,
                  float* out, double* theta_out, int32_t pairs, int32_t C, int64_t P, void* stream);
 /*
+ * Classifier-free guidance on the output of one doubled U-Net evaluation (the reference has no counterpart; Ho & Salimans 2022,
+ * rescale: Lin et al. 2023, section 3.4).  Every sampler consumes the combined eps_hat as it consumes the U-Net's.
+ *   eps2: fp32 [2*batch][n]: rows 0..batch-1 the conditional evaluation ec, rows batch..2*batch-1 the null-class evaluation eu
+ *   w   : fp32 [batch], the guidance scale of every sample
+ *   md_cfg_combine: out[b][i] = fmaf(w[b], ec - eu, eu): one float32 subtraction and one fused multiply-add, round to nearest.
+ *                   w = 0 gives eu bit for bit wherever ec - eu is finite; NaN and inf propagate.  One pass over eps2.  With
+ *                   slabs given (double[batch][MD_LANGEVIN_SLABS][4]) workgroup s of sample b also writes (not adds)
+ *                   slabs[b][s] = {sum ec, sum ec^2, sum out, sum out^2} over its strided share, every term and sum in double
+ *                   (the square of a float is exact there), in a fixed order: no atomics, the same bits every run.
+ *   md_cfg_rescale: per sample, adds the slabs in ascending order in double; mean = sum/n, var = sum2/n - mean^2 (population,
+ *                   over all n values), f = phi*sqrt(var_ec/var_out) + (1 - phi) finished in double; out[b][i] *= (float)f, one
+ *                   float32 product.  Where var_out is not > 0 or f is not finite (a constant sample, a non-finite value in either
+ *                   tensor) the sample is left as it is and f reads 1.  factor_out (double[batch], may be NULL) receives f.
+ * n is any positive count: four values per thread where n % 4 == 0, one value at a time otherwise, the sums in the same order.
+ * MD_ERR_BAD_ARG, before any launch: eps2, out null or not 16-byte aligned where n % 4 == 0 (4-byte otherwise); w null or not
+ * 4-byte aligned; slabs not 8-byte aligned (md_cfg_rescale: or null), factor_out not 8-byte aligned; batch < 1, n < 1; phi outside
+ * [0, 1] or NaN; an output sharing memory with an input or with another output (out may alias neither half of eps2).
+ * Purely additive: MD_ABI_VERSION stays 16.
+ */
+int md_cfg_combine(const float* eps2, const float* w, int32_t batch, int64_t n, float* out, double* slabs, void* stream);
+int md_cfg_rescale(float* out, const double* slabs, double phi, double* factor_out, int32_t batch, int64_t n, void* stream);
+/*
  * Inpainting blend of one channel (sampling.py:443-467):
  *   v = (x*(1-m) + src*m) * gm     applied in place to channel `ch` of x [B][C][P];
  *   src has batch stride src_bstride (0 = shared partial grid).

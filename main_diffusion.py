@@ -14,6 +14,10 @@ samples with DPM-Solver++ in 20 evaluations, in uncond_gen and cond_gen (with or
 `--mode=interp --config.sampling.method=ddim|dpmpp|ode [--config.eval.interp_points=K --config.eval.interp_pairs=Np]` writes
 {eval_dir}/interp.npy: K shapes per pair on the walk between two latents; `--config.eval.interp_sources=grids.npy` walks between
 given grids instead of prior draws, encoded by DDIM (method ddim) or ODE (method ode) inversion.
+`--config.model.num_classes=K --config.data.class_meta_path=classes.json [--config.training.class_dropout=0.1]` trains one
+class-conditional model; `--config.eval.class_id=C [--config.eval.cfg_scale=3.0 --config.eval.cfg_rescale=0.7]` then steers
+uncond_gen, cond_gen and interp with classifier-free guidance under every sampler (not with guidance_scale > 0, likelihood or
+interp_sources).
 """
 import sys
 

@@ -73,20 +73,24 @@ def apply_overrides(config, argv):
 
 
 def get_default_configs():
+    """Class conditioning (not in the reference; every field inert at its default): model.num_classes (0: the reference's
+    unconditional model), data.class_meta_path (JSON {grid path: class id}), training.class_dropout (share of labels replaced by the
+    null class), eval.class_id (an int or one per sample), eval.cfg_scale, eval.cfg_rescale."""
     c = ConfigDict()
     c.training = ConfigDict(batch_size=64, n_iters=2400001, snapshot_freq=50000, log_freq=50, eval_freq=100,
                             snapshot_freq_for_preemption=5000, snapshot_sampling=True,
                             likelihood_weighting=False, continuous=True, reduce_mean=False, iter_size=1,
-                            loss_type="l2", train_dir="PLACEHOLDER")
+                            loss_type="l2", train_dir="PLACEHOLDER", class_dropout=0.1)
     c.sampling = ConfigDict(n_steps_each=1, noise_removal=True, probability_flow=False, snr=0.075)
     c.eval = ConfigDict(begin_ckpt=50, end_ckpt=96, batch_size=512, enable_sampling=True, num_samples=50000,
                         enable_loss=True, enable_bpd=False, bpd_dataset="test", ckpt_path="PLACEHOLDER",
-                        partial_dmtet_path="PLACEHOLDER", tet_path="PLACEHOLDER", freeze_iters=950)
+                        partial_dmtet_path="PLACEHOLDER", tet_path="PLACEHOLDER", freeze_iters=950,
+                        class_id=None, cfg_scale=1.0, cfg_rescale=0.0)
     c.data = ConfigDict(dataset="LSUN", image_size=256, random_flip=True, uniform_dequantization=False,
                         centered=False, num_channels=3, num_workers=4, normalize_sdf=True,
-                        meta_path="PLACEHOLDER", filter_meta_path="PLACEHOLDER", extension="pt")
+                        meta_path="PLACEHOLDER", filter_meta_path="PLACEHOLDER", extension="pt", class_meta_path=None)
     c.model = ConfigDict(sigma_max=378, sigma_min=0.01, num_scales=2000, beta_min=0.1, beta_max=20.0,
-                         dropout=0.0, embedding_type="fourier", deform_scale=1.0)
+                         dropout=0.0, embedding_type="fourier", deform_scale=1.0, num_classes=0)
     c.optim = ConfigDict(weight_decay=0, optimizer="Adam", lr=2e-4, beta1=0.9, eps=1e-8, warmup=5000,
                          grad_clip=1.0)
     c.seed = 42

@@ -610,6 +610,112 @@ __global__ __launch_bounds__(256) void md_slerp_mix_kernel(const float* __restri
   }
 }
 
+// ---- classifier-free guidance: combine the two halves of a doubled evaluation, optional guidance rescale ------------------------
+// up to four values of a row of n at i: one vector load where the rows are 16-byte aligned (n % 4 == 0), else one value at a time;
+// a slot past the end reads as zero and is neither stored nor summed
+static __device__ __forceinline__ f32x4 md_load4_of(const float* row, int64_t i, int64_t n, bool vec) {
+  if (vec) return md_load4(row + i);
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (i + e < n) v[e] = row[i + e];
+  return v;
+}
+static __device__ __forceinline__ void md_store4_of(float* row, int64_t i, int64_t n, bool vec, f32x4 v) {
+  if (vec) {
+    md_store4(row + i, v);
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (i + e < n) row[i + e] = v[e];
+}
+
+// grid (S, B): workgroup (s, b) combines its strided share of sample b, out = fmaf(w_b, ec - eu, eu) (an explicit fma: this file
+// contracts nothing by itself), and with slabs (then S = MD_LANGEVIN_SLABS) writes slabs[b][s] = {sum ec, sum ec^2, sum out,
+// sum out^2}: terms and sums in double, four values as (t0 + t1) + (t2 + t3), then md_block_sum -- a fixed order.
+__global__ __launch_bounds__(256) void md_cfg_combine_kernel(const float* __restrict__ eps2, const float* __restrict__ w,
+                                                             float* __restrict__ out, double* __restrict__ slabs, int B, int64_t n,
+                                                             int vec) {
+  const int b = blockIdx.y;
+  const float wb = w[b];
+  const float* ec = eps2 + (int64_t)b * n;
+  const float* eu = eps2 + ((int64_t)B + b) * n;
+  float* po = out + (int64_t)b * n;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  MD_STREAM4(i, n) {
+    const f32x4 cv = md_load4_of(ec, i, n, vec), uv = md_load4_of(eu, i, n, vec);
+    f32x4 ov;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ov[e] = fmaf(wb, cv[e] - uv[e], uv[e]);
+    md_store4_of(po, i, n, vec, ov);
+    if (slabs) {
+      double c[4], o[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool in = i + e < n;
+        c[e] = in ? (double)cv[e] : 0.0;
+        o[e] = in ? (double)ov[e] : 0.0;
+      }
+      acc[0] += (c[0] + c[1]) + (c[2] + c[3]);
+      acc[1] += (c[0] * c[0] + c[1] * c[1]) + (c[2] * c[2] + c[3] * c[3]);
+      acc[2] += (o[0] + o[1]) + (o[2] + o[3]);
+      acc[3] += (o[0] * o[0] + o[1] * o[1]) + (o[2] * o[2] + o[3] * o[3]);
+    }
+  }
+  if (slabs && md_block_sum(acc)) {
+    double* row = slabs + ((int64_t)b * MD_LANGEVIN_SLABS + blockIdx.x) * 4;      // 8-byte aligned: one double at a time
+    row[0] = acc[0];
+    row[1] = acc[1];
+    row[2] = acc[2];
+    row[3] = acc[3];
+  }
+}
+
+// guidance rescale.  Prologue: the sample's slabs added in ascending order (thread 0), mean = sum/n, var = sum2/n - mean^2 for ec and
+// out, f = phi*sqrt(var_ec/var_out) + (1 - phi) in double.  A var_out at or below 2^-40 of out's mean square counts as zero: below
+// that the double sums cannot tell a spread from their own rounding (a constant sample comes out there, not at exactly 0).  Such a
+// sample, and one whose f is not finite, keeps its values and reports f = 1.  Then out *= (float)f.
+__global__ __launch_bounds__(256) void md_cfg_rescale_kernel(float* __restrict__ out, const double* __restrict__ slabs, double phi,
+                                                             double* __restrict__ factor_out, int64_t n, int vec) {
+  const int b = blockIdx.y;
+  __shared__ double s_slab[MD_LANGEVIN_SLABS][4];
+  __shared__ float s_f;
+  __shared__ int s_keep;
+  if (threadIdx.x < MD_LANGEVIN_SLABS) {
+    const double* row = slabs + ((int64_t)b * MD_LANGEVIN_SLABS + threadIdx.x) * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s_slab[threadIdx.x][k] = row[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int j = 0; j < MD_LANGEVIN_SLABS; ++j) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s[k] += s_slab[j][k];
+    }
+    const double dn = (double)n;
+    const double mc = s[0] / dn, mo = s[2] / dn, msc = s[1] / dn, mso = s[3] / dn;
+    const double vc = msc - mc * mc, vo = mso - mo * mo;
+    double f = phi * sqrt(vc / vo) + (1.0 - phi);
+    const bool keep = !(vo > 0x1p-40 * mso) || !(f == f) || f - f != 0.0;      // zero spread, NaN, inf
+    if (keep) f = 1.0;
+    s_f = (float)f;
+    s_keep = keep ? 1 : 0;
+    if (blockIdx.x == 0 && factor_out) factor_out[b] = f;
+  }
+  __syncthreads();
+  if (s_keep) return;
+  const float f = s_f;
+  float* po = out + (int64_t)b * n;
+  MD_STREAM4(i, n) {
+    f32x4 v = md_load4_of(po, i, n, vec);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = v[e] * f;
+    md_store4_of(po, i, n, vec, v);
+  }
+}
+
 // ---- exports ------------------------------------------------------------------------------------------------------------
 // The tail of an export: one launch of 256-thread workgroups on `stream`, the export's last parameter.
 #define MD_LAUNCH_STEP(kernel, grid, ...)                                                       \
@@ -803,4 +909,30 @@ extern "C" int md_slerp_mix(const float* a, const float* b, const float* mask, c
   if (md_any_alias(outs, in)) return MD_ERR_BAD_ARG;
   MD_LAUNCH_STEP(md_slerp_mix_kernel, dim3(stream_blocks(CP, pairs), (unsigned)pairs), a, b, mask, slabs, alpha, (int)K, out,
                  theta_out, CP, P);
+}
+
+extern "C" int md_cfg_combine(const float* eps2, const float* w, int32_t batch, int64_t n, float* out, double* slabs, void* stream) {
+  const bool vec = n > 0 && n % 4 == 0;
+  if (vec ? md_any_bad<16>(eps2, out) : md_any_bad<4>(eps2, out)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<4>(w) || md_any_misaligned<8>(slabs)) return MD_ERR_BAD_ARG;
+  if (batch < 1 || n < 1) return MD_ERR_BAD_ARG;
+  const int64_t bytes = 4 * n * batch;
+  const md_span outs[] = {{out, bytes}, {slabs, 32LL * MD_LANGEVIN_SLABS * batch}};
+  const md_span in[] = {{eps2, 2 * bytes}, {w, 4LL * batch}};
+  if (md_any_alias(outs, in)) return MD_ERR_BAD_ARG;
+  const unsigned gx = slabs ? (unsigned)MD_LANGEVIN_SLABS : stream_blocks(n + 3, batch);
+  MD_LAUNCH_STEP(md_cfg_combine_kernel, dim3(gx, (unsigned)batch), eps2, w, out, slabs, (int)batch, n, vec ? 1 : 0);
+}
+
+extern "C" int md_cfg_rescale(float* out, const double* slabs, double phi, double* factor_out, int32_t batch, int64_t n,
+                              void* stream) {
+  const bool vec = n > 0 && n % 4 == 0;
+  if (vec ? md_any_bad<16>(out) : md_any_bad<4>(out)) return MD_ERR_BAD_ARG;
+  if (md_any_bad<8>(slabs) || md_any_misaligned<8>(factor_out)) return MD_ERR_BAD_ARG;
+  if (batch < 1 || n < 1 || !(phi >= 0.0 && phi <= 1.0)) return MD_ERR_BAD_ARG;
+  const md_span outs[] = {{out, 4 * n * batch}, {factor_out, 8LL * batch}};
+  const md_span in[] = {{slabs, 32LL * MD_LANGEVIN_SLABS * batch}};
+  if (md_any_alias(outs, in)) return MD_ERR_BAD_ARG;
+  MD_LAUNCH_STEP(md_cfg_rescale_kernel, dim3(stream_blocks(n + 3, batch), (unsigned)batch), out, slabs, phi, factor_out, n,
+                 vec ? 1 : 0);
 }

@@ -1390,6 +1390,36 @@ def slerp(a, b, alphas, mask=None):
     return out, theta
 
 
+def cfg_combine(eps2, w, rescale=0.0, stats=False):
+    """Classifier-free guidance on a doubled evaluation (md_cfg_combine, then md_cfg_rescale when rescale > 0; no host
+    synchronisation).  eps2: [2B, ...] fp32, rows 0..B-1 the conditional and B..2B-1 the null-class output; w: [B] fp32 guidance
+    scales on the device, or one float for all.  Returns out [B, ...] = fma(w, ec - eu, eu), scaled per sample by
+    rescale*std(ec)/std(out) + (1 - rescale) (include/meshdiffusion_hip.h).  stats: returns (out, slabs [B,64,4] float64 =
+    partial sums of ec, ec^2, out, out^2 of the combine, factor [B] float64) instead; slabs are taken then even without rescale."""
+    f32, f64 = torch.float32, torch.float64
+    eps2 = _operand(eps2, "eps2", f32, copy=True)
+    assert eps2.dim() >= 1 and eps2.shape[0] >= 2 and eps2.shape[0] % 2 == 0, tuple(eps2.shape)
+    B = eps2.shape[0] // 2
+    n = eps2[0].numel()
+    if not torch.is_tensor(w):
+        w = torch.full((B,), float(w), dtype=f32, device=eps2.device)
+    w = _operand(w, "w", f32, shape=(B,), copy=True)
+    phi = float(rescale)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"cfg_combine: rescale must lie in [0, 1], got {rescale}")
+    out = torch.empty((B,) + tuple(eps2.shape[1:]), dtype=f32, device=eps2.device)
+    slabs = factor = None
+    if phi > 0.0 or stats:
+        slabs = torch.empty((B, _lib.LANGEVIN_SLABS, 4), dtype=f64, device=eps2.device)
+    call("md_cfg_combine", eps2, w, B, n, out, slabs)
+    if phi > 0.0:
+        factor = torch.empty(B, dtype=f64, device=eps2.device) if stats else None
+        call("md_cfg_rescale", out, slabs, phi, factor, B, n)
+    elif stats:
+        factor = torch.ones(B, dtype=f64, device=eps2.device)
+    return (out, slabs, factor) if stats else out
+
+
 def inpaint_blend_(x, src, pmask, gmask, ch, src_bstride=0):
     """In place on channel `ch` of x: (x*(1-pmask) + src*pmask) * gmask."""
     B, Cc, P = _state_dims(x)

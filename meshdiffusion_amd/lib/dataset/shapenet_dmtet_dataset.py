@@ -10,6 +10,9 @@ Each item is one `[4, r, r, r]` fp32 cubic grid (channel 0 = SDF, 1..3 = deforma
   by `resolution / r` when the stored grid is smaller than the model grid, then multiplies by the grid mask
   (cropped to r^3), and finally zero-pads up to the model resolution at the high end of every axis.
 
+Class labels (not in the reference): with `class_meta_path`, a JSON dict {grid file path: class id}, every item is `(grid, y)` with
+`y` an int64 scalar; a listed grid without an entry is refused at construction.  Without it an item is the grid alone, as ever.
+
 RNG: the augmentation uses the process-global torch CPU generator like the reference (`torch.rand(3)`).
 """
 import json
@@ -21,7 +24,7 @@ from torch.utils.data import Dataset
 
 class ShapeNetDMTetDataset(Dataset):
     def __init__(self, root, grid_mask, deform_scale=1.0, aug=False, filter_meta_path=None, normalize_sdf=True,
-                 extension="pt"):
+                 extension="pt", class_meta_path=None):
         super().__init__()
         with open(root, "r") as f:
             self.fpath_list = json.load(f)
@@ -36,6 +39,18 @@ class ShapeNetDMTetDataset(Dataset):
             cut = len(extension) + 1
             ids = [int(p.rstrip().split("_")[-1][:-cut]) for p in self.fpath_list]
             self.fpath_list = [p for p, i in zip(self.fpath_list, ids) if i in keep]
+        # class labels (not in the reference): a JSON dict {grid file path: class id}; with it every item is (grid, y)
+        self.labels = None
+        if class_meta_path is not None:
+            with open(class_meta_path, "r") as f:
+                meta = json.load(f)
+            missing = [p for p in self.fpath_list if p not in meta]
+            if missing:
+                raise KeyError(f"{class_meta_path} has no class for {len(missing)} of {len(self.fpath_list)} grids, the first: {missing[0]!r}")
+            bad = [p for p in self.fpath_list if isinstance(meta[p], bool) or not isinstance(meta[p], int) or meta[p] < 0]
+            if bad:
+                raise ValueError(f"{class_meta_path}: class ids are integers >= 0, got {meta[bad[0]]!r} for {bad[0]!r}")
+            self.labels = [int(meta[p]) for p in self.fpath_list]
 
     def __len__(self):
         return len(self.fpath_list)
@@ -61,4 +76,6 @@ class ShapeNetDMTetDataset(Dataset):
             if r < R:
                 d = R - r
                 datum = torch.nn.functional.pad(datum, (0, d, 0, d, 0, d, 0, 0))
+        if self.labels is not None:
+            return datum, torch.tensor(self.labels[idx], dtype=torch.int64)
         return datum

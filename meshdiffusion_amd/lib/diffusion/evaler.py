@@ -43,6 +43,37 @@ def _load_model(config):
     return score_model, sde
 
 
+def class_ids_of(config, total, start=0, count=None):
+    """config.eval.class_id as the class ids of samples start .. start+count-1 of a batch of `total`: an int (every sample) or a
+    list of length `total`, sliced together with the batch when it is sharded over ranks.  None when the field is unset."""
+    cid = getattr(config.eval, "class_id", None)
+    if cid is None:
+        return None
+    count = total - start if count is None else count
+    if isinstance(cid, (int, np.integer)) and not isinstance(cid, bool):
+        return [int(cid)] * count
+    if not isinstance(cid, (list, tuple)) or len(cid) != total or not all(isinstance(c, (int, np.integer)) for c in cid):
+        raise ValueError(f"eval.class_id must be an int or a list of {total} ints (one per sample of the batch), got {cid!r}")
+    return [int(c) for c in cid[start:start + count]]
+
+
+def check_class_config(config):
+    """eval.class_id with a class-less model is refused with the way out, before a checkpoint is read."""
+    if getattr(config.eval, "class_id", None) is not None and int(getattr(config.model, "num_classes", 0) or 0) <= 0:
+        raise ValueError("eval.class_id is set, but the model has no classes (model.num_classes = 0): train a class-conditional "
+                         "model (model.num_classes > 0 with data.class_meta_path), or drop eval.class_id")
+
+
+def with_classes(config, score_model, ids):
+    """The model the samplers are given: `score_model` itself without eval.class_id (a class-conditional model then runs under its
+    null class), else sampling.ClassifierFreeModel over it with eval.cfg_scale (default 1.0) and eval.cfg_rescale (default 0.0)."""
+    if ids is None:
+        return score_model
+    check_class_config(config)
+    return sampling.ClassifierFreeModel(score_model, ids, scale=getattr(config.eval, "cfg_scale", 1.0),
+                                        rescale=getattr(config.eval, "cfg_rescale", 0.0))
+
+
 def _grid_mask(config, shape):
     R = config.data.image_size
     mask_path = getattr(config.eval, "grid_mask_path", None) or f"./data/grid_mask_{R}.pt"
@@ -87,11 +118,15 @@ def _generate(config, mask_shape, fname, run):
     rank, world = _ranks(config)
     total = int(config.eval.batch_size)
 
+    start = sum(parallel.shard_sizes(total, world)[:rank])
+    check_class_config(config)
+    class_ids_of(config, total)                         # a malformed eval.class_id: refused before the checkpoint is read
+
     def shard(local_batch, seed):
         if world > 1:
             torch.manual_seed(seed)                     # CPU generator (prior) and this rank's device generator (per-step noise)
         model, sampling_fn, _ = _setup(config, mask_shape, local_batch=local_batch)
-        return run(model, sampling_fn)
+        return run(with_classes(config, model, class_ids_of(config, total, start, local_batch)), sampling_fn)
 
     with torch.no_grad():
         samples = parallel.sharded_sample(shard, total, int(getattr(config, "seed", 0)))
@@ -151,12 +186,17 @@ def _interp(config, fname, plan, sources=None):
     from ... import hip_ops as ops
     pairs, K, method, encoded = plan
     dev, R, C = config.device, config.data.image_size, config.data.num_channels
+    check_class_config(config)
+    if encoded and class_ids_of(config, K) is not None:
+        raise NotImplementedError("interp_sources (encode=True inversions) under classifier-free guidance is not implemented: "
+                                  "drop eval.class_id or the sources")
     with torch.no_grad():
         score_model, sde = _load_model(config)
         grid_mask = _grid_mask(config, (1, R, R, R))
         fn_for = lambda batch: sampling.get_sampling_fn(config, sde, (batch, C, R, R, R), lambda x: x, 1e-3, grid_mask=grid_mask)   # noqa: E731
         decode = fn_for(K)
         _calibrate(score_model, config, K)
+        score_model = with_classes(config, score_model, class_ids_of(config, K))   # eval.class_id: an int, or one id per point of a walk
         if encoded:
             encode = fn_for(2)
             ends = torch.cat([encode(score_model, x0=sources[2 * p:2 * p + 2].to(dev), encode=True)[0].float() for p in range(pairs)])
@@ -210,6 +250,10 @@ def tet_vertices_to_grid_index(vertices):
 def cond_gen(config, save_fname="0"):
     """Conditional generation from a partial DMTet (2.5D view) scattered into the cubic grid."""
     R = config.data.image_size
+    scale = float(getattr(config.eval, "guidance_scale", 0.0) or 0.0)
+    if scale > 0 and getattr(config.eval, "class_id", None) is not None:
+        raise NotImplementedError("eval.class_id (classifier-free guidance) together with eval.guidance_scale > 0 is not implemented: "
+                                  "reconstruction guidance needs the Jacobian of the combined output")
     partial = torch.load(config.eval.partial_dmtet_path, map_location="cpu", weights_only=False)
     tet = np.load(config.eval.tet_path)
     idx = tet_vertices_to_grid_index(torch.tensor(tet["vertices"]))
@@ -221,7 +265,6 @@ def cond_gen(config, save_fname="0"):
     # reconstruction guidance (sampling.guidance_terms): optional config.eval fields guidance_scale (unset or 0: none, the call
     # below is the unguided one), guidance_replace (True: the replacement of the known voxels stays), guidance_chunk (samples per
     # taped forward).  The load-time calibration still runs; the taped forward of a guided step is bf16x3 and does not read it.
-    scale = float(getattr(config.eval, "guidance_scale", 0.0) or 0.0)
     method = str(getattr(getattr(config, "sampling", None), "method", "pc")).lower()
     kw = {} if method == "dpmpp" else dict(freeze_iters=config.eval.freeze_iters)      # DPM-Solver++ has its own time grid
     if scale > 0:
@@ -247,6 +290,9 @@ def likelihood(config):
     from ..dataset.shapenet_dmtet_dataset import ShapeNetDMTetDataset
     from . import likelihood as lk
     ev = config.eval
+    if getattr(ev, "class_id", None) is not None:
+        raise NotImplementedError("--mode=likelihood under classifier-free guidance (eval.class_id) is not implemented: the "
+                                  "divergence needs the Jacobian of the combined output")
     R = config.data.image_size
     score_model, sde = _load_model(config)
     score_model.eval()

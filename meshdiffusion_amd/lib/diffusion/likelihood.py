@@ -208,6 +208,8 @@ def get_likelihood_fn(sde, inverse_scaler, hutchinson_type='Rademacher', rtol=1e
         raise NotImplementedError(f"Hutchinson type {hutchinson_type} unknown.")
 
     def likelihood_fn(model, data, return_parts=False, probe=None):
+        from .sampling import _refuse_cfg
+        _refuse_cfg(model, "the likelihood (the divergence needs the Jacobian of the combined output)")
         with torch.no_grad():
             shape, dev = tuple(data.shape), data.device
             B = shape[0]

@@ -196,18 +196,39 @@ def masked_sq_err(eps_hat, noise, mask_flat, want_grad=False, gscale=1.0):
     return sums, grad
 
 
-def get_ddpm_loss_fn(vpsde, train, mask=None, loss_type="l2"):
+def draw_step_randoms(batch, N, y=None, class_dropout=0.0, null_class=None):
+    """The random numbers of one loss evaluation, in their order: timesteps, noise, then -- only with class ids `y` and
+    class_dropout > 0 -- one uniform per sample, below class_dropout replacing that sample's id by `null_class` (the training half
+    of classifier-free guidance).  The class draw comes last, so the first two draws of a run without classes, whatever
+    class_dropout says, are the ones they were before class conditioning existed.  Plain torch on batch.device (the process
+    generator of that device); returns (labels int64 [B], noise like batch, y or None)."""
+    labels = torch.randint(0, N, (batch.shape[0],), device=batch.device)
+    noise = torch.randn_like(batch)
+    if y is not None and float(class_dropout) > 0.0:
+        drop = torch.rand(batch.shape[0], device=batch.device) < float(class_dropout)
+        y = torch.where(drop, torch.full_like(y, int(null_class)), y)
+    return labels, noise, y
+
+
+def get_ddpm_loss_fn(vpsde, train, mask=None, loss_type="l2", class_dropout=0.0):
     if loss_type != "l2":
         raise NotImplementedError("only the l2 loss of the configured path is implemented")
     assert isinstance(vpsde, VPSDE)
+    if not 0.0 <= float(class_dropout) <= 1.0:
+        raise ValueError(f"class_dropout must lie in [0, 1], got {class_dropout}")
 
-    def loss_fn(model, batch):
+    def loss_fn(model, batch, y=None):
         model_fn = mutils.get_model_fn(model, train=train)
-        labels = torch.randint(0, vpsde.N, (batch.shape[0],), device=batch.device)
-        noise = torch.randn_like(batch)
+        if y is not None:
+            # checked on the host before anything is drawn or launched (ValueError: a class-less model, an id out of range)
+            net = getattr(model, "module", model)
+            y = net.class_ids(y, batch.shape[0], batch.device)
+            labels, noise, y = draw_step_randoms(batch, vpsde.N, y, class_dropout if train else 0.0, net.null_class)
+        else:
+            labels, noise, _ = draw_step_randoms(batch, vpsde.N)
         mask_flat = mask.reshape(-1).to(batch.device, torch.float32).contiguous() if mask is not None else None
         perturbed = ddpm_perturb(vpsde, batch, labels, noise, mask_flat)
-        score = model_fn(perturbed, labels)
+        score = model_fn(perturbed, labels, y)
         norm = 1.0
         if mask is not None:
             norm = float(np.prod(mask.size())) / float(mask.sum())
@@ -235,11 +256,14 @@ class _MaskedDDPMLoss(torch.autograd.Function):
         return (ctx.grad * g if ctx.grad is not None else None), None, None, None
 
 
-def get_step_fn(sde, train, optimize_fn=None, mask=None, loss_type="l2"):
-    loss_fn = get_ddpm_loss_fn(sde, train, mask=mask, loss_type=loss_type)
+def get_step_fn(sde, train, optimize_fn=None, mask=None, loss_type="l2", class_dropout=0.1):
+    """step_fn(state, batch, ...): `batch` is the grids [B,C,R,R,R], or (grids, y) with int64 [B] class ids for a class-conditional
+    model; class_dropout (config.training.class_dropout): the share of ids a training step replaces by the null class."""
+    loss_fn = get_ddpm_loss_fn(sde, train, mask=mask, loss_type=loss_type, class_dropout=class_dropout)
 
     def step_fn(state, batch, clear_grad=True, update_param=True):
         model = state["model"]
+        batch, y = batch if isinstance(batch, (tuple, list)) else (batch, None)
         tm = state.get("timers")              # bench.py: a dict -> device-synchronised phase times of this step (ms)
         clock = [0.0]
 
@@ -264,7 +288,7 @@ def get_step_fn(sde, train, optimize_fn=None, mask=None, loss_type="l2"):
                     fg.zero_()
             if fg is not None:
                 fg.attach()
-            loss = loss_fn(model, batch)
+            loss = loss_fn(model, batch, y)
             mark("fwd_loss")
             # one process per GPU: the replicas' gradients meet here.  On the step that updates the parameters the
             # U-Net backward announces finished layers to the reducer, whose bucket all-reduces overlap the rest of
@@ -297,7 +321,7 @@ def get_step_fn(sde, train, optimize_fn=None, mask=None, loss_type="l2"):
                 ema = state["ema"]
                 ema.store(model.parameters())
                 ema.copy_to(model.parameters())
-                loss = loss_fn(model, batch)
+                loss = loss_fn(model, batch, y)
                 ema.restore(model.parameters())
         return {"loss": loss}
 

@@ -101,9 +101,60 @@ class DDPMUNet3D(layers.HipLayer):
         # arithmetic of this model's inference convs: "bf16x3" | "f16f8" | "f16f6" | "fp16x2" (hip_ops); None = the
         # process default.  It is entered as a scope by every call and left again: a property of the model, not of the process.
         self.hip_precision = m.get("hip_precision", None) if hasattr(m, "get") else None
+        # class conditioning (not in the reference): one embedding row per class plus the null class (the last row) of classifier-free
+        # guidance, added to temb.  Registered after every module above so that no `all_modules.{i}` key moves; with
+        # model.num_classes = 0 (the default) nothing is registered, drawn or launched.
+        self.num_classes = int(getattr(m, "num_classes", 0) or 0)
+        if self.num_classes < 0:
+            raise ValueError(f"model.num_classes must be >= 0, got {self.num_classes}")
+        if self.num_classes > 0:
+            self.class_emb = nn.Embedding(self.num_classes + 1, 4 * nf)
+            nn.init.normal_(self.class_emb.weight, mean=0.0, std=0.02)
 
     def _blocks_at(self, lvl):
         return self.LEVEL0_BLOCKS if (lvl == 0 and self.LEVEL0_BLOCKS) else self.num_res_blocks
+
+    # ---- class conditioning ------------------------------------------------------------------
+    @property
+    def null_class(self):
+        """The id of the null class: the last row of class_emb."""
+        return self.num_classes
+
+    def class_ids(self, y, B, device):
+        """The int64 [B] class ids of a call on `device`, checked on the host before any launch: None is the null class for every
+        sample of a conditional model; ids outside 0..num_classes (the null id included) and any `y` given to a class-less model
+        are a ValueError.  A tensor this method returned passes again without the check (and without its device-to-host copy):
+        the samplers check once and call every step."""
+        if self.num_classes == 0:
+            if y is not None:
+                raise ValueError("this model has no classes (model.num_classes = 0): it takes no class ids `y`")
+            return None
+        if y is None:
+            return torch.full((B,), self.num_classes, dtype=torch.int64, device=device)
+        if getattr(y, "_md_class_ids_of", None) == (self.num_classes, B) and y.device == torch.device(device):
+            return y
+        ids = torch.as_tensor(y).detach().cpu()
+        if ids.dtype not in (torch.int64, torch.int32) or ids.dim() != 1 or ids.numel() != B:
+            raise ValueError(f"class ids must be an integer tensor of shape [{B}], got {ids.dtype} {tuple(ids.shape)}")
+        ids = ids.long()
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) > self.num_classes):
+            raise ValueError(f"class ids must lie in 0..{self.num_classes} ({self.num_classes} is the null class), got "
+                             f"{int(ids.min())}..{int(ids.max())}")
+        out = ids.to(device).contiguous()
+        out._md_class_ids_of = (self.num_classes, B)
+        return out
+
+    def class_row_sums(self, ids, d_temb):
+        """d class_emb [num_classes + 1, 4*nf] from d_temb [B, 4*nf]: row c is the sum of d_temb[b] over the samples of class c --
+        a masked sum over the batch axis, one output row per class.  torch's sum over an axis adds in an order fixed by the shape
+        and uses no atomics (index_add_ on the device does): for the same d_temb, repeated classes give the same bits every
+        run.  The rows of absent classes are exactly zero (the mask selects, it does not multiply: a NaN elsewhere stays there)."""
+        hit = ids[None, :] == torch.arange(self.num_classes + 1, device=d_temb.device)[:, None]
+        return torch.where(hit[:, :, None], d_temb[None], d_temb.new_zeros(())).sum(1)
+
+    def _add_class_row(self, temb, ids):
+        """temb + class_emb[ids]: the row joins after the second linear, before the FiLM linear and Dense_0 read silu(temb)."""
+        return temb if ids is None else temb + self.class_emb.weight.detach()[ids]
 
     # ---- cached, input-independent pieces --------------------------------------------------
     def _stem_const(self):
@@ -152,10 +203,12 @@ class DDPMUNet3D(layers.HipLayer):
             self.__dict__["_md_anchor"] = a
         return a
 
-    def forward_train(self, x, labels):
-        """Forward pass that records what `backward` needs.  Returns (eps_hat NCDHW, ctx).  Always bf16x3 (hip_ops.precision_scope)."""
+    def forward_train(self, x, labels, y=None):
+        """Forward pass that records what `backward` needs.  Returns (eps_hat NCDHW, ctx).  Always bf16x3 (hip_ops.precision_scope).
+        y: int64 [B] class ids of a conditional model (None: the null class)."""
+        ids = self.class_ids(y, x.shape[0], x.device)
         with ops.precision_scope(None, training=True):
-            return self._forward_train(x, labels)
+            return self._forward_train(x, labels) if ids is None else self._forward_train(x, labels, ids)
 
     def backward(self, ctx, d_eps, input_grad=False, param_grads=True):
         """Accumulate d(loss)/d(parameter) into `.grad` for every trainable parameter, given d(loss)/d(eps_hat).
@@ -166,7 +219,7 @@ class DDPMUNet3D(layers.HipLayer):
         with ops.precision_scope(None, training=True):
             return self._backward(ctx, d_eps, input_grad, param_grads)
 
-    def _forward_train(self, x, labels):
+    def _forward_train(self, x, labels, ids=None):
         if self.scale_by_sigma:
             # the inference forward divides by sigma[labels] (ddpm_res64.py:196-198 of the reference); neither registered
             # config enables it, and the HIP backward does not carry the 1/sigma factor
@@ -180,7 +233,7 @@ class DDPMUNet3D(layers.HipLayer):
         i = 0
         emb = layers.get_timestep_embedding(labels, self.nf)
         t1 = ops.linear(emb, mods[0].weight, mods[0].bias); i += 1
-        temb = ops.linear(t1, mods[1].weight, mods[1].bias, silu_in=True); i += 1
+        temb = self._add_class_row(ops.linear(t1, mods[1].weight, mods[1].bias, silu_in=True), ids); i += 1
         stem = mods[i]; i += 1
         xin = x if self.centered else 2 * x - 1.0
         # unfolded operand of the three input convolutions' weight gradients (stem on x, mask_layer on the mask, pos_layer on
@@ -258,7 +311,7 @@ class DDPMUNet3D(layers.HipLayer):
         head = mods[i]
         out = self._head_forward(head, a, B, R)
         ctx = dict(B=B, R=R, P=P, emb=emb, t1=t1, temb=temb, x16=x16, v0=v0, last=v, acts=acts, tape=tape, gn_prm=prm,
-                   a_final=a, foffs=foffs, ftot=ftot, fw=fw)
+                   a_final=a, foffs=foffs, ftot=ftot, fw=fw, class_ids=ids)
         return out, ctx
 
     def _backward(self, ctx, d_eps, input_grad=False, param_grads=True):
@@ -349,6 +402,8 @@ class DDPMUNet3D(layers.HipLayer):
         d_temb = (d_film @ ctx["fw"]) * dsilu(temb)
         bw._grad_of(mods[1].weight).add_(d_temb.t() @ F.silu(t1))
         bw._grad_of(mods[1].bias).add_(d_temb.sum(0))
+        if ctx.get("class_ids") is not None:
+            bw._grad_of(self.class_emb.weight).add_(self.class_row_sums(ctx["class_ids"], d_temb))
         d_t1 = (d_temb @ mods[1].weight.detach()) * dsilu(t1)
         bw._grad_of(mods[0].weight).add_(d_t1.t() @ emb)
         bw._grad_of(mods[0].bias).add_(d_t1.sum(0))
@@ -460,16 +515,18 @@ class DDPMUNet3D(layers.HipLayer):
         return ops.fold_dx(y, head.bias, B, co, k, rows_alloc, R)
 
     # ---- forward ------------------------------------------------------------------------------
-    def forward(self, x, labels):
+    def forward(self, x, labels, y=None):
+        """y: int64 [B] class ids of a conditional model (model.num_classes > 0); None there is the null class for every sample."""
         if not x.is_cuda:
             raise RuntimeError(f"{type(self).__name__} (meshdiffusion_amd) runs on the GPU only: no CPU fallback")
         if torch.is_grad_enabled() and (self.training or x.requires_grad):
             # training: the HIP forward records a tape and the HIP backward accumulates parameter .grad; torch
             # autograd only sees one opaque node (so `loss.backward()` of the reference's step_fn works).
             # x.requires_grad: the same node hands back d/dx; in eval mode that is all it computes (no dropout, no `.grad`)
-            return _UNetTrainFn.apply(x, labels, self, self._autograd_anchor())
+            return _UNetTrainFn.apply(x, labels, self, self._autograd_anchor(), y)
+        ids = self.class_ids(y, x.shape[0], x.device)
         with ops.precision_scope(self.hip_precision):
-            return self._forward_eval(x, labels)
+            return self._forward_eval(x, labels) if ids is None else self._forward_eval(x, labels, ids)
 
     def calibrate(self, x, labels, bar=4e-5):
         """Load-time calibration of the reduced-precision conv arithmetic on THESE weights (call it once after `load_state_dict` /
@@ -483,6 +540,8 @@ class DDPMUNet3D(layers.HipLayer):
           2. one audited evaluation per batch (`hip_ops.AUDIT`: every reduced-precision launch repeated in bf16x3 on the same operand):
              a conv whose relative difference exceeds `bar` on any batch is taken off the reduced-precision path for good
              (`layer.md_bf16x3_sites`).
+        A conditional model is calibrated under the null class (every evaluation here runs with y = None); whether equalisers
+        measured there hold under the other classes has not been measured.
         Returns {"measured": n convs, "audited": n launches, "worst": largest difference kept, "demoted": [(module name, site, diff)]}."""
         xs, ls = (list(x), list(labels)) if isinstance(x, (list, tuple)) else ([x], [labels])
         assert len(xs) == len(ls) and not self.training
@@ -520,7 +579,7 @@ class DDPMUNet3D(layers.HipLayer):
         kept = [r["rel_l2"] for r in worst.values() if r["rel_l2"] <= bar]
         return dict(measured=len(cal), audited=n_audited, worst=max(kept) if kept else 0.0, demoted=sorted(demoted))
 
-    def _forward_eval(self, x, labels):
+    def _forward_eval(self, x, labels, ids=None):
         mods = self.all_modules
         B, R = x.shape[0], self.img_size
         P = R ** 3
@@ -529,7 +588,7 @@ class DDPMUNet3D(layers.HipLayer):
         i = 0
         temb = layers.get_timestep_embedding(labels, self.nf)
         temb = ops.linear(temb, mods[i].weight, mods[i].bias); i += 1
-        temb = ops.linear(temb, mods[i].weight, mods[i].bias, silu_in=True); i += 1
+        temb = self._add_class_row(ops.linear(temb, mods[i].weight, mods[i].bias, silu_in=True), ids); i += 1
 
         h_in = x if self.centered else 2 * x - 1.0
         stem = mods[i]; i += 1
@@ -600,9 +659,9 @@ class _UNetTrainFn(torch.autograd.Function):
     backward runs, so the node is differentiable once."""
 
     @staticmethod
-    def forward(ctx, x, labels, model, anchor):
+    def forward(ctx, x, labels, model, anchor, y=None):
         with torch.no_grad():
-            out, tape_ctx = model.forward_train(x, labels)
+            out, tape_ctx = model.forward_train(x, labels) if y is None else model.forward_train(x, labels, y)
         ctx.model, ctx.tape_ctx, ctx.param_grads = model, tape_ctx, model.training
         return out
 
@@ -615,4 +674,4 @@ class _UNetTrainFn(torch.autograd.Function):
         if ctx.param_grads or ctx.needs_input_grad[0]:
             dx = ctx.model.backward(ctx.tape_ctx, d_eps.contiguous(), input_grad=ctx.needs_input_grad[0], param_grads=ctx.param_grads)
         ctx.tape_ctx = None
-        return dx, None, None, None
+        return dx, None, None, None, None

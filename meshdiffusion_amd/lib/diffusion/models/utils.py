@@ -46,8 +46,8 @@ class ModelReplica(torch.nn.Module):
         super().__init__()
         self.module = module
 
-    def forward(self, x, labels):
-        return self.module(x, labels)
+    def forward(self, x, labels, y=None):
+        return self.module(x, labels) if y is None else self.module(x, labels, y=y)
 
 
 def create_model(config, use_parallel=True):
@@ -82,9 +82,10 @@ def calibrate_model(model, config, batch=2, timesteps=(900.0, 400.0, 60.0), seed
 
 
 def get_model_fn(model, train=False):
-    def model_fn(x, labels):
+    """model_fn(x, labels, y=None): y, the int64 [B] class ids of a class-conditional model, is handed on only when given."""
+    def model_fn(x, labels, y=None):
         model.train() if train else model.eval()
-        return model(x, labels)
+        return model(x, labels) if y is None else model(x, labels, y=y)
 
     return model_fn
 

@@ -352,11 +352,77 @@ def _check_pc_pair(sde, predictor, corrector, n_steps, probability_flow, continu
                                   "it: evaler.interp / --mode=interp")
 
 
-def _check_guidance(guidance_scale, partial, predictor=None, corrector=None, probability_flow=False):
+class ClassifierFreeModel(torch.nn.Module):
+    """A class-conditional U-Net (model.num_classes > 0) with its class ids and classifier-free guidance folded in: called as
+    (x, labels) -> eps_hat like the U-Net itself, so get_model_fn, the steppers, the PC loop, DDIM, DPM-Solver++ and the ODE sampler
+    take it as they take the U-Net.
+        y       int64 [B] class ids (a sequence or tensor), checked here on the host, once; the null id (num_classes) is allowed
+                per sample
+        scale   the guidance scale w, one float or B of them: eps_hat = eps_null + w (eps_y - eps_null)
+        rescale phi in [0, 1]: eps_hat times phi std(eps_y)/std(eps_hat) + (1 - phi) per sample (hip_ops.cfg_combine)
+    scale == 1 for every sample: one evaluation at batch B with y, no doubling and no combine; scale == 0: one evaluation with
+    the null class; otherwise one evaluation at batch 2B (x twice, y then the null class) and one md_cfg_combine launch.
+    Not implemented (NotImplementedError): reconstruction guidance (guidance_scale > 0: it needs the Jacobian of the combined
+    output), the likelihood and `encode=True` inversions."""
+
+    def __init__(self, model, y, scale=1.0, rescale=0.0):
+        super().__init__()
+        self.model = model
+        net = self.net
+        if int(getattr(net, "num_classes", 0) or 0) <= 0:
+            raise ValueError("classifier-free guidance needs a class-conditional model (model.num_classes > 0); this one has no classes")
+        y = torch.as_tensor(y)
+        if y.dim() != 1 or y.numel() < 1:
+            raise ValueError(f"y must hold one class id per sample, got shape {tuple(y.shape)}")
+        self.B = int(y.numel())
+        self._y = net.class_ids(y, self.B, "cpu")                  # the host check: ValueError on an id out of range
+        w = torch.as_tensor(scale, dtype=torch.float32).reshape(-1)
+        if w.numel() not in (1, self.B) or not bool(torch.isfinite(w).all()):
+            raise ValueError(f"scale must be one finite number or one per sample ({self.B}), got {scale}")
+        self._w = w.expand(self.B).contiguous()
+        self.rescale = float(rescale)
+        if not 0.0 <= self.rescale <= 1.0:
+            raise ValueError(f"rescale must lie in [0, 1], got {rescale}")
+        self.mode = "cond" if bool((w == 1).all()) else ("null" if bool((w == 0).all()) else "both")
+        self._dev = {}
+
+    @property
+    def net(self):
+        return self.model.module if hasattr(self.model, "module") else self.model
+
+    def _operands(self, device):
+        """(class ids of the evaluation, w [B] or None) on `device`, built once per device."""
+        key = str(device)
+        if key not in self._dev:
+            net, null = self.net, torch.full_like(self._y, self.net.null_class)
+            ids = {"cond": self._y, "null": null, "both": torch.cat([self._y, null])}[self.mode]
+            self._dev[key] = (net.class_ids(ids, ids.numel(), device), self._w.to(device) if self.mode == "both" else None)
+        return self._dev[key]
+
+    def forward(self, x, labels):
+        if x.shape[0] != self.B:
+            raise ValueError(f"this ClassifierFreeModel holds {self.B} class ids; the batch has {x.shape[0]} samples")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("classifier-free guidance under a gradient with respect to x (reconstruction guidance, "
+                                      "likelihood) is not implemented: it needs the Jacobian of the combined output")
+        ids, w = self._operands(x.device)
+        if self.mode != "both":
+            return self.model(x, labels, y=ids)
+        eps2 = self.model(torch.cat([x, x]), torch.cat([labels, labels]), y=ids)
+        return ops.cfg_combine(eps2, w, rescale=self.rescale)
+
+
+def _refuse_cfg(model, what):
+    if isinstance(model, ClassifierFreeModel):
+        raise NotImplementedError(f"classifier-free guidance with {what} is not implemented")
+
+
+def _check_guidance(guidance_scale, partial, predictor=None, corrector=None, probability_flow=False, model=None):
     """Refuse, before any GPU work, the guided runs that are not implemented.  Returns whether the run is guided."""
     scale = float(guidance_scale)
     if scale == 0.0:
         return False
+    _refuse_cfg(model, "reconstruction guidance (guidance_scale > 0: it needs the Jacobian of the combined output)")
     if not scale > 0.0:
         raise ValueError(f"guidance_scale must be >= 0, got {guidance_scale}")
     if partial is None:
@@ -429,7 +495,7 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
         """guidance_scale > 0 (reconstruction guidance; needs `partial`, the ancestral predictor, no corrector): each iteration
         is guidance_terms at the state it starts from, md_ancestral_step with that eps_hat, md_guide_apply_f32 on (x, x_mean),
         then the blend and re-noise below unless guidance_replace is off.  guidance_chunk: samples per taped forward."""
-        guided = _check_guidance(guidance_scale, partial, predictor, corrector, probability_flow)
+        guided = _check_guidance(guidance_scale, partial, predictor, corrector, probability_flow, model=model)
         with torch.no_grad():
             if freeze_iters is None:
                 freeze_iters = sde.N + 10
@@ -537,11 +603,12 @@ def get_ddim_sampler(sde, shape, predictor, inverse_scaler, n_steps=1, denoise=F
         direction of time.  n_iters limits the upward steps.  Returns the float64 state at the top level -- what
         ddim_sampler(x0=latent) starts from -- whatever `denoise` says, without the inverse scaler: a latent is no data grid."""
         if encode:
+            _refuse_cfg(model, "DDIM inversion (encode=True)")
             if x0 is None:
                 raise ValueError("encode=True needs x0: the data grids to invert")
             if partial is not None or float(guidance_scale) != 0.0:
                 raise NotImplementedError("DDIM inversion (encode=True) of a partial grid or under guidance is not implemented")
-        guided = _check_guidance(guidance_scale, partial)
+        guided = _check_guidance(guidance_scale, partial, model=model)
         with torch.no_grad():
             if encode:
                 x, gm, gm_flat, _, _ = prepare_run(sde, shape, dev, grid_mask, x0)
@@ -728,7 +795,7 @@ def get_dpmpp_sampler(sde, shape, inverse_scaler, steps=20, order=2, variant="ta
 
     def dpmpp_sampler(model, x0=None, partial=None, partial_mask=None, partial_channel=0, n_iters=None, guidance_scale=0.0,
                       guidance_replace=True, guidance_chunk=None, draw=torch.randn_like):
-        guided = _check_guidance(guidance_scale, partial)
+        guided = _check_guidance(guidance_scale, partial, model=model)
         with torch.no_grad():
             ch = partial_channel
             replace = partial is not None and (guidance_replace or not guided)
@@ -781,6 +848,8 @@ def get_ode_sampler(sde, shape, inverse_scaler, rtol=1e-5, atol=1e-5, eps=1e-3, 
     def ode_sampler(model, x0=None, partial=None, encode=False, **unknown):
         if partial is not None or unknown:
             raise NotImplementedError(f"the ODE sampler takes no conditioning or other options ({['partial'] * (partial is not None) + sorted(unknown)})")
+        if encode:
+            _refuse_cfg(model, "ODE inversion (encode=True)")
         if encode and x0 is None:
             raise ValueError("encode=True needs x0: the data grids to invert")
         with torch.no_grad():

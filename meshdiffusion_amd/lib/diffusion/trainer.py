@@ -96,9 +96,18 @@ def train(config):
     if config.training.batch_size % world:
         raise ValueError(f"training.batch_size={config.training.batch_size} must divide over {world} ranks")
     local_batch = config.training.batch_size // world
+    # class conditioning: with model.num_classes > 0 the grids' classes come from data.class_meta_path and every batch is (grids, y)
+    num_classes = int(getattr(config.model, "num_classes", 0) or 0)
+    class_meta_path = getattr(config.data, "class_meta_path", None)
+    if (num_classes > 0) != (class_meta_path is not None):
+        raise ValueError(f"model.num_classes = {num_classes} and data.class_meta_path = {class_meta_path!r}: a class-conditional "
+                         "model trains on labelled grids, set both or neither")
     dataset = ShapeNetDMTetDataset(config.data.meta_path, deform_scale=config.model.deform_scale, aug=True,
                                    grid_mask=mask, filter_meta_path=config.data.filter_meta_path,
-                                   normalize_sdf=config.data.normalize_sdf, extension=config.data.extension)
+                                   normalize_sdf=config.data.normalize_sdf, extension=config.data.extension,
+                                   class_meta_path=class_meta_path)
+    if dataset.labels is not None and max(dataset.labels) >= num_classes:
+        raise ValueError(f"{class_meta_path} holds class id {max(dataset.labels)}; model.num_classes = {num_classes} takes 0..{num_classes - 1}")
     sampler = RankShardSampler(len(dataset), rank, world, seed=config.seed)
     loader = torch.utils.data.DataLoader(dataset, batch_size=local_batch, sampler=sampler, drop_last=True,
                                          num_workers=config.data.num_workers, pin_memory=True)
@@ -113,7 +122,8 @@ def train(config):
     sde = sde_lib.VPSDE(beta_min=config.model.beta_min, beta_max=config.model.beta_max, N=config.model.num_scales)
     optimize_fn = losses.optimization_manager(config)
     train_step_fn = losses.get_step_fn(sde, train=True, optimize_fn=optimize_fn, mask=mask,
-                                       loss_type=config.training.loss_type)
+                                       loss_type=config.training.loss_type,
+                                       class_dropout=float(getattr(config.training, "class_dropout", 0.1)))
     iter_size = config.training.iter_size
     num_train_steps = config.training.n_iters
     logging.info("Starting training loop at step %d." % (initial_step // iter_size,))
@@ -126,7 +136,10 @@ def train(config):
             except StopIteration:
                 data_iter = iter(loader)
                 batch = next(data_iter)
-            batch = batch.to(config.device, non_blocking=True)
+            if isinstance(batch, (tuple, list)):        # (grids, y): the ids stay on the host, where the step checks them
+                batch = (batch[0].to(config.device, non_blocking=True), batch[1])
+            else:
+                batch = batch.to(config.device, non_blocking=True)
             loss = train_step_fn(state, batch, clear_grad=(inner == 0), update_param=(inner == iter_size - 1))["loss"]
             tmp_loss += loss.item()
         tmp_loss /= iter_size
