@@ -401,6 +401,23 @@ int md_conv3_wino_upsdh(int32_t fmt, const void* t_in, const void* wpk, float* o
                         int32_t D, int32_t H, int32_t W, void* stream);
 
 /*
+ * md_conv3_wino_upsfold (csrc/conv3_wino_upsfold.hip; inference, purely additive): the Upsample conv with the nearest-x2 taps
+ * folded into the weights.  Output (Z, Y) = (2z + a, 2y + b) is a 2 x 2 (d, h) x 3 (w) conv of the SOURCE rows for each phase
+ * p = 2a + b: 4 (kd, kh) tap steps per 16-channel chunk instead of 9.
+ *   fmt      : MD_WINO_FMT_F16F6 only; any other format, or a residual operand, is MD_ERR_UNSUPPORTED
+ *   t_in     : the operand of md_wino_prep_upsdh (t_full = 0, compact layout) or of md_wino_prep_f6 with ups = 1 (t_full = 1): the
+ *              kernel reads row (z', y') of the one, row (2z', 2y') of the other -- the same bits, the same result
+ *   wpk      : md_wino_pack_weights_f6 with rows = 4 cout of the folded tensor [4 cout][cin][3][3][3]: row p * cout + co holds phase
+ *              p of output channel co, taps pre-summed over the coinciding source rows (a = 0: (w0, w1 + w2, 0), a = 1: (0, w0 + w1, w2)
+ *              along d; b likewise along h), the five dead (kd, kh) taps zero.  The image keeps its 9-tap layout; dead taps are not read.
+ *   cout     : the conv's output channels (multiple of 128); cin a multiple of 32; D, H, W the OUTPUT grid: D / 2 a multiple of 4,
+ *              H / 2 of 8, W of 8.  out, bias, stats as md_conv3_wino_f6.
+ */
+int md_conv3_wino_upsfold(int32_t fmt, const void* t_in, int32_t t_full, const void* wpk, float* out, const float* bias,
+                          int64_t bias_bstride, const float* residual, int64_t res_bstride, double* stats, int32_t batch,
+                          int32_t cin, int32_t cout, int32_t D, int32_t H, int32_t W, void* stream);
+
+/*
  * md_conv3_stem: the dx-folded 3x3x3 input convolution from 4 channels (csrc/conv3_stem.hip; ddpm_res64.py:87-92 applied
  * :138-146: conv3x3(channels, nf)(x) + pos_layer(coords) + mask_layer(mask)) with the GroupNorm sums of its output: replaces
  * md_gemm_conv(MD_CFG_C3X_128_K16) + md_gn_stats.

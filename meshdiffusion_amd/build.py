@@ -17,7 +17,7 @@ _SUFFIX = os.environ.get("MD_LIB_SUFFIX", "")
 OBJDIR = os.path.join(CSRC, "build" + _SUFFIX)
 LIB_PATH = os.path.join(HERE, f"libmeshdiffusion_hip{_SUFFIX}.so")
 ARCH = "gfx950"
-SOURCES = ["capi.hip", "gemm_conv.hip", "conv3_main.hip", "conv3_low.hip", "conv3_wino.hip", "conv3_s2.hip", "conv3_head.hip", "conv3_stem.hip", "pack_batch.hip", "wino_prep2.hip", "wino_eq.hip", "norm.hip", "elementwise.hip", "sde_steps.hip", "attention.hip", "nin_stream.hip", "gemm_stream.hip", "block_pass.hip", "train.hip", "backward.hip", "wgrad.hip", "wgrad_wino.hip", "dmtet.hip", "dmtet_bwd.hip", "pointcloud.hip", "raster.hip", "antialias.hip", "interp.hip", "fixedtopo.hip", "visibility.hip", "shape_metrics.hip", "emd.hip", "lfd.hip", "meshpost.hip", "remesh.hip", "meshdist.hip", "texture.hip"]
+SOURCES = ["capi.hip", "gemm_conv.hip", "conv3_main.hip", "conv3_low.hip", "conv3_wino.hip", "conv3_wino_upsfold.hip", "conv3_s2.hip", "conv3_head.hip", "conv3_stem.hip", "pack_batch.hip", "wino_prep2.hip", "wino_eq.hip", "norm.hip", "elementwise.hip", "sde_steps.hip", "attention.hip", "nin_stream.hip", "gemm_stream.hip", "block_pass.hip", "train.hip", "backward.hip", "wgrad.hip", "wgrad_wino.hip", "dmtet.hip", "dmtet_bwd.hip", "pointcloud.hip", "raster.hip", "antialias.hip", "interp.hip", "fixedtopo.hip", "visibility.hip", "shape_metrics.hip", "emd.hip", "lfd.hip", "meshpost.hip", "remesh.hip", "meshdist.hip", "texture.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", f"-I{INCLUDE}", f"-I{CSRC}",
          "-munsafe-fp-atomics", "-Wno-unused-result"]
 

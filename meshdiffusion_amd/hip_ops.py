@@ -6,7 +6,7 @@ Blocked device layouts: F32B float32 [B][C/8][P][8]; S16B bf16 [B][C
 Which kernels a 3x3x3 convolution runs through is decided in one place, layers.plan_conv3 (-> Conv3Plan), from the `*_ok` predicates
 of this module and the flags of the conv's F32Operand; the predicates read shapes and the module state below, never tensor data.
 The environment is read for the arithmetic (MD_PRECISION, MD_FORCE_PRECISION, MD_WINO_EQ), the A/B switches bench.py, the tests or
-the documents still use (MD_WINO, MD_WINO_PREP_V2, MD_WINO_TRAIN_FWD, MD_PREP_COMPACT_UPS, MD_FUSE_GN_APPLY, MD_FUSE_ATTN,
+the documents still use (MD_WINO, MD_WINO_PREP_V2, MD_WINO_TRAIN_FWD, MD_PREP_COMPACT_UPS, MD_UPS_FOLD, MD_FUSE_GN_APPLY, MD_FUSE_ATTN,
 MD_PACK_BATCH, MD_DGRAD_F6, MD_DGRAD_LIFT) and nothing else: the switches of experiments that were closed (DESIGN.md section 3,
 docs/HISTORY.md) are gone, their measured thresholds (WINO_MIN_WGS, WINO_MIN_WGS_TRAIN, S2_MIN_WGS) are constants.
 """
@@ -695,6 +695,18 @@ def prep_compact_ok(ups, D, H, W, drop=None, keep=False):
                 and ((D // 2) * (H // 2) * W) % 256 == 0)
 
 
+# An Upsample conv with the nearest-x2 taps folded into the weights (md_conv3_wino_upsfold: 4 (kd, kh) tap steps per chunk instead of 9;
+# f16f6 inference launches).  A/B switch; the floor counts the workgroups of the UNFOLDED launch (the fold has four times as many): one per CU.
+UPS_FOLD = os.environ.get("MD_UPS_FOLD", "1") == "1"
+UPS_FOLD_MIN_WGS = 256
+
+
+def ups_fold_ok(ups, fmt, rows, B, D, H, W):
+    """Launches md_conv3_wino_upsfold takes and is meant for (layers.plan_conv3 adds: an inference launch)."""
+    return bool(UPS_FOLD and ups and fmt == "f6" and D % 8 == 0 and H % 16 == 0 and W % 8 == 0
+                and B * (D * H * W // 256) * (rows // 128) >= UPS_FOLD_MIN_WGS)
+
+
 def wino_prep(parts, ac, silu, ups, B, S, drop=None, keep=False, dual=False, sums=None, f8=False, eq=None, tscale=1.0, amax=None, dims=None,
               compact=False):
     """fp32 F32B parts (+ folded GroupNorm affine, SiLU, nearest-x2 upsampling) -> transformed split operand T.
@@ -755,6 +767,7 @@ def wino_prep(parts, ac, silu, ups, B, S, drop=None, keep=False, dual=False, sum
     t._md_fmt = ("f6" if f8 == "f6" else "f8") if f8 else False
     t._md_eq = eq.data_ptr() if eq is not None else 0
     t._md_compact = bool(compact)
+    t._md_ups = bool(ups)
     return (t, u) if dual else t
 
 
@@ -820,6 +833,31 @@ def conv3_wino(ww, t, B, S, *, bias=None, bias_bstride=0, residual=None, res_bst
               4.0 * (2 * B * ww.kdim * P + ww.rows * ww.kdim * 36 + B * ww.rows * P * (2 if residual is not None else 1)),
               f"{ww.kdim}->{ww.rows}@{D}x{H}x{W}" + ("/res" if residual is not None else "") + ("/stats" if stats is not None else "")
               + (("/" + ww.fmt) if f8 else ""))
+    return out
+
+
+def conv3_wino_upsfold(wf, t, B, S, *, bias=None, bias_bstride=0, stats=None, out=None, dims=None):
+    """The Upsample conv on the folded weights `wf` (WinoWeightF8(layers.fold_upsample_weight(w), ..., "f6", eq=...): 4 x Cout rows)
+    and the upsampled f16f6 operand `t` of wino_prep(ups=1, f8="f6"), compact or full -- md_conv3_wino_upsfold.
+    dims: the output grid (D, H, W) where it is not the cube S^3 (`S` is ignored then)."""
+    lib = _lib.load()
+    D, H, W = dims if dims is not None else (S, S, S)
+    P = D * H * W
+    assert isinstance(wf, WinoWeightF8) and wf.fmt == "f6" and wf.rows % 4 == 0
+    rows = wf.rows // 4
+    t_fmt = getattr(t, "_md_fmt", None)
+    if t_fmt is not None:                    # an operand that went through wino_prep: upsampled, f16f6, equalised with the weights' vector
+        if t_fmt != "f6" or not getattr(t, "_md_ups", False) or getattr(t, "_md_eq", 0) != (wf.eq.data_ptr() if wf.eq is not None else 0):
+            raise _lib.MeshDiffusionHipError(f"conv3_wino_upsfold: operand (format {t_fmt!r}) does not belong to these weights")
+    if out is None:
+        out = f32b_empty(B, rows, P, t.device)
+    ev = _prof_begin()
+    check(lib.md_conv3_wino_upsfold(_lib.WINO_FMT["f6"], _ptr(t), 0 if getattr(t, "_md_compact", False) else 1, _ptr(wf.data), _ptr(out),
+                                    _ptr(bias), bias_bstride, None, 0, _ptr(stats), B, wf.kdim, rows, D, H, W, _stream()),
+          "md_conv3_wino_upsfold")
+    # the algorithmic flops of the conv it replaces: roofline and per-shape figures keep their meaning
+    _prof_end(ev, "wino", 2.0 * B * rows * wf.kdim * 27 * P, 4.0 * (2 * B * wf.kdim * P // 4 + wf.rows * wf.kdim * 36 + B * rows * P),
+              f"{wf.kdim}->{rows}@{D}x{H}x{W}" + ("/stats" if stats is not None else "") + "/fold/f6")
     return out
 
 

@@ -113,6 +113,22 @@ def conv3_packed(layer, name, conv, cfg):
                          lambda: ops.PackedWeight(conv.weight, "conv", cfg, conv.weight.device, prec))
 
 
+def fold_upsample_weight(w):
+    """[Cout, Cin, 3, 3, 3] -> [4 Cout, Cin, 3, 3, 3] (the dtype of w; fp32 for a layer's weight): the conv on a nearest-x2 upsampled
+    input as four phase convs on the SOURCE rows along d and h.  Output plane Z = 2z + a reads source planes z - 1, z, z + 1 with
+    (w0, w1 + w2, 0) for a = 0 and (0, w0 + w1, w2) for a = 1 (two of the three taps hit the same source value); likewise
+    Y = 2y + b along h; the w axis is untouched.  Row p * Cout + co holds phase p = 2a + b of output channel co; kd is summed first,
+    then kh; the five dead (kd, kh) taps are exact zeros (md_conv3_wino_upsfold never reads them)."""
+    def fold(v, dim, phase):
+        v0, v1, v2 = v.unbind(dim)
+        z = torch.zeros_like(v0)
+        return torch.stack((v0, v1 + v2, z) if phase == 0 else (z, v0 + v1, v2), dim)
+
+    w = w.detach()
+    assert w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3)
+    return torch.cat([fold(fold(w, 2, a), 3, b) for a in (0, 1) for b in (0, 1)], 0).contiguous()
+
+
 def conv3_wino_packed(layer, name, conv, gn=None):
     """Lazy builder of the Winograd-transformed weight tiles of `conv` (cached like conv3_packed); f8: the fragments of the
     f16f8 / f16f6 arithmetic (hip_ops.WinoWeightF8, inference).  gn: the nn.GroupNorm whose output (through SiLU) the conv reads --
@@ -135,18 +151,25 @@ def conv3_wino_packed(layer, name, conv, gn=None):
                              lambda: ops.wino_equaliser(gn.weight if gn is not None else None, gn.bias if gn is not None else None,
                                                         conv.weight, a2m=ms), mark=False)
 
+    def reduced(fmt, fold=False):
+        ms = measured() if ops.WINO_EQ else None
+        use_eq = ms is not None or (gn is not None and ops.WINO_EQ)
+        deps = [conv.weight] + ([gn.weight, gn.bias] if (use_eq and gn is not None) else []) + ([ms] if ms is not None else [])
+        # mark=False (here and for the equalisers): inference-only entries -- a training step's prewarm_packs must not rebuild them
+        # after every evaluation in between
+        # fold: the four phase kernels of the conv on a nearest-x2 upsampled input (fold_upsample_weight), packed like any other weight --
+        # with the SAME equaliser, the one of the original weights: operand, calibration state and md_bf16x3_sites are shared with the
+        # unfolded route
+        return layer._cached(f"{name}/wino_{'fold_' if fold else ''}{fmt}{('m' if ms is not None else 'e') if use_eq else ''}", deps,
+                             lambda: ops.WinoWeightF8(fold_upsample_weight(conv.weight) if fold else conv.weight, conv.weight.device, fmt,
+                                                      eq=eq()), mark=False)
+
     def build(f8=False):
         if f8:
-            fmt = "f6" if f8 == "f6" else "f8"
-            ms = measured() if ops.WINO_EQ else None
-            use_eq = ms is not None or (gn is not None and ops.WINO_EQ)
-            deps = [conv.weight] + ([gn.weight, gn.bias] if (use_eq and gn is not None) else []) + ([ms] if ms is not None else [])
-            # mark=False (here and for the equalisers): inference-only entries -- a training step's prewarm_packs must not rebuild them
-            # after every evaluation in between
-            return layer._cached(f"{name}/wino_{fmt}{('m' if ms is not None else 'e') if use_eq else ''}", deps,
-                                 lambda: ops.WinoWeightF8(conv.weight, conv.weight.device, fmt, eq=eq()), mark=False)
+            return reduced("f6" if f8 == "f6" else "f8")
         return layer._cached(f"{name}/wino", [conv.weight], lambda: ops.WinoWeight(conv.weight, conv.weight.device))
     build.eq, build.measured = eq, measured
+    build.fold = lambda: reduced("f6", fold=True)
     build.owner, build.site = layer, name      # identifies the conv for per-layer overrides (layer.md_bf16x3_sites), the audit and the calibration
     return build
 
@@ -170,6 +193,7 @@ class Conv3Plan(NamedTuple):
     stats: bool                # this launch accumulates the GroupNorm sums of its output
     ksplit: int                # direct: split-K factor
     fused_loader: bool         # direct: the kernel reads the fp32 parts itself (GroupNorm affine + SiLU + split in its halo loader)
+    ups_fold: bool = False     # wino: the nearest-x2 taps folded into the weights (md_conv3_wino_upsfold: 4 tap steps per chunk, not 9)
 
 
 def plan_conv3(pw, operand, B, S_out, *, ups, out_mode, rows_alloc, want_stats, wino):
@@ -196,7 +220,10 @@ def plan_conv3(pw, operand, B, S_out, *, ups, out_mode, rows_alloc, want_stats, 
         # a block with a NIN shortcut: the shortcut comes out of the operand pass, which holds the block input anyway
         shortcut = bool(operand.nin is not None and fmt == "f6" and not compact and not ups
                         and ops.block_pass_ok(operand.parts, operand.nin[0].rows, B, S_out, S_out, S_out))
-        return Conv3Plan("wino", fmt, compact, shortcut, operand.keep, sums, 1, False)
+        # an f16f6 Upsample conv that fills the chip: four phase convs of 4 live (kd, kh) taps on the source rows.  The operand pass is
+        # the one chosen above (the kernel reads either layout)
+        fold = bool(infer and hasattr(wino, "fold") and ops.ups_fold_ok(ups, fmt, pw.rows, B, S_out, S_out, S_out))
+        return Conv3Plan("wino", fmt, compact, shortcut, operand.keep, sums, 1, False, fold)
     ksplit = ops.ksplit_for(pw.cfg, B, pw.rows, pw.kdim, S_out) if out_mode == ops.OUT_F32B else 1
     # statistics of the output: the dedicated kernel's epilogue, or (8^3 / 4^3 levels) the split-K finish kernel
     # (one block per (sample, 8-channel group) there: only where that fills the chip -- at B = 1 the 32^3 level would run on 16 blocks)
@@ -260,7 +287,12 @@ def _conv3_wino(plan, pw, op, wino, B, S_out, ups, out, stats, **epilogue):
         t = ops.wino_prep(op.parts, op.ac, op.silu, ups, B, S_out, drop=op.drop, keep=plan.keep, f8=plan.fmt, eq=eq, compact=plan.compact)
     if plan.keep:
         op.t_kept = t                    # training: the Winograd weight gradient reads the operand again (tape)
-    ops.conv3_wino(wino(plan.fmt) if plan.fmt else wino(), t, B, S_out, stats=stats, out=out, **epilogue)
+    if plan.ups_fold:
+        assert epilogue.get("residual") is None, "md_conv3_wino_upsfold has no residual operand"
+        ops.conv3_wino_upsfold(wino.fold(), t, B, S_out, stats=stats, out=out, bias=epilogue.get("bias"),
+                               bias_bstride=epilogue.get("bias_bstride", 0))
+    else:
+        ops.conv3_wino(wino(plan.fmt) if plan.fmt else wino(), t, B, S_out, stats=stats, out=out, **epilogue)
     if plan.fmt and ops.AUDIT is not None:
         # diagnostic mode (tools/audit_precision.py): the same launch once more in bf16x3; the pair's relative difference is the
         # error the reduced-precision format adds on THIS layer with THESE weights and activations
