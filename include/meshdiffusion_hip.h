@@ -418,6 +418,24 @@ int md_conv3_wino_upsfold(int32_t fmt, const void* t_in, int32_t t_full, const v
                           int32_t cin, int32_t cout, int32_t D, int32_t H, int32_t W, void* stream);
 
 /*
+ * md_conv3_wino_splitk (csrc/conv3_wino.hip; inference, purely additive: MD_ABI_VERSION stays 16): md_conv3_wino / _f8 / _f6 with the K
+ * loop cut into `ksplit` slices of cin / ksplit channels, for launches whose (tiles x batch x cout / 128) workgroups leave most of the
+ * chip idle (the 8^3 level).  A slice is a batch entry of the same operand: the conv kernel runs ksplit times the workgroups and writes
+ * fp32 partial sums to `workspace` [ksplit][batch][cout/8][P][8]; the split-K finish kernel of md_gemm_conv then adds the slices in the
+ * order 0 .. ksplit-1 and applies bias, residual and statistics.  Two runs give the same bits.
+ *   fmt             : MD_WINO_FMT_*; t_in and wpk are the unsplit launch's operand and packed weights (md_wino_prep* / md_wino_pack_weights*)
+ *   workspace       : at least md_conv3_wino_splitk_workspace_bytes(batch, cout, D, H, W, ksplit) = ksplit * batch * cout * P * 4 bytes
+ *   bias, residual, stats, strides, batch, cin, cout, D, H, W : as md_conv3_wino
+ * MD_ERR_BAD_ARG (nothing is launched): ksplit < 2, a null or misaligned pointer (16 bytes; bias 4, stats 8), a workspace that is too
+ * small; MD_ERR_UNSUPPORTED (nothing is launched): cin not a multiple of 32 * ksplit (a slice is whole pair-steps), cout not a multiple
+ * of 128, a grid md_conv3_wino does not take, more workgroups than a launch can have.
+ */
+int64_t md_conv3_wino_splitk_workspace_bytes(int32_t batch, int32_t cout, int32_t D, int32_t H, int32_t W, int32_t ksplit);
+int md_conv3_wino_splitk(int32_t fmt, const void* t_in, const void* wpk, void* workspace, int64_t workspace_bytes, float* out,
+                         const float* bias, int64_t bias_bstride, const float* residual, int64_t res_bstride, double* stats,
+                         int32_t batch, int32_t cin, int32_t cout, int32_t D, int32_t H, int32_t W, int32_t ksplit, void* stream);
+
+/*
  * md_conv3_stem: the dx-folded 3x3x3 input convolution from 4 channels (csrc/conv3_stem.hip; ddpm_res64.py:87-92 applied
  * :138-146: conv3x3(channels, nf)(x) + pos_layer(coords) + mask_layer(mask)) with the GroupNorm sums of its output: replaces
  * md_gemm_conv(MD_CFG_C3X_128_K16) + md_gn_stats.

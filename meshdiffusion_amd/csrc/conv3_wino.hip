@@ -26,6 +26,7 @@
 //                        y0 / y1 + bias + residual + GroupNorm sums as in md_conv3_main_kernel.
 #include <type_traits>
 #include "md_common.h"
+#include "md_args.h"
 #include "md_pack.h"
 
 namespace {
@@ -201,6 +202,11 @@ struct WnArgs {
   float out_scale;         // F8: multiplies the weights' descale (1, or 1 / tscale of md_wino_prep_dual_f6: a power of two)
   const uint32_t* amax;    // F8, may be null: the operand was lifted by 2^md_dgrad_lift_log2(amax[0]) (md_wino_prep_dual_f6's dynamic form)
   int ups_dh;              // 1: T is the compact upsampled operand [..][D/2][H/2][W/2] (md_wino_prep_ex, ups = 2); else 0
+  // K slices (md_conv3_wino_splitk; 1 everywhere else).  Slice s of sample b is "sample" b * ks + s of the SAME T read as
+  // [batch * ks][cin / 8]..: `cin` is then the channels of ONE slice, `nsteps_full` the (chunk, tap) steps of the whole weight row block
+  // (the stride between row blocks of wpk; the slice starts s * (cin / 16) * 9 steps into its row block), and the launch writes raw
+  // fp32 partial sums [ks][batch][cout / 8][P][8] to `out` (no bias, residual or statistics: the split-K finish kernel adds them).
+  int ks, nsteps_full;
 };
 
 // ABL (timing only, results invalid; -DMD_BUILD_ABLATIONS, tools/bench_wino.py): bit 0 no halo traffic, bit 1 halo traffic in the
@@ -258,7 +264,9 @@ __global__ __launch_bounds__(WN_THREADS) void md_conv3_wino_kernel(const WnArgs 
   const int tiles = ntx * nty * ntz;
   int bid = blockIdx.x;     // XCD-aware order: one contiguous run of tiles per XCD (block b runs on XCD b % 8)
   if ((gridDim.x & 7) == 0) bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  const int b = bid / tiles, t = bid % tiles;
+  const int bp = bid / tiles, t = bid % tiles;                     // bp: (sample, K slice); with A.ks = 1 the sample itself
+  // (a sliced launch has no residual operand -- the finish adds it -- so the RES forms keep the one index, and their registers)
+  const int sl = RES ? 0 : bp % A.ks, b = RES ? bp : bp / A.ks;
   const int x0 = (t % ntx) * WN_TX, y0 = ((t / ntx) % nty) * WN_TY, z0 = (t / (ntx * nty)) * WN_TZ;
   const int rtb = blockIdx.y;                                      // 128-row block of output channels
   const int CG = A.cin >> 3, nchunk = A.cin >> 4;
@@ -287,7 +295,7 @@ __global__ __launch_bounds__(WN_THREADS) void md_conv3_wino_kernel(const WnArgs 
     }
     return live ? (int)((int64_t)(hp >> 1) * 8 * Ph + (int64_t)(hp & 1) * Ph + (int64_t)row * Wp + (x0 >> 1) + pr) : -1;
   };
-  const uint4* tbase = A.T + ((int64_t)b * CG * 8 + wid * 2) * Ph;                              // + chunk * 16 * Ph
+  const uint4* tbase = A.T + ((int64_t)bp * CG * 8 + wid * 2) * Ph;                             // + chunk * 16 * Ph
   const uint4* zsrc = &wn_zero16;
   auto halo_load = [&](int chunk, int k) -> uint4 {
     const int dk = halo_off(k);
@@ -305,7 +313,7 @@ __global__ __launch_bounds__(WN_THREADS) void md_conv3_wino_kernel(const WnArgs 
   // weights: step s = chunk * 9 + tap; this wave's 8 fragments (row tile 4 x plane 2) of step s are 8 KB contiguous, a
   // fragment (32 rows x 16 k, one plane) 1 KB = one 16-byte load per lane: they go straight to registers (no other wave
   // wants them), ring of three sets, requested two steps ahead
-  const uint4* wbase = A.wpk + (((int64_t)rtb * nsteps) * 4 + wid) * 512 + lane;               // + s * 2048 + i * 64
+  const uint4* wbase = A.wpk + (((int64_t)rtb * A.nsteps_full + sl * nsteps) * 4 + wid) * 512 + lane;              // + s * 2048 + i * 64
   auto load_A = [&](int s, bf16x8 (&dst)[8]) {
     const uint4* wp = wbase + (int64_t)s * 2048;
 #pragma unroll
@@ -373,7 +381,7 @@ __global__ __launch_bounds__(WN_THREADS) void md_conv3_wino_kernel(const WnArgs 
     auto slot3_of_store = [](int u) constexpr -> int { return (u == 0 || u == 3 || u == 6) ? 0 : ((u == 2 || u == 5 || u == 8) ? 1 : 2); };
     auto slot3_of_request = [](int u) constexpr -> int { return (u == 0 || u == 3 || u == 6) ? 0 : ((u == 2 || u == 5 || u == 8) ? 1 : 2); };
     const int npairs = nsteps >> 1;
-    const uint4* wbase8 = A.wpk + (((int64_t)rtb * npairs) * 4 + wid) * 1024 + lane;       // + p * 4096 + piece * 64
+    const uint4* wbase8 = A.wpk + (((int64_t)rtb * (A.nsteps_full >> 1) + sl * npairs) * 4 + wid) * 1024 + lane;       // + p * 4096 + piece * 64
     // weights [set][row tile]: the two fp16 fragments (step 2p, 2p+1) and the 32-byte fp8 fragment (8 consecutive registers: its two
     // 16-byte loads write the halves directly); halo fragments of one group [group parity] likewise; halo pieces in flight [slot][group]
     uint4 A8h[2][4][2], B8h[2][2], hs8[W8_HG == 3 ? 3 : 2][4];
@@ -729,7 +737,7 @@ __global__ __launch_bounds__(WN_THREADS) void md_conv3_wino_kernel(const WnArgs 
   float* xreg = (float*)wn_smem;
   float* red = xreg + 2 * XREG_FLOATS;
   const int rows_total = A.cout;
-  float* outp = A.out + (int64_t)b * rows_total * P;
+  float* outp = A.out + ((int64_t)sl * A.batch + b) * rows_total * P;      // K slices: workspace [ks][B][cout / 8][P][8]
   const float* resp = A.residual ? A.residual + (int64_t)b * A.res_bstride : nullptr;
   const float* biasp = A.bias ? A.bias + (int64_t)b * A.bias_bstride : nullptr;
   const bool want_stats = (ABL & 128) ? false : A.stats != nullptr;
@@ -975,6 +983,7 @@ static int md_conv3_wino_f8_launch(bool f6, const void* t_in, const void* wpk, f
   a.bias_bstride = bias_bstride; a.res_bstride = res_bstride;
   a.batch = batch; a.cin = cin; a.cout = cout; a.D = D; a.H = H; a.W = W;
   a.ups_dh = upsdh ? 1 : 0;      // (D and H are multiples of 4 and 8: the compact operand's rows are whole)
+  a.ks = 1; a.nsteps_full = (cin / 16) * 9;
   const int tiles = (D / WN_TZ) * (H / WN_TY) * (W / WN_TX);
   const dim3 grid((unsigned)(tiles * batch), (unsigned)(cout / 128));
   MD_HIP_CLEAR_ERROR();
@@ -1025,6 +1034,7 @@ static int md_conv3_wino_launch(const void* t_in, const void* wpk, float* out, c
   a.bias_bstride = bias_bstride; a.res_bstride = res_bstride;
   a.batch = batch; a.cin = cin; a.cout = cout; a.D = D; a.H = H; a.W = W;
   a.ups_dh = upsdh ? 1 : 0;
+  a.ks = 1; a.nsteps_full = (cin / 16) * 9;
   const int tiles = (D / WN_TZ) * (H / WN_TY) * (W / WN_TX);
   MD_HIP_CLEAR_ERROR();
   const dim3 grid((unsigned)(tiles * batch), (unsigned)(cout / 128));
@@ -1070,4 +1080,54 @@ extern "C" int md_conv3_wino_upsdh(int32_t fmt, const void* t_in, const void* wp
   if (fmt != MD_WINO_FMT_F16F8 && fmt != MD_WINO_FMT_F16F6) return MD_ERR_BAD_ARG;
   return md_conv3_wino_f8_launch(fmt == MD_WINO_FMT_F16F6, t_in, wpk, out, bias, bias_bstride, residual, res_bstride, stats, batch, cin, cout, D, H,
                                  W, stream, 1.0f, nullptr, true);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// K slices: the 8^3 level at B = 8 has 64 workgroups per launch.  A slice of `cin / ksplit` channels is a batch entry of the same T, so
+// the kernel above runs ksplit times as many workgroups on a ksplit-th of the K loop each and writes raw partial sums; the split-K finish
+// kernels of gemm_conv.hip add them in slice order with bias / residual / statistics (deterministic: no atomics on the result).
+// ------------------------------------------------------------------------------------------------------------------
+int md_splitk_finish(const float* partial, float* out, const float* bias, int64_t bias_bstride, const float* residual, int64_t res_bstride,
+                     double* stats, int batch, int rows, int D, int H, int W, int ksplit, hipStream_t stream);      // gemm_conv.hip
+
+extern "C" int64_t md_conv3_wino_splitk_workspace_bytes(int32_t batch, int32_t cout, int32_t D, int32_t H, int32_t W, int32_t ksplit) {
+  if (batch <= 0 || cout <= 0 || (cout & 7) || D <= 0 || H <= 0 || W <= 0 || ksplit < 2) return MD_ERR_BAD_ARG;
+  return (int64_t)ksplit * batch * cout * ((int64_t)D * H * W) * 4;
+}
+
+extern "C" int md_conv3_wino_splitk(int32_t fmt, const void* t_in, const void* wpk, void* workspace, int64_t workspace_bytes, float* out,
+                                    const float* bias, int64_t bias_bstride, const float* residual, int64_t res_bstride, double* stats,
+                                    int32_t batch, int32_t cin, int32_t cout, int32_t D, int32_t H, int32_t W, int32_t ksplit, void* stream) {
+  if (fmt != MD_WINO_FMT_BF16X3 && fmt != MD_WINO_FMT_F16F8 && fmt != MD_WINO_FMT_F16F6) return MD_ERR_BAD_ARG;
+  if (md_any_bad<16>(t_in, wpk, workspace, out) || md_any_misaligned<16>(residual) || md_any_misaligned<4>(bias) ||
+      md_any_misaligned<8>(stats))
+    return MD_ERR_BAD_ARG;
+  if (batch <= 0 || ksplit < 2 || bias_bstride < 0 || res_bstride < 0 || (res_bstride & 3)) return MD_ERR_BAD_ARG;
+  if (cin <= 0 || cout <= 0 || (cout % 128) || (cin % (32 * (int64_t)ksplit))) return MD_ERR_UNSUPPORTED;      // a slice: whole pair-steps
+  if (D <= 0 || H <= 0 || W <= 0 || (D % WN_TZ) || (H % WN_TY) || (W % WN_TX)) return MD_ERR_UNSUPPORTED;
+  const int64_t P = (int64_t)D * H * W;
+  if (P * 8 >= (int64_t)1 << 31) return MD_ERR_UNSUPPORTED;       // 32-bit halo offsets (16 Ph items)
+  const int64_t tiles = (D / WN_TZ) * (int64_t)(H / WN_TY) * (W / WN_TX);
+  if (!md_fits_i32(tiles * batch * ksplit, (int64_t)batch * ksplit) || cout / 128 > 65535 || batch * (cout / 8) > 0x7fffffffLL)
+    return MD_ERR_UNSUPPORTED;
+  if (workspace_bytes < (int64_t)ksplit * batch * cout * P * 4) return MD_ERR_BAD_ARG;
+  WnArgs a;
+  a.T = (const uint4*)t_in; a.wpk = (const uint4*)wpk; a.out = (float*)workspace; a.bias = nullptr; a.residual = nullptr; a.stats = nullptr;
+  a.hdr = fmt == MD_WINO_FMT_BF16X3 ? nullptr : (const float*)((const unsigned char*)wpk + (int64_t)cout * cin * 36 * 4);
+  a.out_scale = 1.0f; a.amax = nullptr;
+  a.bias_bstride = 0; a.res_bstride = 0;
+  a.batch = batch; a.cin = cin / ksplit; a.cout = cout; a.D = D; a.H = H; a.W = W;
+  a.ups_dh = 0;
+  a.ks = ksplit; a.nsteps_full = (cin / 16) * 9;
+  const dim3 grid((unsigned)(tiles * batch * ksplit), (unsigned)(cout / 128));
+  MD_HIP_CLEAR_ERROR();
+  if (fmt == MD_WINO_FMT_BF16X3)
+    hipLaunchKernelGGL((md_conv3_wino_kernel<0, false, false, false>), grid, dim3(WN_THREADS), 0, (hipStream_t)stream, a);
+  else if (fmt == MD_WINO_FMT_F16F8)
+    hipLaunchKernelGGL((md_conv3_wino_kernel<0, true, false, false>), grid, dim3(WN_THREADS), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((md_conv3_wino_kernel<0, true, true, false>), grid, dim3(WN_THREADS), 0, (hipStream_t)stream, a);
+  MD_HIP_CHECK_LAUNCH();
+  return md_splitk_finish((const float*)workspace, out, bias, bias_bstride, residual, res_bstride, stats, batch, cout, D, H, W, ksplit,
+                          (hipStream_t)stream);
 }

@@ -651,6 +651,19 @@ int md_launch_splitk_reduce(const MdGemmConvArgs& a, hipStream_t stream) {
   return MD_OK;
 }
 
+// The finish alone, for a producer outside this file whose workspace has the layout above ([ksplit][batch][rows / 8][P][8] fp32 partial
+// sums; md_conv3_wino_splitk): out = sum over slices in order + bias + residual, GroupNorm sums ADDED to `stats` when given.
+int md_splitk_finish(const float* partial, float* out, const float* bias, int64_t bias_bstride, const float* residual, int64_t res_bstride,
+                     double* stats, int batch, int rows, int D, int H, int W, int ksplit, hipStream_t stream) {
+  if (!partial || !out || batch <= 0 || rows <= 0 || (rows & 7) || ksplit < 1 || D <= 0 || H <= 0 || W <= 0) return MD_ERR_BAD_ARG;
+  MdGemmConvArgs a = {};
+  a.partial = const_cast<float*>(partial); a.out = out; a.bias = bias; a.residual = residual; a.stats = stats;
+  a.bias_bstride = bias_bstride; a.res_bstride = res_bstride;
+  a.alpha = 1.0f; a.batch = batch; a.rows = rows; a.rows_alloc = rows; a.D = D; a.H = H; a.W = W; a.ksplit = ksplit;
+  a.out_mode = MD_OUT_F32B;
+  return md_launch_splitk_reduce(a, stream);
+}
+
 extern "C" int64_t md_gemm_conv_partial_bytes(const MdGemmConvArgs* a) {
   if (a == nullptr) return MD_ERR_BAD_ARG;
   if (a->ksplit <= 1) return 0;

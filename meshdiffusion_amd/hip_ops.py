@@ -628,6 +628,30 @@ def wino_ok(rows, kdim, S, B):
             and B * (S ** 3 // 256) * (rows // 128) >= (max(WINO_MIN_WGS, WINO_MIN_WGS_TRAIN) if TRAINING_SCOPE else WINO_MIN_WGS))
 
 
+# The 3x3x3 convs of the 8^3 level through the Winograd kernel with K slices (md_conv3_wino_splitk) instead of the direct kernel with
+# split-K: an 8^3 launch at B = 8 and 512 output channels has 64 Winograd workgroups, below WINO_MIN_WGS; each slice of the input
+# channels is a workgroup of its own and the split-K finish kernel adds them.  A/B switch, default on (profiles/wino_splitk_ab.txt).
+WINO_SPLITK = os.environ.get("MD_WINO_SPLITK", "1") == "1"
+WINO_SPLITK_MIN_WGS = 64          # unsplit workgroups from which the route is taken
+WINO_SPLITK_MAX_WGS = 256         # workgroups of the split launch: one round of the chip
+WINO_SPLITK_MIN_K = 256
+
+
+def wino_splitk_for(rows, kdim, S, B, ups=0):
+    """K slices of the Winograd conv at the 8^3 level, or 0 where the route does not apply (layers.plan_conv3 adds: an inference
+    launch).  The largest of 8, 4, 2 whose slices are whole pair-steps (32 channels) and whose launch is at most one workgroup per CU."""
+    if not (WINO_SPLITK and WINO and PRECISION == "bf16x3" and not TRAINING_SCOPE and not ups and S == 8
+            and rows % 128 == 0 and kdim % 32 == 0 and kdim >= WINO_SPLITK_MIN_K):
+        return 0
+    n = B * (S ** 3 // 256) * (rows // 128)
+    if not (WINO_SPLITK_MIN_WGS <= n < WINO_MIN_WGS):
+        return 0
+    for ks in (8, 4, 2):
+        if kdim % (32 * ks) == 0 and n * ks <= WINO_SPLITK_MAX_WGS:
+            return ks
+    return 0
+
+
 def wgrad_nin_ok(co, ci, P):
     """NIN weight gradients straight from S16B tensors (md_wgrad_nin)."""
     return co % 128 == 0 and ci % 128 == 0 and P % 16 == 0
@@ -858,6 +882,40 @@ def conv3_wino_upsfold(wf, t, B, S, *, bias=None, bias_bstride=0, stats=None, ou
     # the algorithmic flops of the conv it replaces: roofline and per-shape figures keep their meaning
     _prof_end(ev, "wino", 2.0 * B * rows * wf.kdim * 27 * P, 4.0 * (2 * B * wf.kdim * P // 4 + wf.rows * wf.kdim * 36 + B * rows * P),
               f"{wf.kdim}->{rows}@{D}x{H}x{W}" + ("/stats" if stats is not None else "") + "/fold/f6")
+    return out
+
+
+def conv3_wino_splitk(ww, t, B, S, ksplit, *, bias=None, bias_bstride=0, residual=None, res_bstride=0, stats=None, out=None, dims=None):
+    """conv3_wino with the input channels cut into `ksplit` slices, one workgroup set each, and the split-K finish kernel behind it
+    (md_conv3_wino_splitk; wino_splitk_for says where).  `ww` and `t` are the unsplit launch's weights and operand.
+    dims: the output grid (D, H, W) where it is not the cube S^3 (`S` is ignored then)."""
+    lib = _lib.load()
+    D, H, W = dims if dims is not None else (S, S, S)
+    P = D * H * W
+    f8 = isinstance(ww, WinoWeightF8)
+    assert f8 or isinstance(ww, WinoWeight), "the weights of conv3_wino (no scaled data-gradient form)"
+    t_fmt = getattr(t, "_md_fmt", None)
+    if t_fmt is not None:                    # as conv3_wino: format and equaliser of the operand must be the weight object's
+        want = ww.fmt if f8 else False
+        if (t_fmt != want or getattr(t, "_md_compact", False)
+                or getattr(t, "_md_eq", 0) != ((ww.eq.data_ptr() if ww.eq is not None else 0) if f8 else 0)):
+            raise _lib.MeshDiffusionHipError(f"conv3_wino_splitk: operand format {t_fmt!r} / equaliser does not belong to these weights ({want!r})")
+    if out is None:
+        out = f32b_empty(B, ww.rows, P, t.device)
+    nbytes = lib.md_conv3_wino_splitk_workspace_bytes(B, ww.rows, D, H, W, ksplit)
+    if nbytes <= 0:
+        raise _lib.MeshDiffusionHipError("md_conv3_wino_splitk_workspace_bytes: unsupported shape")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=t.device)
+    ev = _prof_begin()
+    check(lib.md_conv3_wino_splitk(_lib.WINO_FMT[ww.fmt if f8 else False], _ptr(t), _ptr(ww.data), _ptr(ws), nbytes, _ptr(out), _ptr(bias),
+                                   bias_bstride, _ptr(residual), res_bstride, _ptr(stats), B, ww.kdim, ww.rows, D, H, W, ksplit, _stream()),
+          "md_conv3_wino_splitk")
+    # conv + finish as one record of its own kind, with the algorithmic flops of the conv: the "wino" records stay the launches of the
+    # conv kernel alone (bench.py's roofline of the dominant kernel counts and times them), per-shape figures list this one beside them
+    _prof_end(ev, "wino_splitk", 2.0 * B * ww.rows * ww.kdim * 27 * P,
+              4.0 * (2 * B * ww.kdim * P + ww.rows * ww.kdim * 36 + B * ww.rows * P * (2 * ksplit + (2 if residual is not None else 1))),
+              f"{ww.kdim}->{ww.rows}@{D}x{H}x{W}/ks{ksplit}" + ("/res" if residual is not None else "") + ("/stats" if stats is not None else "")
+              + (("/" + ww.fmt) if f8 else ""))
     return out
 
 

@@ -191,7 +191,7 @@ class Conv3Plan(NamedTuple):
     shortcut_in_pass: bool     # wino: the operand pass also writes the block's NIN shortcut (md_wino_prep_f6_nin)
     keep: bool                 # wino: T in a tensor of its own, handed back for the Winograd weight gradient
     stats: bool                # this launch accumulates the GroupNorm sums of its output
-    ksplit: int                # direct: split-K factor
+    ksplit: int                # direct: split-K factor; wino: K slices (md_conv3_wino_splitk), 1 = the unsplit launch
     fused_loader: bool         # direct: the kernel reads the fp32 parts itself (GroupNorm affine + SiLU + split in its halo loader)
     ups_fold: bool = False     # wino: the nearest-x2 taps folded into the weights (md_conv3_wino_upsfold: 4 tap steps per chunk, not 9)
 
@@ -202,10 +202,13 @@ def plan_conv3(pw, operand, B, S_out, *, ups, out_mode, rows_alloc, want_stats, 
     P = S_out ** 3
     plain = out_mode == ops.OUT_F32B and rows_alloc == pw.rows      # what the Winograd kernels and every statistics epilogue write
     sums = bool(want_stats and ops.FUSE_GN_STATS and plain)         # asked for, switched on, a layout an epilogue can sum
-    if (operand is not None and wino is not None and plain and pw.prec == ops.PREC_BF16X3
-            and ops.wino_ok(pw.rows, pw.kdim, S_out, B)):
-        # reduced precision, the compact operand and the block pass are inference layouts: no dropout, T not kept for a backward
-        infer = not (operand.wino_only or operand.drop or operand.keep)
+    # reduced precision, the compact operand, the block pass and the K slices are inference layouts: no dropout, T not kept for a backward
+    infer = operand is not None and not (operand.wino_only or operand.drop or operand.keep)
+    wino_ks = 0                      # 0: not a Winograd launch; 1: unsplit; > 1: K slices
+    if operand is not None and wino is not None and plain and pw.prec == ops.PREC_BF16X3:
+        # the 8^3 level at batches whose unsplit launch leaves the chip half empty: the same kernel on slices of the input channels
+        wino_ks = 1 if ops.wino_ok(pw.rows, pw.kdim, S_out, B) else (ops.wino_splitk_for(pw.rows, pw.kdim, S_out, B, ups) if infer else 0)
+    if wino_ks:
         # f16f8 / f16f6: inference operands that come out of a GroupNorm (the layer's static equaliser flattens their channels), or
         # any operand whose layer holds a measured equaliser (DDPMUNet3D.calibrate); an uncalibrated raw residual stream (Upsample:
         # ac None) stays in bf16x3
@@ -223,7 +226,7 @@ def plan_conv3(pw, operand, B, S_out, *, ups, out_mode, rows_alloc, want_stats, 
         # an f16f6 Upsample conv that fills the chip: four phase convs of 4 live (kd, kh) taps on the source rows.  The operand pass is
         # the one chosen above (the kernel reads either layout)
         fold = bool(infer and hasattr(wino, "fold") and ops.ups_fold_ok(ups, fmt, pw.rows, B, S_out, S_out, S_out))
-        return Conv3Plan("wino", fmt, compact, shortcut, operand.keep, sums, 1, False, fold)
+        return Conv3Plan("wino", fmt, compact, shortcut, operand.keep, sums, wino_ks, False, fold)
     ksplit = ops.ksplit_for(pw.cfg, B, pw.rows, pw.kdim, S_out) if out_mode == ops.OUT_F32B else 1
     # statistics of the output: the dedicated kernel's epilogue, or (8^3 / 4^3 levels) the split-K finish kernel
     # (one block per (sample, 8-channel group) there: only where that fills the chip -- at B = 1 the 32^3 level would run on 16 blocks)
@@ -241,7 +244,8 @@ def run_conv3(pw, act_s16, B, S_out, *, bias=None, bias_bstride=0, residual=None
     GroupNorm affine instead of `act_s16` (fused_operand_ok); `act_s16` may be None where nothing reads it (inference; training
     layers with b_f32.keep).
     wino (with b_f32): builder of the layer's WinoWeight (conv3_wino_packed); where hip_ops.wino_ok says so the conv runs as
-    md_wino_prep + md_conv3_wino (Winograd F(2,3) along w: 2/3 of the matrix-core work) instead of the direct kernel.
+    md_wino_prep + md_conv3_wino (Winograd F(2,3) along w: 2/3 of the matrix-core work) instead of the direct kernel; at the 8^3 level,
+    where hip_ops.wino_splitk_for says so, as md_wino_prep + md_conv3_wino_splitk (the same kernel on slices of the input channels).
     The route is plan_conv3's; what follows only carries it out."""
     P = S_out ** 3
     b_f32 = ops.F32Operand.of(b_f32)
@@ -291,6 +295,8 @@ def _conv3_wino(plan, pw, op, wino, B, S_out, ups, out, stats, **epilogue):
         assert epilogue.get("residual") is None, "md_conv3_wino_upsfold has no residual operand"
         ops.conv3_wino_upsfold(wino.fold(), t, B, S_out, stats=stats, out=out, bias=epilogue.get("bias"),
                                bias_bstride=epilogue.get("bias_bstride", 0))
+    elif plan.ksplit > 1:
+        ops.conv3_wino_splitk(wino(plan.fmt) if plan.fmt else wino(), t, B, S_out, plan.ksplit, stats=stats, out=out, **epilogue)
     else:
         ops.conv3_wino(wino(plan.fmt) if plan.fmt else wino(), t, B, S_out, stats=stats, out=out, **epilogue)
     if plan.fmt and ops.AUDIT is not None:
